@@ -8,15 +8,18 @@ A step = one pass of the hot path (NormalizePAD -> hctr trunk -> head -> argmax 
 + one RCCL gather to rank 0 when N > 1) over one batch of synthetic line images.
 N = 1: BASELINE.json configs[1], B=64 lines of 1x128x2000, greedy decode. N > 1: configs[3], a FIXED global batch of
 4096 lines cut into contiguous shards of 4096/N (strong scaling), every rank's labels gathered to rank 0 once per step.
-Inputs are uint8 images already resident in HBM when the timed region starts; value = global lines / max-over-ranks
-time. The N = 1 line also carries, from the same process and the same timing loop:
+Inputs are uint8 images already resident in HBM when the timed region starts, drawn from fixed seeds (identical from
+run to run); value = global lines / max-over-ranks time, ms_per_step = that time / K. A plain run times the headline
+mode only. With --full the line also carries roofline / whole_forward (per-layer HIP events on the engine's stream
+during the timed steps) and, at N = 1, from the same process and the same timing loop:
+  parity_vs_cpu                the headline's 64-line text parity against the REAL reference's strings
   value_f16x3 / value_auto     the two other precision modes (one context holds both weight sets), with the 64-line text
                                parity of each against the REAL reference's strings and auto's re-run line count
   value_incl_h2d               the reference's own bracket (test.py:189-195): u8 batch in pinned host memory -> labels
   trained_checkpoint           f16 and auto on the trained-like checkpoint (peaky logits)
   configs.c3 / configs.c5      BASELINE configs[2] (512 lines, 4 width buckets) and configs[4] (256 lines, beam 10/10)
-  roofline, cpu_baseline       dominant kernel (HIP events on the engine's stream) and the oracle on the host cores
-Prints ONE JSON line on rank 0.
+  cpu_baseline                 the oracle on the host cores
+--dump-outputs DIR writes the labels of the headline's last timed step (dump_outputs). Prints ONE JSON line on rank 0.
 """
 import argparse
 import json
@@ -225,7 +228,21 @@ def parse_args():
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c5"],
                     help="c2 (default, the driver's line): B=64 x W=2000 greedy at 1 GPU (+ the c3 / c5 records), configs[3] "
                          "(B=4096 sharded) at N > 1; c3 / c5: only that configuration (1 GPU)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: per-layer profile and roofline, text parity against the reference's "
+                         "strings, and at 1 GPU the other precision modes, the pinned-host bracket, the configs[2] / "
+                         "configs[4] records, the trained-like checkpoint and the CPU baseline (a plain run times the "
+                         "headline mode only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the labels the timed path returned in its last step to DIR/*.npy (float32)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if (args.layers or args.layer_file) and not args.full:
+        ap.error("--layers / --layer-file need --full (the per-layer profile is taken only there)")
+    if args.dump_outputs and args.config != "c2":
+        ap.error("--dump-outputs covers the default configuration (--config c2) only")
+    return args
 
 
 def main():
@@ -255,7 +272,7 @@ def main():
         seed, cfg_name = SEED_C4, "BASELINE configs[3]"
     lo, hi = hdist.shard_range(n_global, rank, world)
     B = hi - lo
-    full_line = world == 1 and args.config == "c2" and not args.no_second_mode
+    full_line = args.full and world == 1 and args.config == "c2" and not args.no_second_mode
     want_c3 = args.config == "c3" or (full_line and not args.no_extra_configs)
     want_c5 = args.config == "c5" or (full_line and not args.no_extra_configs)
     t0 = time.perf_counter()
@@ -356,7 +373,7 @@ def main():
         return out, dt, prof
 
     setup["before_first_step_s"] = round(time.perf_counter() - t_start, 2)
-    out, dt, prof = timed(model, imgs, True)
+    out, dt, prof = timed(model, imgs, args.full)
     fwd_ms, gather_ms = t_fwd[0] / args.steps * 1e3, t_gather[0] / args.steps * 1e3
     per_rank = None
     if dist is not None:                                      # every rank's own forward time, for the record
@@ -375,38 +392,8 @@ def main():
 
     lines_per_s = n_global * args.steps / dt
     log("headline (%s): %.1f lines/s, %.2f ms/step" % (args.precision, lines_per_s, dt / args.steps * 1e3))
-    # the dominant kernel's launch covers one internal pass of the engine (hctr_lines_per_pass: HCTR_MAX_COLS pixel
-    # columns, a third of that in f16x3); last_profile adds the passes' entries of one name up
-    x3 = args.precision == "f16x3"
-    pass_lines = model.lines_per_pass(B, W, x3)
-    n_pass = -(-B // pass_lines)
-    dom_ms = [np.mean(prof[n]) / n_pass for n in DOMINANT if n in prof]
-    dom_avg_ms = float(np.mean(dom_ms)) if dom_ms else float("nan")
-    flop_per_launch = FLOP_PER_COL_DOM * (B * W / n_pass)
-    dom_tflops = flop_per_launch / (dom_avg_ms * 1e-3) / 1e12
-    kernel_ms = float(sum(np.mean(v) for v in prof.values()))
-    # HBM-side traffic and matrix-pipe counters of the dominant kernel per launch: rocprofv3 PMC passes of this same
-    # command (tools/profile_rocprof.sh: FETCH_SIZE, WRITE_SIZE and the SQ set in separate runs, KiB units, FETCH_SIZE x2
-    # on gfx950 as MI355X_MICROARCH.md prescribes), summarised into profiles/per_layer_latest.json - NOT measured in
-    # this run (a PMC pass cannot share a process with the timed region).
-    traffic = traffic_src = busy = clock = None
-    pj = os.path.join(ROOT, "profiles", "per_layer_latest.json")
-    if os.path.isfile(pj) and world == 1 and B == B_PER_GPU and W == W_LINE and args.precision == "f16":
-        with open(pj) as f:
-            rows = [r for r in json.load(f) if r["layer"] in DOMINANT and r.get("fetch_gb_x2") is not None]
-        if rows:
-            traffic = float(np.mean([(r["fetch_gb_x2"] + r["write_gb"]) * 1e9 for r in rows]))
-            traffic_src = "profiles/per_layer_latest.json (rocprofv3 --pmc, separate passes of this command; not this run)"
-            b_ = [r["mfma_busy_pct"] for r in rows if r.get("mfma_busy_pct") is not None]
-            c_ = [r["clock_ghz"] for r in rows if r.get("clock_ghz") is not None]
-            busy = round(float(np.mean(b_)), 1) if b_ else None
-            clock = round(float(np.mean(c_)), 3) if c_ else None
-    if args.layers:
-        for name, v in prof.items():
-            print("%-24s %9.3f ms" % (name, float(np.mean(v))), file=sys.stderr)
-    if args.layer_file:
-        with open(args.layer_file, "w") as f:
-            f.write("\n".join(prof.keys()) + "\n")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, W)
     result = {
         "metric": "text-lines/sec (1x128x2000 synth) greedy decode",
         "value": round(lines_per_s, 3), "unit": "lines/s", "n_gpus": world, "steps": args.steps,
@@ -420,20 +407,11 @@ def main():
                                 "" if world == 1 else ", one gather to rank 0"),
                    "global_lines": n_global, "lines_per_gpu": B, "width": W, "classes": C,
                    "checkpoint": args.checkpoint, "parallelism": "batch-shard x%d" % world},
-        "roofline": {"bound": "mfma", "kernel": "conv3x3_halo4 3x3 512->512 @H=16 (%d launches per pass averaged)" % len(dom_ms),
-                     "achieved": round(dom_tflops, 2), "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(dom_tflops / PEAK_F16_TFLOPS, 4), "traffic": traffic,
-                     "traffic_unit": "bytes/launch (algorithmic: 2.36e9 in + 2.36e9 out + 4.7e6 weights)",
-                     "traffic_source": traffic_src, "mfma_busy_pct": busy, "clock_ghz": clock,
-                     "avg_launch_ms": round(dom_avg_ms, 4), "flops_per_launch": flop_per_launch,
-                     "launches_per_step_and_layer": n_pass,
-                     "note": "algorithmic FLOPs (2*Cin*Cout*9 per output pixel); in f16x3 the kernel issues 3x that "
-                             "in MFMA work" if x3 else None},
-        "whole_forward": {"kernel_ms_per_step": round(kernel_ms, 3),
-                          "tflops": round(FLOP_PER_COL_ALL * B * W / (kernel_ms * 1e-3) / 1e12, 2)},
         "setup_s": setup,
         "lib": lib_override or "in-tree libhctr_hip.so (source hash checked)",
     }
+    if args.full:
+        result.update(profile_records(args, model, prof, B, W, world))
     if world > 1:
         result["multi_gpu"] = {"world_size_reported_by_backend": dist.get_world_size(), "backend": backend,
                                "per_rank": {"columns": ["greedy ms (forward+decode+D2H)", "gather ms", "set-up s before the first step"],
@@ -441,7 +419,7 @@ def main():
                                "gather_bytes_per_rank": int(-(-n_global // world) * (1 + W) * 4),
                                "gather_cap": "W labels per line: random-init weights emit a label on every second column (978 of 2000 on average), so no smaller constant is safe; 4.1 MB per rank at 512 lines"}
 
-    if world == 1:
+    if world == 1 and args.full:
         codec = hctr_amd.ctc_codec(synth.characters())
         std = n_global == B_PER_GPU and W == W_LINE
         meta = load_golden("c2_lines" if args.checkpoint == "random" else "c2_trained_lines") if std else None
@@ -518,7 +496,7 @@ def main():
                     "f16x3": "%s lines/s, %d/%d" % (result.get("value_f16x3"), result.get("parity_vs_cpu_f16x3", {}).get("exact_lines", -1), n_global),
                     "auto": "%s lines/s, %d/%d (= f16x3's text; near-tie-rich logits, see parity_note)" % (
                         result.get("value_auto"), pa.get("exact_lines", -1), n_global)}}
-    if not args.no_cpu_baseline and world == 1:          # reported baseline: rank 0 of the 1-GPU run only
+    if args.full and not args.no_cpu_baseline and world == 1:     # reported baseline: rank 0 of the 1-GPU run only
         # the CPU restatement (bit-equal to the reference here) on B=4 lines of the same
         # workload, 1 warm-up + 3 timed passes, on the physical host cores this process may use
         from oracle import ctc_ref, hctr_ref
@@ -559,6 +537,78 @@ def make_checkpoint(synth, C, kind):
     if kind == "trained":
         return synth.make_state_dict(C, seed=0, head="trained")
     return synth.make_state_dict(C, seed=0)
+
+
+def profile_records(args, model, prof, B, W, world):
+    """--full: the roofline and whole-forward records from the per-layer profile of the headline's timed steps."""
+    # the dominant kernel's launch covers one internal pass of the engine (hctr_lines_per_pass: HCTR_MAX_COLS pixel
+    # columns, a third of that in f16x3); last_profile adds the passes' entries of one name up
+    x3 = args.precision == "f16x3"
+    pass_lines = model.lines_per_pass(B, W, x3)
+    n_pass = -(-B // pass_lines)
+    dom_ms = [np.mean(prof[n]) / n_pass for n in DOMINANT if n in prof]
+    dom_avg_ms = float(np.mean(dom_ms)) if dom_ms else float("nan")
+    flop_per_launch = FLOP_PER_COL_DOM * (B * W / n_pass)
+    dom_tflops = flop_per_launch / (dom_avg_ms * 1e-3) / 1e12
+    kernel_ms = float(sum(np.mean(v) for v in prof.values()))
+    # HBM-side traffic and matrix-pipe counters of the dominant kernel per launch: rocprofv3 PMC passes of this same
+    # command (tools/profile_rocprof.sh: FETCH_SIZE, WRITE_SIZE and the SQ set in separate runs, KiB units, FETCH_SIZE x2
+    # on gfx950 as MI355X_MICROARCH.md prescribes), summarised into profiles/per_layer_latest.json - NOT measured in
+    # this run (a PMC pass cannot share a process with the timed region).
+    traffic = traffic_src = busy = clock = None
+    pj = os.path.join(ROOT, "profiles", "per_layer_latest.json")
+    if os.path.isfile(pj) and world == 1 and B == B_PER_GPU and W == W_LINE and args.precision == "f16":
+        with open(pj) as f:
+            rows = [r for r in json.load(f) if r["layer"] in DOMINANT and r.get("fetch_gb_x2") is not None]
+        if rows:
+            traffic = float(np.mean([(r["fetch_gb_x2"] + r["write_gb"]) * 1e9 for r in rows]))
+            traffic_src = "profiles/per_layer_latest.json (rocprofv3 --pmc, separate passes of this command; not this run)"
+            b_ = [r["mfma_busy_pct"] for r in rows if r.get("mfma_busy_pct") is not None]
+            c_ = [r["clock_ghz"] for r in rows if r.get("clock_ghz") is not None]
+            busy = round(float(np.mean(b_)), 1) if b_ else None
+            clock = round(float(np.mean(c_)), 3) if c_ else None
+    if args.layers:
+        for name, v in prof.items():
+            print("%-24s %9.3f ms" % (name, float(np.mean(v))), file=sys.stderr)
+    if args.layer_file:
+        with open(args.layer_file, "w") as f:
+            f.write("\n".join(prof.keys()) + "\n")
+    return {
+        "roofline": {"bound": "mfma", "kernel": "conv3x3_halo4 3x3 512->512 @H=16 (%d launches per pass averaged)" % len(dom_ms),
+                     "achieved": round(dom_tflops, 2), "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
+                     "frac": round(dom_tflops / PEAK_F16_TFLOPS, 4), "traffic": traffic,
+                     "traffic_unit": "bytes/launch (algorithmic: 2.36e9 in + 2.36e9 out + 4.7e6 weights)",
+                     "traffic_source": traffic_src, "mfma_busy_pct": busy, "clock_ghz": clock,
+                     "avg_launch_ms": round(dom_avg_ms, 4), "flops_per_launch": flop_per_launch,
+                     "launches_per_step_and_layer": n_pass,
+                     "note": "algorithmic FLOPs (2*Cin*Cout*9 per output pixel); in f16x3 the kernel issues 3x that "
+                             "in MFMA work" if x3 else None},
+        "whole_forward": {"kernel_ms_per_step": round(kernel_ms, 3),
+                          "tflops": round(FLOP_PER_COL_ALL * B * W / (kernel_ms * 1e-3) / 1e12, 2)},
+    }
+
+
+DUMP_BUDGET_BYTES = 60 << 20          # the .npy files of --dump-outputs stay below 64 MB in all
+
+
+def dump_outputs(dirname, labels, width):
+    """--dump-outputs: the label arrays the timed path returned in its last step (all lines, in batch order), as float32
+    .npy files (exact: labels are below 2**24): labels.npy [lines, width] holds each line's labels followed by -1
+    padding, lengths.npy [lines] their counts, line_index.npy [lines] the batch position of each row. A batch beyond
+    the size budget is cut to a fixed sample of lines (seed 0, kept in batch order)."""
+    n = len(labels)
+    rows = np.arange(n)
+    per_line = (width + 2) * 4
+    if n * per_line > DUMP_BUDGET_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_BUDGET_BYTES // per_line, replace=False))
+    padded = np.full((len(rows), width), -1, np.float32)
+    for i, r in enumerate(rows):
+        padded[i, :len(labels[r])] = labels[r]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "labels.npy"), padded)
+    np.save(os.path.join(dirname, "lengths.npy"), np.array([len(labels[r]) for r in rows], np.float32))
+    np.save(os.path.join(dirname, "line_index.npy"), rows.astype(np.float32))
+    log("outputs of the last timed step: %d of %d lines -> %s" % (len(rows), n, dirname))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -822,13 +822,43 @@ def test_bench_single_gpu_line_has_every_record():
     from conftest import ROOT
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--batch", "4",
-                        "--width", "256", "--no-cpu-baseline", "--no-extra-configs"], env=env, capture_output=True, text=True,
-                       timeout=900)
+                        "--width", "256", "--no-cpu-baseline", "--no-extra-configs", "--full"], env=env, capture_output=True,
+                       text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     for key in ("value", "value_f16x3", "value_auto", "value_incl_h2d", "roofline", "flagged_lines_auto", "setup_s", "lib"):
         assert key in res, key
     assert res["n_gpus"] == 1 and res["roofline"]["launches_per_step_and_layer"] == 1 and res["value_auto"] > 0
+
+
+def test_bench_plain_run_dumps_the_timed_labels(engine, synth, tmp_path):
+    """A plain bench run (no --full) times the headline only: its line has the headline keys and K timed steps, none of
+    the --full records, and --dump-outputs writes exactly the labels the timed path returns for the seeded lines."""
+    import subprocess
+    import sys
+    from conftest import ROOT
+    sys.path.insert(0, ROOT)
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "4",
+                        "--width", "256", "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True,
+                       timeout=900)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0
+    assert res["unit"] == "lines/s" and res["higher_is_better"] is True and res["dtype"] == bench.DTYPE_NAME["f16"]
+    assert abs(res["value"] - 4 * 1e3 / res["ms_per_step"]) <= 1e-3 * res["value"]
+    for key in ("roofline", "whole_forward", "parity_vs_cpu", "value_f16x3", "cpu_baseline"):
+        assert key not in res, key
+    want = engine.greedy(synth.make_line_images(4, 256, bench.SEED))
+    labels, lengths = np.load(tmp_path / "labels.npy"), np.load(tmp_path / "lengths.npy")
+    assert labels.dtype == np.float32 and labels.shape == (4, 256)
+    assert np.array_equal(np.load(tmp_path / "line_index.npy"), np.arange(4))
+    assert np.array_equal(lengths, [len(w) for w in want])
+    for row, w in zip(labels, want):
+        assert np.array_equal(row[:len(w)], w) and (row[len(w):] == -1).all()
 
 
 def _c2_columns(model, imgs, chunk=8):

@@ -438,6 +438,38 @@ def test_bench_multi_gpu_launch_fails_loudly_without_gpus():
     assert "starting 2 ranks" in r.stderr
 
 
+def test_bench_dump_outputs_format(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 labels padded with -1 to the line width, their lengths and batch positions;
+    a batch beyond the size budget is cut to the same seeded sample of lines every time, kept in batch order."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(7)
+    labels = [rng.integers(1, 7359, size=n).astype(np.int32) for n in (0, 5, 12, 3, 12, 1)]
+    bench.dump_outputs(str(tmp_path / "all"), labels, 12)
+    got = {n: np.load(tmp_path / "all" / (n + ".npy")) for n in ("labels", "lengths", "line_index")}
+    assert all(a.dtype == np.float32 for a in got.values()) and got["labels"].shape == (6, 12)
+    assert np.array_equal(got["line_index"], np.arange(6)) and np.array_equal(got["lengths"], [len(l) for l in labels])
+    for row, l in zip(got["labels"], labels):
+        assert np.array_equal(row[:len(l)], l) and (row[len(l):] == -1).all()
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 3 * (12 + 2) * 4)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), labels, 12)
+    idx = np.load(tmp_path / "s1" / "line_index.npy").astype(int)
+    assert len(idx) == 3 and (np.diff(idx) > 0).all()
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "line_index.npy"))
+    sample = np.load(tmp_path / "s1" / "labels.npy")
+    for row, i in zip(sample, idx):
+        assert np.array_equal(row[:len(labels[i])], labels[i])
+
+
+def test_bench_rejects_options_it_cannot_honour():
+    """--steps below 1 and a per-layer table without --full are refused at the command line (exit 2), before any set-up."""
+    for extra in (["--steps", "0"], ["--layers"], ["--layer-file", "x.txt"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra, capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 2 and not r.stdout, (extra, r.stderr[-500:])
+
+
 def test_beam_pipeline_chunk_schedule(pkg):
     """pipeline.chunk_schedule: contiguous cover of the batch, chunks never above the limit, large chunks first and a
     taper to small ones at the end (nothing overlaps the host search of the last chunk)."""

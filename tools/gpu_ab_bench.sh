@@ -15,7 +15,7 @@ rm -f $OUT/*.npz
 for i in $(seq 1 $R); do
   for V in "$@"; do
     if [ $V = default ]; then unset HCTR_LIB_PATH; else export HCTR_LIB_PATH=ab_libs/$V.so; fi
-    timeout -k 10 200 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-second-mode --no-extra-configs --no-oracle-check > $OUT/b_${V}_$i.json 2> $OUT/b_${V}_$i.err
+    timeout -k 10 200 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-second-mode --no-extra-configs --no-oracle-check > $OUT/b_${V}_$i.json 2> $OUT/b_${V}_$i.err
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[1], d['ms_per_step'], d['roofline']['frac'])" $OUT/b_${V}_$i.json
   done
 done
