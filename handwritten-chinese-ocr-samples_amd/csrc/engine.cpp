@@ -193,6 +193,9 @@ struct hctr_ctx {
     std::vector<int64_t> cand_off;
     std::vector<int32_t> cand_idx;
     std::vector<float> cand_logp;
+    // CTC loss scratch (hctr_ctc_loss*): per-line tables, per-line results and the emission rows; grows, never shrinks
+    char* ctc_buf = nullptr;
+    size_t ctc_cap = 0;
 };
 
 namespace {
@@ -1011,6 +1014,103 @@ struct SplitScope {
     ~SplitScope() { c->split = c->mode == 1; }
 };
 
+// ---------------------------------------------------------------------------------------------
+// CTC loss (hctr_ctc_loss*): argument checks, the per-line tables of kernels.h CtcLines, scratch
+// ---------------------------------------------------------------------------------------------
+struct CtcHost {
+    std::vector<int32_t> tab;     // T[B] | L[B] | off[B] | nd[B] | cls[B][D] | slot[sum L], uploaded as one block
+    int B = 0, D = 1, max_states = 1;
+};
+
+// torch.nn.functional.ctc_loss's conventions with blank 0: a target id outside [1, C-1] is an argument error; a line
+// with L + (adjacent equal labels) > T has no alignment and gets T = 0 (the kernel writes +inf without reading a row)
+int ctc_prepare(hctr_ctx* c, int B, int W, int C, const int32_t* targets, const int32_t* target_lengths,
+                const int32_t* input_lengths, CtcHost* h) {
+    if (!target_lengths) return fail(c, HCTR_ERR_ARG, "target_lengths is NULL");
+    int64_t total = 0;
+    for (int b = 0; b < B; ++b) {
+        if (target_lengths[b] < 0) return fail(c, HCTR_ERR_ARG, "target_lengths[%d]=%d < 0", b, target_lengths[b]);
+        total += target_lengths[b];
+    }
+    if (total > 0 && !targets) return fail(c, HCTR_ERR_ARG, "targets is NULL");
+    if (total > INT32_MAX) return fail(c, HCTR_ERR_ARG, "too many targets (%lld)", (long long)total);
+    std::vector<std::vector<int32_t>> dist((size_t)B);
+    std::vector<int32_t> T((size_t)B), nd((size_t)B);
+    int D = 1, max_states = 1;
+    int64_t o = 0;
+    for (int b = 0; b < B; ++b) {
+        const int L = target_lengths[b];
+        const int32_t* tg = targets + o;
+        const int Tb = input_lengths ? input_lengths[b] : W;
+        if (Tb < 1 || Tb > W) return fail(c, HCTR_ERR_ARG, "input_lengths[%d]=%d outside [1,%d]", b, Tb, W);
+        int rep = 0;
+        for (int j = 0; j < L; ++j) {
+            if (tg[j] < 1 || tg[j] > C - 1)
+                return fail(c, HCTR_ERR_ARG, "target id %d (line %d, position %d) outside [1,%d]", tg[j], b, j, C - 1);
+            rep += (j > 0 && tg[j] == tg[j - 1]) ? 1 : 0;
+        }
+        const bool feasible = (int64_t)L + rep <= Tb;
+        if (feasible && 2 * (int64_t)L + 1 > kCtcMaxStates)
+            return fail(c, HCTR_ERR_ARG, "target_lengths[%d]=%d exceeds the %d labels one line supports", b, L,
+                        (kCtcMaxStates - 1) / 2);
+        std::vector<int32_t>& d = dist[(size_t)b];
+        d.assign(tg, tg + L);
+        std::sort(d.begin(), d.end());
+        d.erase(std::unique(d.begin(), d.end()), d.end());
+        T[(size_t)b] = feasible ? Tb : 0;
+        nd[(size_t)b] = 1 + (int)d.size();
+        if (feasible) {
+            D = std::max(D, nd[(size_t)b]);
+            max_states = std::max(max_states, 2 * L + 1);
+        }
+        o += L;
+    }
+    h->B = B; h->D = D; h->max_states = max_states;
+    std::vector<int32_t>& tab = h->tab;
+    tab.assign((size_t)4 * B + (size_t)B * D + (size_t)total, 0);
+    int32_t* cls = tab.data() + 4 * (size_t)B;
+    int32_t* slot = cls + (size_t)B * D;
+    o = 0;
+    for (int b = 0; b < B; ++b) {
+        const int L = target_lengths[b];
+        const std::vector<int32_t>& d = dist[(size_t)b];
+        tab[(size_t)b] = T[(size_t)b];
+        tab[(size_t)B + b] = L;
+        tab[2 * (size_t)B + b] = (int32_t)o;
+        tab[3 * (size_t)B + b] = T[(size_t)b] ? nd[(size_t)b] : 1;
+        for (size_t j = 0; j < d.size() && T[(size_t)b]; ++j) cls[(size_t)b * D + 1 + j] = d[j];
+        for (int j = 0; j < L; ++j)
+            slot[o + j] = 1 + (int32_t)(std::lower_bound(d.begin(), d.end(), targets[o + j]) - d.begin());
+        o += L;
+    }
+    return HCTR_OK;
+}
+
+// device scratch of a CTC call: the tables (uploaded), nll[B] and `emis_floats` emission floats
+int ctc_scratch(hctr_ctx* c, const CtcHost& h, size_t emis_floats, CtcLines* m, float** nll, float** emis) {
+    const size_t tab_b = (h.tab.size() * 4 + 255) & ~(size_t)255, nll_b = ((size_t)h.B * 4 + 255) & ~(size_t)255;
+    const size_t need = tab_b + nll_b + emis_floats * 4;
+    if (need > c->ctc_cap) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (c->ctc_buf) (void)hipFree(c->ctc_buf);
+        c->ctc_buf = nullptr; c->ctc_cap = 0;
+        void* p = nullptr;
+        hipError_t e = hipMalloc(&p, need);
+        if (e != hipSuccess)
+            return fail(c, HCTR_ERR_NOMEM, "hipMalloc(%zu bytes) for the CTC scratch failed: %s", need, hipGetErrorString(e));
+        c->ctc_buf = (char*)p;
+        c->ctc_cap = need;
+    }
+    const int32_t* d = (const int32_t*)c->ctc_buf;
+    const size_t B = (size_t)h.B;
+    m->T = d; m->L = d + B; m->off = d + 2 * B; m->nd = d + 3 * B; m->cls = d + 4 * B; m->slot = d + 4 * B + B * h.D;
+    m->D = h.D;
+    *nll = (float*)(c->ctc_buf + tab_b);
+    *emis = (float*)(c->ctc_buf + tab_b + nll_b);
+    HIP_TRY(c, hipMemcpyAsync(c->ctc_buf, h.tab.data(), h.tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return HCTR_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1087,6 +1187,7 @@ void hctr_destroy(hctr_ctx* c) {
     if (c->pin) (void)hipHostFree(c->pin);
     free_pool(c->wallocs);
     free_pool(c->beam_allocs);
+    if (c->ctc_buf) (void)hipFree(c->ctc_buf);
     if (c->stamp_buf) (void)hipFree(c->stamp_buf);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -1633,6 +1734,101 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
         }
         if (num_candidates) *num_candidates = tot;
         return HCTR_OK;
+    });
+}
+
+int hctr_ctc_loss(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
+                  const int32_t* targets, const int32_t* target_lengths, const int32_t* input_lengths, float* nll) {
+    return guard(c, [&]() -> int {
+        TRY(check_forward_args(c, img, img_dtype, B, W));
+        if (B == 0) return HCTR_OK;
+        if (!nll) return fail(c, HCTR_ERR_ARG, "nll is NULL");
+        HIP_TRY(c, hipSetDevice(c->device));
+        const int C = c->num_classes;
+        CtcHost h;
+        TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
+        SplitScope scope(c);
+        c->split = c->mode != 0;                  // mode 2 scores every line in f16x3: its guard certifies argmaxes, not losses
+        if (!c->wts().built) return fail(c, HCTR_ERR_STATE, "the weight set of this precision mode is not resident");
+        prof_reset(c);
+        const int nbmax = sub_batch(c, B, W, c->split);
+        CtcLines m;
+        float *d_nll = nullptr, *emis = nullptr;
+        TRY(ctc_scratch(c, h, (size_t)nbmax * W * h.D, &m, &d_nll, &emis));
+        std::vector<int> all((size_t)B);
+        for (int b = 0; b < B; ++b) all[(size_t)b] = b;
+        // one pass: the lines [b0, b0 + nb) through the forward into stored logits, then emissions and the recursion
+        auto pass = [&](int b0, int nb) -> int {
+            TRY(ensure_workspace(c, nb, W, ws_need(c, HEAD_LOGITS)));
+            TRY(stage_input(c, img, img_dtype, img_on_device, widths, all.data() + b0, nb, W));
+            TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, HEAD_LOGITS, false));
+            Prof pf(c);
+            pf.begin("ctc_lse");
+            HIP_TRY(c, launch_ctc_lse(c->ws.logits, c->cpad, W, 1, C, m, b0, nb, W, emis, c->stream));
+            pf.end();
+            pf.begin("ctc_alpha");
+            HIP_TRY(c, launch_ctc_alpha(emis, m, b0, nb, W, h.max_states, d_nll, c->stream));
+            pf.end();
+            return HCTR_OK;
+        };
+        int rc = HCTR_OK;
+        for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax) rc = pass(b0, std::min(nbmax, B - b0));
+        if (rc == HCTR_OK) {
+            hipError_t e = hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
+            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "D2H nll: %s", hipGetErrorString(e));
+        }
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
+        return rc;
+    });
+}
+
+int hctr_ctc_loss_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W, int B, int C, const int32_t* targets,
+                         const int32_t* target_lengths, const int32_t* input_lengths, float* nll) {
+    return guard(c, [&]() -> int {
+        if (!c) return HCTR_ERR_ARG;
+        if (W < 0 || B < 0 || C < 2) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
+        if (B == 0) return HCTR_OK;
+        if (W < 1) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
+        if (!logits_wbc || !nll) return fail(c, HCTR_ERR_ARG, "NULL pointer");
+        HIP_TRY(c, hipSetDevice(c->device));
+        CtcHost h;
+        TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
+        prof_reset(c);
+        std::vector<void*> tmp;
+        PoolGuard tmp_guard{tmp};
+        CtcLines m;
+        float *d_nll = nullptr, *emis = nullptr, *up = nullptr;
+        TRY(ctc_scratch(c, h, (size_t)B * W * h.D, &m, &d_nll, &emis));
+        const float* dev = logits_wbc;
+        int rc = HCTR_OK;
+        if (!on_device) {
+            const size_t n = (size_t)W * B * C;
+            rc = dev_alloc(c, tmp, &up, n, false);
+            if (rc == HCTR_OK) {
+                hipError_t e = hipMemcpyAsync(up, logits_wbc, n * 4, hipMemcpyHostToDevice, c->stream);
+                if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "H2D logits: %s", hipGetErrorString(e));
+            }
+            dev = up;
+        }
+        if (rc == HCTR_OK) {
+            Prof pf(c);
+            // rows of the WBC tensor are r = t*B + b
+            pf.begin("ctc_lse");
+            hipError_t e = launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, c->stream);
+            pf.end();
+            if (e == hipSuccess) {
+                pf.begin("ctc_alpha");
+                e = launch_ctc_alpha(emis, m, 0, B, W, h.max_states, d_nll, c->stream);
+                pf.end();
+            }
+            if (e == hipSuccess) e = hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
+            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_loss_logits: %s", hipGetErrorString(e));
+        }
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
+        free_pool(tmp);
+        return rc;
     });
 }
 

@@ -191,6 +191,26 @@ hipError_t launch_row_candidates(const float* logits, int64_t ld, int B, int W, 
 // contiguous rows [rows][C] -> float32 log-softmax per row
 hipError_t launch_log_softmax_rows(const float* x, int64_t rows, int C, float* y, hipStream_t s);
 
+// ---- CTC loss (hctr_ctc_loss*): per-line tables on the device, indexed by the line's place gb in the caller's batch ----
+constexpr int kCtcMaxStates = 64 * 64;   // extended target 2L + 1 of one wave64 line (ctc_alpha_kernel's largest instance)
+struct CtcLines {
+    const int32_t* T;       // [B] steps read (input_lengths); 0 = the line has no alignment (nll = +inf, nothing read)
+    const int32_t* L;       // [B] target length
+    const int32_t* off;     // [B] offset of the line's targets in slot
+    const int32_t* nd;      // [B] |D_b| + 1: distinct target classes of the line plus the blank
+    const int32_t* cls;     // [B][D] class of each emission slot (slot 0 = class 0, the blank)
+    const int32_t* slot;    // [sum L] emission slot of every target position
+    int D;                  // emission slots per row (max nd)
+};
+// rows of logits at x + (b*sb + t*st) * ld for the pass's lines b = 0..nb-1 (line gb = b0 + b of the tables), C classes:
+// emis[(b*W + t) * D + j] = z[cls[gb][j]] - logsumexp(z) for t < T[gb], j < nd[gb]
+hipError_t launch_ctc_lse(const float* x, int64_t ld, int64_t sb, int64_t st, int C, const CtcLines& m, int b0, int nb,
+                          int W, float* emis, hipStream_t s);
+// forward (alpha) recursion of the pass's lines over those emissions -> nll[b0 + b]; max_states = largest 2L + 1 among
+// the lines with T > 0 (<= kCtcMaxStates)
+hipError_t launch_ctc_alpha(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states, float* nll,
+                            hipStream_t s);
+
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {
     int64_t src_off;          // byte offset of the image inside the packed source buffer

@@ -3223,4 +3223,185 @@ hipError_t launch_beam_candidates(const int32_t* emit_cnt, const int32_t* emit_l
     return hipGetLastError();
 }
 
+
+// -------------------------------------------------------------------------------------------
+// CTC loss: torch.nn.CTCLoss over preds.log_softmax(2) (main.py:205,379-409), forward only.
+// Emissions: for row (line b, step t) the log-probs of the line's distinct classes D_b (slot 0 = blank) at
+// emis[(b*W + t) * D + j]; the alpha recursion reads nothing else. See CtcLines in kernels.h.
+// -------------------------------------------------------------------------------------------
+
+// One 256-thread block per (t, line): log-sum-exp of the row (float32 max, float64 exp-sum and log) in one pass over it,
+// then the slots of D_b as float32(z - lse). Rows t >= T_b are not read.
+__global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ x, int64_t ld, int64_t sb, int64_t st,
+                                                      int C, const CtcLines m, int b0, int W,
+                                                      float* __restrict__ emis) {
+    __shared__ float rv[4];
+    __shared__ double rd[4];
+    const int64_t r = blockIdx.x;                  // b*W + t
+    const int b = (int)(r / W), t = (int)(r % W), gb = b0 + b;
+    if (t >= m.T[gb]) return;                      // (block-uniform)
+    const float* p = x + ((int64_t)b * sb + (int64_t)t * st) * ld;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    // one pass over the row: eight loads in flight per thread, a running (max, exp-sum) rescaled when the max grows
+    float tm = -INFINITY;
+    double ts = 0.0;
+    for (int c0 = tid; c0 < C; c0 += 8 * 256) {
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = c0 + k * 256 < C ? p[c0 + k * 256] : -INFINITY;
+        float cm = v[0];
+#pragma unroll
+        for (int k = 1; k < 8; ++k) cm = fmaxf(cm, v[k]);
+        if (cm > tm) {
+            ts *= (double)expf(tm - cm);
+            tm = cm;
+        }
+        if (tm != -INFINITY) {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) ts += (double)expf(v[k] - tm);
+        }
+    }
+    float mx = tm;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    if (lane == 0) rv[wv] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(rv[0], rv[1]), fmaxf(rv[2], rv[3]));
+    const double s = block_sum_d(tm == -INFINITY ? 0.0 : ts * (double)expf(tm - mx), rd);
+    const double lse = (double)mx + log(s);
+    const int nd = m.nd[gb];
+    const int32_t* cls = m.cls + (int64_t)gb * m.D;
+    float* e = emis + ((int64_t)b * W + t) * m.D;
+    for (int j = tid; j < nd; j += 256) e[j] = (float)((double)p[cls[j]] - lse);
+}
+
+__device__ __forceinline__ float ctc_logadd(float a, float b) {
+    const float mx = fmaxf(a, b);
+    if (mx == -INFINITY) return -INFINITY;
+    return mx + log1pf(expf(-fabsf(a - b)));
+}
+
+// One workgroup of NW wave64s per line: the log-space forward recursion over the extended target (blank, l1, blank, ...,
+// lL, blank), S = 2L + 1 states; thread i holds the NS contiguous states [i*NS, i*NS + NS), the two states below them
+// come from the left neighbour lane over __shfl_up, and across a wave boundary from a double-buffered LDS slot written
+// at the end of the previous step - one barrier per step when NW > 1, none for a one-wave line. The emissions of the
+// next PF steps are in flight while a step is computed (a ring of PF rows, statically indexed by unrolling the step loop
+// PF times). alpha is float32; the three-way log-add is max + log(1 + exp(mid - max) + exp(min - max)) (torch's CPU
+// kernel's, with the max term's exp(0) = 1 folded); the skip transition s-2 -> s only where l_s != l_{s-2}.
+// nll[b0 + b] = -logaddexp(alpha_T[S-1], alpha_T[S-2]) (-alpha_T[0] for L = 0), +inf for a line marked T = 0.
+template <int NS, int PF, int NW>
+__global__ __launch_bounds__(64 * NW) void ctc_alpha_kernel(const float* __restrict__ emis, const CtcLines m, int b0,
+                                                             int W, float* __restrict__ nll) {
+    static_assert(NW == 1 || NS >= 2, "a wave boundary hands over two states from one lane");
+    __shared__ float xb[2][NW][2];                 // [step parity][wave] = {state wave_end-1, state wave_end-2}
+    __shared__ float fin[2];
+    const int b = blockIdx.x, gb = b0 + b, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int T = m.T[gb], L = m.L[gb], S = 2 * L + 1;
+    if (T == 0) {                                  // no alignment (host-side feasibility test); block-uniform
+        if (tid == 0) nll[gb] = INFINITY;
+        return;
+    }
+    const int32_t* ts = m.slot + m.off[gb];
+    int slot[NS];
+    bool skip[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int s = tid * NS + i;
+        const bool lab = (s & 1) && s < S;
+        slot[i] = lab ? ts[s >> 1] : 0;
+        skip[i] = lab && s >= 3 && ts[s >> 1] != ts[(s >> 1) - 1];
+    }
+    const int D = m.D;
+    const float* base = emis + (int64_t)b * W * D;
+    float a[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int s = tid * NS + i;
+        a[i] = (s == 0 || (s == 1 && S > 1)) ? base[slot[i]] : -INFINITY;
+    }
+    auto publish = [&](int parity) {
+        if (NW > 1) {
+            if (lane == 63) {
+                xb[parity][wv][0] = a[NS - 1];
+                xb[parity][wv][1] = a[NS >= 2 ? NS - 2 : 0];
+            }
+            __syncthreads();
+        }
+    };
+    publish(0);
+    float e[PF][NS];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+        const float* r = base + (int64_t)min(1 + k, T - 1) * D;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) e[k][i] = r[slot[i]];
+    }
+    for (int t0 = 1; t0 < T; t0 += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+            const int t = t0 + k;
+            if (t < T) {                           // (block-uniform)
+                float p1 = __shfl_up(a[NS - 1], 1);
+                float p2 = NS >= 2 ? __shfl_up(a[NS >= 2 ? NS - 2 : 0], 1) : __shfl_up(a[NS - 1], 2);
+                if (lane == 0) {
+                    p1 = wv > 0 ? xb[(t - 1) & 1][wv > 0 ? wv - 1 : 0][0] : -INFINITY;
+                    p2 = wv > 0 ? xb[(t - 1) & 1][wv > 0 ? wv - 1 : 0][1] : -INFINITY;
+                }
+                if (NS == 1 && lane == 1) p2 = -INFINITY;      // (NS == 1 only with NW == 1)
+#pragma unroll
+                for (int i = NS - 1; i >= 0; --i) {      // descending: a[i-1], a[i-2] still hold step t-1
+                    const float la1 = a[i];
+                    const float la2 = i >= 1 ? a[i >= 1 ? i - 1 : 0] : p1;
+                    const float la3 = skip[i] ? (i >= 2 ? a[i >= 2 ? i - 2 : 0] : (i == 1 ? p1 : p2)) : -INFINITY;
+                    const float mx = fmaxf(la1, fmaxf(la2, la3));
+                    const float mn = fminf(la1, fminf(la2, la3));
+                    const float md = __builtin_amdgcn_fmed3f(la1, la2, la3);
+                    const float v = mx + __logf(1.f + __expf(md - mx) + __expf(mn - mx));
+                    a[i] = (mx == -INFINITY ? -INFINITY : v) + e[k][i];
+                }
+                publish(t & 1);
+            }
+            const float* r = base + (int64_t)min(t + PF, T - 1) * D;   // refill the slot just used
+#pragma unroll
+            for (int i = 0; i < NS; ++i) e[k][i] = r[slot[i]];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int s = tid * NS + i;
+        if (s == S - 1) fin[0] = a[i];
+        if (s == S - 2) fin[1] = a[i];
+    }
+    __syncthreads();
+    if (tid == 0) nll[gb] = L == 0 ? -fin[0] : -ctc_logadd(fin[0], fin[1]);
+}
+
+hipError_t launch_ctc_lse(const float* x, int64_t ld, int64_t sb, int64_t st, int C, const CtcLines& m, int b0, int nb,
+                          int W, float* emis, hipStream_t s) {
+    if (nb <= 0 || W <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ctc_lse_kernel, dim3((unsigned)((int64_t)nb * W)), dim3(256), 0, s, x, ld, sb, st, C, m, b0, W, emis);
+    return hipGetLastError();
+}
+
+hipError_t launch_ctc_alpha(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states, float* nll,
+                            hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+#define CTC_ALPHA(NS, PF, NW)                                                                                     \
+    if (max_states <= 64 * NS * NW) {                                                                                 \
+        hipLaunchKernelGGL((ctc_alpha_kernel<NS, PF, NW>), dim3((unsigned)nb), dim3(64 * NW), 0, s, emis, m, b0, W, nll); \
+        return hipGetLastError();                                                                                     \
+    }
+    // a long target spreads over more waves (one barrier per step) rather than more states per lane: the recursion is
+    // latency-bound, and a batch of lines occupies few of the 1024 SIMDs
+    CTC_ALPHA(1, 4, 1)
+    CTC_ALPHA(2, 4, 1)
+    CTC_ALPHA(2, 4, 2)
+    CTC_ALPHA(2, 4, 4)
+    CTC_ALPHA(2, 4, 8)
+    CTC_ALPHA(2, 4, 16)
+    CTC_ALPHA(4, 2, 16)
+#undef CTC_ALPHA
+    return hipErrorInvalidValue;
+}
+
 }  // namespace hctr

@@ -241,6 +241,25 @@ class hctr_model(object):
         wd = self._widths(widths, B)
         return beam_frontend_call(ctx, x, dt, on_dev, wd, None, 0, B, W, int(self.noutput), k, want_candidates)
 
+    def ctc_loss(self, input, targets, target_lengths, input_lengths=None, widths=None, reduction="mean",
+                 zero_infinity=True):
+        """CTC loss of line images against transcriptions, the logits never leaving the device: the reference's
+        ``CTCLoss(zero_infinity=True)(model(input).log_softmax(2), targets, input_lengths, target_lengths)``
+        (main.py:205,379-409), forward only. ``targets``: 1-D concatenated (``codec.encode``) or 2-D padded ``[B, S]``;
+        ``input_lengths`` None = W for every line (main.py's preds_sizes). ``reduction`` / ``zero_infinity`` as
+        torch.nn.CTCLoss. Returns a float32 torch tensor when ``input`` is one, numpy otherwise. In "auto" precision every
+        line is scored in f16x3 (include/hctr_hip.h ``hctr_ctc_loss``)."""
+        from . import ctc
+        ctx = self._require_ctx()
+        x, dt, on_dev, B, W = self._img_args(input)
+        wd = self._widths(widths, B)
+        tg, tl = ctc.normalize_targets(targets, target_lengths, B)
+        il = ctc.normalize_input_lengths(input_lengths, B)
+        nll = np.empty((B,), dtype=np.float32)
+        _lib.check(_lib.load().hctr_ctc_loss(ctx, _lib.ptr(x), dt, on_dev, _lib.ptr(wd), B, W, _lib.ptr(tg), _lib.ptr(tl),
+                                             _lib.ptr(il), _lib.ptr(nll)), ctx)
+        return ctc.wrap(ctc.reduce(nll, tl, reduction, zero_infinity), input)
+
     # -- precision mode ---------------------------------------------------------------------------
     def set_precision(self, precision):
         """Switch the mode of a loaded model among those whose weight set is resident (all three for a model built

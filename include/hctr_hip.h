@@ -138,6 +138,32 @@ int hctr_beam_fetch_candidates(hctr_ctx* ctx, int64_t* cand_off, int32_t* cand_i
 int hctr_log_softmax(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C,
                      float* out_host);
 
+/* ---- CTC loss on the device: replaces CTCLoss(zero_infinity=True) over preds.log_softmax(2) ------------
+ * main.py:205 (criterion), :379-409 (targets from codec.encode, preds_sizes = [W] * B). Forward only: no gradient.
+ * nll[b] = -log sum over the alignments pi of line b's targets of prod_t softmax(z_t)[pi_t], with blank = class 0:
+ * torch.nn.functional.ctc_loss(log_softmax(z), ..., blank=0, reduction='none', zero_infinity=False). A line with no
+ * alignment (L + number of adjacent equal labels > T) gets +inf; a line with L = 0 gets -sum_t log p_t(blank).
+ *   targets:        int32, the lines' labels back to back (what codec.encode returns), sum(target_lengths) entries;
+ *                   every id in [1, C-1] (C-1 = the "<unknown>" id encode emits), else HCTR_ERR_ARG. Host pointer.
+ *   target_lengths: int32 [B], >= 0; a line's 2L + 1 extended states must fit 4096 (L <= 2047) unless it has no alignment.
+ *   input_lengths:  int32 [B] in [1, W] (steps 0..T-1 of the line count), or NULL = W for every line as main.py has it
+ *                   (the pad columns count, as in the reference).
+ *   nll:            float32 [B], host.
+ * B == 0 is a no-op. hctr_ctc_loss runs the forward of img (arguments as hctr_greedy) and scores its logits on the device,
+ * in internal passes like every other entry point; a line's result depends on its own pixels, W and its targets only.
+ * Precision: mode 0 f16, mode 1 f16x3; mode 2 ("auto") scores EVERY line in f16x3 - its top-1/top-2 margin certificate
+ * bounds argmax flips, not losses - and leaves hctr_last_guard's figures as they were.
+ * Error of a loss from a logit error dz: |dNLL| <= 2 * sum_t max_c |dz_{t,c}| (the gradient of NLL in z_t is softmax
+ * minus the posterior occupancy, of L1 norm <= 2).
+ * hctr_ctc_loss_logits scores caller logits (or log-probs: log_softmax is idempotent) in WBC layout with C classes, host
+ * or device pointer; it needs no weights (a context made for ctc_codec serves). */
+int hctr_ctc_loss(hctr_ctx* ctx, const void* img, int img_dtype, int img_on_device, const int32_t* widths,
+                  int B, int W, const int32_t* targets, const int32_t* target_lengths,
+                  const int32_t* input_lengths, float* nll);
+int hctr_ctc_loss_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C,
+                         const int32_t* targets, const int32_t* target_lengths,
+                         const int32_t* input_lengths, float* nll);
+
 /* ---- host prefix beam search: replaces ctc_codec.__cbs_full__/__cbs_skip__ -------------------
  * utils/ctc_codec.py:124-285 (Beam :288-307), float64 accumulators over float32 log-probs.
  * The language model stays behind callbacks, as in the reference (kenlm / transformer objects are

@@ -1,0 +1,87 @@
+"""Time the CTC loss of the image path against greedy decoding on the same batch (run on the GPU box):
+
+    python tools/bench_ctc.py [--lines 64] [--width 2000] [--steps 5] [--warmup 2] [--precision f16] [--layers]
+
+The batch is BASELINE configs[1]'s shape (64 synthetic lines of 2000 columns, random-head checkpoint) and each line is
+scored against its own greedy text, as a validation loss of decoded output would be. hctr_ctc_loss and hctr_greedy run
+alternately (device-synchronised wall time per call; both are synchronous at return), after warm-up calls of each.
+--layers adds the engine's per-launch device times of one call of each (HIP events; names as rocprofv3 groups them:
+head.linear, ctc_lse, ctc_alpha vs head.linear+argmax). Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lines", type=int, default=64)
+    ap.add_argument("--width", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--precision", default="f16", choices=["f16", "f16x3", "auto"])
+    ap.add_argument("--layers", action="store_true")
+    args = ap.parse_args()
+    import torch
+    import hctr_amd
+    s = hctr_amd.synth
+    C = s.DEFAULT_VOCAB + 2
+    m = hctr_amd.hctr_model(C, precision=args.precision).cuda(0)
+    m.load_state_dict(s.make_state_dict(C, seed=0))
+    imgs = torch.from_numpy(s.make_line_images(args.lines, args.width, seed=2)).cuda(0)
+    labels = m.greedy(imgs)
+    tl = np.array([len(v) for v in labels], np.int32)
+    targets = np.concatenate(labels).astype(np.int32)
+
+    def t_greedy():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        m.greedy(imgs)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def t_ctc():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        nll = m.ctc_loss(imgs, targets, tl, reduction="none", zero_infinity=False)
+        torch.cuda.synchronize()
+        assert torch.isfinite(nll).all()
+        return time.perf_counter() - t0
+
+    for _ in range(args.warmup):
+        t_greedy()
+        t_ctc()
+    g, c = [], []
+    for _ in range(args.steps):
+        g.append(t_greedy())
+        c.append(t_ctc())
+    rec = {"lines": args.lines, "width": args.width, "precision": args.precision,
+           "mean_target_length": float(tl.mean()), "max_target_length": int(tl.max()),
+           "greedy_ms": [round(1e3 * v, 3) for v in g], "ctc_loss_ms": [round(1e3 * v, 3) for v in c],
+           "greedy_ms_median": round(1e3 * float(np.median(g)), 3), "ctc_loss_ms_median": round(1e3 * float(np.median(c)), 3),
+           "ratio_median": round(float(np.median(c) / np.median(g)), 4)}
+    if args.layers:
+        m.set_profiling(True)
+        m.greedy(imgs)
+        gprof = dict(m.last_profile())
+        m.ctc_loss(imgs, targets, tl)
+        prof = dict(m.last_profile())
+        rec["greedy_layers_ms"] = {k: round(v, 4) for k, v in gprof.items() if "head" in k or "ctc" in k}
+        rec["ctc_layers_ms"] = {k: round(v, 4) for k, v in prof.items() if "head" in k or "ctc" in k}
+        rec["greedy_total_device_ms"] = round(sum(gprof.values()), 3)
+        rec["ctc_total_device_ms"] = round(sum(prof.values()), 3)
+        # every launch name whose time differs by more than 0.05 ms between the two calls (trunk layers are shared)
+        rec["layer_delta_ms"] = {k: round(prof.get(k, 0.0) - gprof.get(k, 0.0), 4) for k in set(gprof) | set(prof)
+                                 if abs(prof.get(k, 0.0) - gprof.get(k, 0.0)) > 0.05}
+        m.set_profiling(False)
+    print(json.dumps(rec))
+
+
+if __name__ == "__main__":
+    main()
