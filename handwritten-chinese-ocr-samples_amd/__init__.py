@@ -7,7 +7,7 @@ module at the repository root.
 Public surface = the reference's surface for this path:
   hctr_model   drop-in for models/handwritten_ctr_model.py:156 (engine-backed)
   ctc_codec    drop-in for utils/ctc_codec.py:14                (engine-backed)
-  CTCLoss      drop-in for the criterion of main.py:205           (engine-backed, forward only)
+  CTCLoss      drop-in for the criterion of main.py:205           (engine-backed, with backward())
 plus ``synth`` (deterministic synthetic checkpoints / line images) and ``build`` / ``load_library``.
 """
 from . import preprocess, synth  # noqa: F401

@@ -1086,10 +1086,13 @@ int ctc_prepare(hctr_ctx* c, int B, int W, int C, const int32_t* targets, const 
     return HCTR_OK;
 }
 
-// device scratch of a CTC call: the tables (uploaded), nll[B] and `emis_floats` emission floats
-int ctc_scratch(hctr_ctx* c, const CtcHost& h, size_t emis_floats, CtcLines* m, float** nll, float** emis) {
+// device scratch of a CTC call: the tables (uploaded), nll[B], `emis_floats` emission floats and, for the gradient,
+// `extra_b` more bytes at *extra (256-byte aligned)
+int ctc_scratch(hctr_ctx* c, const CtcHost& h, size_t emis_floats, CtcLines* m, float** nll, float** emis,
+                size_t extra_b = 0, char** extra = nullptr) {
     const size_t tab_b = (h.tab.size() * 4 + 255) & ~(size_t)255, nll_b = ((size_t)h.B * 4 + 255) & ~(size_t)255;
-    const size_t need = tab_b + nll_b + emis_floats * 4;
+    const size_t emis_b = extra_b ? (emis_floats * 4 + 255) & ~(size_t)255 : emis_floats * 4;
+    const size_t need = tab_b + nll_b + emis_b + extra_b;
     if (need > c->ctc_cap) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         if (c->ctc_buf) (void)hipFree(c->ctc_buf);
@@ -1107,6 +1110,7 @@ int ctc_scratch(hctr_ctx* c, const CtcHost& h, size_t emis_floats, CtcLines* m, 
     m->D = h.D;
     *nll = (float*)(c->ctc_buf + tab_b);
     *emis = (float*)(c->ctc_buf + tab_b + nll_b);
+    if (extra) *extra = c->ctc_buf + tab_b + nll_b + emis_b;
     HIP_TRY(c, hipMemcpyAsync(c->ctc_buf, h.tab.data(), h.tab.size() * 4, hipMemcpyHostToDevice, c->stream));
     return HCTR_OK;
 }
@@ -1825,6 +1829,111 @@ int hctr_ctc_loss_logits(hctr_ctx* c, const float* logits_wbc, int on_device, in
             if (e == hipSuccess) e = hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
             if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_loss_logits: %s", hipGetErrorString(e));
         }
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
+        free_pool(tmp);
+        return rc;
+    });
+}
+
+int hctr_ctc_loss_logits_grad(hctr_ctx* c, const float* logits_wbc, int on_device, int W, int B, int C,
+                              const int32_t* targets, const int32_t* target_lengths, const int32_t* input_lengths,
+                              const float* line_weight, float* nll, float* grad_wbc, int grad_on_device) {
+    return guard(c, [&]() -> int {
+        if (!c) return HCTR_ERR_ARG;
+        if (W < 0 || B < 0 || C < 2) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
+        if (B == 0) return HCTR_OK;
+        if (W < 1) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
+        if (!logits_wbc || !grad_wbc) return fail(c, HCTR_ERR_ARG, "NULL pointer");
+        if ((const float*)grad_wbc == logits_wbc) return fail(c, HCTR_ERR_ARG, "grad_wbc aliases the logits");
+        HIP_TRY(c, hipSetDevice(c->device));
+        CtcHost h;
+        TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
+        prof_reset(c);
+        // host side of the gradient's tables: where each line's alpha rows start, and its target positions grouped by
+        // emission slot (a counting sort of the slot table ctc_prepare made)
+        const int32_t *hT = h.tab.data(), *hL = hT + B, *hoff = hT + 2 * (size_t)B;
+        const int32_t* hslot = hT + 4 * (size_t)B + (size_t)B * h.D;
+        const size_t total = h.tab.size() - 4 * (size_t)B - (size_t)B * h.D, D1 = (size_t)h.D + 1;
+        std::vector<int64_t> aoff((size_t)B);
+        std::vector<int32_t> gtab((size_t)B * D1 + total, 0);      // soff[B][D + 1] | pos[sum L]
+        std::vector<float> wt((size_t)B, 1.f);
+        int64_t ast_floats = 0;
+        for (int b = 0; b < B; ++b) {
+            aoff[(size_t)b] = ast_floats;
+            ast_floats += (int64_t)hT[b] * (2 * (int64_t)hL[b] + 1);
+            if (line_weight) wt[(size_t)b] = line_weight[b];
+            if (!hT[b]) continue;
+            int32_t* so = gtab.data() + (size_t)b * D1;
+            int32_t* ps = gtab.data() + (size_t)B * D1 + hoff[b];
+            for (int j = 0; j < hL[b]; ++j) ++so[hslot[hoff[b] + j] + 1];
+            so[0] = so[1] = 0;
+            for (size_t j = 2; j < D1; ++j) so[j] += so[j - 1];     // so[j] = end of slot j - 1 = start of slot j
+            std::vector<int32_t> fill(so, so + D1);
+            for (int j = 0; j < hL[b]; ++j) ps[fill[(size_t)hslot[hoff[b] + j]]++] = j;
+        }
+        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        const size_t BW = (size_t)B * W;
+        const size_t lse_b = al(BW * 8), aoff_b = al((size_t)B * 8), wt_b = al((size_t)B * 4), gtab_b = al(gtab.size() * 4);
+        std::vector<void*> tmp;
+        PoolGuard tmp_guard{tmp};
+        CtcLines m;
+        float *d_nll = nullptr, *emis = nullptr, *up = nullptr, *dgrad = grad_wbc;
+        char* extra = nullptr;
+        TRY(ctc_scratch(c, h, BW * h.D, &m, &d_nll, &emis, lse_b + aoff_b + wt_b + gtab_b + (size_t)ast_floats * 4 + 16,
+                        &extra));
+        double* d_lse = (double*)extra;
+        int64_t* d_aoff = (int64_t*)(extra + lse_b);
+        float* d_wt = (float*)(extra + lse_b + aoff_b);
+        int32_t* d_soff = (int32_t*)(extra + lse_b + aoff_b + wt_b);
+        int32_t* d_pos = d_soff + (size_t)B * D1;
+        float* d_ast = (float*)(extra + lse_b + aoff_b + wt_b + gtab_b);
+        const size_t n = (size_t)W * B * C;
+        const float* dev = logits_wbc;
+        int rc = HCTR_OK;
+        if (!on_device) {
+            rc = dev_alloc(c, tmp, &up, n, false);
+            if (rc == HCTR_OK) {
+                hipError_t e = hipMemcpyAsync(up, logits_wbc, n * 4, hipMemcpyHostToDevice, c->stream);
+                if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "H2D logits: %s", hipGetErrorString(e));
+            }
+            dev = up;
+        }
+        if (rc == HCTR_OK && !grad_on_device) rc = dev_alloc(c, tmp, &dgrad, n, false);
+        if (rc == HCTR_OK) {
+            hipError_t e = hipMemcpyAsync(d_aoff, aoff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess) e = hipMemcpyAsync(d_wt, wt.data(), (size_t)B * 4, hipMemcpyHostToDevice, c->stream);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(d_soff, gtab.data(), gtab.size() * 4, hipMemcpyHostToDevice, c->stream);
+            Prof pf(c);
+            // rows of the WBC tensor are r = t*B + b
+            if (e == hipSuccess) {
+                pf.begin("ctc_rowlse");
+                e = launch_ctc_rowlse(dev, C, 1, B, C, m, 0, B, W, emis, d_lse, c->stream);
+                pf.end();
+            }
+            if (e == hipSuccess) {
+                pf.begin("ctc_alpha_store");
+                e = launch_ctc_alpha_beta(emis, m, B, W, h.max_states, d_nll, d_aoff, d_ast, false, c->stream);
+                pf.end();
+            }
+            if (e == hipSuccess) {
+                pf.begin("ctc_beta");
+                e = launch_ctc_alpha_beta(emis, m, B, W, h.max_states, d_nll, d_aoff, d_ast, true, c->stream);
+                pf.end();
+            }
+            if (e == hipSuccess) {
+                pf.begin("ctc_grad_rows");
+                e = launch_ctc_grad_rows(dev, C, B, W, m, d_lse, d_nll, d_wt, d_aoff, d_ast, d_soff, d_pos, dgrad,
+                                         c->stream);
+                pf.end();
+            }
+            if (e == hipSuccess && nll) e = hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
+            if (e == hipSuccess && !grad_on_device)
+                e = hipMemcpyAsync(grad_wbc, dgrad, n * 4, hipMemcpyDeviceToHost, c->stream);
+            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_loss_logits_grad: %s", hipGetErrorString(e));
+        }
+        // the host tables above are pageable: their copies were staged before hipMemcpyAsync returned
         hipError_t e = hipStreamSynchronize(c->stream);
         if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
         free_pool(tmp);

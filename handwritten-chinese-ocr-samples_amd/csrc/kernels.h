@@ -210,6 +210,21 @@ hipError_t launch_ctc_lse(const float* x, int64_t ld, int64_t sb, int64_t st, in
 // the lines with T > 0 (<= kCtcMaxStates)
 hipError_t launch_ctc_alpha(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states, float* nll,
                             hipStream_t s);
+// gradient of the per-line loss in caller logits (hctr_ctc_loss_logits_grad), whole batch (b0 = 0):
+// launch_ctc_rowlse = launch_ctc_lse that also keeps lse[b*W + t] (float64) of the rows t < T[b];
+// launch_ctc_alpha_beta, beta = false: the alpha recursion storing its rows at ast[aoff[b] + t*S_b + s] (aoff[b] = sum
+//   of T*S of the lines before b), nll as launch_ctc_alpha writes it; then beta = true: the beta recursion, which
+//   overwrites the rows with y = alpha + nll + (beta before its emission), the log of each state's posterior share;
+// launch_ctc_grad_rows: grad[t][b][c] = wt[b] * (softmax(z_t)[c] - gamma_t(c)) for t < T[b], zeros for t >= T[b] and for
+//   lines with nll = +inf. soff[b][D + 1], pos[off[b] + ...]: target positions of line b grouped by emission slot
+//   (slot j's are pos[off[b] + soff[b][j] .. off[b] + soff[b][j+1]), j >= 1). x and grad are contiguous [W][B][C].
+hipError_t launch_ctc_rowlse(const float* x, int64_t ld, int64_t sb, int64_t st, int C, const CtcLines& m, int b0, int nb,
+                             int W, float* emis, double* lse, hipStream_t s);
+hipError_t launch_ctc_alpha_beta(const float* emis, const CtcLines& m, int B, int W, int max_states, float* nll,
+                                 const int64_t* aoff, float* ast, bool beta, hipStream_t s);
+hipError_t launch_ctc_grad_rows(const float* x, int C, int B, int W, const CtcLines& m, const double* lse,
+                                const float* nll, const float* wt, const int64_t* aoff, const float* ast,
+                                const int32_t* soff, const int32_t* pos, float* grad, hipStream_t s);
 
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {

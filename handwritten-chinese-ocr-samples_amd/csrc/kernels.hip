@@ -3225,16 +3225,18 @@ hipError_t launch_beam_candidates(const int32_t* emit_cnt, const int32_t* emit_l
 
 
 // -------------------------------------------------------------------------------------------
-// CTC loss: torch.nn.CTCLoss over preds.log_softmax(2) (main.py:205,379-409), forward only.
+// CTC loss: torch.nn.CTCLoss over preds.log_softmax(2) (main.py:205,379-409); its gradient follows further down.
 // Emissions: for row (line b, step t) the log-probs of the line's distinct classes D_b (slot 0 = blank) at
 // emis[(b*W + t) * D + j]; the alpha recursion reads nothing else. See CtcLines in kernels.h.
 // -------------------------------------------------------------------------------------------
 
 // One 256-thread block per (t, line): log-sum-exp of the row (float32 max, float64 exp-sum and log) in one pass over it,
-// then the slots of D_b as float32(z - lse). Rows t >= T_b are not read.
-__global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ x, int64_t ld, int64_t sb, int64_t st,
-                                                      int C, const CtcLines m, int b0, int W,
-                                                      float* __restrict__ emis) {
+// then the slots of D_b as float32(z - lse). Rows t >= T_b are not read. KEEP (the gradient's pass) also keeps the row's
+// log-sum-exp, lse_out[b*W + t]; the arithmetic is the same, so emis is bit-identical either way.
+template <bool KEEP>
+__device__ __forceinline__ void ctc_lse_row(const float* __restrict__ x, int64_t ld, int64_t sb, int64_t st, int C,
+                                            const CtcLines& m, int b0, int W, float* __restrict__ emis,
+                                            double* __restrict__ lse_out) {
     __shared__ float rv[4];
     __shared__ double rd[4];
     const int64_t r = blockIdx.x;                  // b*W + t
@@ -3273,6 +3275,19 @@ __global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ 
     const int32_t* cls = m.cls + (int64_t)gb * m.D;
     float* e = emis + ((int64_t)b * W + t) * m.D;
     for (int j = tid; j < nd; j += 256) e[j] = (float)((double)p[cls[j]] - lse);
+    if (KEEP && tid == 0) lse_out[r] = lse;
+}
+
+__global__ __launch_bounds__(256) void ctc_lse_kernel(const float* __restrict__ x, int64_t ld, int64_t sb, int64_t st,
+                                                      int C, const CtcLines m, int b0, int W,
+                                                      float* __restrict__ emis) {
+    ctc_lse_row<false>(x, ld, sb, st, C, m, b0, W, emis, nullptr);
+}
+
+__global__ __launch_bounds__(256) void ctc_rowlse_kernel(const float* __restrict__ x, int64_t ld, int64_t sb, int64_t st,
+                                                         int C, const CtcLines m, int b0, int W,
+                                                         float* __restrict__ emis, double* __restrict__ lse_out) {
+    ctc_lse_row<true>(x, ld, sb, st, C, m, b0, W, emis, lse_out);
 }
 
 __device__ __forceinline__ float ctc_logadd(float a, float b) {
@@ -3289,9 +3304,12 @@ __device__ __forceinline__ float ctc_logadd(float a, float b) {
 // PF times). alpha is float32; the three-way log-add is max + log(1 + exp(mid - max) + exp(min - max)) (torch's CPU
 // kernel's, with the max term's exp(0) = 1 folded); the skip transition s-2 -> s only where l_s != l_{s-2}.
 // nll[b0 + b] = -logaddexp(alpha_T[S-1], alpha_T[S-2]) (-alpha_T[0] for L = 0), +inf for a line marked T = 0.
-template <int NS, int PF, int NW>
-__global__ __launch_bounds__(64 * NW) void ctc_alpha_kernel(const float* __restrict__ emis, const CtcLines m, int b0,
-                                                             int W, float* __restrict__ nll) {
+// STORE (the gradient's pass) also writes every row of alpha, ast[aoff[gb] + t*S + s] for s < S; the recursion's
+// arithmetic is the same, so nll is bit-identical either way.
+template <int NS, int PF, int NW, bool STORE>
+__device__ __forceinline__ void ctc_alpha_line(const float* __restrict__ emis, const CtcLines& m, int b0, int W,
+                                               float* __restrict__ nll, const int64_t* __restrict__ aoff,
+                                               float* __restrict__ ast) {
     static_assert(NW == 1 || NS >= 2, "a wave boundary hands over two states from one lane");
     __shared__ float xb[2][NW][2];                 // [step parity][wave] = {state wave_end-1, state wave_end-2}
     __shared__ float fin[2];
@@ -3319,6 +3337,16 @@ __global__ __launch_bounds__(64 * NW) void ctc_alpha_kernel(const float* __restr
         const int s = tid * NS + i;
         a[i] = (s == 0 || (s == 1 && S > 1)) ? base[slot[i]] : -INFINITY;
     }
+    float* arow = STORE ? ast + aoff[gb] + tid * NS : nullptr;
+    auto keep = [&]() {
+        if (STORE) {
+#pragma unroll
+            for (int i = 0; i < NS; ++i)
+                if (tid * NS + i < S) arow[i] = a[i];
+            arow += S;
+        }
+    };
+    keep();
     auto publish = [&](int parity) {
         if (NW > 1) {
             if (lane == 63) {
@@ -3359,6 +3387,7 @@ __global__ __launch_bounds__(64 * NW) void ctc_alpha_kernel(const float* __restr
                     const float v = mx + __logf(1.f + __expf(md - mx) + __expf(mn - mx));
                     a[i] = (mx == -INFINITY ? -INFINITY : v) + e[k][i];
                 }
+                keep();
                 publish(t & 1);
             }
             const float* r = base + (int64_t)min(t + PF, T - 1) * D;   // refill the slot just used
@@ -3374,6 +3403,20 @@ __global__ __launch_bounds__(64 * NW) void ctc_alpha_kernel(const float* __restr
     }
     __syncthreads();
     if (tid == 0) nll[gb] = L == 0 ? -fin[0] : -ctc_logadd(fin[0], fin[1]);
+}
+
+template <int NS, int PF, int NW>
+__global__ __launch_bounds__(64 * NW) void ctc_alpha_kernel(const float* __restrict__ emis, const CtcLines m, int b0,
+                                                             int W, float* __restrict__ nll) {
+    ctc_alpha_line<NS, PF, NW, false>(emis, m, b0, W, nll, nullptr, nullptr);
+}
+
+template <int NS, int PF, int NW>
+__global__ __launch_bounds__(64 * NW) void ctc_alpha_store_kernel(const float* __restrict__ emis, const CtcLines m, int b0,
+                                                                   int W, float* __restrict__ nll,
+                                                                   const int64_t* __restrict__ aoff,
+                                                                   float* __restrict__ ast) {
+    ctc_alpha_line<NS, PF, NW, true>(emis, m, b0, W, nll, aoff, ast);
 }
 
 hipError_t launch_ctc_lse(const float* x, int64_t ld, int64_t sb, int64_t st, int C, const CtcLines& m, int b0, int nb,
@@ -3402,6 +3445,220 @@ hipError_t launch_ctc_alpha(const float* emis, const CtcLines& m, int b0, int nb
     CTC_ALPHA(4, 2, 16)
 #undef CTC_ALPHA
     return hipErrorInvalidValue;
+}
+
+// -------------------------------------------------------------------------------------------
+// CTC loss gradient with respect to caller logits: w_b * (softmax(z_t) - gamma_t), gamma the posterior occupancy.
+// ctc_rowlse_kernel keeps each row's log-sum-exp, ctc_alpha_store_kernel keeps every alpha row; ctc_beta_kernel runs
+// the backward recursion and overwrites the alpha rows with the states' log-occupancies; ctc_grad_rows_kernel writes
+// the gradient rows.
+// -------------------------------------------------------------------------------------------
+
+// The mirror image of ctc_alpha_line: same lane / wave state layout, t running down from T-1, the two states above a
+// lane's own come from the right neighbour over __shfl_down and across a wave boundary from the double-buffered LDS
+// slot. a[] holds beta_{t+1} (torch's convention: the emission at t+1 included); step t forms
+// bp(s) = logsumexp(beta_{t+1}(s), beta_{t+1}(s+1), beta_{t+1}(s+2) if l_{s+2} != l_s), overwrites the stored
+// alpha_t(s) with y_t(s) = alpha_t(s) + nll + bp(s) (the log of the state's share of the posterior: alpha_t * beta_t
+// has the emission twice, alpha_t * bp once), and continues with beta_t = bp + lp_t. The virtual row beta_T = (0 at
+// state S-1, -inf elsewhere) makes step T-1 like every other. The alpha rows and the emissions of the next PF steps
+// are in flight while a step is computed. Lines without an alignment (T = 0) and lines whose loss is +inf are left
+// alone: the row kernel writes their zeros.
+template <int NS, int PF, int NW>
+__global__ __launch_bounds__(64 * NW) void ctc_beta_kernel(const float* __restrict__ emis, const CtcLines m, int W,
+                                                            const float* __restrict__ nll,
+                                                            const int64_t* __restrict__ aoff, float* __restrict__ ast) {
+    static_assert(NW == 1 || NS >= 2, "a wave boundary hands over two states from one lane");
+    __shared__ float xb[2][NW][2];                 // [step parity][wave] = {state wave_begin, state wave_begin+1}
+    const int gb = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int T = m.T[gb], L = m.L[gb], S = 2 * L + 1;
+    if (T == 0) return;                            // (block-uniform)
+    const float nl = nll[gb];
+    if (nl == INFINITY) return;                    // (block-uniform)
+    const int32_t* ts = m.slot + m.off[gb];
+    int slot[NS];
+    bool skip[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int s = tid * NS + i;
+        const bool lab = (s & 1) && s < S;
+        slot[i] = lab ? ts[s >> 1] : 0;
+        skip[i] = lab && s + 2 < S && ts[(s >> 1) + 1] != ts[s >> 1];
+    }
+    const int D = m.D;
+    const float* base = emis + (int64_t)gb * W * D;
+    float* abase = ast + aoff[gb];
+    int sc[NS];                                    // the lane's states, clamped into the row for the loads
+    float a[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int s = tid * NS + i;
+        sc[i] = min(s, S - 1);
+        a[i] = s == S - 1 ? 0.f : -INFINITY;
+    }
+    auto publish = [&](int parity) {
+        if (NW > 1) {
+            if (lane == 0) {
+                xb[parity][wv][0] = a[0];
+                xb[parity][wv][1] = a[NS >= 2 ? 1 : 0];
+            }
+            __syncthreads();
+        }
+    };
+    publish(0);
+    float e[PF][NS], al[PF][NS];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+        const int row = max(T - 1 - k, 0);
+        const float* r = base + (int64_t)row * D;
+        const float* ar = abase + (int64_t)row * S;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) {
+            e[k][i] = r[slot[i]];
+            al[k][i] = ar[sc[i]];
+        }
+    }
+    int par = 0;
+    for (int t0 = T - 1; t0 >= 0; t0 -= PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+            const int t = t0 - k;
+            if (t >= 0) {                          // (block-uniform)
+                float q1 = __shfl_down(a[0], 1);
+                float q2 = NS >= 2 ? __shfl_down(a[NS >= 2 ? 1 : 0], 1) : __shfl_down(a[0], 2);
+                if (lane == 63) {
+                    q1 = wv < NW - 1 ? xb[par][wv < NW - 1 ? wv + 1 : 0][0] : -INFINITY;
+                    q2 = wv < NW - 1 ? xb[par][wv < NW - 1 ? wv + 1 : 0][1] : -INFINITY;
+                }
+                if (NS == 1 && lane == 62) q2 = -INFINITY;     // (NS == 1 only with NW == 1)
+                float* yr = abase + (int64_t)t * S + tid * NS;
+#pragma unroll
+                for (int i = 0; i < NS; ++i) {         // ascending: a[i+1], a[i+2] still hold step t+1
+                    const float la1 = a[i];
+                    const float la2 = i + 1 < NS ? a[i + 1 < NS ? i + 1 : 0] : q1;
+                    const float la3 = skip[i] ? (i + 2 < NS ? a[i + 2 < NS ? i + 2 : 0] : (i + 2 == NS ? q1 : q2))
+                                              : -INFINITY;
+                    const float mx = fmaxf(la1, fmaxf(la2, la3));
+                    const float mn = fminf(la1, fminf(la2, la3));
+                    const float md = __builtin_amdgcn_fmed3f(la1, la2, la3);
+                    const float v = mx + __logf(1.f + __expf(md - mx) + __expf(mn - mx));
+                    const float bp = mx == -INFINITY ? -INFINITY : v;
+                    if (tid * NS + i < S) yr[i] = (al[k][i] + nl) + bp;
+                    a[i] = bp + e[k][i];
+                }
+                par ^= 1;
+                publish(par);
+            }
+            const int row = max(t - PF, 0);        // refill the slot just used
+            const float* r = base + (int64_t)row * D;
+            const float* ar = abase + (int64_t)row * S;
+#pragma unroll
+            for (int i = 0; i < NS; ++i) {
+                e[k][i] = r[slot[i]];
+                al[k][i] = ar[sc[i]];
+            }
+        }
+    }
+}
+
+// One 256-thread block per (line, step), like ctc_lse: the row of y (S log-occupancies) gives the states' shares
+// q_s = exp(y_s); they are normalised by their own sum over the row (exp(-nll) * exp(nll) = 1 in exact arithmetic; the
+// division takes out the rounding drift that alpha_t and beta_t have in common, so gamma sums to 1 to float32 rounding
+// at every step), the even states are the blank's share, and the share of class slot j is summed over the target
+// positions pos[soff[j] .. soff[j+1]) that carry it, in a fixed order (no atomics: the result does not depend on
+// scheduling). The logits row is read once, eight loads in flight: grad = w * exp(z - lse) for all C classes, then the
+// line's <= D classes again as w * (exp(z - lse) - gamma). Rows t >= T and the rows of lines whose loss is +inf are
+// zeros.
+__global__ __launch_bounds__(256) void ctc_grad_rows_kernel(const float* __restrict__ x, int C, int B, int W,
+                                                            const CtcLines m, const double* __restrict__ lse,
+                                                            const float* __restrict__ nll, const float* __restrict__ wt,
+                                                            const int64_t* __restrict__ aoff,
+                                                            const float* __restrict__ ast,
+                                                            const int32_t* __restrict__ soff,
+                                                            const int32_t* __restrict__ pos, float* __restrict__ grad) {
+    __shared__ double rd[4];
+    const int64_t r = blockIdx.x;                  // b*W + t
+    const int b = (int)(r / W), t = (int)(r % W), tid = threadIdx.x;
+    const float* p = x + ((int64_t)t * B + b) * C;
+    float* o = grad + ((int64_t)t * B + b) * C;
+    const int T = m.T[b];
+    if (t >= T || nll[b] == INFINITY) {            // (block-uniform)
+        for (int c = tid; c < C; c += 256) o[c] = 0.f;
+        return;
+    }
+    const int S = 2 * m.L[b] + 1;
+    const float* y = ast + aoff[b] + (int64_t)t * S;
+    double qe = 0.0, qo = 0.0;
+    for (int s = 2 * tid; s < S; s += 512) {
+        qe += (double)expf(y[s]);
+        if (s + 1 < S) qo += (double)expf(y[s + 1]);
+    }
+    const double blank = block_sum_d(qe, rd);
+    const double Z = blank + block_sum_d(qo, rd);
+    const double l = lse[r];
+    const float w = wt[b];
+    for (int c0 = tid; c0 < C; c0 += 8 * 256) {
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = c0 + k * 256 < C ? p[c0 + k * 256] : 0.f;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (c0 + k * 256 < C) o[c0 + k * 256] = w * expf((float)((double)v[k] - l));
+    }
+    __syncthreads();                               // the line's classes are written a second time, by other threads
+    const int nd = m.nd[b];
+    const int32_t* cls = m.cls + (int64_t)b * m.D;
+    const int32_t* so = soff + (int64_t)b * (m.D + 1);
+    const int32_t* ps = pos + m.off[b];
+    for (int j = tid; j < nd; j += 256) {
+        double g = blank;
+        if (j > 0) {
+            g = 0.0;
+            for (int k = so[j]; k < so[j + 1]; ++k) g += (double)expf(y[2 * ps[k] + 1]);
+        }
+        const int c = cls[j];
+        o[c] = w * (expf((float)((double)p[c] - l)) - (float)(g / Z));
+    }
+}
+
+hipError_t launch_ctc_rowlse(const float* x, int64_t ld, int64_t sb, int64_t st, int C, const CtcLines& m, int b0, int nb,
+                             int W, float* emis, double* lse, hipStream_t s) {
+    if (nb <= 0 || W <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ctc_rowlse_kernel, dim3((unsigned)((int64_t)nb * W)), dim3(256), 0, s, x, ld, sb, st, C, m, b0, W,
+                       emis, lse);
+    return hipGetLastError();
+}
+
+hipError_t launch_ctc_alpha_beta(const float* emis, const CtcLines& m, int B, int W, int max_states, float* nll,
+                                 const int64_t* aoff, float* ast, bool beta, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+#define CTC_AB(NS, PF, NW)                                                                                              \
+    if (max_states <= 64 * NS * NW) {                                                                                   \
+        if (beta)                                                                                                       \
+            hipLaunchKernelGGL((ctc_beta_kernel<NS, PF, NW>), dim3((unsigned)B), dim3(64 * NW), 0, s, emis, m, W, nll,  \
+                               aoff, ast);                                                                              \
+        else                                                                                                            \
+            hipLaunchKernelGGL((ctc_alpha_store_kernel<NS, PF, NW>), dim3((unsigned)B), dim3(64 * NW), 0, s, emis, m, 0, \
+                               W, nll, aoff, ast);                                                                      \
+        return hipGetLastError();                                                                                       \
+    }
+    CTC_AB(1, 4, 1)                                // the instances of launch_ctc_alpha
+    CTC_AB(2, 4, 1)
+    CTC_AB(2, 4, 2)
+    CTC_AB(2, 4, 4)
+    CTC_AB(2, 4, 8)
+    CTC_AB(2, 4, 16)
+    CTC_AB(4, 2, 16)
+#undef CTC_AB
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_ctc_grad_rows(const float* x, int C, int B, int W, const CtcLines& m, const double* lse,
+                                const float* nll, const float* wt, const int64_t* aoff, const float* ast,
+                                const int32_t* soff, const int32_t* pos, float* grad, hipStream_t s) {
+    if (B <= 0 || W <= 0) return hipSuccess;
+    hipLaunchKernelGGL(ctc_grad_rows_kernel, dim3((unsigned)((int64_t)B * W)), dim3(256), 0, s, x, C, B, W, m, lse, nll, wt,
+                       aoff, ast, soff, pos, grad);
+    return hipGetLastError();
 }
 
 }  // namespace hctr

@@ -1,10 +1,11 @@
 """CTC loss on the engine: the criterion of the reference's evaluation stack (``CTCLoss(zero_infinity=True)`` over
-``preds.log_softmax(2)``, main.py:205,379-409), forward only.
+``preds.log_softmax(2)``, main.py:205,379-409), and its gradient in caller logits (``loss.backward()``, main.py:426).
 
 ``CTCLoss`` is the drop-in for that criterion on caller logits (``criterion(preds, targets, input_lengths,
-target_lengths)``); ``hctr_model.ctc_loss`` scores line images without the logits ever leaving the device. Both run the
-C ABI's ``hctr_ctc_loss*`` (include/hctr_hip.h); target normalisation and the reductions are the host-side helpers below,
-with the semantics of ``torch.nn.CTCLoss``.
+target_lengths)``), differentiable when its input requires a gradient; ``hctr_model.ctc_loss`` scores line images
+without the logits ever leaving the device (forward only: the engine's trunk has no backward pass). All run the C ABI's
+``hctr_ctc_loss*`` (include/hctr_hip.h); target normalisation, the reductions and the per-line gradient weights are the
+host-side helpers below, with the semantics of ``torch.nn.CTCLoss``.
 """
 import ctypes
 
@@ -82,6 +83,46 @@ def reduce(nll, target_lengths, reduction="mean", zero_infinity=False):
     return np.float32((loss / tl).mean(dtype=np.float32))
 
 
+def line_weights(target_lengths, reduction="mean", grad_output=None, nll=None, zero_infinity=False):
+    """(w float32 [B], nan bool [B]): d(reduced loss)/d(nll_b) times the incoming gradient, i.e. the per-line weight
+    hctr_ctc_loss_logits_grad takes, with torch.nn.CTCLoss's semantics: 'mean' gives line b ``g / (B * max(L_b, 1))``,
+    'sum' ``g``, 'none' ``g_b`` (``grad_output`` None = 1). A line whose ``nll`` is +inf has an all-zero gradient under
+    ``zero_infinity`` (weight 0; the engine writes its zeros whatever the weight) and otherwise the NaN rows torch's CPU
+    kernel leaves there: ``nan[b]`` marks it, for ``fill_nan_rows``."""
+    if reduction not in _REDUCTIONS:
+        raise ValueError("reduction must be one of %s" % (_REDUCTIONS,))
+    tl = np.asarray(target_lengths).reshape(-1)
+    B = tl.size
+    if grad_output is None:
+        g = np.ones((B,) if reduction == "none" else (), np.float64)
+    else:
+        g = np.asarray(grad_output, dtype=np.float64)
+    if reduction == "none":
+        if g.shape != (B,):
+            raise ValueError("grad_output of reduction 'none' must have %d entries, got shape %s" % (B, g.shape))
+        w = g.copy()
+    elif g.size != 1:
+        raise ValueError("grad_output of reduction %r must be a scalar" % reduction)
+    elif reduction == "sum":
+        w = np.full((B,), float(g.reshape(())), np.float64)
+    else:
+        w = float(g.reshape(())) / (B * np.maximum(tl.astype(np.float64), 1.0))
+    inf = np.zeros((B,), bool) if nll is None else np.isposinf(np.asarray(nll, dtype=np.float64).reshape(-1))
+    if inf.shape != (B,):
+        raise ValueError("nll must have %d entries" % B)
+    w[inf] = 0.0
+    return w.astype(np.float32), inf & (not zero_infinity)
+
+
+def fill_nan_rows(grad, nan, input_lengths):
+    """torch's CPU kernel on a line without an alignment and zero_infinity off: the line's rows t < input_length are
+    NaN (rows past it stay zero). ``grad``: [T, B, C] numpy array or torch tensor, changed in place."""
+    for b in np.flatnonzero(nan):
+        T = grad.shape[0] if input_lengths is None else int(input_lengths[b])
+        grad[:T, int(b)] = float("nan")
+    return grad
+
+
 def wrap(value, like):
     """numpy result -> a float32 torch tensor on `like`'s device when `like` is a torch tensor."""
     if not _is_torch(like):
@@ -103,10 +144,83 @@ def loss_logits(ctx, logits, on_dev, targets, target_lengths, input_lengths):
     return nll
 
 
+def loss_grad_logits(ctx, logits, on_dev, targets, target_lengths, input_lengths, weights, grad=None):
+    """(per-line NLL float32 [B], gradient) of caller logits / log-probs in WBC layout (hctr_ctc_loss_logits_grad):
+    grad[t, b] = weights[b] * (softmax(z[t, b]) - gamma[t, b]); ``weights`` None = 1 for every line. The gradient is a
+    float32 tensor on the logits' device when they are a CUDA tensor, a numpy array otherwise (``grad``: a buffer of
+    that kind to write into)."""
+    W, B, C = (int(v) for v in logits.shape)
+    tg, tl = normalize_targets(targets, target_lengths, B)
+    il = normalize_input_lengths(input_lengths, B)
+    nll = np.empty((B,), dtype=np.float32)
+    if grad is None:
+        if on_dev:
+            import torch
+            grad = torch.empty((W, B, C), dtype=torch.float32, device=logits.device)
+        else:
+            grad = np.empty((W, B, C), dtype=np.float32)
+    if B == 0 or W == 0:
+        return nll, grad
+    wt = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    if wt is not None and wt.shape != (B,):
+        raise ValueError("weights must have %d entries, got %d" % (B, wt.size))
+    _lib.check(_lib.load().hctr_ctc_loss_logits_grad(ctx, _lib.ptr(logits), on_dev, W, B, C, _lib.ptr(tg), _lib.ptr(tl),
+                                                     _lib.ptr(il), _lib.ptr(wt), _lib.ptr(nll), _lib.ptr(grad),
+                                                     on_dev), ctx)
+    return nll, grad
+
+
+_FN = None
+
+
+def _autograd_fn():
+    """The torch.autograd.Function behind CTCLoss on an input that requires a gradient (made on first use: the package
+    imports without torch). forward is the forward-only entry, exactly what an input without requires_grad gets;
+    backward runs the gradient entry once, with the final per-line weights, so nothing of the input's size is kept
+    between the two and no pass over the gradient is needed to scale it."""
+    global _FN
+    if _FN is not None:
+        return _FN
+    import torch
+
+    class _CtcFn(torch.autograd.Function):
+        @staticmethod
+        def forward(fn_ctx, log_probs, crit, targets, input_lengths, target_lengths):
+            from .codec import ctc_codec
+            logits, on_dev = ctc_codec._as_logits(log_probs)
+            B = int(logits.shape[1])
+            tg, tl = normalize_targets(targets, target_lengths, B)
+            il = normalize_input_lengths(input_lengths, B)
+            nll = loss_logits(crit._context(), logits, on_dev, tg, tl, il)
+            fn_ctx.save_for_backward(log_probs)
+            fn_ctx.hctr = (crit, tg, tl, il, nll)
+            return wrap(reduce(nll, tl, crit.reduction, crit.zero_infinity), log_probs)
+
+        @staticmethod
+        @torch.autograd.function.once_differentiable
+        def backward(fn_ctx, grad_output):
+            from .codec import ctc_codec
+            (log_probs,) = fn_ctx.saved_tensors
+            crit, tg, tl, il, nll = fn_ctx.hctr
+            w, nan = line_weights(tl, crit.reduction, grad_output.detach().double().cpu().numpy(), nll,
+                                  crit.zero_infinity)
+            logits, on_dev = ctc_codec._as_logits(log_probs)
+            _, grad = loss_grad_logits(crit._context(), logits, on_dev, tg, tl, il, w)
+            grad = torch.as_tensor(grad, device=log_probs.device)
+            fill_nan_rows(grad, nan, il)
+            return grad.to(log_probs.dtype).reshape(log_probs.shape), None, None, None, None
+
+    _FN = _CtcFn
+    return _FN
+
+
 class CTCLoss(object):
     """Drop-in for the reference's criterion ``CTCLoss(zero_infinity=True)`` (main.py:205) on the engine:
     ``criterion(log_probs_or_logits, targets, input_lengths, target_lengths)`` with ``[T, B, C]`` input - raw logits or
-    log-probs give the same result (log_softmax is idempotent). Forward only (no gradient). Bind it to a GPU with
+    log-probs give the same result (log_softmax is idempotent). A torch input that requires a gradient gets a loss with
+    a ``grad_fn``: ``loss.backward()`` deposits ``w_b * (softmax - posterior occupancy)`` in the input's ``.grad``, the
+    derivative in raw logits and, for log-probs, what torch's own ctc_loss hands to the ``log_softmax`` before it (which
+    passes it through unchanged). ``loss_and_grad`` is the same without autograd. Bind it to a GPU with
     ``.cuda(device)``, or share an hctr_model's engine context with ``.attach(model)``. Only blank=0 is supported."""
 
     def __init__(self, blank=0, reduction="mean", zero_infinity=False):
@@ -165,9 +279,37 @@ class CTCLoss(object):
 
     def forward(self, log_probs, targets, input_lengths, target_lengths):
         from .codec import ctc_codec
+        if _is_torch(log_probs) and log_probs.requires_grad:
+            import torch
+            if torch.is_grad_enabled():
+                return _autograd_fn().apply(log_probs, self, targets, input_lengths, target_lengths)
         logits, on_dev = ctc_codec._as_logits(log_probs)
         nll = loss_logits(self._context(), logits, on_dev, targets, target_lengths, input_lengths)
         tl = normalize_targets(targets, target_lengths, int(logits.shape[1]))[1]
         return wrap(reduce(nll, tl, self.reduction, self.zero_infinity), log_probs)
 
     __call__ = forward
+
+    def loss_and_grad(self, log_probs, targets, input_lengths, target_lengths):
+        """(loss, grad) without autograd, for numpy input and torch input alike: ``loss`` as ``forward`` returns it,
+        ``grad`` = d(reduced loss)/d(input) (for 'none': of the sum of the lines' losses), of the input's shape, kind,
+        device and dtype. With ``zero_infinity=False`` a line without an alignment has NaN rows, as in torch."""
+        from .codec import ctc_codec
+        logits, on_dev = ctc_codec._as_logits(log_probs)
+        B = int(logits.shape[1])
+        tg, tl = normalize_targets(targets, target_lengths, B)
+        il = normalize_input_lengths(input_lengths, B)
+        ctx = self._context()
+        # the weights need the lines' losses only where one is +inf and zero_infinity is off: the engine writes zeros
+        # for such a line, and its rows are filled afterwards
+        w, _ = line_weights(tl, self.reduction, None, None, self.zero_infinity)
+        nll, grad = loss_grad_logits(ctx, logits, on_dev, tg, tl, il, w)
+        nan = line_weights(tl, self.reduction, None, nll, self.zero_infinity)[1]
+        fill_nan_rows(grad, nan, il)
+        loss = wrap(reduce(nll, tl, self.reduction, self.zero_infinity), log_probs)
+        if _is_torch(log_probs):
+            import torch
+            grad = torch.as_tensor(grad, device=log_probs.device).to(log_probs.dtype)
+        elif np.issubdtype(np.asarray(log_probs).dtype, np.floating):
+            grad = grad.astype(np.asarray(log_probs).dtype, copy=False)
+        return loss, grad

@@ -245,7 +245,7 @@ class hctr_model(object):
                  zero_infinity=True):
         """CTC loss of line images against transcriptions, the logits never leaving the device: the reference's
         ``CTCLoss(zero_infinity=True)(model(input).log_softmax(2), targets, input_lengths, target_lengths)``
-        (main.py:205,379-409), forward only. ``targets``: 1-D concatenated (``codec.encode``) or 2-D padded ``[B, S]``;
+        (main.py:205,379-409), forward only (``CTCLoss`` on logits has the gradient). ``targets``: 1-D concatenated (``codec.encode``) or 2-D padded ``[B, S]``;
         ``input_lengths`` None = W for every line (main.py's preds_sizes). ``reduction`` / ``zero_infinity`` as
         torch.nn.CTCLoss. Returns a float32 torch tensor when ``input`` is one, numpy otherwise. In "auto" precision every
         line is scored in f16x3 (include/hctr_hip.h ``hctr_ctc_loss``)."""

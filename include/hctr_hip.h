@@ -139,7 +139,7 @@ int hctr_log_softmax(hctr_ctx* ctx, const float* logits_wbc, int on_device, int 
                      float* out_host);
 
 /* ---- CTC loss on the device: replaces CTCLoss(zero_infinity=True) over preds.log_softmax(2) ------------
- * main.py:205 (criterion), :379-409 (targets from codec.encode, preds_sizes = [W] * B). Forward only: no gradient.
+ * main.py:205 (criterion), :379-409 (targets from codec.encode, preds_sizes = [W] * B). The gradient: hctr_ctc_loss_logits_grad below.
  * nll[b] = -log sum over the alignments pi of line b's targets of prod_t softmax(z_t)[pi_t], with blank = class 0:
  * torch.nn.functional.ctc_loss(log_softmax(z), ..., blank=0, reduction='none', zero_infinity=False). A line with no
  * alignment (L + number of adjacent equal labels > T) gets +inf; a line with L = 0 gets -sum_t log p_t(blank).
@@ -163,6 +163,32 @@ int hctr_ctc_loss(hctr_ctx* ctx, const void* img, int img_dtype, int img_on_devi
 int hctr_ctc_loss_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C,
                          const int32_t* targets, const int32_t* target_lengths,
                          const int32_t* input_lengths, float* nll);
+
+/* ---- gradient of the CTC loss in caller logits: what scaler.scale(loss).backward() needs (main.py:426) ----
+ * Arguments, checks, error codes and the L <= 2047 limit as hctr_ctc_loss_logits. For line b with T = input_lengths[b]:
+ *   grad[t][b][c] = line_weight[b] * (softmax(z_t)[c] - gamma_t(c))   for t < T
+ *   grad[t][b][c] = 0                                                  for t >= T, and for every t of a line whose loss is
+ *                                                                      +inf, whatever its weight (zero_infinity=True)
+ * gamma_t(c) = sum over the extended-target states s of class c of exp(alpha_t(s) + beta_t(s) - lp_t(c) + nll_b), the
+ * posterior occupancy (sum_c gamma_t(c) = 1); classes that are neither the blank nor a target of the line get
+ * line_weight[b] * softmax exactly. Every element of grad_wbc is written (it need not be cleared).
+ * With respect to what: for raw logits z this is the exact derivative d(sum_b line_weight[b] * nll_b) / dz. For log-probs
+ * it is what torch.nn.functional.ctc_loss returns for its log_probs argument (softmax - gamma, not -gamma); its rows sum
+ * to zero, so the log_softmax backward that follows in the caller's graph passes it through unchanged - one definition
+ * serves both kinds of input.
+ *   line_weight: float32 [B], host; NULL = 1 for every line.
+ *   nll:         float32 [B], host, or NULL; bit-identical to hctr_ctc_loss_logits' for the same arguments.
+ *   grad_wbc:    float32 [W][B][C], host (grad_on_device = 0) or device pointer; must not alias the logits.
+ * Device scratch (the context's grow-only CTC scratch, as the forward's; HCTR_ERR_NOMEM leaves the context usable):
+ *   4 * B*W*D (emissions, D = the largest number of distinct classes of a line, blank included) + 8 * B*W (log-sum-exp
+ *   of every row) + 4 * sum_b T_b * (2 L_b + 1) (the alpha rows, overwritten by the states' posterior shares; lines
+ *   without an alignment take none; worst case one line 2000 * 4095 * 4 = 33 MB) + the per-line tables; plus W*B*C
+ *   floats for each of logits / gradient that is passed as a host pointer.
+ * Precision: alpha and beta are float32 log-space recursions; each row's gamma is normalised by its own sum, so a
+ * gradient row sums to zero to float32 rounding. Needs no weights, like hctr_ctc_loss_logits. */
+int hctr_ctc_loss_logits_grad(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C,
+                              const int32_t* targets, const int32_t* target_lengths, const int32_t* input_lengths,
+                              const float* line_weight, float* nll, float* grad_wbc, int grad_on_device);
 
 /* ---- host prefix beam search: replaces ctc_codec.__cbs_full__/__cbs_skip__ -------------------
  * utils/ctc_codec.py:124-285 (Beam :288-307), float64 accumulators over float32 log-probs.

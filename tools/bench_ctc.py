@@ -6,7 +6,16 @@ The batch is BASELINE configs[1]'s shape (64 synthetic lines of 2000 columns, ra
 scored against its own greedy text, as a validation loss of decoded output would be. hctr_ctc_loss and hctr_greedy run
 alternately (device-synchronised wall time per call; both are synchronous at return), after warm-up calls of each.
 --layers adds the engine's per-launch device times of one call of each (HIP events; names as rocprofv3 groups them:
-head.linear, ctc_lse, ctc_alpha vs head.linear+argmax). Prints one JSON line."""
+head.linear, ctc_lse, ctc_alpha vs head.linear+argmax). Prints one JSON line.
+
+    python tools/bench_ctc.py --backward [--layers] ...
+
+times the criterion on caller logits instead (the engine's own logits of that batch, a device tensor [W, lines, C], each
+line's greedy text as targets): loss only (hctr_ctc_loss_logits), loss + gradient (hctr_ctc_loss_logits_grad into a
+preallocated device tensor) and torch.nn.functional.ctc_loss over log_softmax, forward + backward, on the same device
+tensors - alternately, after warm-up calls of each. --layers adds the device times of the gradient call's launches and
+the bytes per second of its two row passes (ctc_rowlse reads the logits once; ctc_grad_rows reads them once and writes
+the gradient once)."""
 import argparse
 import json
 import os
@@ -27,6 +36,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--precision", default="f16", choices=["f16", "f16x3", "auto"])
     ap.add_argument("--layers", action="store_true")
+    ap.add_argument("--backward", action="store_true")
     args = ap.parse_args()
     import torch
     import hctr_amd
@@ -38,6 +48,9 @@ def main():
     labels = m.greedy(imgs)
     tl = np.array([len(v) for v in labels], np.int32)
     targets = np.concatenate(labels).astype(np.int32)
+    if args.backward:
+        print(json.dumps(backward(args, hctr_amd, m, imgs, targets, tl)))
+        return
 
     def t_greedy():
         torch.cuda.synchronize()
@@ -81,6 +94,71 @@ def main():
                                  if abs(prof.get(k, 0.0) - gprof.get(k, 0.0)) > 0.05}
         m.set_profiling(False)
     print(json.dumps(rec))
+
+
+def backward(args, hctr_amd, m, imgs, targets, tl):
+    import torch
+    ctc = hctr_amd.CTCLoss(reduction="none", zero_infinity=True).attach(m)
+    mod = sys.modules[type(ctc).__module__]
+    ctx = ctc._context()
+    logits = m(imgs)                                             # device tensor [W, lines, C]
+    W, B, C = (int(v) for v in logits.shape)
+    grad = torch.empty_like(logits)
+    tg_t, tl_t = torch.from_numpy(targets).long().cuda(0), torch.from_numpy(tl).long().cuda(0)
+    il_t = torch.full((B,), W, dtype=torch.long, device="cuda:0")
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def loss_only():
+        assert np.isfinite(mod.loss_logits(ctx, logits, 1, targets, tl, None)).all()
+
+    def loss_grad():
+        assert np.isfinite(mod.loss_grad_logits(ctx, logits, 1, targets, tl, None, None, grad=grad)[0]).all()
+
+    def torch_fb():
+        x = logits.detach().requires_grad_()
+        loss = torch.nn.functional.ctc_loss(x.log_softmax(2), tg_t, il_t, tl_t, reduction="sum", zero_infinity=True)
+        loss.backward()
+        assert x.grad is not None
+
+    fns = (("loss_only", loss_only), ("loss_grad", loss_grad), ("torch_fwd_bwd", torch_fb))
+    for _ in range(args.warmup):
+        for _, fn in fns:
+            fn()
+    ms = {k: [] for k, _ in fns}
+    for _ in range(args.steps):
+        for k, fn in fns:
+            ms[k].append(1e3 * timed(fn))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    rec = {"mode": "backward", "lines": B, "width": W, "classes": C, "precision": args.precision,
+           "mean_target_length": float(tl.mean()), "max_target_length": int(tl.max())}
+    for k, v in ms.items():
+        rec[k + "_ms"] = [round(x, 3) for x in v]
+        rec[k + "_ms_median"] = round(med[k], 3)
+    rec["loss_grad_over_loss_only"] = round(med["loss_grad"] / med["loss_only"], 4)
+    rec["loss_grad_over_torch"] = round(med["loss_grad"] / med["torch_fwd_bwd"], 4)
+    if args.layers:
+        m.set_profiling(True)
+        loss_only()
+        fprof = dict(m.last_profile())
+        loss_grad()
+        gprof = dict(m.last_profile())
+        m.set_profiling(False)
+        rec["loss_only_layers_ms"] = {k: round(v, 4) for k, v in fprof.items()}
+        rec["loss_grad_layers_ms"] = {k: round(v, 4) for k, v in gprof.items()}
+        row = 4.0 * W * B * C
+        if fprof.get("ctc_lse"):
+            rec["ctc_lse_TBps"] = round(row / (1e-3 * fprof["ctc_lse"]) / 1e12, 3)
+        if gprof.get("ctc_rowlse"):
+            rec["ctc_rowlse_TBps"] = round(row / (1e-3 * gprof["ctc_rowlse"]) / 1e12, 3)
+        if gprof.get("ctc_grad_rows"):
+            rec["ctc_grad_rows_TBps"] = round(2 * row / (1e-3 * gprof["ctc_grad_rows"]) / 1e12, 3)
+    return rec
 
 
 if __name__ == "__main__":
