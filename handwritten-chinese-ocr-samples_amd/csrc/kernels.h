@@ -72,8 +72,6 @@ struct ConvArgs {
     const float* stem_b;
     int split;              // f16x3 mode: activations are [hi | lo | hi] fp16 planes of Cout channels each
                             // (input side: Cin already counts the tripled channels)
-    int rpre;               // halo4 kernel, conv2 of an identity block: fetch the residual during the last K step (HCTR_RPRE)
-    int rtouch;             // halo4 kernel, conv2 of an identity block: pre-touch the residual tile's cache lines (HCTR_RTOUCH)
     int drop_lo;            // f16x3 diagnostic (HCTR_X3_MASK, precision attribution): round this layer's output to ONE fp16
                             // value like the f16 mode does (the lo plane is written as zeros)
     // fused 1x1 downsample of a block's input (first block of stages 1-3): the halo4 kernel first accumulates
@@ -90,6 +88,8 @@ struct ConvArgs {
     // timing experiments only (HCTR_DBG), results INVALID. 8-wave/generic kernels: 1 = DMA from fixed hot addresses,
     // 2 = no DMA in the loop. halo4 kernel, bit mask: 32 = no halo reload at chunk boundaries, 64 = no K loop,
     // 128 = no epilogue, 256 = no output stores, 512 = no weight DMA inside the K loop, 1024 = no per-step barrier.
+    // Bit 32 has NO effect on the instances that issue the halo reload inside tap 8 (the plain f16 / f16x3 / fused-
+    // downsample instances, i.e. every default launch): it only reaches the persistent, RESPRE and STAMP instances.
     int dbg;
 };
 

@@ -6,54 +6,6 @@
 
 #include <cstdlib>
 
-#ifndef RING
-#define RING 3         // A-fragment ring slots (prefetch distance RING-1 groups)
-#endif
-#ifndef BHALF_AT
-#define BHALF_AT 1     // MFMA group before which the second half of the B fragments is read
-#endif
-#ifndef DMA_SPREAD
-#define DMA_SPREAD 0   // A/B build switch: 0 = a step's 4 weight-DMA pieces right after the first fragment reads; 1 = one piece
-                       // after each of MFMA groups 0..3; 2 = after groups 0, 2, 4, 6 (issue cost in the MFMAs' shadow);
-                       // 3 = all four BEFORE the first fragment reads
-#endif
-#ifndef NOPRIO
-#define NOPRIO 0       // A/B build switch (tools/ab_build.sh): 1 drops the s_setprio around MFMA groups
-#endif
-#ifndef RPRE
-#define RPRE 0         // A/B build switch: 1 compiles the residual prefetch of conv2's last K step in (then HCTR_RPRE=0/1 selects it
-                       // at run time). Measured neutral (132.5-133.6 ms either way; the epilogue's residual phase stays 3.3 us
-                       // because the second half's loads still start there), so it is compiled out by default.
-#endif
-#ifndef RPRE_GROUPS
-#define RPRE_GROUPS 4  // MFMA groups of the last K step after which two residual vectors each are fetched: 4 = the 8 vectors of
-                       // the first 64-cout block (the most that stays in registers: 5, 6 and 8 groups spill 144 B per lane);
-                       // the second block's 8 vectors are loaded at the start of the epilogue
-#endif
-#ifndef GEN_ROLL
-#define GEN_ROLL 1     // A/B: generic kernel, 8-accumulator-tile waves (256x256 tile: the head GEMM): 1 = the halo kernels' rolling
-                       // fragment pipeline (A pairs read two MFMA groups ahead, second-half B fragments during group 1, the next
-                       // step's DMA burst after the first reads) instead of "all reads of a half step, then its 32 MFMAs"
-#endif
-#ifndef GEN_ASM_DMA
-#define GEN_ASM_DMA 1  // A/B: generic conv_mfma kernel (head GEMM, conv0_2 A/B paths): 1 = its LDS-DMA issued from inline asm like the
-                       // halo kernels (hidden from hipcc's waitcnt pass, which otherwise drains lgkmcnt(0) at every wait)
-#endif
-#ifndef GEN_PRIO
-#define GEN_PRIO 0     // A/B: generic conv_mfma kernel (head GEMM): 1 = static priority 1 over the whole K loop instead of flips
-#endif
-#ifndef STEM_PRIO
-#define STEM_PRIO 0    // A/B: fused stem kernel: 1 = static priority 1 over the whole conv0_2 (MFMA) phase instead of flips
-#endif
-#ifndef PRIO_MODE
-#define PRIO_MODE 1    // A/B build switch, halo4 kernel: 0 = priority 1 around every MFMA group, 0 elsewhere; 1 = the whole K
-                       // loop at priority 1 (its LDS reads / DMA issue / barrier beat the partner workgroup's epilogue and
-                       // prologue VALU work, which stays at 0), no per-group flips; 2 = loop at 1, MFMA groups at 2;
-                       // 3 = as 0 inside the loop, but prologue and epilogue at priority 2 (a slot's overhead phases are
-                       // short and fully exposed: let them win the issue port against the partner's loop);
-                       // 4 = as 1, with the prologue at priority 1 too (only the epilogue at 0)
-#endif
-
 namespace hctr {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
@@ -61,7 +13,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef const void __attribute__((address_space(1))) * gptr_t;
 typedef void __attribute__((address_space(3))) * lptr_t;
 
 // One 1-KiB LDS-DMA piece (global_load_lds_dwordx4: lane i -> LDS lds_dst + 16*i) issued from inline
@@ -73,17 +24,6 @@ __device__ __forceinline__ void glds16_asm(const char* gsrc, char* lds_dst) {
     const uint32_t lds = (uint32_t)(uintptr_t)((lptr_t)lds_dst);
     uint32_t keep;
     asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep)
-                 : "v"(gsrc), "s"(lds)
-                 : "memory");
-}
-
-// 4-byte-per-lane LDS-DMA with per-lane source addresses (lane i -> LDS lds_dst + 4*i): used to TOUCH cache lines (the
-// data is never read) without a register destination, so no VGPR is clobbered when the load returns late
-__device__ __forceinline__ void glds4_asm(const char* gsrc, char* lds_dst) {
-    const uint32_t lds = (uint32_t)(uintptr_t)((lptr_t)lds_dst);
-    uint32_t keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
                  : "=&s"(keep)
                  : "v"(gsrc), "s"(lds)
                  : "memory");
@@ -161,9 +101,7 @@ template <int WN, int WM, int JT, bool LINEAR, bool SPLIT, bool PRIVATE_RED = fa
           bool RESID_IN_ACC = false>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[JT][4], char* smem, int tid, int lane,
                                               int wn, int wm, int n0, int mt, int img, int th, int tw, int hbase,
-                                              int w0, unsigned long long* st = nullptr,
-                                              const f16x8 (*pre_lo)[4] = nullptr, const f16x8 (*pre_hi)[4] = nullptr,
-                                              bool use_pre = false) {
+                                              int w0, unsigned long long* st = nullptr) {
     // diagnostic instance only: st = this workgroup's stamp slots 8.. (after bias, residual, rounding, SE sums)
     auto estamp = [&](int i) {
         if (st != nullptr) {
@@ -358,21 +296,15 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x4 (&acc)[JT
     } else if (a.se_scale != nullptr) {
         const float* sc = a.se_scale + (int64_t)img * a.Cout + cw0;
         if (w < a.out_wlimit) {
-            // all residual loads first (one latency exposure), 2 x 8 couts = 2 x 16 B per (cb, n) - unless the caller has
-            // fetched them already (halo4 kernel: during its last K step, pre_lo / pre_hi)
+            // all residual loads first (one latency exposure), 2 x 8 couts = 2 x 16 B per (cb, n)
             f16x8 rlo[JT / 4][4], rhi[JT / 4][4];
 #pragma unroll
             for (int cb = 0; cb < JT / 4; ++cb)
 #pragma unroll
                 for (int n = 0; n < 4; ++n) {
-                    if (pre_lo != nullptr && use_pre && cb * 4 + n < RPRE_GROUPS) {       // (pre_lo: compile-time per call site; use_pre: run time -
-                        rlo[cb][n] = pre_lo[cb][n];           //  a run-time SELECTED pointer would force the arrays into scratch)
-                        rhi[cb][n] = pre_hi[cb][n];
-                    } else {
-                        const half_t* r = a.resid + pix0 + (int64_t)(hbase + n) * a.out_sh + cb * 64;
-                        rlo[cb][n] = *(const f16x8*)r;
-                        rhi[cb][n] = *(const f16x8*)(r + 32);
-                    }
+                    const half_t* r = a.resid + pix0 + (int64_t)(hbase + n) * a.out_sh + cb * 64;
+                    rlo[cb][n] = *(const f16x8*)r;
+                    rhi[cb][n] = *(const f16x8*)(r + 32);
                 }
 #pragma unroll
             for (int j = 0; j < JT; ++j) {
@@ -697,16 +629,15 @@ __global__ __launch_bounds__(WN* WM * 64) void conv_mfma_kernel(const ConvArgs a
         }
         wo = ((int64_t)tap * a.CoutPad * cin + (int64_t)kc * kBK) * 2;
     };
-    // one 1-KiB LDS-DMA piece (idx < NIW: weight tile, else pixel tile) into buffer buf
+    // one 1-KiB LDS-DMA piece (idx < NIW: weight tile, else pixel tile) into buffer buf, issued from inline asm like the
+    // halo kernels' (see glds16_asm; measured 3.63 -> 3.53 ms per head-GEMM launch against the builtin)
     auto stage_piece = [&](const char* wsrc, const char* xsrc, int buf, int idx) {
         if (idx < NIW) {
             char* wdst = smem + buf * TILE_BYTES + (wv * NIW) * 1024;
-            if (GEN_ASM_DMA) glds16_asm_s(wsrc, woff[idx], wdst + idx * 1024);
-            else __builtin_amdgcn_global_load_lds((gptr_t)(wsrc + woff[idx]), (lptr_t)(wdst + idx * 1024), 16, 0, 0);
+            glds16_asm_s(wsrc, woff[idx], wdst + idx * 1024);
         } else {
             char* xdst = smem + buf * TILE_BYTES + BN * 128 + (wv * NIX) * 1024;
-            if (GEN_ASM_DMA) glds16_asm_s(xsrc, xoff[idx - NIW], xdst + (idx - NIW) * 1024);
-            else __builtin_amdgcn_global_load_lds((gptr_t)(xsrc + xoff[idx - NIW]), (lptr_t)(xdst + (idx - NIW) * 1024), 16, 0, 0);
+            glds16_asm_s(xsrc, xoff[idx - NIW], xdst + (idx - NIW) * 1024);
         }
     };
     auto stage = [&](int k, int buf) {
@@ -729,14 +660,16 @@ __global__ __launch_bounds__(WN* WM * 64) void conv_mfma_kernel(const ConvArgs a
     const int foff1 = frow * 128 + (((4 + q) ^ (lane & 7)) << 4);
 
     stage(0, 0);
-    if (GEN_PRIO) __builtin_amdgcn_s_setprio(1);
     if (!PIPE) {
         for (int k = 0; k < nk; ++k) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
             const char* wt = smem + (k & 1) * TILE_BYTES + (wn * WC) * 128;
             const char* xt = smem + (k & 1) * TILE_BYTES + BN * 128 + (wm * 64) * 128;
-            if (GEN_ROLL && JT == 8) {
+            if (JT == 8) {
+                // 8-accumulator-tile waves (256x256 tile: the head GEMM) run the halo kernels' rolling fragment pipeline:
+                // A pairs read two MFMA groups ahead, second-half B fragments during group 1, the next step's DMA burst
+                // after the first reads (measured 3.53 -> 3.39 ms per head launch against the half-step form below)
                 f16x8 ar[3][2], bq[2][4];
                 auto read_a = [&](int g, f16x8 (&dst)[2]) {
                     const char* base = wt + ((g >> 2) ? foff1 : foff0);
@@ -760,14 +693,14 @@ __global__ __launch_bounds__(WN* WM * 64) void conv_mfma_kernel(const ConvArgs a
                     if (g + 2 < 8) read_a(g + 2, ar[(g + 2) % 3]);
                     __builtin_amdgcn_sched_barrier(0);
                     if (g == 1) { read_b(1, bq[1]); __builtin_amdgcn_sched_barrier(0); }
-                    if (!GEN_PRIO) __builtin_amdgcn_s_setprio(1);
+                    __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                     for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
                         for (int n = 0; n < 4; ++n)
                             acc[2 * (g & 3) + jj][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ar[g % 3][jj], bq[g >> 2][n],
                                                                                              acc[2 * (g & 3) + jj][n], 0, 0, 0);
-                    if (!GEN_PRIO) __builtin_amdgcn_s_setprio(0);
+                    __builtin_amdgcn_s_setprio(0);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 continue;
@@ -781,13 +714,13 @@ __global__ __launch_bounds__(WN* WM * 64) void conv_mfma_kernel(const ConvArgs a
                 for (int n = 0; n < 4; ++n) bf[n] = *(const f16x8*)(xt + n * 2048 + fo);
 #pragma unroll
                 for (int j = 0; j < JT; ++j) af[j] = *(const f16x8*)(wt + j * 2048 + fo);
-                if (!GEN_PRIO) __builtin_amdgcn_s_setprio(1);     // keeps the MFMA cluster together (measured +4 %)
+                __builtin_amdgcn_s_setprio(1);     // keeps the MFMA cluster together (measured +4 %)
 #pragma unroll
                 for (int j = 0; j < JT; ++j)
 #pragma unroll
                     for (int n = 0; n < 4; ++n)
                         acc[j][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j], bf[n], acc[j][n], 0, 0, 0);
-                if (!GEN_PRIO) __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_s_setprio(0);
             }
         }
     } else {
@@ -836,7 +769,6 @@ __global__ __launch_bounds__(WN* WM * 64) void conv_mfma_kernel(const ConvArgs a
         }
     }
 
-    if (GEN_PRIO) __builtin_amdgcn_s_setprio(0);
     conv_epilogue<WN, WM, JT, LINEAR, SPLIT>(a, acc, smem, tid, lane, wn, wm, n0, mt, img, th, tw,
                                              th * (4 * WM) + wm * 4, tw * kTileW);
 }
@@ -1060,7 +992,25 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(const ConvArgs a) {
 // DESIGN.md). The halo of the next chunk can only be fetched after the last tap of the current one
 // (single buffer); the partner workgroup covers that stall.
 // -------------------------------------------------------------------------------------------
-constexpr int kHalo4Lds = 2 * 16384 + kHaloBytes;          // 78848
+// LDS layout of conv3x3_halo4_kernel and conv3x3_halo4h_kernel (byte offsets into the dynamic LDS)
+namespace halo4_lds {
+constexpr int kWeightBuf = 16384;                          // one K step's weight tile; buffer b at kWeights + b * kWeightBuf
+constexpr int kWeights = 0;
+constexpr int kHalo = kWeights + 2 * kWeightBuf;           // 32768: the halo image (halo4h: its two 32-channel halves)
+constexpr int kScratch = kHalo + kHaloBytes;               // 78848: epilogue scratch, [WM = 4][BN = 128] floats of SE sums
+constexpr int kScratchBytes = 4 * 128 * 4;
+// Halo-offset table of the prefetching instances (kPrefetch in conv3x3_halo4_kernel): 4 waves x 12 pieces x 8 rows x 4 B.
+// It ALIASES the epilogue scratch on purpose: the table is read for the last time inside the tile's last K step and the
+// scratch is first written after it, so a workgroup that runs ONE tile never has both live. A persistent workgroup's
+// epilogue would overwrite the table of its next tile, hence !(kPrefetch && PERSIST) in the kernel.
+constexpr int kHaloTable = kScratch;
+constexpr int kHaloTableBytes = 4 * 12 * 8 * 4;
+constexpr int kNextTile = kScratch + kScratchBytes;        // 80896: two words, the persistent instances' drawn tile index
+constexpr int kTotal = kNextTile + 16;                     // 80912
+static_assert(kHaloTableBytes <= kScratchBytes, "the halo-offset table fits inside the epilogue scratch it aliases");
+static_assert(kNextTile >= kScratch + kScratchBytes, "the next-tile words lie behind the epilogue scratch");
+static_assert(kTotal <= 80 * 1024, "two workgroups per CU on 160 KB of LDS");
+}  // namespace halo4_lds
 
 // GEOM 0: 16 rows x 16 columns (halo 18 x 18, row stride 20); GEOM 1: 8 rows x 32 columns for the
 // H = 8 stage (halo 10 x 34, row stride 36). Both strides are 4 (mod 8) and both halos are 360 rows.
@@ -1073,38 +1023,9 @@ constexpr int kHalo4Lds = 2 * 16384 + kHaloBytes;          // 78848
 // pre-phase of conv2's K loop instead of as its own launch: acc = Wd * x over the block input's channels (centre
 // tap of x's halo), then acc <- (acc + bd) / s + b2, then the 3x3 taps of conv2 accumulate on top and the epilogue
 // multiplies by s: s * (W2*t + b2) + (Wd*x + bd). The residual is neither written nor read back (4.2 GB per launch).
-#ifndef LEAN
-#define LEAN 1         // K loop with its nine taps unrolled (tap / row / parity arithmetic and the step's branches fold into
-                       // constants), ONE per-lane weight offset (the piece stride moves into the scalar base) and one M0
-                       // save / restore per four pieces. -DLEAN=0: the rolled loop of rounds 1-3 (A/B, bit-identical).
-#endif
-#ifndef BPRE
-#define BPRE 1         // (with LEAN) next tap's first pixel fragments are read during the current step, see mma_step
-#endif
-#ifndef BPRE_AT
-#define BPRE_AT 4      // ... behind the MFMAs of this group (4..7)
-#endif
-#ifndef EARLY_HALO
-#define EARLY_HALO 1   // (with LEAN, plain f16 instances) next chunk's halo reload issued inside the last tap, see the tap loop
-#endif
-#ifndef SPLIT_FAST
-#define SPLIT_FAST 1   // fragment prefetch + early halo request in the f16x3 instances too (their K loop is the same code)
-#endif
-#ifndef EARLY_LGKM
-#define EARLY_LGKM 0
-#endif
-#ifndef EARLY_AT
-#define EARLY_AT 1     // ... behind this MFMA group of tap 8
-#endif
-#ifndef DS_BPRE
-#define DS_BPRE 1      // fragment prefetch + early halo request in the main loop of the fused-downsample instances too
-#endif
-#ifndef RESPRE_BPRE
-#define RESPRE_BPRE 0  // BPRE in the residual-in-prologue instances too (spills eight halo offsets as of this writing)
-#endif
-#ifndef RTOUCH
-#define RTOUCH 0       // residual pre-touch experiment (HCTR_RTOUCH=1 needs -DRTOUCH=1; measured neutral, see below)
-#endif
+// The K loop has its nine taps unrolled: tap / row / parity arithmetic and the step's branches fold into constants, the
+// four weight pieces of a wave share ONE per-lane offset (the piece stride moves into the scalar base) and one M0 save /
+// restore (measured -2.0 % per step against the rolled loop of rounds 1-3, bit-identical).
 // RESPRE: conv2 of an identity block (BasicBlock :54-58, out = relu(o * s + x)). The SE scale s is known before conv2 runs
 // (se_premean), so the residual x is fetched in the PROLOGUE - its HBM round trip overlaps the first operands' DMA wait -
 // and the accumulators start at x / max(s, floor) + bias; the epilogue multiplies by max(s, floor), exactly what the
@@ -1125,17 +1046,23 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
         if (STAMP && tid == 0) a.stamps[(size_t)blockIdx.x * 16 + i] = __builtin_amdgcn_s_memrealtime();
     };
     stamp(0);
-    if (PRIO_MODE == 3) __builtin_amdgcn_s_setprio(2);
-    if (PRIO_MODE == 4) __builtin_amdgcn_s_setprio(1);
     const int lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wv;
     const int cin = a.Cin;
     const int nkc = (a.dbg & 64) ? 0 : cin / kBK;       // dbg 64: timing experiment without the K loop
     const int nk = 9 * nkc;
-    // (not with RTOUCH builds: the pre-touch experiment lands its dummy loads in the same LDS scratch as the offset table;
-    //  not in persistent instances: their epilogue overwrites the table after every tile)
-    constexpr bool kEarly = LEAN && EARLY_HALO && !RTOUCH && !(DSFUSE && !DS_BPRE) && !(SPLIT && !SPLIT_FAST) && !PERSIST && !STAMP && !RESPRE;
+    // The plain instances (f16 and f16x3, with or without the fused downsample) prefetch: a K step reads the NEXT tap's
+    // first pixel fragments behind its own MFMA group kBpreAt (see mma_step), and the next chunk's halo reload is issued
+    // inside tap 8, behind group kEarlyAt, from a table of piece offsets in LDS (halo4_lds::kHaloTable). Three instance
+    // kinds cannot: STAMP and RESPRE have no registers left for the fragments that live across the step boundary (they
+    // would spill), and a persistent workgroup's epilogue overwrites the table, which aliases its scratch, after every tile.
+    constexpr bool kPrefetch = !PERSIST && !STAMP && !RESPRE;
+    static_assert(!(kPrefetch && PERSIST), "the halo-offset table aliases the epilogue scratch: one tile per workgroup");
+    constexpr int kRing = 3;        // A-fragment ring slots (prefetch distance kRing - 1 groups); 4 measured within +-0.3 %
+    constexpr int kBhalfAt = 1;     // MFMA group before which the second half of the B fragments is read; 0 / 2 within +-0.3 %
+    constexpr int kBpreAt = 4;      // group behind which the next tap's fragments are read (bq[0] is dead after group 3); 6: +4.4 %
+    constexpr int kEarlyAt = 1;     // group of tap 8 behind which the halo reload is issued; 2 and 3 measured no better
 
     // ---- tiles of this workgroup. Every XCD owns a contiguous run of the (pixel-tile major, cout-tile
     //      minor) order. Non-persistent: one tile per workgroup. Persistent: the workgroups of an XCD
@@ -1183,43 +1110,28 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
     // draw's latency hides behind a whole K loop and the hardware dispatcher's balancing is kept.
     const bool dynamic = PERSIST && a.tile_counter != nullptr;
     int tnext = local + nloc;
-    volatile int* lds_next = (volatile int*)(smem + kHalo4Lds + 4 * 128 * 4);       // two words behind the epilogue scratch
+    volatile int* lds_next = (volatile int*)(smem + halo4_lds::kNextTile);
 
     const int wrow = GEOM ? (wm >> 1) * 4 : wm * 4;               // this wave's 4 x 16 patch inside the tile
     const int wcol = GEOM ? (wm & 1) * 16 : 0;
     uint32_t woff[4], hoff[12];
-    // BPRE: with bq[0] living across the step boundary the loop sits at the 256-register limit, and a spilled halo offset is
-    // reloaded in front of its DMA (a reload drains vmcnt: the K loop must not spill). The pieces' (hy, hx) pairs are
-    // therefore also kept packed in six registers and the offsets rebuilt from them in tap 8's last four MFMA groups,
-    // where bq[0] is free. hipcc is free to hoist that arithmetic (it is loop-invariant) and does for some instances; what
-    // is checked is the outcome - tools/kernel_resources.sh must show scratch 0 for the four <GEOM, false, false, false, *>
-    // instances after any change here (without this formulation GEOM 1 spills 8 bytes per lane, measured).
-    uint32_t hpk[6], hcp16 = 0;
     const int q = lane >> 4, c = lane & 15;
     const int aoff0 = c * 128 + (((0 + q) ^ (lane & 7)) << 4);
     const int aoff1 = c * 128 + (((4 + q) ^ (lane & 7)) << 4);
 
+    auto weight_buf = [&](int k) { return smem + halo4_lds::kWeights + (k & 1) * halo4_lds::kWeightBuf; };      // of K step k
     auto stage_w = [&](const char* wb, int rowcin, const uint32_t (&wo)[4], int kc, int tap, int buf) {
         const char* src = wb + ((int64_t)tap * a.CoutPad * rowcin + (int64_t)kc * kBK) * 2;
-        char* dst = smem + buf * 16384 + (wv * 4) * 1024;
-        if (LEAN) {                                          // piece i = 8 cout rows further on: same lane offset, scalar stride
-            const int64_t ps = (int64_t)rowcin * 16;
-            glds16x4_asm_s(src, src + ps, src + 2 * ps, src + 3 * ps, wo[0], dst, dst + 1024, dst + 2048, dst + 3072);
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) glds16_asm_s(src, wo[i], dst + i * 1024);
+        char* dst = weight_buf(buf) + (wv * 4) * 1024;
+        const int64_t ps = (int64_t)rowcin * 16;            // piece i = 8 cout rows further on: same lane offset, scalar stride
+        glds16x4_asm_s(src, src + ps, src + 2 * ps, src + 3 * ps, wo[0], dst, dst + 1024, dst + 2048, dst + 3072);
     };
     auto stage_weights = [&](const char* wb, int kc, int tap, int buf) { stage_w(wb, cin, woff, kc, tap, buf); };
-    auto stage_weights_piece = [&](const char* wb, int kc, int tap, int buf, int i) {
-        const char* src = wb + ((int64_t)tap * a.CoutPad * cin + (int64_t)kc * kBK) * 2;
-        glds16_asm_s(src, woff[i], smem + buf * 16384 + (wv * 4) * 1024 + i * 1024);
-    };
     auto stage_halo = [&](const char* xb, int kc) {
         const char* src = xb + (int64_t)kc * (kBK * 2);
 #pragma unroll
         for (int r = 0; r < 12; ++r)
-            if (wv + 4 * r < kHaloPieces) glds16_asm_s(src, hoff[r], smem + 32768 + (wv + 4 * r) * 1024);
+            if (wv + 4 * r < kHaloPieces) glds16_asm_s(src, hoff[r], smem + halo4_lds::kHalo + (wv + 4 * r) * 1024);
     };
     // per-lane DMA offsets of a source tensor with `rowcin` channels and `in_sh` elements per image row
     // (recomputed where needed - from an opaque lane id, so they are not kept alive across the epilogue)
@@ -1241,36 +1153,24 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
             if (hx > TC + 1) hx = TC + 1;                       // pad columns: any valid address
             if (hy > TR + 1) hy = TR + 1;                       // pieces >= 45 are never issued
             hoff[r] = ((uint32_t)hy * (uint32_t)in_sh + (uint32_t)hx * (uint32_t)rowcin) * 2u + cp * 16;
-            hcp16 = cp * 16;                                    // (row & 7 does not depend on r: pieces are 32 rows apart)
-            const uint32_t pk = (uint32_t)hy << 8 | (uint32_t)hx;
-            if (r & 1) hpk[r >> 1] |= pk << 16;
-            else hpk[r >> 1] = pk;
         }
     };
-    // offsets of pieces r0 .. r0+2 back from the packed coordinates
-    auto unpack_hoff = [&](int r0, uint32_t insh2, uint32_t cin2) {
-#pragma unroll
-        for (int r = r0; r < r0 + 3; ++r) {
-            const uint32_t pk = hpk[r >> 1] >> ((r & 1) * 16);
-            hoff[r] = ((pk >> 8) & 0xff) * insh2 + (pk & 0xff) * cin2 + hcp16;
-        }
-    };
-    // EARLY_HALO: the twelve piece offsets are not kept in registers through the K loop; their lane-row part
-    // (hy * in_sh + hx * cin, the same for the eight lanes of an LDS row) goes into a table in the epilogue's scratch
-    // (unused until the loop ends), 4 waves x 12 pieces x 8 rows x 4 B = 1.5 KB; the lane's own 16-byte chunk term is added
-    // back when a piece is issued. Called right after the lane_offsets() of the tensor the K loop reads.
+    // kPrefetch: the twelve piece offsets are not kept in registers through the K loop; their lane-row part
+    // (hy * in_sh + hx * cin, the same for the eight lanes of an LDS row) goes into the table at halo4_lds::kHaloTable;
+    // the lane's own 16-byte chunk term is added back when a piece is issued. Called right after the lane_offsets() of the
+    // tensor the K loop reads.
     auto write_halo_table = [&]() {
-        uint32_t* htab = (uint32_t*)(smem + kHalo4Lds);
+        uint32_t* htab = (uint32_t*)(smem + halo4_lds::kHaloTable);
         if ((lane & 7) == 0) {
             const uint32_t cp0 = (uint32_t)((lane >> 3) & 7) << 4;           // chunk term of lane & 7 == 0
 #pragma unroll
             for (int r = 0; r < 12; ++r) htab[(wv * 12 + r) * 8 + (lane >> 3)] = hoff[r] - cp0;
         }
     };
-    const int hbuf = 32768 + wrow * (S * 128);
-    // fragment addresses of a tap inside the halo image
-    // LEAN: all 18 (tap, even / odd) fragment addresses are six per-lane values (dx = -1, 0, 1; swizzle parity) plus
-    // constants - spelled out so that the unrolled loop keeps six address registers, not one or two per tap
+    const int hbuf = halo4_lds::kHalo + wrow * (S * 128);
+    // fragment addresses of a tap inside the halo image: all 18 (tap, even / odd) addresses are six per-lane values
+    // (dx = -1, 0, 1; swizzle parity) plus constants - spelled out so that the unrolled loop keeps six address
+    // registers, not one or two per tap
     int bx[3][2];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
@@ -1280,18 +1180,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
         bx[d][1] = hbuf + (v0 ^ 64);
     }
     auto b_ptrs = [&](int tap, const char*& be, const char*& bo) {
-        if (LEAN) {
-            const int tdy = tap / 3, d = tap - tdy * 3;
-            be = smem + bx[d][tdy & 1] + tdy * (S * 128);
-            bo = smem + bx[d][(tdy & 1) ^ 1] + tdy * (S * 128);
-            return;
-        }
-        const int tdy = tap / 3, dx = tap - tdy * 3 - 1;
-        const int u = wcol + c + 1 + dx;
-        const int v0 = u * 128 + (((q ^ (u & 7) ^ ((tdy & 1) << 2)) & 7) << 4);
-        const char* hb = smem + hbuf + tdy * (S * 128);
-        be = hb + v0;
-        bo = hb + (v0 ^ 64);
+        const int tdy = tap / 3, d = tap - tdy * 3;
+        be = smem + bx[d][tdy & 1] + tdy * (S * 128);
+        bo = smem + bx[d][(tdy & 1) ^ 1] + tdy * (S * 128);
     };
 
     Tile cur = tile_at(tidx);
@@ -1316,15 +1207,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
         // Rolling fragment pipeline: 8 groups of 8 MFMAs (2 A fragments x 4 B fragments); A pairs are read two
         // groups ahead into a 3-slot ring, the second half's B fragments during group 1; `stage_next` issues the
         // next step's weight DMA after the first reads so its issue cost overlaps their LDS latency.
-        // BPRE (LEAN only): the pixel fragments of the NEXT tap's first half are read during this step's groups 4-7 into
+        // kPrefetch: the pixel fragments of the NEXT tap's first half are read behind this step's group kBpreAt into
         // bq[0] (dead after group 3) - the halo does not change inside a chunk - so only weight fragments are read between
         // the barrier and the first MFMA. `have_b0`: bq[0] was filled that way by the previous step; `nbe`: != nullptr ->
         // prefetch from (nbe, nbo).
         f16x8 bq[2][4];
-        auto mma_step = [&](const char* wt, const char* be, const char* bo, auto&& stage_next, auto&& stage_piece,
-                            auto&& after_group, bool have_b0 = false, const char* nbe = nullptr, const char* nbo = nullptr,
-                            int bhalf_at = BHALF_AT) {
-            f16x8 ar[RING][2];
+        auto mma_step = [&](const char* wt, const char* be, const char* bo, auto&& stage_next, auto&& after_group,
+                            bool have_b0 = false, const char* nbe = nullptr, const char* nbo = nullptr,
+                            int bhalf_at = kBhalfAt) {
+            f16x8 ar[kRing][2];
             auto read_a = [&](int g, f16x8 (&dst)[2]) {
                 const int ks = g >> 2, jp = g & 3;
                 const char* base = wt + (ks ? aoff1 : aoff0);
@@ -1337,34 +1228,27 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
                     dst[n] = *(const f16x8*)((((n & 1) ^ ks) ? bo : be) + n * (S * 128));
             };
             __builtin_amdgcn_sched_barrier(0);
-            if (DMA_SPREAD == 3) { stage_next(); __builtin_amdgcn_sched_barrier(0); }      // (A/B: DMA before the first reads)
             if (!have_b0) read_b(0, bq[0]);
             read_a(0, ar[0]);
             __builtin_amdgcn_sched_barrier(0);
-            read_a(1, ar[1]);
-            if (RING > 3) read_a(2, ar[2]);
+#pragma unroll
+            for (int g = 1; g < kRing - 1; ++g) read_a(g, ar[g]);
             __builtin_amdgcn_sched_barrier(0);
-            if (DMA_SPREAD != 3) stage_next();
+            stage_next();
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int g = 0; g < 8; ++g) {
                 const int ks = g >> 2, jp = g & 3;
-                if (g + RING - 1 < 8) read_a(g + RING - 1, ar[(g + RING - 1) % RING]);
+                if (g + kRing - 1 < 8) read_a(g + kRing - 1, ar[(g + kRing - 1) % kRing]);
                 __builtin_amdgcn_sched_barrier(0);
                 if (g == bhalf_at) { read_b(1, bq[1]); __builtin_amdgcn_sched_barrier(0); }
-                if (!(NOPRIO) && (PRIO_MODE == 0 || PRIO_MODE == 3)) __builtin_amdgcn_s_setprio(1);
-                if (PRIO_MODE == 2) __builtin_amdgcn_s_setprio(2);
 #pragma unroll
                 for (int jj = 0; jj < 2; ++jj)
 #pragma unroll
                     for (int n = 0; n < 4; ++n)
                         acc[2 * jp + jj][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
-                            ar[g % RING][jj], bq[ks][n], acc[2 * jp + jj][n], 0, 0, 0);
-                if (!(NOPRIO) && (PRIO_MODE == 0 || PRIO_MODE == 3)) __builtin_amdgcn_s_setprio(0);
-                if (PRIO_MODE == 2) __builtin_amdgcn_s_setprio(1);
-                if (DMA_SPREAD == 1 && g < 4) stage_piece(g);
-                if (DMA_SPREAD == 2 && (g & 1) == 0) stage_piece(g >> 1);
-                if (g == BPRE_AT && nbe != nullptr) {
+                            ar[g % kRing][jj], bq[ks][n], acc[2 * jp + jj][n], 0, 0, 0);
+                if (g == kBpreAt && nbe != nullptr) {
 #pragma unroll
                     for (int n = 0; n < 4; ++n) bq[0][n] = *(const f16x8*)(((n & 1) ? nbo : nbe) + n * (S * 128));
                 }
@@ -1385,7 +1269,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
             lane_offsets(cin, a.in_sh, woff, false);
             stage_halo(dxb, 0);
             stage_w(dwb, dcin, woff_x, 0, 0, 0);
-            if (PRIO_MODE == 1 || PRIO_MODE == 2 || PRIO_MODE == 4) __builtin_amdgcn_s_setprio(1);
+            __builtin_amdgcn_s_setprio(1);                    // (as the main K loop below)
 #pragma unroll
             for (int j = 0; j < JT; ++j)
 #pragma unroll
@@ -1398,10 +1282,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
                 asm volatile("" ::: "memory");
                 const char *be, *bo;
                 b_ptrs(4, be, bo);
-                mma_step(smem + (kc & 1) * 16384, be, bo, [&] {
+                mma_step(weight_buf(kc), be, bo, [&] {
                     if (kc + 1 < nds) stage_w(dwb, dcin, woff_x, kc + 1, 0, (kc + 1) & 1);
                     else stage_w(cur.wb, cin, woff, 0, 0, (kc + 1) & 1);            // conv2's first step
-                }, [&](int) {}, [&](int) {});
+                }, [&](int) {});
                 __builtin_amdgcn_s_barrier();                 // every wave has consumed this chunk's fragments
                 asm volatile("" ::: "memory");
                 if (kc + 1 < nds) {
@@ -1409,7 +1293,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
                 } else {
                     lane_offsets(cin, a.in_sh, woff, true);   // from here on the halo holds conv2's input t
                     stage_halo(cur.xb, 0);
-                    if (kEarly) write_halo_table();
+                    if (kPrefetch) write_halo_table();
                 }
             }
             kbase = nds;
@@ -1433,7 +1317,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
             if (first) {
                 stage_halo(cur.xb, 0);
                 stage_weights(cur.wb, 0, 0, 0);
-                if (kEarly) write_halo_table();
+                if (kPrefetch) write_halo_table();
                 first = false;
                 if (STAMP) {
                     stamp(1);
@@ -1488,33 +1372,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
         // hipcc's counter model "dirty" on every iteration (scalar loads return out of order), and it then
         // drains lgkmcnt(0) at the first MFMA group of each K step instead of the counted wait.
         __builtin_amdgcn_s_waitcnt(0xc07f);                 // lgkmcnt(0), vmcnt/expcnt untouched
-        // Residual pre-touch (A/B experiment, HCTR_RTOUCH=1, OFF by default): three steps before the end every thread
-        // touches the two 128-byte lines of one pixel of conv2's residual tile with 4-byte LDS-DMA loads into the
-        // epilogue's scratch (no register destination; issued after that step's weight pieces, so the next step's counted
-        // wait leaves them in flight). Measured (profiles/r03_overhead_experiments.txt): the epilogue's residual phase
-        // drops 3.6 -> 2.7 us, the K loop grows by as much, the step time is unchanged - the phase is the latency of 16
-        // dependent-free loads through a busy memory pipeline, not an HBM miss.
-        const bool rtouch = RTOUCH && !SPLIT && !DSFUSE && a.rtouch && a.resid != nullptr && nk >= 6;
-        const int ktouch = nk - 3;
-        // residual prefetch during the last K step (f16, identity blocks; a.rpre: A/B switch HCTR_RPRE)
-        const bool rpre = RPRE && !SPLIT && !DSFUSE && !PERSIST && a.rpre && a.resid != nullptr && a.se_scale != nullptr && nk >= 1;
-
-        if (PRIO_MODE == 1 || PRIO_MODE == 2 || PRIO_MODE == 4) __builtin_amdgcn_s_setprio(1);
-        if (PRIO_MODE == 3) __builtin_amdgcn_s_setprio(0);
+        // The whole K loop runs at priority 1 (no flips around the MFMA groups): its LDS reads, DMA issue and barrier beat
+        // the partner workgroup's prologue and epilogue VALU work, which stays at 0 (measured -1.5 to -1.9 % per step against flips)
+        __builtin_amdgcn_s_setprio(1);
         for (int kc = 0; kc < nkc; ++kc) {
             const bool next_chunk = kc + 1 < nkc;
-            // with the residual prefetch the very last K step (tap 8 of the last chunk) runs after this loop, where the
-            // loop's per-lane DMA offsets are dead and their registers can hold the residual
-            const int ntap = (rpre && !next_chunk) ? 8 : 9;
-#if LEAN
 #pragma unroll
-#else
-#pragma unroll 1
-#endif
-            for (int tap = 0; tap < ntap; ++tap) {
+            for (int tap = 0; tap < 9; ++tap) {
                 const int k = kc * 9 + tap;
-                if (rtouch && k == ktouch + 1) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (!(a.dbg & 1024)) __builtin_amdgcn_s_barrier();       // dbg 1024: timing experiment without the per-step barrier
                 asm volatile("" ::: "memory");
                 const char *be, *bo;
@@ -1524,48 +1390,30 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
                 const int tap1 = more ? (wrap ? 0 : tap + 1) : 0;
                 const int kc1 = more ? (wrap ? kc + 1 : kc) : 0;
                 const char* wsrc = more ? cur.wb : nwb;
-                const bool bpre = LEAN && BPRE && !(DSFUSE && !DS_BPRE) && !(SPLIT && !SPLIT_FAST) && !PERSIST && !STAMP && !(RESPRE && !RESPRE_BPRE);      // (the others would spill)
                 const char *nbe = nullptr, *nbo = nullptr;
-                if (bpre && tap < 8) b_ptrs(tap + 1, nbe, nbo);
-                const bool early = kEarly;
-                const bool reload = kEarly ? next_chunk : ((next_chunk || has_next) && !(a.dbg & 32));
-                mma_step(smem + ((kbase + k) & 1) * 16384, be, bo, [&] {
+                if (kPrefetch && tap < 8) b_ptrs(tap + 1, nbe, nbo);
+                mma_step(weight_buf(kbase + k), be, bo, [&] {
                     // the next K step's weights into the other buffer; on a tile's last step that is the
                     // next tile's first step (persistent variant only).
                     // nothing to stage on the very last step: no DMA is then in flight when the epilogue
                     // starts, so the workgroup can retire without waiting for its output stores
-                    if ((DMA_SPREAD == 0 || DMA_SPREAD == 3) && (more || has_next) && !(a.dbg & 512))    // dbg 512: no weight DMA
+                    if ((more || has_next) && !(a.dbg & 512))    // dbg 512: no weight DMA
                         stage_weights(wsrc, kc1, tap1, (kbase + k + 1) & 1);
-                    if (rtouch && k == ktouch) {
-                        const int prow = GEOM ? (tid >> 5) : (tid >> 4), pcol = GEOM ? (tid & 31) : (tid & 15);
-                        const char* rp = (const char*)(a.resid + a.out_off + cur.img * a.out_sb +
-                                                       (int64_t)(cur.th * TR + prow) * a.out_sh +
-                                                       (int64_t)(cur.tw * TC + pcol) * a.out_sw + cur.n0);
-                        char* sc = smem + kHalo4Lds + wv * 512;
-                        glds4_asm(rp, sc);
-                        glds4_asm(rp + 128, sc + 256);
-                    }
-                }, [&](int i) {
-                    if (more || has_next) stage_weights_piece(wsrc, kc1, tap1, (kbase + k + 1) & 1, i);
                 }, [&](int g) {
-                    if (bpre && !early && tap == 8 && g >= 4) unpack_hoff(3 * (g - 4), (uint32_t)a.in_sh * 2u, (uint32_t)cin * 2u);
-                    if (early && tap == 8 && g == EARLY_AT && reload) {
-                        // EARLY_HALO: the last tap reads its second-half pixel fragments at group 0, so after group EARLY_AT
-                        // every fragment of the chunk is in registers: one extra barrier, and the next chunk's halo streams
-                        // in during the remaining MFMA groups instead of after them
-                        // (in-order LDS returns: with EARLY_LGKM = 2 only the two weight-fragment reads issued after the
-                        // pixel fragments may still be in flight)
-                        if (EARLY_LGKM == 2) asm volatile("s_waitcnt lgkmcnt(2)" ::: "memory");
-                        else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    if (kPrefetch && tap == 8 && g == kEarlyAt && next_chunk) {
+                        // the last tap reads its second-half pixel fragments at group 0 (bhalf_at below), so after group
+                        // kEarlyAt every fragment of the chunk is in registers: one extra barrier, and the next chunk's halo
+                        // streams in during the remaining MFMA groups instead of after them
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                         __builtin_amdgcn_s_barrier();
                         asm volatile("" ::: "memory");
                         // pieces wv + 4r: r <= 10 exist for every wave (45 pieces), r = 11 for wave 0 only
                         static_assert(kHaloPieces == 45, "halo piece count");
                         const char* hsrc = (next_chunk ? cur.xb + (int64_t)(kc + 1) * (kBK * 2) : nxb);
-                        char* d = smem + 32768 + wv * 1024;
+                        char* d = smem + halo4_lds::kHalo + wv * 1024;
                         int ln = lane;
                         asm volatile("" : "+v"(ln));                       // (nothing of this is hoisted out of the loop)
-                        const uint32_t* hrow = (const uint32_t*)(smem + kHalo4Lds) + wv * 96 + (ln >> 3);
+                        const uint32_t* hrow = (const uint32_t*)(smem + halo4_lds::kHaloTable) + wv * 96 + (ln >> 3);
                         const uint32_t cpl = (uint32_t)((ln ^ (ln >> 3)) & 7) << 4;
                         uint32_t ho[4];
 #pragma unroll
@@ -1573,16 +1421,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
                         glds16x4v_asm_s<4096>(hsrc, ho[0], ho[1], ho[2], ho[3], d);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) ho[r] = hrow[(4 + r) * 8] + cpl;
-                        glds16x4v_asm_s<4096>(hsrc, ho[0], ho[1], ho[2], ho[3], d + 16384);
+                        glds16x4v_asm_s<4096>(hsrc, ho[0], ho[1], ho[2], ho[3], d + 4 * 4096);
 #pragma unroll
                         for (int r = 0; r < 4; ++r) ho[r] = hrow[(8 + r) * 8] + cpl;
 #pragma unroll
                         for (int r = 8; r < 11; ++r) glds16_asm_s(hsrc, ho[r - 8], d + r * 4096);
                         if (wv == 0) glds16_asm_s(hsrc, ho[3], d + 11 * 4096);
                     }
-                }, bpre && tap > 0, nbe, nbo, (early && tap == 8) ? 0 : BHALF_AT);
+                }, kPrefetch && tap > 0, nbe, nbo, (kPrefetch && tap == 8) ? 0 : kBhalfAt);
             }
-            if ((next_chunk || has_next) && !(a.dbg & 32) && !kEarly) {     // dbg 32: timing experiment without the reload
+            if (!kPrefetch && (next_chunk || has_next) && !(a.dbg & 32)) {     // dbg 32: timing experiment without the reload
                 // single halo buffer: every wave has consumed its last B fragments of this chunk (they fed
                 // the MFMAs above), so after this barrier the buffer may be overwritten - with the next
                 // chunk, or with the next tile's first chunk (whose latency then hides behind the epilogue).
@@ -1592,29 +1440,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
                 else stage_halo(nxb, 0);
             }
         }
-        f16x8 rlo[2][4], rhi[2][4];
-        if (rpre) {
-            // LAST K step of a conv2 with an identity residual (non-persistent: nothing is staged any more): the 16
-            // residual vectors of the epilogue are fetched here, two after each MFMA group, into the registers the
-            // step's operand fragments and the loop's DMA offsets leave behind - their latency (2.7-3.6 us of a 6.6 us
-            // epilogue when issued there) hides under the step's MFMAs
-            const half_t* rbase = a.resid + a.out_off + cur.img * a.out_sb + (int64_t)(cur.tw * TC + wcol + c) * a.out_sw +
-                                  cur.n0 + q * 8 + (int64_t)(cur.th * TR + wrow) * a.out_sh;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            const char *be, *bo;
-            b_ptrs(8, be, bo);
-            mma_step(smem + ((kbase + nk - 1) & 1) * 16384, be, bo, [&] {}, [&](int) {}, [&](int g) {
-                if (g < RPRE_GROUPS) {
-                    const half_t* r = rbase + (int64_t)(g & 3) * a.out_sh + (g >> 2) * 64;
-                    rlo[g >> 2][g & 3] = *(const f16x8*)r;
-                    rhi[g >> 2][g & 3] = *(const f16x8*)(r + 32);
-                }
-            });
-        }
-        if (PRIO_MODE == 1 || PRIO_MODE == 2 || PRIO_MODE == 4) __builtin_amdgcn_s_setprio(0);
-        if (PRIO_MODE == 3) __builtin_amdgcn_s_setprio(2);
+        __builtin_amdgcn_s_setprio(0);
         // the epilogue's scratch (SE partial sums) lives after the DMA buffers, so DMA may stay in flight
         stamp(3);
         if (a.dbg & 128) {       // dbg 128: timing experiment without the epilogue (keeps the MFMAs alive)
@@ -1627,9 +1453,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4_kernel(const ConvArgs a)
         } else
         {
             const int tw = cur.tw, th = cur.th, img = cur.img;
-            conv_epilogue<WN, WM, JT, false, SPLIT, true, true, DSFUSE || RESPRE>(a, acc, smem + kHalo4Lds, tid, lane, 0, wm, cur.n0, cur.mt,
-                                                          img, th, tw, th * TR + wrow, tw * TC + wcol,
-                                                          STAMP ? a.stamps + (size_t)blockIdx.x * 16 : nullptr, rlo, rhi, rpre);
+            conv_epilogue<WN, WM, JT, false, SPLIT, true, true, DSFUSE || RESPRE>(
+                a, acc, smem + halo4_lds::kScratch, tid, lane, 0, wm, cur.n0, cur.mt, img, th, tw, th * TR + wrow,
+                tw * TC + wcol, STAMP ? a.stamps + (size_t)blockIdx.x * 16 : nullptr);
         }
         if (!has_next) break;
         kbase += nk;
@@ -1735,14 +1561,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4h_kernel(const ConvArgs a
         const int u = 2 * s + (wv >> 1);
         const int tap = u < 9 ? u : u - 9, half = u < 9 ? 0 : 1;
         const char* src = wb + ((int64_t)tap * a.CoutPad * cin + (int64_t)kc * kBK + half * 32) * 2;
-        char* dst = smem + buf * 16384 + (wv * 4) * 1024;
+        char* dst = smem + halo4_lds::kWeights + buf * halo4_lds::kWeightBuf + (wv * 4) * 1024;
 #pragma unroll
         for (int i = 0; i < 4; ++i) glds16_asm_s(src + i * wpiece, woff0, dst + i * 1024);
     };
     // pieces r0, r0+1 (of this wave's six; piece wv + 4r, the 24th slot repeats piece 22) of half `half` of chunk kc
     auto stage_h2 = [&](int kc, int half, int r0) {
         const char* src = xb + ((int64_t)kc * kBK + half * 32) * 2;
-        char* dst = smem + 32768 + half * kHalf;
+        char* dst = smem + halo4_lds::kHalo + half * kHalf;
         int ln = lane;
         asm volatile("" : "+v"(ln));
         const int prow = ln >> 2, slot = ln & 3;
@@ -1791,7 +1617,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4h_kernel(const ConvArgs a
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             // fragment addresses of the step's two units
-            const char* wt = smem + (gstep & 1) * 16384 + aoff;
+            const char* wt = smem + halo4_lds::kWeights + (gstep & 1) * halo4_lds::kWeightBuf + aoff;
             const char *be[2], *bo[2];
 #pragma unroll
             for (int uu = 0; uu < 2; ++uu) {
@@ -1799,7 +1625,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4h_kernel(const ConvArgs a
                 const int tap = u < 9 ? u : u - 9, half = u < 9 ? 0 : 1;
                 const int tdy = tap / 3, dx = tap - tdy * 3 - 1;
                 const int hr0 = (wrow + tdy) * S + wcol + c + 1 + dx;           // halo pixel of pixel-repeat n = 0
-                const char* hb = smem + 32768 + half * kHalf + hr0 * 64;
+                const char* hb = smem + halo4_lds::kHalo + half * kHalf + hr0 * 64;
                 const int slot = q ^ (((hr0 >> 2) & 1) << 1);
                 be[uu] = hb + (slot << 4);                                      // even n (S / 4 is odd: the key flips with n)
                 bo[uu] = hb + ((slot ^ 2) << 4);
@@ -1848,23 +1674,26 @@ __global__ __launch_bounds__(256, 2) void conv3x3_halo4h_kernel(const ConvArgs a
         }
     }
     __builtin_amdgcn_s_setprio(0);
-    conv_epilogue<WN, WM, JT, false, false, true, true, false>(a, acc, smem + kHalo4Lds, tid, lane, 0, wm, n0, mt, img, th, tw,
+    conv_epilogue<WN, WM, JT, false, false, true, true, false>(a, acc, smem + halo4_lds::kScratch, tid, lane, 0, wm, n0, mt, img, th, tw,
                                                                th * TR + wrow, tw * TC + wcol);
 }
 
-#ifndef LDS_PAD
-#define LDS_PAD 0      // A/B build switch: extra LDS bytes per workgroup (e.g. 40000 forces ONE workgroup per CU)
-#endif
-constexpr int kHalo4LdsTotal = kHalo4Lds + 4 * 128 * 4 + 16 + LDS_PAD;   // + [WM][BN] floats of epilogue scratch + 2 queue words
-
-template <int GEOM, bool SPLIT, bool PERSIST>
-static hipError_t launch_conv_halo4_tp(const ConvArgs& a0, hipStream_t s) {
+// One launch of a halo4 / halo4h instance: LDS limit raised once per device (one done[] table per instance: the static
+// lives in the template), HCTR_DBG applied unless `with_env_dbg` is false.
+template <auto KERNEL>
+static hipError_t launch_halo4_instance(const ConvArgs& a0, int grid, hipStream_t s, bool with_env_dbg = true) {
     static bool done[64] = {};
-    hipError_t e0 = raise_lds_limit((const void*)conv3x3_halo4_kernel<GEOM, SPLIT, PERSIST>, kHalo4LdsTotal, done);
+    hipError_t e0 = raise_lds_limit((const void*)KERNEL, halo4_lds::kTotal, done);
     if (e0 != hipSuccess) return e0;
     static const int dbg = env_dbg();
     ConvArgs a = a0;
-    a.dbg |= dbg;
+    if (with_env_dbg) a.dbg |= dbg;
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), halo4_lds::kTotal, s, a);
+    return hipGetLastError();
+}
+
+template <int GEOM, bool SPLIT, bool PERSIST>
+static hipError_t launch_conv_halo4_tp(const ConvArgs& a, hipStream_t s) {
     int grid = a.mtiles * a.ntiles;
     if (PERSIST) {
         static int cus[64] = {};
@@ -1879,31 +1708,17 @@ static hipError_t launch_conv_halo4_tp(const ConvArgs& a0, hipStream_t s) {
         if (grid > resident) grid = resident;
         grid = (grid + 7) / 8 * 8;                         // whole XCD rounds (extra workgroups exit at once)
     }
-    hipLaunchKernelGGL((conv3x3_halo4_kernel<GEOM, SPLIT, PERSIST>), dim3(grid), dim3(256), kHalo4LdsTotal, s, a);
-    return hipGetLastError();
+    return launch_halo4_instance<conv3x3_halo4_kernel<GEOM, SPLIT, PERSIST>>(a, grid, s);
 }
 template <int GEOM, bool SPLIT>
 static hipError_t launch_conv_halo4_t(const ConvArgs& a, hipStream_t s) {
+    const int grid = a.mtiles * a.ntiles;
     if (a.ds_x != nullptr) {
         if (GEOM != 0) return hipErrorInvalidValue;               // (the engine only fuses on the 16x16 geometry)
-        static bool done_ds[64] = {};
-        hipError_t e0 = raise_lds_limit((const void*)conv3x3_halo4_kernel<0, SPLIT, false, false, true>, kHalo4LdsTotal, done_ds);
-        if (e0 != hipSuccess) return e0;
-        static const int dbg = env_dbg();
-        ConvArgs b = a;
-        b.dbg |= dbg;
-        hipLaunchKernelGGL((conv3x3_halo4_kernel<0, SPLIT, false, false, true>), dim3(a.mtiles * a.ntiles), dim3(256),
-                           kHalo4LdsTotal, s, b);
-        return hipGetLastError();
+        return launch_halo4_instance<conv3x3_halo4_kernel<0, SPLIT, false, false, true>>(a, grid, s);
     }
-    if (a.stamps != nullptr && !SPLIT) {
-        static bool done[64] = {};
-        hipError_t e0 = raise_lds_limit((const void*)conv3x3_halo4_kernel<GEOM, false, false, true>, kHalo4LdsTotal, done);
-        if (e0 != hipSuccess) return e0;
-        hipLaunchKernelGGL((conv3x3_halo4_kernel<GEOM, false, false, true>), dim3(a.mtiles * a.ntiles), dim3(256),
-                           kHalo4LdsTotal, s, a);
-        return hipGetLastError();
-    }
+    if (a.stamps != nullptr && !SPLIT)       // (the diagnostic instance times the real kernel: no HCTR_DBG)
+        return launch_halo4_instance<conv3x3_halo4_kernel<GEOM, false, false, true>>(a, grid, s, false);
     // persistent tiles with a STATIC stride measured 6-8 % slower on every layer (r01); HCTR_PERSIST=2 draws tiles
     // from an atomic queue instead (a.tile_counter, zeroed by the engine once per forward)
     static const int persist = [] { const char* e = getenv("HCTR_PERSIST"); return e ? atoi(e) : 0; }();
@@ -1912,18 +1727,8 @@ static hipError_t launch_conv_halo4_t(const ConvArgs& a, hipStream_t s) {
         // OFF by default - measured 126.7 vs 125.4 ms per step (three interleaved rounds): the fetch costs the same ~4 us
         // in the prologue as in the epilogue, and the instance has no room for the next-tap fragment prefetch
         static const int respre = [] { const char* e = getenv("HCTR_RESPRE"); return e ? atoi(e) : 0; }();
-        if (respre && persist == 0 && a.resid != nullptr && a.se_scale != nullptr) {
-            static bool done_rp[64] = {};
-            hipError_t e0 = raise_lds_limit((const void*)conv3x3_halo4_kernel<GEOM, false, false, false, false, true>,
-                                            kHalo4LdsTotal, done_rp);
-            if (e0 != hipSuccess) return e0;
-            static const int dbg = env_dbg();
-            ConvArgs b = a;
-            b.dbg |= dbg;
-            hipLaunchKernelGGL((conv3x3_halo4_kernel<GEOM, false, false, false, false, true>), dim3(a.mtiles * a.ntiles),
-                               dim3(256), kHalo4LdsTotal, s, b);
-            return hipGetLastError();
-        }
+        if (respre && persist == 0 && a.resid != nullptr && a.se_scale != nullptr)
+            return launch_halo4_instance<conv3x3_halo4_kernel<GEOM, false, false, false, false, true>>(a, grid, s);
     }
     if (persist == 0 || (persist == 2 && a.tile_counter == nullptr)) return launch_conv_halo4_tp<GEOM, SPLIT, false>(a, s);
     ConvArgs b = a;
@@ -1941,15 +1746,8 @@ static hipError_t launch_conv_halo4(const ConvArgs& a0, hipStream_t s) {
     // HCTR_HALFHALO=1: the half-buffered halo variant for the plain f16 launches (A/B)
     static const bool halfhalo = [] { const char* e = getenv("HCTR_HALFHALO"); return e ? atoi(e) != 0 : false; }();
     static const int persist = [] { const char* e = getenv("HCTR_PERSIST"); return e ? atoi(e) : 0; }();
-    if (halfhalo && !a.split && a.ds_x == nullptr && a.stamps == nullptr && persist == 0 && a.Cin % kBK == 0) {
-        static bool done[64] = {};
-        hipError_t e0 = raise_lds_limit((const void*)conv3x3_halo4h_kernel<GEOM>, kHalo4LdsTotal, done);
-        if (e0 != hipSuccess) return e0;
-        static const int dbg = env_dbg();
-        a.dbg |= dbg;
-        hipLaunchKernelGGL((conv3x3_halo4h_kernel<GEOM>), dim3(a.mtiles * a.ntiles), dim3(256), kHalo4LdsTotal, s, a);
-        return hipGetLastError();
-    }
+    if (halfhalo && !a.split && a.ds_x == nullptr && a.stamps == nullptr && persist == 0 && a.Cin % kBK == 0)
+        return launch_halo4_instance<conv3x3_halo4h_kernel<GEOM>>(a, a.mtiles * a.ntiles, s);
     return a.split ? launch_conv_halo4_t<GEOM, true>(a, s) : launch_conv_halo4_t<GEOM, false>(a, s);
 }
 
@@ -2246,7 +2044,6 @@ __global__ __launch_bounds__(256, 2) void stem_conv0_2_kernel(const ConvArgs a) 
     for (int j = 0; j < JT; ++j)
 #pragma unroll
         for (int n = 0; n < 4; ++n) acc[j][n] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (STEM_PRIO) __builtin_amdgcn_s_setprio(1);
     for (int st = 0; st < 5; ++st) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // this wave's weight pieces of step st have landed
         __syncthreads();                                               // ... everyone's, and (st == 0) the halo is written
@@ -2268,17 +2065,16 @@ __global__ __launch_bounds__(256, 2) void stem_conv0_2_kernel(const ConvArgs a) 
                 for (int n = 0; n < 4; ++n) bf[n] = *(const f16x8*)((((n & 1) ^ ks) ? bo : be) + n * (S * 128));
 #pragma unroll
                 for (int j = 0; j < JT; ++j) af[j] = *(const f16x8*)(wtile + j * 2048 + (ks ? aoff1 : aoff0));
-                if (!STEM_PRIO) __builtin_amdgcn_s_setprio(1);
+                __builtin_amdgcn_s_setprio(1);
 #pragma unroll
                 for (int j = 0; j < JT; ++j)
 #pragma unroll
                     for (int n = 0; n < 4; ++n)
                         acc[j][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af[j], bf[n], acc[j][n], 0, 0, 0);
-                if (!STEM_PRIO) __builtin_amdgcn_s_setprio(0);
+                __builtin_amdgcn_s_setprio(0);
             }
         }
     }
-    if (STEM_PRIO) __builtin_amdgcn_s_setprio(0);
     conv_epilogue<1, 4, JT, false, false>(a, acc, smem, tid, lane, 0, wv, 0, lin, img, th, tw, th * 16 + wrow, tw * 16);
 }
 

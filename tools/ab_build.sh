@@ -1,12 +1,12 @@
 #!/bin/bash
-# Build an alternative libhctr_hip.so with extra compile flags for a same-box A/B (run here, no GPU needed):
-#   bash tools/ab_build.sh <name> -DNOPRIO=1     ->  gpurun_out/ab/<name>.so     (travels with the snapshot? no:
-# gpurun_out/ is not sent - the library is written to ab_libs/<name>.so, which is git-ignored via *.so)
-# Use on the GPU box:  HCTR_LIB_PATH=ab_libs/<name>.so python bench.py ...
+# Build an alternative libhctr_hip.so for a same-box A/B (no GPU needed): this tree's sources, or another revision's
+# (HCTR_SRC=<its csrc directory>), with extra compiler flags. The kernels carry no -D build switches of their own.
+#   [HCTR_SRC=<dir>] bash tools/ab_build.sh <name> [flags...]     ->  ab_libs/<name>.so   (git-ignored via *.so)
+# Use on the GPU box:  HCTR_LIB_PATH=ab_libs/<name>.so python bench.py ...   or tools/gpu_ab_bench.sh
 set -e
 NAME=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-SRC=$ROOT/handwritten-chinese-ocr-samples_amd/csrc
+SRC=${HCTR_SRC:-$ROOT/handwritten-chinese-ocr-samples_amd/csrc}
 OUT=$ROOT/ab_libs; mkdir -p $OUT/obj_$NAME
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 COMMON="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function"

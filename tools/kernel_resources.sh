@@ -2,8 +2,9 @@
 # Register / scratch / LDS usage of every kernel in csrc/kernels.hip (hipcc -Rpass-analysis=kernel-resource-usage):
 #   bash tools/kernel_resources.sh [filter-regex]
 # A non-zero ScratchSize on an MFMA kernel means spills: far more expensive than the instructions suggest.
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c /root/repo/handwritten-chinese-ocr-samples_amd/csrc/kernels.hip \
+${HIPCC:-/opt/rocm/bin/hipcc} --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c $ROOT/handwritten-chinese-ocr-samples_amd/csrc/kernels.hip \
   -o /tmp/kernel_resources.o -Rpass-analysis=kernel-resource-usage 2>&1 | python3 -c '
 import re, sys
 cur = {}
