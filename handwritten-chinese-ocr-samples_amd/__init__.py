@@ -8,12 +8,13 @@ Public surface = the reference's surface for this path:
   hctr_model   drop-in for models/handwritten_ctr_model.py:156 (engine-backed)
   ctc_codec    drop-in for utils/ctc_codec.py:14                (engine-backed)
   CTCLoss      drop-in for the criterion of main.py:205           (engine-backed, with backward())
+  CTCAligner   forced alignment: character spans and confidences  (engine-backed; no counterpart)
 plus ``synth`` (deterministic synthetic checkpoints / line images) and ``build`` / ``load_library``.
 """
 from . import preprocess, synth  # noqa: F401
 from ._lib import build, load as load_library  # noqa: F401
 from .codec import ArpaLM, ToyBigramLM, ZeroLM, ctc_codec  # noqa: F401
-from .ctc import CTCLoss  # noqa: F401
+from .ctc import CTCAligner, CTCAlignment, CTCLoss  # noqa: F401
 from .model import hctr_model  # noqa: F401
 
-__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]
+__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]

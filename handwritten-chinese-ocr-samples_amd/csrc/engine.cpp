@@ -1111,6 +1111,70 @@ int ctc_scratch(hctr_ctx* c, const CtcHost& h, size_t emis_floats, CtcLines* m, 
     return HCTR_OK;
 }
 
+// forced alignment (hctr_ctc_align*): the scratch beyond the loss's, carved from ctc_scratch's `extra` block
+struct AlignDev {
+    std::vector<int64_t> boff;    // [B] byte offset of each line's backpointer rows (host copy)
+    size_t total = 0;             // sum L
+    int64_t* d_boff = nullptr;
+    int32_t *d_end = nullptr, *d_path = nullptr, *d_st = nullptr, *d_en = nullptr;
+    float* d_lp = nullptr;
+    uint8_t* d_bp = nullptr;
+    size_t boff_b = 0, end_b = 0, path_b = 0, span_b = 0, bp_b = 0;
+    size_t bytes() const { return boff_b + end_b + path_b + 3 * span_b + bp_b; }
+};
+
+void align_layout(const CtcHost& h, int W, AlignDev* a) {
+    const int B = h.B, ns = ctc_viterbi_lane_states(h.max_states);
+    const int32_t *hT = h.tab.data(), *hL = hT + B;
+    a->total = h.tab.size() - 4 * (size_t)B - (size_t)B * h.D;
+    a->boff.assign((size_t)B, 0);
+    int64_t bytes = 0;
+    for (int b = 0; b < B; ++b) {
+        a->boff[(size_t)b] = bytes;
+        bytes += (int64_t)hT[b] * ((2 * (int64_t)hL[b] + ns) / ns);     // T * ceil((2L + 1) / ns); none without an alignment
+    }
+    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    a->boff_b = al((size_t)B * 8); a->end_b = al((size_t)B * 4); a->path_b = al((size_t)B * W * 4);
+    a->span_b = al(a->total * 4); a->bp_b = al((size_t)bytes);
+}
+
+void align_carve(char* extra, AlignDev* a) {
+    a->d_boff = (int64_t*)extra;
+    a->d_end = (int32_t*)(extra + a->boff_b);
+    a->d_path = (int32_t*)(extra + a->boff_b + a->end_b);
+    char* sp = extra + a->boff_b + a->end_b + a->path_b;
+    a->d_st = (int32_t*)sp; a->d_en = (int32_t*)(sp + a->span_b); a->d_lp = (float*)(sp + 2 * a->span_b);
+    a->d_bp = (uint8_t*)(sp + 3 * a->span_b);
+}
+
+// recursion and back-trace of the pass's lines [b0, b0 + nb) over their emissions
+hipError_t align_launch(hctr_ctx* c, Prof& pf, const float* emis, const CtcLines& m, const CtcHost& h, const AlignDev& a,
+                        int b0, int nb, int W, float* d_score) {
+    pf.begin("ctc_viterbi");
+    hipError_t e = launch_ctc_viterbi(emis, m, b0, nb, W, h.max_states, a.d_boff, a.d_bp, d_score, a.d_end, c->stream);
+    pf.end();
+    if (e != hipSuccess) return e;
+    pf.begin("ctc_backtrace");
+    e = launch_ctc_backtrace(emis, m, b0, nb, W, h.max_states, a.d_boff, a.d_bp, a.d_end, a.d_path, a.d_st, a.d_en, a.d_lp,
+                             c->stream);
+    pf.end();
+    return e;
+}
+
+hipError_t align_fetch(hctr_ctx* c, const AlignDev& a, int B, int W, const float* d_score, int32_t* path,
+                       int32_t* span_start, int32_t* span_end, float* span_logp, float* score) {
+    hipError_t e = hipSuccess;
+    if (path) e = hipMemcpyAsync(path, a.d_path, (size_t)B * W * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && span_start && a.total)
+        e = hipMemcpyAsync(span_start, a.d_st, a.total * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && span_end && a.total)
+        e = hipMemcpyAsync(span_end, a.d_en, a.total * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && span_logp && a.total)
+        e = hipMemcpyAsync(span_logp, a.d_lp, a.total * 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && score) e = hipMemcpyAsync(score, d_score, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
+    return e;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1928,6 +1992,109 @@ int hctr_ctc_loss_logits_grad(hctr_ctx* c, const float* logits_wbc, int on_devic
             if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_loss_logits_grad: %s", hipGetErrorString(e));
         }
         // the host tables above are pageable: their copies were staged before hipMemcpyAsync returned
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
+        free_pool(tmp);
+        return rc;
+    });
+}
+
+int hctr_ctc_align(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
+                   const int32_t* targets, const int32_t* target_lengths, const int32_t* input_lengths, int32_t* path,
+                   int32_t* span_start, int32_t* span_end, float* span_logp, float* score) {
+    return guard(c, [&]() -> int {
+        TRY(check_forward_args(c, img, img_dtype, B, W));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        const int C = c->num_classes;
+        CtcHost h;
+        TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
+        SplitScope scope(c);
+        c->split = c->mode != 0;                  // mode 2 aligns every line in f16x3, like hctr_ctc_loss
+        if (!c->wts().built) return fail(c, HCTR_ERR_STATE, "the weight set of this precision mode is not resident");
+        prof_reset(c);
+        const int nbmax = sub_batch(c, B, W, c->split);
+        AlignDev a;
+        align_layout(h, W, &a);
+        CtcLines m;
+        float *d_score = nullptr, *emis = nullptr;
+        char* extra = nullptr;
+        TRY(ctc_scratch(c, h, (size_t)nbmax * W * h.D, &m, &d_score, &emis, a.bytes() + 16, &extra));
+        align_carve(extra, &a);
+        HIP_TRY(c, hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
+        std::vector<int> all((size_t)B);
+        for (int b = 0; b < B; ++b) all[(size_t)b] = b;
+        // one pass: the lines [b0, b0 + nb) through the forward into stored logits, then emissions, recursion, back-trace
+        auto pass = [&](int b0, int nb) -> int {
+            TRY(ensure_workspace(c, nb, W, ws_need(c, HEAD_LOGITS)));
+            TRY(stage_input(c, img, img_dtype, img_on_device, widths, all.data() + b0, nb, W));
+            TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, HEAD_LOGITS, false));
+            Prof pf(c);
+            pf.begin("ctc_lse");
+            HIP_TRY(c, launch_ctc_lse(c->ws.logits, c->cpad, W, 1, C, m, b0, nb, W, emis, c->stream));
+            pf.end();
+            HIP_TRY(c, align_launch(c, pf, emis, m, h, a, b0, nb, W, d_score));
+            return HCTR_OK;
+        };
+        int rc = HCTR_OK;
+        for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax) rc = pass(b0, std::min(nbmax, B - b0));
+        if (rc == HCTR_OK) {
+            hipError_t e = align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
+            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "D2H alignment: %s", hipGetErrorString(e));
+        }
+        // the host table above is pageable: its copy was staged before hipMemcpyAsync returned
+        hipError_t e = hipStreamSynchronize(c->stream);
+        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
+        return rc;
+    });
+}
+
+int hctr_ctc_align_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W, int B, int C, const int32_t* targets,
+                          const int32_t* target_lengths, const int32_t* input_lengths, int32_t* path, int32_t* span_start,
+                          int32_t* span_end, float* span_logp, float* score) {
+    return guard(c, [&]() -> int {
+        if (!c) return HCTR_ERR_ARG;
+        if (W < 0 || B < 0 || C < 2) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
+        if (B == 0) return HCTR_OK;
+        if (W < 1) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
+        if (!logits_wbc) return fail(c, HCTR_ERR_ARG, "NULL pointer");
+        HIP_TRY(c, hipSetDevice(c->device));
+        CtcHost h;
+        TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
+        prof_reset(c);
+        AlignDev a;
+        align_layout(h, W, &a);
+        std::vector<void*> tmp;
+        PoolGuard tmp_guard{tmp};
+        CtcLines m;
+        float *d_score = nullptr, *emis = nullptr, *up = nullptr;
+        char* extra = nullptr;
+        TRY(ctc_scratch(c, h, (size_t)B * W * h.D, &m, &d_score, &emis, a.bytes() + 16, &extra));
+        align_carve(extra, &a);
+        const float* dev = logits_wbc;
+        int rc = HCTR_OK;
+        if (!on_device) {
+            const size_t n = (size_t)W * B * C;
+            rc = dev_alloc(c, tmp, &up, n, false);
+            if (rc == HCTR_OK) {
+                hipError_t e = hipMemcpyAsync(up, logits_wbc, n * 4, hipMemcpyHostToDevice, c->stream);
+                if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "H2D logits: %s", hipGetErrorString(e));
+            }
+            dev = up;
+        }
+        if (rc == HCTR_OK) {
+            hipError_t e = hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream);
+            Prof pf(c);
+            if (e == hipSuccess) {
+                // rows of the WBC tensor are r = t*B + b
+                pf.begin("ctc_lse");
+                e = launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, c->stream);
+                pf.end();
+            }
+            if (e == hipSuccess) e = align_launch(c, pf, emis, m, h, a, 0, B, W, d_score);
+            if (e == hipSuccess) e = align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
+            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_align_logits: %s", hipGetErrorString(e));
+        }
         hipError_t e = hipStreamSynchronize(c->stream);
         if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
         free_pool(tmp);

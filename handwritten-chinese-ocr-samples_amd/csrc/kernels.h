@@ -226,6 +226,21 @@ hipError_t launch_ctc_grad_rows(const float* x, int C, int B, int W, const CtcLi
                                 const float* nll, const float* wt, const int64_t* aoff, const float* ast,
                                 const int32_t* soff, const int32_t* pos, float* grad, hipStream_t s);
 
+// forced alignment (hctr_ctc_align*) over the emissions of launch_ctc_lse, the instances of launch_ctc_alpha:
+// launch_ctc_viterbi: the max-plus recursion; the lane of states [i*NS, i*NS + NS) stores its 2-bit backpointers (0, 1
+//   or 2 states down; state k of the lane at bits 2k) of step t >= 1 at bp[boff[gb] + t * ceil(S_gb / NS) + i], with
+//   NS = ctc_viterbi_lane_states(max_states); score[gb] = the best path's log-probability, endst[gb] its last state
+//   (-inf and -1 for a line with T = 0);
+// launch_ctc_backtrace: path[gb*W + t] = class of the best path at step t (-1 for t >= T), and for target position j of
+//   the line, at off[gb] + j: its first step, the step after its last and the float32 sum of its emissions (-1, -1,
+//   -inf for a line with T = 0).
+constexpr int ctc_viterbi_lane_states(int max_states) { return max_states <= 64 ? 1 : max_states <= 2048 ? 2 : 4; }
+hipError_t launch_ctc_viterbi(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states,
+                              const int64_t* boff, uint8_t* bp, float* score, int32_t* endst, hipStream_t s);
+hipError_t launch_ctc_backtrace(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states,
+                                const int64_t* boff, const uint8_t* bp, const int32_t* endst, int32_t* path,
+                                int32_t* span_start, int32_t* span_end, float* span_logp, hipStream_t s);
+
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {
     int64_t src_off;          // byte offset of the image inside the packed source buffer

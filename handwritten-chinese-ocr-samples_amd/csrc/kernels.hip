@@ -3457,4 +3457,235 @@ hipError_t launch_ctc_grad_rows(const float* x, int C, int B, int W, const CtcLi
     return hipGetLastError();
 }
 
+// -------------------------------------------------------------------------------------------
+// CTC forced alignment (hctr_ctc_align*): the best path of a known transcription over the emissions of ctc_lse_kernel.
+// ctc_viterbi_kernel is the max-plus sibling of ctc_alpha_line with 2-bit backpointers, ctc_backtrace_kernel walks
+// them back and writes the path, the character spans and their log-probabilities.
+// -------------------------------------------------------------------------------------------
+
+// Same lane / wave state layout, neighbour hand-over and emission prefetch as ctc_alpha_line; the step is
+// v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), [l_s != l_{s-2}] v_{t-1}(s-2)) + lp_t(s) in float32. Ties are part of the
+// contract: a predecessor replaces the running best only when strictly greater, in the order s, s-1, s-2. The choice
+// (0, 1 or 2 states down) of the lane's NS states is packed into one byte, state i at bits 2i, and stored at
+// bp[boff[gb] + t * ceil(S / NS) + lane index] for t >= 1: consecutive lanes, consecutive bytes. score[gb] is the
+// better of v_{T-1}(S-1) and v_{T-1}(S-2) (S-1 on a tie; state 0 for L = 0) and endst[gb] that state; a line marked
+// T = 0 gets -inf and -1.
+template <int NS, int PF, int NW>
+__global__ __launch_bounds__(64 * NW) void ctc_viterbi_kernel(const float* __restrict__ emis, const CtcLines m, int b0,
+                                                               int W, const int64_t* __restrict__ boff,
+                                                               uint8_t* __restrict__ bp, float* __restrict__ score,
+                                                               int32_t* __restrict__ endst) {
+    static_assert(NW == 1 || NS >= 2, "a wave boundary hands over two states from one lane");
+    static_assert(NS <= 4, "one byte holds the backpointers of a lane");
+    __shared__ float xb[2][NW][2];                 // [step parity][wave] = {state wave_end-1, state wave_end-2}
+    __shared__ float fin[2];
+    const int b = blockIdx.x, gb = b0 + b, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int T = m.T[gb], L = m.L[gb], S = 2 * L + 1;
+    if (T == 0) {                                  // no alignment (host-side feasibility test); block-uniform
+        if (tid == 0) {
+            score[gb] = -INFINITY;
+            endst[gb] = -1;
+        }
+        return;
+    }
+    const int32_t* ts = m.slot + m.off[gb];
+    int slot[NS];
+    bool skip[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int s = tid * NS + i;
+        const bool lab = (s & 1) && s < S;
+        slot[i] = lab ? ts[s >> 1] : 0;
+        skip[i] = lab && s >= 3 && ts[s >> 1] != ts[(s >> 1) - 1];
+    }
+    const int D = m.D;
+    const float* base = emis + (int64_t)b * W * D;
+    float a[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int s = tid * NS + i;
+        a[i] = (s == 0 || (s == 1 && S > 1)) ? base[slot[i]] : -INFINITY;
+    }
+    const int stride = (S + NS - 1) / NS;          // bytes per step: the lanes that hold a state
+    const bool own = tid < stride;
+    uint8_t* brow = bp + boff[gb] + tid;
+    auto publish = [&](int parity) {
+        if (NW > 1) {
+            if (lane == 63) {
+                xb[parity][wv][0] = a[NS - 1];
+                xb[parity][wv][1] = a[NS >= 2 ? NS - 2 : 0];
+            }
+            __syncthreads();
+        }
+    };
+    publish(0);
+    float e[PF][NS];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) {
+        const float* r = base + (int64_t)min(1 + k, T - 1) * D;
+#pragma unroll
+        for (int i = 0; i < NS; ++i) e[k][i] = r[slot[i]];
+    }
+    for (int t0 = 1; t0 < T; t0 += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+            const int t = t0 + k;
+            if (t < T) {                           // (block-uniform)
+                float p1 = __shfl_up(a[NS - 1], 1);
+                float p2 = NS >= 2 ? __shfl_up(a[NS >= 2 ? NS - 2 : 0], 1) : __shfl_up(a[NS - 1], 2);
+                if (lane == 0) {
+                    p1 = wv > 0 ? xb[(t - 1) & 1][wv > 0 ? wv - 1 : 0][0] : -INFINITY;
+                    p2 = wv > 0 ? xb[(t - 1) & 1][wv > 0 ? wv - 1 : 0][1] : -INFINITY;
+                }
+                if (NS == 1 && lane == 1) p2 = -INFINITY;      // (NS == 1 only with NW == 1)
+                unsigned code = 0;
+#pragma unroll
+                for (int i = NS - 1; i >= 0; --i) {      // descending: a[i-1], a[i-2] still hold step t-1
+                    const float la2 = i >= 1 ? a[i >= 1 ? i - 1 : 0] : p1;
+                    const float la3 = skip[i] ? (i >= 2 ? a[i >= 2 ? i - 2 : 0] : (i == 1 ? p1 : p2)) : -INFINITY;
+                    float best = a[i];
+                    unsigned from = 0;
+                    if (la2 > best) { best = la2; from = 1; }
+                    if (la3 > best) { best = la3; from = 2; }
+                    a[i] = best + e[k][i];
+                    code |= from << (2 * i);
+                }
+                if (own) brow[(int64_t)t * stride] = (uint8_t)code;
+                publish(t & 1);
+            }
+            const float* r = base + (int64_t)min(t + PF, T - 1) * D;   // refill the slot just used
+#pragma unroll
+            for (int i = 0; i < NS; ++i) e[k][i] = r[slot[i]];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int s = tid * NS + i;
+        if (s == S - 1) fin[0] = a[i];
+        if (s == S - 2) fin[1] = a[i];
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const bool last = L == 0 || fin[0] >= fin[1];
+        score[gb] = last ? fin[0] : fin[1];
+        endst[gb] = last ? S - 1 : S - 2;
+    }
+}
+
+// One 256-thread workgroup per line. The walk t = T-1 .. 1 is serial and every step's read depends on the one before,
+// so the backpointers are staged kBtSteps steps at a time in LDS: the state falls by at most two per step, so step r of
+// a chunk that starts in state s can only need the bytes of the states [s - 2r, s] of its row. All threads load the
+// window (independent byte loads, all in flight together), then every thread walks the chunk on LDS broadcasts with
+// the same scalar state; thread 0 stores the state of every step and, where the state changes, the span ends. After
+// the walk the steps are mapped to classes and the spans' log-probabilities summed (ascending t, float32) in parallel.
+// sh = log2 of the recursion instance's states per lane. Lines without an alignment: path and spans -1, logp -inf.
+constexpr int kBtSteps = 32;
+__global__ __launch_bounds__(256) void ctc_backtrace_kernel(const float* __restrict__ emis, const CtcLines m, int b0, int W,
+                                                            int sh, const int64_t* __restrict__ boff,
+                                                            const uint8_t* __restrict__ bp,
+                                                            const int32_t* __restrict__ endst, int32_t* __restrict__ path,
+                                                            int32_t* __restrict__ sstart, int32_t* __restrict__ send,
+                                                            float* __restrict__ slogp) {
+    constexpr int WB = 2 * kBtSteps + 2;           // window bytes per step at one state per byte (sh = 0)
+    __shared__ uint8_t win[kBtSteps][WB];
+    const int b = blockIdx.x, gb = b0 + b, tid = threadIdx.x;
+    const int T = m.T[gb], L = m.L[gb], S = 2 * L + 1;
+    const int32_t* ts = m.slot + m.off[gb];
+    int32_t* P = path + (int64_t)gb * W;
+    int32_t* st = sstart + m.off[gb];
+    int32_t* en = send + m.off[gb];
+    float* lg = slogp + m.off[gb];
+    for (int j = tid; j < L; j += 256) {
+        st[j] = -1;
+        en[j] = -1;
+        lg[j] = -INFINITY;
+    }
+    if (T == 0) {                                  // (block-uniform)
+        for (int t = tid; t < W; t += 256) P[t] = -1;
+        return;
+    }
+    __syncthreads();                               // thread 0 overwrites the spans below
+    const int stride = (S + (1 << sh) - 1) >> sh, smask = (1 << sh) - 1;
+    const uint8_t* rows = bp + boff[gb];
+    int s = min(max(endst[gb], 0), S - 1);
+    int above = -1;                                // state of step t + 1
+    for (int t0 = T - 1; t0 >= 1; t0 -= kBtSteps) {
+        const int n = min(kBtSteps, t0);           // steps t0, t0-1, ..., t0-n+1 read rows of the same numbers
+        const int hi = s >> sh, lo = max(s - 2 * (n - 1), 0) >> sh, wb = hi - lo + 1;      // wb <= WB
+        for (int idx = tid; idx < n * wb; idx += 256) {
+            const int r = idx / wb, col = lo + idx % wb;
+            if (col >= (max(s - 2 * r, 0) >> sh)) win[r][col - lo] = rows[(int64_t)(t0 - r) * stride + col];
+        }
+        __syncthreads();
+        for (int r = 0; r < n; ++r) {
+            const int t = t0 - r;
+            const int from = (win[r][(s >> sh) - lo] >> (2 * (s & smask))) & 3;
+            if (tid == 0) {
+                P[t] = s;
+                if (s & 1) {
+                    if (s != above) en[s >> 1] = t + 1;
+                    if (from) st[s >> 1] = t;
+                }
+            }
+            above = s;
+            s = __builtin_amdgcn_readfirstlane(max(s - from, 0));
+        }
+        __syncthreads();                           // the window is loaded again
+    }
+    if (tid == 0) {                                // step 0 has no predecessor
+        P[0] = s;
+        if (s & 1) {
+            if (s != above) en[s >> 1] = 1;
+            st[s >> 1] = 0;
+        }
+    }
+    __syncthreads();
+    const int32_t* cls = m.cls + (int64_t)gb * m.D;
+    for (int t = tid; t < W; t += 256) {
+        const int v = t < T ? P[t] : -1;
+        P[t] = v < 0 ? -1 : ((v & 1) ? cls[ts[v >> 1]] : 0);
+    }
+    const int D = m.D;
+    const float* base = emis + (int64_t)b * W * D;
+    for (int j = tid; j < L; j += 256) {
+        const int t1 = st[j], t2 = en[j];
+        if (t1 < 0 || t2 <= t1) continue;
+        const float* q = base + ts[j];
+        float acc = q[(int64_t)t1 * D];
+        for (int t = t1 + 1; t < t2; ++t) acc += q[(int64_t)t * D];
+        lg[j] = acc;
+    }
+}
+
+hipError_t launch_ctc_viterbi(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states,
+                              const int64_t* boff, uint8_t* bp, float* score, int32_t* endst, hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+#define CTC_VITERBI(NS, PF, NW)                                                                                        \
+    if (max_states <= 64 * NS * NW) {                                                                                  \
+        static_assert(NS == ctc_viterbi_lane_states(64 * NS * NW), "the back-trace unpacks NS states per byte");  \
+        hipLaunchKernelGGL((ctc_viterbi_kernel<NS, PF, NW>), dim3((unsigned)nb), dim3(64 * NW), 0, s, emis, m, b0, W,  \
+                           boff, bp, score, endst);                                                                    \
+        return hipGetLastError();                                                                                      \
+    }
+    CTC_VITERBI(1, 4, 1)                           // the ladder of launch_ctc_alpha
+    CTC_VITERBI(2, 4, 1)
+    CTC_VITERBI(2, 4, 2)
+    CTC_VITERBI(2, 4, 4)
+    CTC_VITERBI(2, 4, 8)
+    CTC_VITERBI(2, 4, 16)
+    CTC_VITERBI(4, 2, 16)
+#undef CTC_VITERBI
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_ctc_backtrace(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states,
+                                const int64_t* boff, const uint8_t* bp, const int32_t* endst, int32_t* path,
+                                int32_t* span_start, int32_t* span_end, float* span_logp, hipStream_t s) {
+    if (nb <= 0 || max_states > kCtcMaxStates) return nb <= 0 ? hipSuccess : hipErrorInvalidValue;
+    const int ns = ctc_viterbi_lane_states(max_states), sh = ns == 1 ? 0 : ns == 2 ? 1 : 2;
+    hipLaunchKernelGGL(ctc_backtrace_kernel, dim3((unsigned)nb), dim3(256), 0, s, emis, m, b0, W, sh, boff, bp, endst, path,
+                       span_start, span_end, span_logp);
+    return hipGetLastError();
+}
+
 }  // namespace hctr

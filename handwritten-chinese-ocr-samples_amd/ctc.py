@@ -6,6 +6,9 @@ target_lengths)``), differentiable when its input requires a gradient; ``hctr_mo
 without the logits ever leaving the device (forward only: the engine's trunk has no backward pass). All run the C ABI's
 ``hctr_ctc_loss*`` (include/hctr_hip.h); target normalisation, the reductions and the per-line gradient weights are the
 host-side helpers below, with the semantics of ``torch.nn.CTCLoss``.
+
+``CTCAligner`` and ``hctr_model.align`` are the third member: the best path of a known transcription
+(``hctr_ctc_align*``), which says where in the line each character lies and how confident the engine is of it.
 """
 import ctypes
 
@@ -170,6 +173,66 @@ def loss_grad_logits(ctx, logits, on_dev, targets, target_lengths, input_lengths
     return nll, grad
 
 
+class CTCAlignment(object):
+    """Result of a forced alignment of B lines of W steps (numpy arrays, on the host):
+    ``paths`` int32 [B, W], the class of the best path at every step (0 = blank, -1 past a line's input length);
+    ``scores`` float32 [B], the best path's log-probability; ``starts`` / ``ends`` int32 and ``logps`` float32
+    [sum L], per target position the first step, the step after the last and the sum of the label's log-probabilities
+    over them; ``offsets`` int64 [B + 1], where each line's positions begin; ``targets`` int32 [sum L]. A line with no
+    alignment has score -inf, -1 everywhere and logps -inf."""
+
+    def __init__(self, paths, scores, starts, ends, logps, targets, target_lengths):
+        self.paths, self.scores = paths, scores
+        self.starts, self.ends, self.logps = starts, ends, logps
+        self.targets = targets
+        self.offsets = np.concatenate([[0], np.cumsum(np.asarray(target_lengths, np.int64))]).astype(np.int64)
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def lines(self):
+        """yields per line the list of (label, start, end, confidence), one per character: its pixel-column span
+        [start, end) and the geometric mean of its probability over the span, exp(logp / (end - start)), in (0, 1];
+        (label, -1, -1, 0.0) for the characters of a line with no alignment."""
+        for b in range(len(self)):
+            out = []
+            for j in range(int(self.offsets[b]), int(self.offsets[b + 1])):
+                st, en = int(self.starts[j]), int(self.ends[j])
+                conf = float(np.exp(np.float64(self.logps[j]) / (en - st))) if en > st else 0.0
+                out.append((int(self.targets[j]), st, en, conf))
+            yield out
+
+
+def _align_outputs(B, W, total):
+    return (np.empty((B, W), np.int32), np.empty((total,), np.int32), np.empty((total,), np.int32),
+            np.empty((total,), np.float32), np.empty((B,), np.float32))
+
+
+def align_logits(ctx, logits, on_dev, targets, target_lengths, input_lengths):
+    """CTCAlignment of caller logits / log-probs in WBC layout (hctr_ctc_align_logits)."""
+    W, B, C = (int(v) for v in logits.shape)
+    tg, tl = normalize_targets(targets, target_lengths, B)
+    il = normalize_input_lengths(input_lengths, B)
+    path, st, en, lp, score = _align_outputs(B, W, int(tg.size))
+    if B:
+        _lib.check(_lib.load().hctr_ctc_align_logits(ctx, _lib.ptr(logits), on_dev, W, B, C, _lib.ptr(tg), _lib.ptr(tl),
+                                                     _lib.ptr(il), _lib.ptr(path), _lib.ptr(st), _lib.ptr(en),
+                                                     _lib.ptr(lp), _lib.ptr(score)), ctx)
+    return CTCAlignment(path, score, st, en, lp, tg, tl)
+
+
+def align_images(ctx, x, dt, on_dev, widths, B, W, targets, target_lengths, input_lengths):
+    """CTCAlignment of line images (hctr_ctc_align); x, dt, on_dev, widths as hctr_model._img_args / _widths give them."""
+    tg, tl = normalize_targets(targets, target_lengths, B)
+    il = normalize_input_lengths(input_lengths, B)
+    path, st, en, lp, score = _align_outputs(B, W, int(tg.size))
+    if B:
+        _lib.check(_lib.load().hctr_ctc_align(ctx, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, _lib.ptr(tg),
+                                              _lib.ptr(tl), _lib.ptr(il), _lib.ptr(path), _lib.ptr(st), _lib.ptr(en),
+                                              _lib.ptr(lp), _lib.ptr(score)), ctx)
+    return CTCAlignment(path, score, st, en, lp, tg, tl)
+
+
 _FN = None
 
 
@@ -214,23 +277,11 @@ def _autograd_fn():
     return _FN
 
 
-class CTCLoss(object):
-    """Drop-in for the reference's criterion ``CTCLoss(zero_infinity=True)`` (main.py:205) on the engine:
-    ``criterion(log_probs_or_logits, targets, input_lengths, target_lengths)`` with ``[T, B, C]`` input - raw logits or
-    log-probs give the same result (log_softmax is idempotent). A torch input that requires a gradient gets a loss with
-    a ``grad_fn``: ``loss.backward()`` deposits ``w_b * (softmax - posterior occupancy)`` in the input's ``.grad``, the
-    derivative in raw logits and, for log-probs, what torch's own ctc_loss hands to the ``log_softmax`` before it (which
-    passes it through unchanged). ``loss_and_grad`` is the same without autograd. Bind it to a GPU with
-    ``.cuda(device)``, or share an hctr_model's engine context with ``.attach(model)``. Only blank=0 is supported."""
+class _EngineBound(object):
+    """context handling shared by CTCLoss and CTCAligner: a lazy weightless context on a chosen GPU, or an attached
+    hctr_model's"""
 
-    def __init__(self, blank=0, reduction="mean", zero_infinity=False):
-        if blank != 0:
-            raise NotImplementedError("the engine's CTC loss uses blank = 0 (the reference's codec)")
-        if reduction not in _REDUCTIONS:
-            raise ValueError("reduction must be one of %s" % (_REDUCTIONS,))
-        self.blank = blank
-        self.reduction = reduction
-        self.zero_infinity = zero_infinity
+    def __init__(self):
         self._ctx = None
         self._model = None
         self._device = 0
@@ -246,7 +297,7 @@ class CTCLoss(object):
         s = str(device)
         if s.startswith("cuda"):
             return self.cuda(int(s.split(":")[1]) if ":" in s else 0)
-        raise ValueError("the engine's CTC loss runs on a GPU only")
+        raise ValueError("the engine's CTC kernels run on a GPU only")
 
     def attach(self, model):
         self._drop_ctx()
@@ -276,6 +327,48 @@ class CTCLoss(object):
             self._drop_ctx()
         except Exception:
             pass
+
+
+class CTCAligner(_EngineBound):
+    """Forced alignment on the engine: ``CTCAligner().cuda(0)(log_probs_or_logits, targets, input_lengths,
+    target_lengths)`` with the arguments of ``CTCLoss`` (``[T, B, C]`` numpy array or torch tensor, a CUDA tensor is read
+    in place; targets 1-D concatenated or 2-D padded) returns the ``CTCAlignment`` of every line's best path: per
+    character its pixel-column span and log-probability, per line the path and its score. Only blank=0 is supported."""
+
+    def __init__(self, blank=0):
+        if blank != 0:
+            raise NotImplementedError("the engine's CTC kernels use blank = 0 (the reference's codec)")
+        _EngineBound.__init__(self)
+        self.blank = blank
+
+    def forward(self, log_probs, targets, input_lengths, target_lengths):
+        from .codec import ctc_codec
+        if _is_torch(log_probs):
+            log_probs = log_probs.detach()
+        logits, on_dev = ctc_codec._as_logits(log_probs)
+        return align_logits(self._context(), logits, on_dev, targets, target_lengths, input_lengths)
+
+    __call__ = forward
+
+
+class CTCLoss(_EngineBound):
+    """Drop-in for the reference's criterion ``CTCLoss(zero_infinity=True)`` (main.py:205) on the engine:
+    ``criterion(log_probs_or_logits, targets, input_lengths, target_lengths)`` with ``[T, B, C]`` input - raw logits or
+    log-probs give the same result (log_softmax is idempotent). A torch input that requires a gradient gets a loss with
+    a ``grad_fn``: ``loss.backward()`` deposits ``w_b * (softmax - posterior occupancy)`` in the input's ``.grad``, the
+    derivative in raw logits and, for log-probs, what torch's own ctc_loss hands to the ``log_softmax`` before it (which
+    passes it through unchanged). ``loss_and_grad`` is the same without autograd. Bind it to a GPU with
+    ``.cuda(device)``, or share an hctr_model's engine context with ``.attach(model)``. Only blank=0 is supported."""
+
+    def __init__(self, blank=0, reduction="mean", zero_infinity=False):
+        if blank != 0:
+            raise NotImplementedError("the engine's CTC loss uses blank = 0 (the reference's codec)")
+        if reduction not in _REDUCTIONS:
+            raise ValueError("reduction must be one of %s" % (_REDUCTIONS,))
+        _EngineBound.__init__(self)
+        self.blank = blank
+        self.reduction = reduction
+        self.zero_infinity = zero_infinity
 
     def forward(self, log_probs, targets, input_lengths, target_lengths):
         from .codec import ctc_codec

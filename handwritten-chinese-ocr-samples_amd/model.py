@@ -260,6 +260,18 @@ class hctr_model(object):
                                              _lib.ptr(il), _lib.ptr(nll)), ctx)
         return ctc.wrap(ctc.reduce(nll, tl, reduction, zero_infinity), input)
 
+    def align(self, input, targets, target_lengths, input_lengths=None, widths=None):
+        """Forced alignment of line images against their transcriptions, the logits never leaving the device: where in
+        the line each character lies. Steps are pixel columns, so the spans are pixel-column ranges of ``input``.
+        Arguments as ``ctc_loss``. Returns a ``ctc.CTCAlignment`` (numpy arrays): ``paths`` [B, W], ``scores`` [B],
+        ``starts`` / ``ends`` / ``logps`` per character, ``offsets``, and ``lines()`` for (label, start, end,
+        confidence) per character. In "auto" precision every line is aligned in f16x3 (include/hctr_hip.h
+        ``hctr_ctc_align``)."""
+        from . import ctc
+        ctx = self._require_ctx()
+        x, dt, on_dev, B, W = self._img_args(input)
+        return ctc.align_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, targets, target_lengths, input_lengths)
+
     # -- precision mode ---------------------------------------------------------------------------
     def set_precision(self, precision):
         """Switch the mode of a loaded model among those whose weight set is resident (all three for a model built

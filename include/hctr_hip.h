@@ -190,6 +190,42 @@ int hctr_ctc_loss_logits_grad(hctr_ctx* ctx, const float* logits_wbc, int on_dev
                               const int32_t* targets, const int32_t* target_lengths, const int32_t* input_lengths,
                               const float* line_weight, float* nll, float* grad_wbc, int grad_on_device);
 
+/* ---- CTC forced alignment on the device: where each character of a known transcription lies -----------------
+ * Steps are pixel columns (one logit row per column, preds_sizes = [W] * B in main.py), so the best CTC path of a line's
+ * transcription gives each character's pixel span, a confidence for it, and the path's log-probability. The reference has
+ * no counterpart (utils/ctc_codec.py only decodes). Arguments, checks, error codes and the L <= 2047 limit as
+ * hctr_ctc_loss_logits / hctr_ctc_loss; B == 0 is a no-op.
+ * With lp_t(c) = z_t[c] - logsumexp(z_t) in float32 (the loss's emissions, bit for bit) and the extended states blank,
+ * l_1, blank, ..., l_L, blank (S = 2L + 1):
+ *   v_0(0) = lp_0(blank), v_0(1) = lp_0(l_1), -inf elsewhere;
+ *   v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), [l_s != l_{s-2}] v_{t-1}(s-2)) + lp_t(class of s), in float32.
+ * Ties are part of the contract: among equal predecessors s wins, then s-1, then s-2; the path ends in state S-1 if
+ * v_{T-1}(S-1) >= v_{T-1}(S-2), else in S-2 (state 0 for L = 0).
+ *   path:       int32 [B][W], host, or NULL: the class of the best path at every step t < T (0 = blank), -1 for t >= T.
+ *   span_start: int32 [sum L], host, in the order of `targets`, or NULL: the first step of each target position;
+ *   span_end:   the step after its last (a label's steps are contiguous), or NULL;
+ *   span_logp:  float32: the sum of lp_t(label) over those steps, ascending t (exp(span_logp / (end - start)) is the
+ *               geometric-mean probability, a per-character confidence), or NULL;
+ *   score:      float32 [B], host, or NULL: v_{T-1}(end state), the best path's log-probability (<= -nll).
+ * A line with no alignment (L + number of adjacent equal labels > T, the loss's test) gets score -inf, path -1
+ * everywhere, spans -1 and span_logp -inf.
+ * hctr_ctc_align runs the forward of img in internal passes and aligns the stored-logits head exactly as hctr_ctc_loss
+ * scores it: mode 0 f16, mode 1 f16x3, mode 2 EVERY line in f16x3, hctr_last_guard's figures left as they were.
+ * hctr_ctc_align_logits takes caller logits or log-probs in WBC layout, host or device pointer, and needs no weights.
+ * Device scratch (the context's grow-only CTC scratch; HCTR_ERR_NOMEM leaves the context usable): 4 * n*W*D (emissions;
+ * n = B, or the lines of one pass for images; D = the largest number of distinct classes of a line, blank included)
+ * + sum_b T_b * ceil((2 L_b + 1) / NS) (2-bit backpointers, one byte per NS states and step; NS = 1, 2 or 4 for a
+ * longest feasible target of <= 31, <= 1023 or more labels; lines without an alignment take none; 64 lines of 2000
+ * steps and 100 labels: 13 MB; worst case one line 2000 * 1024 = 2 MB) + 4 * B*W (path) + 12 * sum L (spans) + the
+ * per-line tables; plus W*B*C floats for logits passed as a host pointer. */
+int hctr_ctc_align(hctr_ctx* ctx, const void* img, int img_dtype, int img_on_device, const int32_t* widths,
+                   int B, int W, const int32_t* targets, const int32_t* target_lengths,
+                   const int32_t* input_lengths, int32_t* path, int32_t* span_start, int32_t* span_end,
+                   float* span_logp, float* score);
+int hctr_ctc_align_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C,
+                          const int32_t* targets, const int32_t* target_lengths, const int32_t* input_lengths,
+                          int32_t* path, int32_t* span_start, int32_t* span_end, float* span_logp, float* score);
+
 /* ---- host prefix beam search: replaces ctc_codec.__cbs_full__/__cbs_skip__ -------------------
  * utils/ctc_codec.py:124-285 (Beam :288-307), float64 accumulators over float32 log-probs.
  * The language model stays behind callbacks, as in the reference (kenlm / transformer objects are

@@ -15,7 +15,13 @@ line's greedy text as targets): loss only (hctr_ctc_loss_logits), loss + gradien
 preallocated device tensor) and torch.nn.functional.ctc_loss over log_softmax, forward + backward, on the same device
 tensors - alternately, after warm-up calls of each. --layers adds the device times of the gradient call's launches and
 the bytes per second of its two row passes (ctc_rowlse reads the logits once; ctc_grad_rows reads them once and writes
-the gradient once)."""
+the gradient once).
+
+    python tools/bench_ctc.py --align [--layers] ...
+
+times the forced alignment on the same caller logits and targets (hctr_ctc_align_logits, every output fetched) and, in
+the same run, the loss (hctr_ctc_loss_logits), alternately after warm-up calls of each. --layers adds the device times
+of the align call's launches: the emission pass, the recursion and the back-trace."""
 import argparse
 import json
 import os
@@ -37,6 +43,7 @@ def main():
     ap.add_argument("--precision", default="f16", choices=["f16", "f16x3", "auto"])
     ap.add_argument("--layers", action="store_true")
     ap.add_argument("--backward", action="store_true")
+    ap.add_argument("--align", action="store_true")
     args = ap.parse_args()
     import torch
     import hctr_amd
@@ -50,6 +57,9 @@ def main():
     targets = np.concatenate(labels).astype(np.int32)
     if args.backward:
         print(json.dumps(backward(args, hctr_amd, m, imgs, targets, tl)))
+        return
+    if args.align:
+        print(json.dumps(align(args, hctr_amd, m, imgs, targets, tl)))
         return
 
     def t_greedy():
@@ -158,6 +168,54 @@ def backward(args, hctr_amd, m, imgs, targets, tl):
             rec["ctc_rowlse_TBps"] = round(row / (1e-3 * gprof["ctc_rowlse"]) / 1e12, 3)
         if gprof.get("ctc_grad_rows"):
             rec["ctc_grad_rows_TBps"] = round(2 * row / (1e-3 * gprof["ctc_grad_rows"]) / 1e12, 3)
+    return rec
+
+
+def align(args, hctr_amd, m, imgs, targets, tl):
+    import torch
+    al = hctr_amd.CTCAligner().attach(m)
+    mod = sys.modules[type(al).__module__]
+    ctx = al._context()
+    logits = m(imgs)                                             # device tensor [W, lines, C]
+    W, B, C = (int(v) for v in logits.shape)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def loss_only():
+        assert np.isfinite(mod.loss_logits(ctx, logits, 1, targets, tl, None)).all()
+
+    def align_all():
+        assert np.isfinite(mod.align_logits(ctx, logits, 1, targets, tl, None).scores).all()
+
+    fns = (("loss_only", loss_only), ("align", align_all))
+    for _ in range(args.warmup):
+        for _, fn in fns:
+            fn()
+    ms = {k: [] for k, _ in fns}
+    for _ in range(args.steps):
+        for k, fn in fns:
+            ms[k].append(1e3 * timed(fn))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    rec = {"mode": "align", "lines": B, "width": W, "classes": C, "precision": args.precision,
+           "mean_target_length": float(tl.mean()), "max_target_length": int(tl.max())}
+    for k, v in ms.items():
+        rec[k + "_ms"] = [round(x, 3) for x in v]
+        rec[k + "_ms_median"] = round(med[k], 3)
+    rec["align_over_loss_only"] = round(med["align"] / med["loss_only"], 4)
+    if args.layers:
+        m.set_profiling(True)
+        loss_only()
+        fprof = dict(m.last_profile())
+        align_all()
+        aprof = dict(m.last_profile())
+        m.set_profiling(False)
+        rec["loss_only_layers_ms"] = {k: round(v, 4) for k, v in fprof.items()}
+        rec["align_layers_ms"] = {k: round(v, 4) for k, v in aprof.items()}
     return rec
 
 
