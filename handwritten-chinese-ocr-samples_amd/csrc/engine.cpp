@@ -270,6 +270,27 @@ struct PoolGuard {          // frees a call's temporaries on every exit path, ex
     ~PoolGuard() { free_pool(pool); }
 };
 
+constexpr size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// caller logits of n floats on the device: the caller's own pointer, or a pooled copy of the host's, queued on the stream
+int logits_on_device(hctr_ctx* c, std::vector<void*>& pool, const float* logits, int on_device, size_t n,
+                     const float** dev) {
+    *dev = logits;
+    if (on_device) return HCTR_OK;
+    float* up = nullptr;
+    TRY(dev_alloc(c, pool, &up, n, false));
+    *dev = up;
+    hipError_t e = hipMemcpyAsync(up, logits, n * 4, hipMemcpyHostToDevice, c->stream);
+    return e == hipSuccess ? HCTR_OK : fail(c, HCTR_ERR_HIP, "H2D logits: %s", hipGetErrorString(e));
+}
+
+// the end of a call that queued work: wait for the stream; a sync error does not mask an earlier one
+int synced(hctr_ctx* c, int rc) {
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
+    return rc;
+}
+
 // ---------------------------------------------------------------------------------------------
 // checkpoint ingest
 // ---------------------------------------------------------------------------------------------
@@ -1016,7 +1037,22 @@ struct SplitScope {
 struct CtcHost {
     std::vector<int32_t> tab;     // T[B] | L[B] | off[B] | nd[B] | cls[B][D] | slot[sum L], uploaded as one block
     int B = 0, D = 1, max_states = 1;
+    // the tables over a copy of tab at d: the host's own, or the device's
+    CtcLines lines(const int32_t* d) const {
+        const size_t b = (size_t)B;
+        return CtcLines{d, d + b, d + 2 * b, d + 3 * b, d + 4 * b, d + 4 * b + b * D, D};
+    }
+    CtcLines host() const { return lines(tab.data()); }
+    size_t total() const { return tab.size() - 4 * (size_t)B - (size_t)B * D; }      // sum L
 };
+
+// shape and pointer checks of the hctr_ctc_*_logits entries; B = 0 passes (the caller returns at once)
+int check_logits_args(hctr_ctx* c, int W, int B, int C, bool have_pointers) {
+    if (!c) return HCTR_ERR_ARG;
+    if (W < 0 || B < 0 || C < 2 || (B > 0 && W < 1)) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
+    if (B > 0 && !have_pointers) return fail(c, HCTR_ERR_ARG, "NULL pointer");
+    return HCTR_OK;
+}
 
 // torch.nn.functional.ctc_loss's conventions with blank 0: a target id outside [1, C-1] is an argument error; a line
 // with L + (adjacent equal labels) > T has no alignment and gets T = 0 (the kernel writes +inf without reading a row)
@@ -1086,8 +1122,8 @@ int ctc_prepare(hctr_ctx* c, int B, int W, int C, const int32_t* targets, const 
 // `extra_b` more bytes at *extra (256-byte aligned)
 int ctc_scratch(hctr_ctx* c, const CtcHost& h, size_t emis_floats, CtcLines* m, float** nll, float** emis,
                 size_t extra_b = 0, char** extra = nullptr) {
-    const size_t tab_b = (h.tab.size() * 4 + 255) & ~(size_t)255, nll_b = ((size_t)h.B * 4 + 255) & ~(size_t)255;
-    const size_t emis_b = extra_b ? (emis_floats * 4 + 255) & ~(size_t)255 : emis_floats * 4;
+    const size_t tab_b = align256(h.tab.size() * 4), nll_b = align256((size_t)h.B * 4);
+    const size_t emis_b = extra_b ? align256(emis_floats * 4) : emis_floats * 4;
     const size_t need = tab_b + nll_b + emis_b + extra_b;
     if (need > c->ctc_cap) {
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -1100,10 +1136,7 @@ int ctc_scratch(hctr_ctx* c, const CtcHost& h, size_t emis_floats, CtcLines* m, 
         c->ctc_buf = (char*)p;
         c->ctc_cap = need;
     }
-    const int32_t* d = (const int32_t*)c->ctc_buf;
-    const size_t B = (size_t)h.B;
-    m->T = d; m->L = d + B; m->off = d + 2 * B; m->nd = d + 3 * B; m->cls = d + 4 * B; m->slot = d + 4 * B + B * h.D;
-    m->D = h.D;
+    *m = h.lines((const int32_t*)c->ctc_buf);
     *nll = (float*)(c->ctc_buf + tab_b);
     *emis = (float*)(c->ctc_buf + tab_b + nll_b);
     if (extra) *extra = c->ctc_buf + tab_b + nll_b + emis_b;
@@ -1124,18 +1157,17 @@ struct AlignDev {
 };
 
 void align_layout(const CtcHost& h, int W, AlignDev* a) {
-    const int B = h.B, ns = ctc_viterbi_lane_states(h.max_states);
-    const int32_t *hT = h.tab.data(), *hL = hT + B;
-    a->total = h.tab.size() - 4 * (size_t)B - (size_t)B * h.D;
+    const int B = h.B, ns = ctc_viterbi_lane_states(h.max_states);      // >= 1: ctc_prepare holds max_states to the ladder
+    const int32_t *hT = h.host().T, *hL = h.host().L;
+    a->total = h.total();
     a->boff.assign((size_t)B, 0);
     int64_t bytes = 0;
     for (int b = 0; b < B; ++b) {
         a->boff[(size_t)b] = bytes;
         bytes += (int64_t)hT[b] * ((2 * (int64_t)hL[b] + ns) / ns);     // T * ceil((2L + 1) / ns); none without an alignment
     }
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    a->boff_b = al((size_t)B * 8); a->end_b = al((size_t)B * 4); a->path_b = al((size_t)B * W * 4);
-    a->span_b = al(a->total * 4); a->bp_b = al((size_t)bytes);
+    a->boff_b = align256((size_t)B * 8); a->end_b = align256((size_t)B * 4); a->path_b = align256((size_t)B * W * 4);
+    a->span_b = align256(a->total * 4); a->bp_b = align256((size_t)bytes);
 }
 
 void align_carve(char* extra, AlignDev* a) {
@@ -1173,6 +1205,46 @@ hipError_t align_fetch(hctr_ctx* c, const AlignDev& a, int B, int W, const float
         e = hipMemcpyAsync(span_logp, a.d_lp, a.total * 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && score) e = hipMemcpyAsync(score, d_score, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
     return e;
+}
+
+// The image path of hctr_ctc_loss / hctr_ctc_align: the lines go through the forward in passes of sub_batch() lines into
+// stored logits and from there into emissions. carve(extra) takes the call's `extra_b` further bytes of scratch;
+// after(pf, m, emis, res, b0, nb) queues what follows the emissions of the pass's lines [b0, b0 + nb), res[B] being the
+// per-line result; fetch(res) queues the copies back (`what` names them in its error).
+template <class Carve, class After, class Fetch>
+int ctc_image_call(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
+                   const CtcHost& h, size_t extra_b, Carve carve, After after, Fetch fetch, const char* what) {
+    SplitScope scope(c);
+    c->split = c->mode != 0;                  // mode 2 takes every line in f16x3: its guard certifies argmaxes, not losses
+    if (!c->wts().built) return fail(c, HCTR_ERR_STATE, "the weight set of this precision mode is not resident");
+    prof_reset(c);
+    const int nbmax = sub_batch(c, B, W, c->split);
+    CtcLines m;
+    float *res = nullptr, *emis = nullptr;
+    char* extra = nullptr;
+    TRY(ctc_scratch(c, h, (size_t)nbmax * W * h.D, &m, &res, &emis, extra_b, &extra));
+    TRY(carve(extra));
+    std::vector<int> all((size_t)B);
+    for (int b = 0; b < B; ++b) all[(size_t)b] = b;
+    auto pass = [&](int b0, int nb) -> int {
+        TRY(ensure_workspace(c, nb, W, ws_need(c, HEAD_LOGITS)));
+        TRY(stage_input(c, img, img_dtype, img_on_device, widths, all.data() + b0, nb, W));
+        TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, HEAD_LOGITS, false));
+        Prof pf(c);
+        pf.begin("ctc_lse");
+        HIP_TRY(c, launch_ctc_lse(c->ws.logits, c->cpad, W, 1, c->num_classes, m, b0, nb, W, emis, nullptr, c->stream));
+        pf.end();
+        HIP_TRY(c, after(pf, m, emis, res, b0, nb));
+        return HCTR_OK;
+    };
+    int rc = HCTR_OK;
+    for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax) rc = pass(b0, std::min(nbmax, B - b0));
+    if (rc == HCTR_OK) {
+        hipError_t e = fetch(res);
+        if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "D2H %s: %s", what, hipGetErrorString(e));
+    }
+    // pageable host tables queued above were staged before hipMemcpyAsync returned
+    return synced(c, rc);
 }
 
 }  // namespace
@@ -1567,19 +1639,9 @@ int hctr_decode_greedy_logits(hctr_ctx* c, const float* logits_wbc, int on_devic
         HIP_TRY(c, hipSetDevice(c->device));
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        const size_t n = (size_t)W * B * C;
-        const float* dev = logits_wbc;
-        float* up = nullptr;
+        const float* dev = nullptr;
         int32_t *idx = nullptr, *dl = nullptr, *dn = nullptr;
-        int rc = HCTR_OK;
-        if (!on_device) {
-            rc = dev_alloc(c, tmp, &up, n, false);
-            if (rc == HCTR_OK) {
-                hipError_t e = hipMemcpyAsync(up, logits_wbc, n * 4, hipMemcpyHostToDevice, c->stream);
-                if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "H2D logits: %s", hipGetErrorString(e));
-            }
-            dev = up;
-        }
+        int rc = logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev);
         if (rc == HCTR_OK) rc = dev_alloc(c, tmp, &idx, (size_t)W * B, false);
         if (rc == HCTR_OK) rc = dev_alloc(c, tmp, &dl, (size_t)W * B, false);
         if (rc == HCTR_OK) rc = dev_alloc(c, tmp, &dn, (size_t)B, false);
@@ -1591,10 +1653,7 @@ int hctr_decode_greedy_logits(hctr_ctx* c, const float* logits_wbc, int on_devic
             if (e == hipSuccess) e = hipMemcpyAsync(lengths, dn, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
             if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "decode_greedy_logits: %s", hipGetErrorString(e));
         }
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-        free_pool(tmp);
-        return rc;
+        return synced(c, rc);
     });
 }
 
@@ -1806,53 +1865,26 @@ int hctr_ctc_loss(hctr_ctx* c, const void* img, int img_dtype, int img_on_device
         if (B == 0) return HCTR_OK;
         if (!nll) return fail(c, HCTR_ERR_ARG, "nll is NULL");
         HIP_TRY(c, hipSetDevice(c->device));
-        const int C = c->num_classes;
         CtcHost h;
-        TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
-        SplitScope scope(c);
-        c->split = c->mode != 0;                  // mode 2 scores every line in f16x3: its guard certifies argmaxes, not losses
-        if (!c->wts().built) return fail(c, HCTR_ERR_STATE, "the weight set of this precision mode is not resident");
-        prof_reset(c);
-        const int nbmax = sub_batch(c, B, W, c->split);
-        CtcLines m;
-        float *d_nll = nullptr, *emis = nullptr;
-        TRY(ctc_scratch(c, h, (size_t)nbmax * W * h.D, &m, &d_nll, &emis));
-        std::vector<int> all((size_t)B);
-        for (int b = 0; b < B; ++b) all[(size_t)b] = b;
-        // one pass: the lines [b0, b0 + nb) through the forward into stored logits, then emissions and the recursion
-        auto pass = [&](int b0, int nb) -> int {
-            TRY(ensure_workspace(c, nb, W, ws_need(c, HEAD_LOGITS)));
-            TRY(stage_input(c, img, img_dtype, img_on_device, widths, all.data() + b0, nb, W));
-            TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, HEAD_LOGITS, false));
-            Prof pf(c);
-            pf.begin("ctc_lse");
-            HIP_TRY(c, launch_ctc_lse(c->ws.logits, c->cpad, W, 1, C, m, b0, nb, W, emis, c->stream));
-            pf.end();
-            pf.begin("ctc_alpha");
-            HIP_TRY(c, launch_ctc_alpha(emis, m, b0, nb, W, h.max_states, d_nll, c->stream));
-            pf.end();
-            return HCTR_OK;
-        };
-        int rc = HCTR_OK;
-        for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax) rc = pass(b0, std::min(nbmax, B - b0));
-        if (rc == HCTR_OK) {
-            hipError_t e = hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "D2H nll: %s", hipGetErrorString(e));
-        }
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-        return rc;
+        TRY(ctc_prepare(c, B, W, c->num_classes, targets, target_lengths, input_lengths, &h));
+        return ctc_image_call(
+            c, img, img_dtype, img_on_device, widths, B, W, h, 0, [](char*) { return HCTR_OK; },
+            [&](Prof& pf, const CtcLines& m, const float* emis, float* d_nll, int b0, int nb) {
+                pf.begin("ctc_alpha");
+                hipError_t e = launch_ctc_alpha(emis, m, b0, nb, W, h.max_states, d_nll, nullptr, nullptr, c->stream);
+                pf.end();
+                return e;
+            },
+            [&](const float* d_nll) { return hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream); },
+            "nll");
     });
 }
 
 int hctr_ctc_loss_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W, int B, int C, const int32_t* targets,
                          const int32_t* target_lengths, const int32_t* input_lengths, float* nll) {
     return guard(c, [&]() -> int {
-        if (!c) return HCTR_ERR_ARG;
-        if (W < 0 || B < 0 || C < 2) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
+        TRY(check_logits_args(c, W, B, C, logits_wbc && nll));
         if (B == 0) return HCTR_OK;
-        if (W < 1) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
-        if (!logits_wbc || !nll) return fail(c, HCTR_ERR_ARG, "NULL pointer");
         HIP_TRY(c, hipSetDevice(c->device));
         CtcHost h;
         TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
@@ -1860,37 +1892,25 @@ int hctr_ctc_loss_logits(hctr_ctx* c, const float* logits_wbc, int on_device, in
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
         CtcLines m;
-        float *d_nll = nullptr, *emis = nullptr, *up = nullptr;
+        float *d_nll = nullptr, *emis = nullptr;
         TRY(ctc_scratch(c, h, (size_t)B * W * h.D, &m, &d_nll, &emis));
-        const float* dev = logits_wbc;
-        int rc = HCTR_OK;
-        if (!on_device) {
-            const size_t n = (size_t)W * B * C;
-            rc = dev_alloc(c, tmp, &up, n, false);
-            if (rc == HCTR_OK) {
-                hipError_t e = hipMemcpyAsync(up, logits_wbc, n * 4, hipMemcpyHostToDevice, c->stream);
-                if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "H2D logits: %s", hipGetErrorString(e));
-            }
-            dev = up;
-        }
+        const float* dev = nullptr;
+        int rc = logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev);
         if (rc == HCTR_OK) {
             Prof pf(c);
             // rows of the WBC tensor are r = t*B + b
             pf.begin("ctc_lse");
-            hipError_t e = launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, c->stream);
+            hipError_t e = launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, nullptr, c->stream);
             pf.end();
             if (e == hipSuccess) {
                 pf.begin("ctc_alpha");
-                e = launch_ctc_alpha(emis, m, 0, B, W, h.max_states, d_nll, c->stream);
+                e = launch_ctc_alpha(emis, m, 0, B, W, h.max_states, d_nll, nullptr, nullptr, c->stream);
                 pf.end();
             }
             if (e == hipSuccess) e = hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
             if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_loss_logits: %s", hipGetErrorString(e));
         }
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-        free_pool(tmp);
-        return rc;
+        return synced(c, rc);
     });
 }
 
@@ -1898,11 +1918,8 @@ int hctr_ctc_loss_logits_grad(hctr_ctx* c, const float* logits_wbc, int on_devic
                               const int32_t* targets, const int32_t* target_lengths, const int32_t* input_lengths,
                               const float* line_weight, float* nll, float* grad_wbc, int grad_on_device) {
     return guard(c, [&]() -> int {
-        if (!c) return HCTR_ERR_ARG;
-        if (W < 0 || B < 0 || C < 2) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
+        TRY(check_logits_args(c, W, B, C, logits_wbc && grad_wbc));
         if (B == 0) return HCTR_OK;
-        if (W < 1) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
-        if (!logits_wbc || !grad_wbc) return fail(c, HCTR_ERR_ARG, "NULL pointer");
         if ((const float*)grad_wbc == logits_wbc) return fail(c, HCTR_ERR_ARG, "grad_wbc aliases the logits");
         HIP_TRY(c, hipSetDevice(c->device));
         CtcHost h;
@@ -1910,33 +1927,33 @@ int hctr_ctc_loss_logits_grad(hctr_ctx* c, const float* logits_wbc, int on_devic
         prof_reset(c);
         // host side of the gradient's tables: where each line's alpha rows start, and its target positions grouped by
         // emission slot (a counting sort of the slot table ctc_prepare made)
-        const int32_t *hT = h.tab.data(), *hL = hT + B, *hoff = hT + 2 * (size_t)B;
-        const int32_t* hslot = hT + 4 * (size_t)B + (size_t)B * h.D;
-        const size_t total = h.tab.size() - 4 * (size_t)B - (size_t)B * h.D, D1 = (size_t)h.D + 1;
+        const CtcLines hl = h.host();
+        const size_t D1 = (size_t)h.D + 1;
         std::vector<int64_t> aoff((size_t)B);
-        std::vector<int32_t> gtab((size_t)B * D1 + total, 0);      // soff[B][D + 1] | pos[sum L]
+        std::vector<int32_t> gtab((size_t)B * D1 + h.total(), 0);      // soff[B][D + 1] | pos[sum L]
         std::vector<float> wt((size_t)B, 1.f);
         int64_t ast_floats = 0;
         for (int b = 0; b < B; ++b) {
             aoff[(size_t)b] = ast_floats;
-            ast_floats += (int64_t)hT[b] * (2 * (int64_t)hL[b] + 1);
+            ast_floats += (int64_t)hl.T[b] * (2 * (int64_t)hl.L[b] + 1);
             if (line_weight) wt[(size_t)b] = line_weight[b];
-            if (!hT[b]) continue;
+            if (!hl.T[b]) continue;
             int32_t* so = gtab.data() + (size_t)b * D1;
-            int32_t* ps = gtab.data() + (size_t)B * D1 + hoff[b];
-            for (int j = 0; j < hL[b]; ++j) ++so[hslot[hoff[b] + j] + 1];
+            int32_t* ps = gtab.data() + (size_t)B * D1 + hl.off[b];
+            const int32_t* sl = hl.slot + hl.off[b];
+            for (int j = 0; j < hl.L[b]; ++j) ++so[sl[j] + 1];
             so[0] = so[1] = 0;
             for (size_t j = 2; j < D1; ++j) so[j] += so[j - 1];     // so[j] = end of slot j - 1 = start of slot j
             std::vector<int32_t> fill(so, so + D1);
-            for (int j = 0; j < hL[b]; ++j) ps[fill[(size_t)hslot[hoff[b] + j]]++] = j;
+            for (int j = 0; j < hl.L[b]; ++j) ps[fill[(size_t)sl[j]]++] = j;
         }
-        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
         const size_t BW = (size_t)B * W;
-        const size_t lse_b = al(BW * 8), aoff_b = al((size_t)B * 8), wt_b = al((size_t)B * 4), gtab_b = al(gtab.size() * 4);
+        const size_t lse_b = align256(BW * 8), aoff_b = align256((size_t)B * 8), wt_b = align256((size_t)B * 4),
+                     gtab_b = align256(gtab.size() * 4);
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
         CtcLines m;
-        float *d_nll = nullptr, *emis = nullptr, *up = nullptr, *dgrad = grad_wbc;
+        float *d_nll = nullptr, *emis = nullptr, *dgrad = grad_wbc;
         char* extra = nullptr;
         TRY(ctc_scratch(c, h, BW * h.D, &m, &d_nll, &emis, lse_b + aoff_b + wt_b + gtab_b + (size_t)ast_floats * 4 + 16,
                         &extra));
@@ -1947,16 +1964,8 @@ int hctr_ctc_loss_logits_grad(hctr_ctx* c, const float* logits_wbc, int on_devic
         int32_t* d_pos = d_soff + (size_t)B * D1;
         float* d_ast = (float*)(extra + lse_b + aoff_b + wt_b + gtab_b);
         const size_t n = (size_t)W * B * C;
-        const float* dev = logits_wbc;
-        int rc = HCTR_OK;
-        if (!on_device) {
-            rc = dev_alloc(c, tmp, &up, n, false);
-            if (rc == HCTR_OK) {
-                hipError_t e = hipMemcpyAsync(up, logits_wbc, n * 4, hipMemcpyHostToDevice, c->stream);
-                if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "H2D logits: %s", hipGetErrorString(e));
-            }
-            dev = up;
-        }
+        const float* dev = nullptr;
+        int rc = logits_on_device(c, tmp, logits_wbc, on_device, n, &dev);
         if (rc == HCTR_OK && !grad_on_device) rc = dev_alloc(c, tmp, &dgrad, n, false);
         if (rc == HCTR_OK) {
             hipError_t e = hipMemcpyAsync(d_aoff, aoff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream);
@@ -1967,17 +1976,17 @@ int hctr_ctc_loss_logits_grad(hctr_ctx* c, const float* logits_wbc, int on_devic
             // rows of the WBC tensor are r = t*B + b
             if (e == hipSuccess) {
                 pf.begin("ctc_rowlse");
-                e = launch_ctc_rowlse(dev, C, 1, B, C, m, 0, B, W, emis, d_lse, c->stream);
+                e = launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, d_lse, c->stream);
                 pf.end();
             }
             if (e == hipSuccess) {
                 pf.begin("ctc_alpha_store");
-                e = launch_ctc_alpha_beta(emis, m, B, W, h.max_states, d_nll, d_aoff, d_ast, false, c->stream);
+                e = launch_ctc_alpha(emis, m, 0, B, W, h.max_states, d_nll, d_aoff, d_ast, c->stream);
                 pf.end();
             }
             if (e == hipSuccess) {
                 pf.begin("ctc_beta");
-                e = launch_ctc_alpha_beta(emis, m, B, W, h.max_states, d_nll, d_aoff, d_ast, true, c->stream);
+                e = launch_ctc_beta(emis, m, B, W, h.max_states, d_nll, d_aoff, d_ast, c->stream);
                 pf.end();
             }
             if (e == hipSuccess) {
@@ -1992,10 +2001,7 @@ int hctr_ctc_loss_logits_grad(hctr_ctx* c, const float* logits_wbc, int on_devic
             if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_loss_logits_grad: %s", hipGetErrorString(e));
         }
         // the host tables above are pageable: their copies were staged before hipMemcpyAsync returned
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-        free_pool(tmp);
-        return rc;
+        return synced(c, rc);
     });
 }
 
@@ -2006,46 +2012,24 @@ int hctr_ctc_align(hctr_ctx* c, const void* img, int img_dtype, int img_on_devic
         TRY(check_forward_args(c, img, img_dtype, B, W));
         if (B == 0) return HCTR_OK;
         HIP_TRY(c, hipSetDevice(c->device));
-        const int C = c->num_classes;
         CtcHost h;
-        TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
-        SplitScope scope(c);
-        c->split = c->mode != 0;                  // mode 2 aligns every line in f16x3, like hctr_ctc_loss
-        if (!c->wts().built) return fail(c, HCTR_ERR_STATE, "the weight set of this precision mode is not resident");
-        prof_reset(c);
-        const int nbmax = sub_batch(c, B, W, c->split);
+        TRY(ctc_prepare(c, B, W, c->num_classes, targets, target_lengths, input_lengths, &h));
         AlignDev a;
         align_layout(h, W, &a);
-        CtcLines m;
-        float *d_score = nullptr, *emis = nullptr;
-        char* extra = nullptr;
-        TRY(ctc_scratch(c, h, (size_t)nbmax * W * h.D, &m, &d_score, &emis, a.bytes() + 16, &extra));
-        align_carve(extra, &a);
-        HIP_TRY(c, hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
-        std::vector<int> all((size_t)B);
-        for (int b = 0; b < B; ++b) all[(size_t)b] = b;
-        // one pass: the lines [b0, b0 + nb) through the forward into stored logits, then emissions, recursion, back-trace
-        auto pass = [&](int b0, int nb) -> int {
-            TRY(ensure_workspace(c, nb, W, ws_need(c, HEAD_LOGITS)));
-            TRY(stage_input(c, img, img_dtype, img_on_device, widths, all.data() + b0, nb, W));
-            TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, HEAD_LOGITS, false));
-            Prof pf(c);
-            pf.begin("ctc_lse");
-            HIP_TRY(c, launch_ctc_lse(c->ws.logits, c->cpad, W, 1, C, m, b0, nb, W, emis, c->stream));
-            pf.end();
-            HIP_TRY(c, align_launch(c, pf, emis, m, h, a, b0, nb, W, d_score));
-            return HCTR_OK;
-        };
-        int rc = HCTR_OK;
-        for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax) rc = pass(b0, std::min(nbmax, B - b0));
-        if (rc == HCTR_OK) {
-            hipError_t e = align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
-            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "D2H alignment: %s", hipGetErrorString(e));
-        }
-        // the host table above is pageable: its copy was staged before hipMemcpyAsync returned
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-        return rc;
+        return ctc_image_call(
+            c, img, img_dtype, img_on_device, widths, B, W, h, a.bytes() + 16,
+            [&](char* extra) -> int {
+                align_carve(extra, &a);
+                HIP_TRY(c, hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
+                return HCTR_OK;
+            },
+            [&](Prof& pf, const CtcLines& m, const float* emis, float* d_score, int b0, int nb) {
+                return align_launch(c, pf, emis, m, h, a, b0, nb, W, d_score);
+            },
+            [&](const float* d_score) {
+                return align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
+            },
+            "alignment");
     });
 }
 
@@ -2053,11 +2037,8 @@ int hctr_ctc_align_logits(hctr_ctx* c, const float* logits_wbc, int on_device, i
                           const int32_t* target_lengths, const int32_t* input_lengths, int32_t* path, int32_t* span_start,
                           int32_t* span_end, float* span_logp, float* score) {
     return guard(c, [&]() -> int {
-        if (!c) return HCTR_ERR_ARG;
-        if (W < 0 || B < 0 || C < 2) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
+        TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
         if (B == 0) return HCTR_OK;
-        if (W < 1) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
-        if (!logits_wbc) return fail(c, HCTR_ERR_ARG, "NULL pointer");
         HIP_TRY(c, hipSetDevice(c->device));
         CtcHost h;
         TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
@@ -2067,38 +2048,26 @@ int hctr_ctc_align_logits(hctr_ctx* c, const float* logits_wbc, int on_device, i
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
         CtcLines m;
-        float *d_score = nullptr, *emis = nullptr, *up = nullptr;
+        float *d_score = nullptr, *emis = nullptr;
         char* extra = nullptr;
         TRY(ctc_scratch(c, h, (size_t)B * W * h.D, &m, &d_score, &emis, a.bytes() + 16, &extra));
         align_carve(extra, &a);
-        const float* dev = logits_wbc;
-        int rc = HCTR_OK;
-        if (!on_device) {
-            const size_t n = (size_t)W * B * C;
-            rc = dev_alloc(c, tmp, &up, n, false);
-            if (rc == HCTR_OK) {
-                hipError_t e = hipMemcpyAsync(up, logits_wbc, n * 4, hipMemcpyHostToDevice, c->stream);
-                if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "H2D logits: %s", hipGetErrorString(e));
-            }
-            dev = up;
-        }
+        const float* dev = nullptr;
+        int rc = logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev);
         if (rc == HCTR_OK) {
             hipError_t e = hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream);
             Prof pf(c);
             if (e == hipSuccess) {
                 // rows of the WBC tensor are r = t*B + b
                 pf.begin("ctc_lse");
-                e = launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, c->stream);
+                e = launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, nullptr, c->stream);
                 pf.end();
             }
             if (e == hipSuccess) e = align_launch(c, pf, emis, m, h, a, 0, B, W, d_score);
             if (e == hipSuccess) e = align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
             if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_align_logits: %s", hipGetErrorString(e));
         }
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-        free_pool(tmp);
-        return rc;
+        return synced(c, rc);
     });
 }
 
@@ -2127,27 +2096,16 @@ int hctr_log_softmax(hctr_ctx* c, const float* logits_wbc, int on_device, int W,
         HIP_TRY(c, hipSetDevice(c->device));
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        const float* dev = logits_wbc;
-        float *up = nullptr, *y = nullptr;
-        int rc = HCTR_OK;
-        if (!on_device) {
-            rc = dev_alloc(c, tmp, &up, (size_t)rows * C, false);
-            if (rc == HCTR_OK) {
-                hipError_t e = hipMemcpyAsync(up, logits_wbc, (size_t)rows * C * 4, hipMemcpyHostToDevice, c->stream);
-                if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "H2D logits: %s", hipGetErrorString(e));
-            }
-            dev = up;
-        }
+        const float* dev = nullptr;
+        float* y = nullptr;
+        int rc = logits_on_device(c, tmp, logits_wbc, on_device, (size_t)rows * C, &dev);
         if (rc == HCTR_OK) rc = dev_alloc(c, tmp, &y, (size_t)rows * C, false);
         if (rc == HCTR_OK) {
             hipError_t e = launch_log_softmax_rows(dev, rows, C, y, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(out_host, y, (size_t)rows * C * 4, hipMemcpyDeviceToHost, c->stream);
             if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "log_softmax: %s", hipGetErrorString(e));
         }
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-        free_pool(tmp);
-        return rc;
+        return synced(c, rc);
     });
 }
 

@@ -192,7 +192,10 @@ hipError_t launch_row_candidates(const float* logits, int64_t ld, int B, int W, 
 hipError_t launch_log_softmax_rows(const float* x, int64_t rows, int C, float* y, hipStream_t s);
 
 // ---- CTC loss (hctr_ctc_loss*): per-line tables on the device, indexed by the line's place gb in the caller's batch ----
-constexpr int kCtcMaxStates = 64 * 64;   // extended target 2L + 1 of one wave64 line (ctc_alpha_kernel's largest instance)
+// kernels.hip's instance ladder of the recursions: the largest extended target 2L + 1 of one line, and the states per
+// lane of the instance that max_states launches
+extern const int kCtcMaxStates;
+int ctc_viterbi_lane_states(int max_states);
 struct CtcLines {
     const int32_t* T;       // [B] steps read (input_lengths); 0 = the line has no alignment (nll = +inf, nothing read)
     const int32_t* L;       // [B] target length
@@ -203,30 +206,28 @@ struct CtcLines {
     int D;                  // emission slots per row (max nd)
 };
 // rows of logits at x + (b*sb + t*st) * ld for the pass's lines b = 0..nb-1 (line gb = b0 + b of the tables), C classes:
-// emis[(b*W + t) * D + j] = z[cls[gb][j]] - logsumexp(z) for t < T[gb], j < nd[gb]
+// emis[(b*W + t) * D + j] = z[cls[gb][j]] - logsumexp(z) for t < T[gb], j < nd[gb]; lse (the gradient's pass, else null)
+// keeps lse[b*W + t] = logsumexp(z) of those rows in float64
 hipError_t launch_ctc_lse(const float* x, int64_t ld, int64_t sb, int64_t st, int C, const CtcLines& m, int b0, int nb,
-                          int W, float* emis, hipStream_t s);
+                          int W, float* emis, double* lse, hipStream_t s);
 // forward (alpha) recursion of the pass's lines over those emissions -> nll[b0 + b]; max_states = largest 2L + 1 among
-// the lines with T > 0 (<= kCtcMaxStates)
+// the lines with T > 0 (<= kCtcMaxStates). ast (the gradient's pass, else null) keeps the rows, ast[aoff[gb] + t*S_gb + s]
+// (aoff[gb] = sum of T*S of the lines before gb); nll is bit-identical either way.
 hipError_t launch_ctc_alpha(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states, float* nll,
-                            hipStream_t s);
+                            const int64_t* aoff, float* ast, hipStream_t s);
 // gradient of the per-line loss in caller logits (hctr_ctc_loss_logits_grad), whole batch (b0 = 0):
-// launch_ctc_rowlse = launch_ctc_lse that also keeps lse[b*W + t] (float64) of the rows t < T[b];
-// launch_ctc_alpha_beta, beta = false: the alpha recursion storing its rows at ast[aoff[b] + t*S_b + s] (aoff[b] = sum
-//   of T*S of the lines before b), nll as launch_ctc_alpha writes it; then beta = true: the beta recursion, which
-//   overwrites the rows with y = alpha + nll + (beta before its emission), the log of each state's posterior share;
+// launch_ctc_beta: the beta recursion, which overwrites the alpha rows with y = alpha + nll + (beta before its
+//   emission), the log of each state's posterior share;
 // launch_ctc_grad_rows: grad[t][b][c] = wt[b] * (softmax(z_t)[c] - gamma_t(c)) for t < T[b], zeros for t >= T[b] and for
 //   lines with nll = +inf. soff[b][D + 1], pos[off[b] + ...]: target positions of line b grouped by emission slot
 //   (slot j's are pos[off[b] + soff[b][j] .. off[b] + soff[b][j+1]), j >= 1). x and grad are contiguous [W][B][C].
-hipError_t launch_ctc_rowlse(const float* x, int64_t ld, int64_t sb, int64_t st, int C, const CtcLines& m, int b0, int nb,
-                             int W, float* emis, double* lse, hipStream_t s);
-hipError_t launch_ctc_alpha_beta(const float* emis, const CtcLines& m, int B, int W, int max_states, float* nll,
-                                 const int64_t* aoff, float* ast, bool beta, hipStream_t s);
+hipError_t launch_ctc_beta(const float* emis, const CtcLines& m, int B, int W, int max_states, const float* nll,
+                           const int64_t* aoff, float* ast, hipStream_t s);
 hipError_t launch_ctc_grad_rows(const float* x, int C, int B, int W, const CtcLines& m, const double* lse,
                                 const float* nll, const float* wt, const int64_t* aoff, const float* ast,
                                 const int32_t* soff, const int32_t* pos, float* grad, hipStream_t s);
 
-// forced alignment (hctr_ctc_align*) over the emissions of launch_ctc_lse, the instances of launch_ctc_alpha:
+// forced alignment (hctr_ctc_align*) over the emissions of launch_ctc_lse:
 // launch_ctc_viterbi: the max-plus recursion; the lane of states [i*NS, i*NS + NS) stores its 2-bit backpointers (0, 1
 //   or 2 states down; state k of the lane at bits 2k) of step t >= 1 at bp[boff[gb] + t * ceil(S_gb / NS) + i], with
 //   NS = ctc_viterbi_lane_states(max_states); score[gb] = the best path's log-probability, endst[gb] its last state
@@ -234,7 +235,6 @@ hipError_t launch_ctc_grad_rows(const float* x, int C, int B, int W, const CtcLi
 // launch_ctc_backtrace: path[gb*W + t] = class of the best path at step t (-1 for t >= T), and for target position j of
 //   the line, at off[gb] + j: its first step, the step after its last and the float32 sum of its emissions (-1, -1,
 //   -inf for a line with T = 0).
-constexpr int ctc_viterbi_lane_states(int max_states) { return max_states <= 64 ? 1 : max_states <= 2048 ? 2 : 4; }
 hipError_t launch_ctc_viterbi(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states,
                               const int64_t* boff, uint8_t* bp, float* score, int32_t* endst, hipStream_t s);
 hipError_t launch_ctc_backtrace(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states,

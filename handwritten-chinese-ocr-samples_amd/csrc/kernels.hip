@@ -4,6 +4,7 @@
 // tiling, layouts and fusion are this engine's own. Wavefront = 64 lanes throughout.
 #include "kernels.h"
 
+#include <algorithm>
 #include <cstdlib>
 
 namespace hctr {
@@ -3092,39 +3093,96 @@ __device__ __forceinline__ float ctc_logadd(float a, float b) {
     return mx + log1pf(expf(-fabsf(a - b)));
 }
 
-// One workgroup of NW wave64s per line: the log-space forward recursion over the extended target (blank, l1, blank, ...,
-// lL, blank), S = 2L + 1 states; thread i holds the NS contiguous states [i*NS, i*NS + NS), the two states below them
-// come from the left neighbour lane over __shfl_up, and across a wave boundary from a double-buffered LDS slot written
-// at the end of the previous step - one barrier per step when NW > 1, none for a one-wave line. The emissions of the
-// next PF steps are in flight while a step is computed (a ring of PF rows, statically indexed by unrolling the step loop
-// PF times). alpha is float32; the three-way log-add is max + log(1 + exp(mid - max) + exp(min - max)) (torch's CPU
-// kernel's, with the max term's exp(0) = 1 folded); the skip transition s-2 -> s only where l_s != l_{s-2}.
-// nll[b0 + b] = -logaddexp(alpha_T[S-1], alpha_T[S-2]) (-alpha_T[0] for L = 0), +inf for a line marked T = 0.
-// STORE (the gradient's pass) also writes every row of alpha, ast[aoff[gb] + t*S + s] for s < S; the recursion's
-// arithmetic is the same, so nll is bit-identical either way.
-template <int NS, int PF, int NW, bool STORE>
-__device__ __forceinline__ void ctc_alpha_line(const float* __restrict__ emis, const CtcLines& m, int b0, int W,
-                                               float* __restrict__ nll, const int64_t* __restrict__ aoff,
-                                               float* __restrict__ ast) {
-    static_assert(NW == 1 || NS >= 2, "a wave boundary hands over two states from one lane");
-    __shared__ float xb[2][NW][2];                 // [step parity][wave] = {state wave_end-1, state wave_end-2}
-    __shared__ float fin[2];
-    const int b = blockIdx.x, gb = b0 + b, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int T = m.T[gb], L = m.L[gb], S = 2 * L + 1;
-    if (T == 0) {                                  // no alignment (host-side feasibility test); block-uniform
-        if (tid == 0) nll[gb] = INFINITY;
-        return;
-    }
-    const int32_t* ts = m.slot + m.off[gb];
-    int slot[NS];
-    bool skip[NS];
+// max + log(1 + exp(mid - max) + exp(min - max)): torch's CPU kernel's three-way log-add with the max term's
+// exp(0) = 1 folded; -inf when all three are
+__device__ __forceinline__ float ctc_logsum3(float la1, float la2, float la3) {
+    const float mx = fmaxf(la1, fmaxf(la2, la3));
+    const float mn = fminf(la1, fminf(la2, la3));
+    const float md = __builtin_amdgcn_fmed3f(la1, la2, la3);
+    const float v = mx + __logf(1.f + __expf(md - mx) + __expf(mn - mx));
+    return mx == -INFINITY ? -INFINITY : v;
+}
+
+// ---- what the three recursions (alpha, beta, Viterbi) share. One workgroup of NW wave64s per line walks the extended
+// target (blank, l1, blank, ..., lL, blank), S = 2L + 1 states; thread i holds the NS contiguous states
+// [i*NS, i*NS + NS). FWD: time runs up and a state is fed from the two states below it; !FWD is the mirror image. ----
+
+// the emission slot of each of the lane's states (0 for a blank and for a state beyond S) and whether the two-state
+// transition exists: into s from s-2 where l_s != l_{s-2} (FWD), out of s into s+2 where l_{s+2} != l_s (!FWD)
+template <int NS, bool FWD>
+__device__ __forceinline__ void ctc_lane_setup(const int32_t* __restrict__ ts, int S, int (&slot)[NS], bool (&skip)[NS]) {
 #pragma unroll
     for (int i = 0; i < NS; ++i) {
-        const int s = tid * NS + i;
+        const int s = (int)threadIdx.x * NS + i;
         const bool lab = (s & 1) && s < S;
         slot[i] = lab ? ts[s >> 1] : 0;
-        skip[i] = lab && s >= 3 && ts[s >> 1] != ts[(s >> 1) - 1];
+        skip[i] = FWD ? lab && s >= 3 && ts[s >> 1] != ts[(s >> 1) - 1]
+                      : lab && s + 2 < S && ts[(s >> 1) + 1] != ts[s >> 1];
     }
+}
+
+// The hand-over across a wave boundary of the forward recursion: xb[step parity][wave] = the wave's two states next to
+// the boundary, nearest first, written by its last lane once a step is done - one barrier per step when NW > 1, none
+// for a one-wave line. (ctc_beta_kernel keeps the mirror image, written by lane 0, as a local lambda.)
+template <int NS, int NW>
+__device__ __forceinline__ void ctc_publish(float (&xb)[2][NW][2], int parity, const float (&a)[NS]) {
+    static_assert(NW == 1 || NS >= 2, "a wave boundary hands over two states from one lane");
+    if (NW > 1) {
+        if ((threadIdx.x & 63) == 63) {
+            xb[parity][threadIdx.x >> 6][0] = a[NS - 1];
+            xb[parity][threadIdx.x >> 6][1] = a[NS >= 2 ? NS - 2 : 0];
+        }
+        __syncthreads();
+    }
+}
+
+// n1, n2 = the states one and two beyond the lane's own, of the step published under `parity`: from the neighbour lane
+// over __shfl_up (FWD) / __shfl_down, across a wave boundary from xb, -inf beyond the line's first / last state
+template <int NS, int NW, bool FWD>
+__device__ __forceinline__ void ctc_neighbours(const float (&xb)[2][NW][2], int parity, const float (&a)[NS], float& n1,
+                                               float& n2) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const float e1 = a[FWD ? NS - 1 : 0], e2 = a[NS >= 2 ? (FWD ? NS - 2 : 1) : 0];
+    n1 = FWD ? __shfl_up(e1, 1) : __shfl_down(e1, 1);
+    n2 = NS >= 2 ? (FWD ? __shfl_up(e2, 1) : __shfl_down(e2, 1)) : (FWD ? __shfl_up(e1, 2) : __shfl_down(e1, 2));
+    if (lane == (FWD ? 0 : 63)) {
+        const bool has = FWD ? wv > 0 : wv < NW - 1;
+        const int from = has ? (FWD ? wv - 1 : wv + 1) : 0;
+        n1 = has ? xb[parity][from][0] : -INFINITY;
+        n2 = has ? xb[parity][from][1] : -INFINITY;
+    }
+    if (NS == 1 && lane == (FWD ? 1 : 62)) n2 = -INFINITY;      // (NS == 1 only with NW == 1)
+}
+
+// one row of a prefetch ring: the lane's NS entries of row r. The rings hold the rows of the next PF steps, in flight
+// while a step is computed, statically indexed by unrolling the step loop PF times.
+template <int NS>
+__device__ __forceinline__ void ctc_ring_load(const float* r, const int (&idx)[NS], float (&e)[NS]) {
+#pragma unroll
+    for (int i = 0; i < NS; ++i) e[i] = r[idx[i]];
+}
+
+// The forward recursion of one line over its emissions, in float32. `step` is the policy:
+//   start(gb, S, a)               once, with the states of step 0
+//   combine(la1, la2, la3, i, code) -> the value of the lane's state i from its three predecessors (s, s-1, s-2; -inf
+//                                 where the skip does not exist), before the emission is added; code is the step's scratch
+//   row(t, a, code)               after step t >= 1
+//   finish(gb, L, S, last, prev)  thread 0, with the final values of states S-1 and S-2;  none(gb) for a line marked T = 0
+template <int PF, int NW, class Step>
+__device__ __forceinline__ void ctc_forward_line(const float* __restrict__ emis, const CtcLines& m, int b0, int W,
+                                                 Step step) {
+    constexpr int NS = Step::NS;
+    __shared__ float xb[2][NW][2];
+    __shared__ float fin[2];
+    const int b = blockIdx.x, gb = b0 + b, tid = threadIdx.x;
+    const int T = m.T[gb], L = m.L[gb], S = 2 * L + 1;
+    if (T == 0) {                                  // no alignment (host-side feasibility test); block-uniform
+        if (tid == 0) step.none(gb);
+        return;
+    }
+    int slot[NS];
+    bool skip[NS];
+    ctc_lane_setup<NS, true>(m.slot + m.off[gb], S, slot, skip);
     const int D = m.D;
     const float* base = emis + (int64_t)b * W * D;
     float a[NS];
@@ -3133,62 +3191,29 @@ __device__ __forceinline__ void ctc_alpha_line(const float* __restrict__ emis, c
         const int s = tid * NS + i;
         a[i] = (s == 0 || (s == 1 && S > 1)) ? base[slot[i]] : -INFINITY;
     }
-    float* arow = STORE ? ast + aoff[gb] + tid * NS : nullptr;
-    auto keep = [&]() {
-        if (STORE) {
-#pragma unroll
-            for (int i = 0; i < NS; ++i)
-                if (tid * NS + i < S) arow[i] = a[i];
-            arow += S;
-        }
-    };
-    keep();
-    auto publish = [&](int parity) {
-        if (NW > 1) {
-            if (lane == 63) {
-                xb[parity][wv][0] = a[NS - 1];
-                xb[parity][wv][1] = a[NS >= 2 ? NS - 2 : 0];
-            }
-            __syncthreads();
-        }
-    };
-    publish(0);
+    step.start(gb, S, a);
+    ctc_publish<NS, NW>(xb, 0, a);
     float e[PF][NS];
 #pragma unroll
-    for (int k = 0; k < PF; ++k) {
-        const float* r = base + (int64_t)min(1 + k, T - 1) * D;
-#pragma unroll
-        for (int i = 0; i < NS; ++i) e[k][i] = r[slot[i]];
-    }
+    for (int k = 0; k < PF; ++k) ctc_ring_load(base + (int64_t)min(1 + k, T - 1) * D, slot, e[k]);
     for (int t0 = 1; t0 < T; t0 += PF) {
 #pragma unroll
         for (int k = 0; k < PF; ++k) {
             const int t = t0 + k;
             if (t < T) {                           // (block-uniform)
-                float p1 = __shfl_up(a[NS - 1], 1);
-                float p2 = NS >= 2 ? __shfl_up(a[NS >= 2 ? NS - 2 : 0], 1) : __shfl_up(a[NS - 1], 2);
-                if (lane == 0) {
-                    p1 = wv > 0 ? xb[(t - 1) & 1][wv > 0 ? wv - 1 : 0][0] : -INFINITY;
-                    p2 = wv > 0 ? xb[(t - 1) & 1][wv > 0 ? wv - 1 : 0][1] : -INFINITY;
-                }
-                if (NS == 1 && lane == 1) p2 = -INFINITY;      // (NS == 1 only with NW == 1)
+                float p1, p2;
+                ctc_neighbours<NS, NW, true>(xb, (t - 1) & 1, a, p1, p2);
+                unsigned code = 0;
 #pragma unroll
                 for (int i = NS - 1; i >= 0; --i) {      // descending: a[i-1], a[i-2] still hold step t-1
-                    const float la1 = a[i];
                     const float la2 = i >= 1 ? a[i >= 1 ? i - 1 : 0] : p1;
                     const float la3 = skip[i] ? (i >= 2 ? a[i >= 2 ? i - 2 : 0] : (i == 1 ? p1 : p2)) : -INFINITY;
-                    const float mx = fmaxf(la1, fmaxf(la2, la3));
-                    const float mn = fminf(la1, fminf(la2, la3));
-                    const float md = __builtin_amdgcn_fmed3f(la1, la2, la3);
-                    const float v = mx + __logf(1.f + __expf(md - mx) + __expf(mn - mx));
-                    a[i] = (mx == -INFINITY ? -INFINITY : v) + e[k][i];
+                    a[i] = step.combine(a[i], la2, la3, i, code) + e[k][i];
                 }
-                keep();
-                publish(t & 1);
+                step.row(t, a, code);
+                ctc_publish<NS, NW>(xb, t & 1, a);
             }
-            const float* r = base + (int64_t)min(t + PF, T - 1) * D;   // refill the slot just used
-#pragma unroll
-            for (int i = 0; i < NS; ++i) e[k][i] = r[slot[i]];
+            ctc_ring_load(base + (int64_t)min(t + PF, T - 1) * D, slot, e[k]);   // refill the slot just used
         }
     }
 #pragma unroll
@@ -3198,13 +3223,49 @@ __device__ __forceinline__ void ctc_alpha_line(const float* __restrict__ emis, c
         if (s == S - 2) fin[1] = a[i];
     }
     __syncthreads();
-    if (tid == 0) nll[gb] = L == 0 ? -fin[0] : -ctc_logadd(fin[0], fin[1]);
+    if (tid == 0) step.finish(gb, L, S, fin[0], fin[1]);
 }
+
+// The log-sum policy: alpha is float32, the step is ctc_logsum3.
+// nll[gb] = -logaddexp(alpha_T[S-1], alpha_T[S-2]) (-alpha_T[0] for L = 0), +inf for a line marked T = 0.
+// STORE (the gradient's pass) also writes every row of alpha, ast[aoff[gb] + t*S + s] for s < S; the recursion's
+// arithmetic is the same, so nll is bit-identical either way.
+template <int NS_, bool STORE>
+struct CtcSum {
+    static constexpr int NS = NS_;
+    float* __restrict__ nll;
+    const int64_t* __restrict__ aoff;              // (STORE only)
+    float* __restrict__ ast;
+    float* arow;
+    int S;
+    __device__ __forceinline__ void start(int gb, int S_, const float (&a)[NS]) {
+        if (STORE) {
+            S = S_;
+            arow = ast + aoff[gb] + (int)threadIdx.x * NS;
+            row(0, a, 0);
+        }
+    }
+    __device__ __forceinline__ float combine(float la1, float la2, float la3, int, unsigned&) const {
+        return ctc_logsum3(la1, la2, la3);
+    }
+    __device__ __forceinline__ void row(int, const float (&a)[NS], unsigned) {
+        if (STORE) {
+#pragma unroll
+            for (int i = 0; i < NS; ++i)
+                if ((int)threadIdx.x * NS + i < S) arow[i] = a[i];
+            arow += S;
+        }
+    }
+    __device__ __forceinline__ void none(int gb) const { nll[gb] = INFINITY; }
+    __device__ __forceinline__ void finish(int gb, int L, int, float last, float prev) const {
+        nll[gb] = L == 0 ? -last : -ctc_logadd(last, prev);
+    }
+};
 
 template <int NS, int PF, int NW>
 __global__ __launch_bounds__(64 * NW) void ctc_alpha_kernel(const float* __restrict__ emis, const CtcLines m, int b0,
                                                              int W, float* __restrict__ nll) {
-    ctc_alpha_line<NS, PF, NW, false>(emis, m, b0, W, nll, nullptr, nullptr);
+    ctc_forward_line<PF, NW>(emis, m, b0, W, CtcSum<NS, false>{nll, nullptr, nullptr, nullptr, 0});
 }
 
 template <int NS, int PF, int NW>
@@ -3212,35 +3273,67 @@ __global__ __launch_bounds__(64 * NW) void ctc_alpha_store_kernel(const float* _
                                                                    int W, float* __restrict__ nll,
                                                                    const int64_t* __restrict__ aoff,
                                                                    float* __restrict__ ast) {
-    ctc_alpha_line<NS, PF, NW, true>(emis, m, b0, W, nll, aoff, ast);
+    ctc_forward_line<PF, NW>(emis, m, b0, W, CtcSum<NS, true>{nll, aoff, ast, nullptr, 0});
 }
 
 hipError_t launch_ctc_lse(const float* x, int64_t ld, int64_t sb, int64_t st, int C, const CtcLines& m, int b0, int nb,
-                          int W, float* emis, hipStream_t s) {
+                          int W, float* emis, double* lse, hipStream_t s) {
     if (nb <= 0 || W <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ctc_lse_kernel, dim3((unsigned)((int64_t)nb * W)), dim3(256), 0, s, x, ld, sb, st, C, m, b0, W, emis);
+    const dim3 grid((unsigned)((int64_t)nb * W));
+    if (lse)
+        hipLaunchKernelGGL(ctc_rowlse_kernel, grid, dim3(256), 0, s, x, ld, sb, st, C, m, b0, W, emis, lse);
+    else
+        hipLaunchKernelGGL(ctc_lse_kernel, grid, dim3(256), 0, s, x, ld, sb, st, C, m, b0, W, emis);
     return hipGetLastError();
 }
 
-hipError_t launch_ctc_alpha(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states, float* nll,
-                            hipStream_t s) {
-    if (nb <= 0) return hipSuccess;
-#define CTC_ALPHA(NS, PF, NW)                                                                                     \
-    if (max_states <= 64 * NS * NW) {                                                                                 \
-        hipLaunchKernelGGL((ctc_alpha_kernel<NS, PF, NW>), dim3((unsigned)nb), dim3(64 * NW), 0, s, emis, m, b0, W, nll); \
-        return hipGetLastError();                                                                                     \
+// The instances (NS states per lane, PF emission rows in flight, NW wave64s per line) of the alpha, beta and Viterbi
+// kernels; a batch launches the first whose 64 * NS * NW states hold its largest extended target 2L + 1. A long target
+// spreads over more waves (one barrier per step) rather than more states per lane: the recursion is latency-bound, and
+// a batch of lines occupies few of the 1024 SIMDs.
+#define HCTR_CTC_LADDER(X) X(1, 4, 1) X(2, 4, 1) X(2, 4, 2) X(2, 4, 4) X(2, 4, 8) X(2, 4, 16) X(4, 2, 16)
+
+template <int NS_, int PF_, int NW_>
+struct CtcRung {
+    static constexpr int NS = NS_, PF = PF_, NW = NW_;
+};
+// visit(CtcRung<NS, PF, NW>) of the rung that max_states launches; false beyond the ladder
+template <class F>
+bool ctc_rung(int max_states, F visit) {
+#define CTC_RUNG(NS, PF, NW)           \
+    if (max_states <= 64 * NS * NW) {  \
+        visit(CtcRung<NS, PF, NW>{});  \
+        return true;                   \
     }
-    // a long target spreads over more waves (one barrier per step) rather than more states per lane: the recursion is
-    // latency-bound, and a batch of lines occupies few of the 1024 SIMDs
-    CTC_ALPHA(1, 4, 1)
-    CTC_ALPHA(2, 4, 1)
-    CTC_ALPHA(2, 4, 2)
-    CTC_ALPHA(2, 4, 4)
-    CTC_ALPHA(2, 4, 8)
-    CTC_ALPHA(2, 4, 16)
-    CTC_ALPHA(4, 2, 16)
-#undef CTC_ALPHA
-    return hipErrorInvalidValue;
+    HCTR_CTC_LADDER(CTC_RUNG)
+#undef CTC_RUNG
+    return false;
+}
+template <class F>
+hipError_t ctc_launch_rung(int max_states, F launch) {
+    return ctc_rung(max_states, launch) ? hipGetLastError() : hipErrorInvalidValue;
+}
+int ctc_viterbi_lane_states(int max_states) {
+    int ns = 0;
+    ctc_rung(max_states, [&](auto r) { ns = decltype(r)::NS; });
+    return ns;
+}
+#define CTC_RUNG_STATES(NS, PF, NW) , 64 * NS * NW
+const int kCtcMaxStates = std::max({0 HCTR_CTC_LADDER(CTC_RUNG_STATES)});
+#undef CTC_RUNG_STATES
+
+hipError_t launch_ctc_alpha(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states, float* nll,
+                            const int64_t* aoff, float* ast, hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+    return ctc_launch_rung(max_states, [&](auto r) {
+        using R = decltype(r);
+        if (ast)
+            hipLaunchKernelGGL((ctc_alpha_store_kernel<R::NS, R::PF, R::NW>), dim3((unsigned)nb), dim3(64 * R::NW), 0, s,
+                               emis, m, b0, W, nll, aoff, ast);
+        else
+            hipLaunchKernelGGL((ctc_alpha_kernel<R::NS, R::PF, R::NW>), dim3((unsigned)nb), dim3(64 * R::NW), 0, s, emis, m,
+                               b0, W, nll);
+    });
 }
 
 // -------------------------------------------------------------------------------------------
@@ -3250,15 +3343,14 @@ hipError_t launch_ctc_alpha(const float* emis, const CtcLines& m, int b0, int nb
 // the gradient rows.
 // -------------------------------------------------------------------------------------------
 
-// The mirror image of ctc_alpha_line: same lane / wave state layout, t running down from T-1, the two states above a
-// lane's own come from the right neighbour over __shfl_down and across a wave boundary from the double-buffered LDS
-// slot. a[] holds beta_{t+1} (torch's convention: the emission at t+1 included); step t forms
+// The mirror image of ctc_forward_line over the shared pieces (FWD = false): t runs down from T-1 and the two states
+// above a lane's own come from the right. a[] holds beta_{t+1} (torch's convention: the emission at t+1 included);
+// step t forms
 // bp(s) = logsumexp(beta_{t+1}(s), beta_{t+1}(s+1), beta_{t+1}(s+2) if l_{s+2} != l_s), overwrites the stored
 // alpha_t(s) with y_t(s) = alpha_t(s) + nll + bp(s) (the log of the state's share of the posterior: alpha_t * beta_t
 // has the emission twice, alpha_t * bp once), and continues with beta_t = bp + lp_t. The virtual row beta_T = (0 at
-// state S-1, -inf elsewhere) makes step T-1 like every other. The alpha rows and the emissions of the next PF steps
-// are in flight while a step is computed. Lines without an alignment (T = 0) and lines whose loss is +inf are left
-// alone: the row kernel writes their zeros.
+// state S-1, -inf elsewhere) makes step T-1 like every other. A second ring holds the alpha rows of the next PF steps.
+// Lines without an alignment (T = 0) and lines whose loss is +inf are left alone: the row kernel writes their zeros.
 template <int NS, int PF, int NW>
 __global__ __launch_bounds__(64 * NW) void ctc_beta_kernel(const float* __restrict__ emis, const CtcLines m, int W,
                                                             const float* __restrict__ nll,
@@ -3270,16 +3362,9 @@ __global__ __launch_bounds__(64 * NW) void ctc_beta_kernel(const float* __restri
     if (T == 0) return;                            // (block-uniform)
     const float nl = nll[gb];
     if (nl == INFINITY) return;                    // (block-uniform)
-    const int32_t* ts = m.slot + m.off[gb];
     int slot[NS];
     bool skip[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int s = tid * NS + i;
-        const bool lab = (s & 1) && s < S;
-        slot[i] = lab ? ts[s >> 1] : 0;
-        skip[i] = lab && s + 2 < S && ts[(s >> 1) + 1] != ts[s >> 1];
-    }
+    ctc_lane_setup<NS, false>(m.slot + m.off[gb], S, slot, skip);
     const int D = m.D;
     const float* base = emis + (int64_t)gb * W * D;
     float* abase = ast + aoff[gb];
@@ -3291,7 +3376,8 @@ __global__ __launch_bounds__(64 * NW) void ctc_beta_kernel(const float* __restri
         sc[i] = min(s, S - 1);
         a[i] = s == S - 1 ? 0.f : -INFINITY;
     }
-    auto publish = [&](int parity) {
+    auto publish = [&](int parity) {             // ctc_publish's mirror, kept local: through the shared helper the
+                                                   // kernel took 4 more VGPRs and 3 % more time at 64 x 2000
         if (NW > 1) {
             if (lane == 0) {
                 xb[parity][wv][0] = a[0];
@@ -3302,9 +3388,7 @@ __global__ __launch_bounds__(64 * NW) void ctc_beta_kernel(const float* __restri
     };
     publish(0);
     float e[PF][NS], al[PF][NS];
-#pragma unroll
-    for (int k = 0; k < PF; ++k) {
-        const int row = max(T - 1 - k, 0);
+    auto ring_load = [&](int k, int row) {         // the emission ring and the alpha ring, a state's two loads together
         const float* r = base + (int64_t)row * D;
         const float* ar = abase + (int64_t)row * S;
 #pragma unroll
@@ -3312,46 +3396,31 @@ __global__ __launch_bounds__(64 * NW) void ctc_beta_kernel(const float* __restri
             e[k][i] = r[slot[i]];
             al[k][i] = ar[sc[i]];
         }
-    }
+    };
+#pragma unroll
+    for (int k = 0; k < PF; ++k) ring_load(k, max(T - 1 - k, 0));
     int par = 0;
     for (int t0 = T - 1; t0 >= 0; t0 -= PF) {
 #pragma unroll
         for (int k = 0; k < PF; ++k) {
             const int t = t0 - k;
             if (t >= 0) {                          // (block-uniform)
-                float q1 = __shfl_down(a[0], 1);
-                float q2 = NS >= 2 ? __shfl_down(a[NS >= 2 ? 1 : 0], 1) : __shfl_down(a[0], 2);
-                if (lane == 63) {
-                    q1 = wv < NW - 1 ? xb[par][wv < NW - 1 ? wv + 1 : 0][0] : -INFINITY;
-                    q2 = wv < NW - 1 ? xb[par][wv < NW - 1 ? wv + 1 : 0][1] : -INFINITY;
-                }
-                if (NS == 1 && lane == 62) q2 = -INFINITY;     // (NS == 1 only with NW == 1)
+                float q1, q2;
+                ctc_neighbours<NS, NW, false>(xb, par, a, q1, q2);
                 float* yr = abase + (int64_t)t * S + tid * NS;
 #pragma unroll
                 for (int i = 0; i < NS; ++i) {         // ascending: a[i+1], a[i+2] still hold step t+1
-                    const float la1 = a[i];
                     const float la2 = i + 1 < NS ? a[i + 1 < NS ? i + 1 : 0] : q1;
                     const float la3 = skip[i] ? (i + 2 < NS ? a[i + 2 < NS ? i + 2 : 0] : (i + 2 == NS ? q1 : q2))
                                               : -INFINITY;
-                    const float mx = fmaxf(la1, fmaxf(la2, la3));
-                    const float mn = fminf(la1, fminf(la2, la3));
-                    const float md = __builtin_amdgcn_fmed3f(la1, la2, la3);
-                    const float v = mx + __logf(1.f + __expf(md - mx) + __expf(mn - mx));
-                    const float bp = mx == -INFINITY ? -INFINITY : v;
+                    const float bp = ctc_logsum3(a[i], la2, la3);
                     if (tid * NS + i < S) yr[i] = (al[k][i] + nl) + bp;
                     a[i] = bp + e[k][i];
                 }
                 par ^= 1;
                 publish(par);
             }
-            const int row = max(t - PF, 0);        // refill the slot just used
-            const float* r = base + (int64_t)row * D;
-            const float* ar = abase + (int64_t)row * S;
-#pragma unroll
-            for (int i = 0; i < NS; ++i) {
-                e[k][i] = r[slot[i]];
-                al[k][i] = ar[sc[i]];
-            }
+            ring_load(k, max(t - PF, 0));          // refill the slots just used
         }
     }
 }
@@ -3416,36 +3485,14 @@ __global__ __launch_bounds__(256) void ctc_grad_rows_kernel(const float* __restr
     }
 }
 
-hipError_t launch_ctc_rowlse(const float* x, int64_t ld, int64_t sb, int64_t st, int C, const CtcLines& m, int b0, int nb,
-                             int W, float* emis, double* lse, hipStream_t s) {
-    if (nb <= 0 || W <= 0) return hipSuccess;
-    hipLaunchKernelGGL(ctc_rowlse_kernel, dim3((unsigned)((int64_t)nb * W)), dim3(256), 0, s, x, ld, sb, st, C, m, b0, W,
-                       emis, lse);
-    return hipGetLastError();
-}
-
-hipError_t launch_ctc_alpha_beta(const float* emis, const CtcLines& m, int B, int W, int max_states, float* nll,
-                                 const int64_t* aoff, float* ast, bool beta, hipStream_t s) {
+hipError_t launch_ctc_beta(const float* emis, const CtcLines& m, int B, int W, int max_states, const float* nll,
+                           const int64_t* aoff, float* ast, hipStream_t s) {
     if (B <= 0) return hipSuccess;
-#define CTC_AB(NS, PF, NW)                                                                                              \
-    if (max_states <= 64 * NS * NW) {                                                                                   \
-        if (beta)                                                                                                       \
-            hipLaunchKernelGGL((ctc_beta_kernel<NS, PF, NW>), dim3((unsigned)B), dim3(64 * NW), 0, s, emis, m, W, nll,  \
-                               aoff, ast);                                                                              \
-        else                                                                                                            \
-            hipLaunchKernelGGL((ctc_alpha_store_kernel<NS, PF, NW>), dim3((unsigned)B), dim3(64 * NW), 0, s, emis, m, 0, \
-                               W, nll, aoff, ast);                                                                      \
-        return hipGetLastError();                                                                                       \
-    }
-    CTC_AB(1, 4, 1)                                // the instances of launch_ctc_alpha
-    CTC_AB(2, 4, 1)
-    CTC_AB(2, 4, 2)
-    CTC_AB(2, 4, 4)
-    CTC_AB(2, 4, 8)
-    CTC_AB(2, 4, 16)
-    CTC_AB(4, 2, 16)
-#undef CTC_AB
-    return hipErrorInvalidValue;
+    return ctc_launch_rung(max_states, [&](auto r) {
+        using R = decltype(r);
+        hipLaunchKernelGGL((ctc_beta_kernel<R::NS, R::PF, R::NW>), dim3((unsigned)B), dim3(64 * R::NW), 0, s, emis, m, W, nll,
+                           aoff, ast);
+    });
 }
 
 hipError_t launch_ctc_grad_rows(const float* x, int C, int B, int W, const CtcLines& m, const double* lse,
@@ -3459,117 +3506,57 @@ hipError_t launch_ctc_grad_rows(const float* x, int C, int B, int W, const CtcLi
 
 // -------------------------------------------------------------------------------------------
 // CTC forced alignment (hctr_ctc_align*): the best path of a known transcription over the emissions of ctc_lse_kernel.
-// ctc_viterbi_kernel is the max-plus sibling of ctc_alpha_line with 2-bit backpointers, ctc_backtrace_kernel walks
+// ctc_viterbi_kernel is ctc_forward_line under the max-plus policy with 2-bit backpointers, ctc_backtrace_kernel walks
 // them back and writes the path, the character spans and their log-probabilities.
 // -------------------------------------------------------------------------------------------
 
-// Same lane / wave state layout, neighbour hand-over and emission prefetch as ctc_alpha_line; the step is
-// v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), [l_s != l_{s-2}] v_{t-1}(s-2)) + lp_t(s) in float32. Ties are part of the
-// contract: a predecessor replaces the running best only when strictly greater, in the order s, s-1, s-2. The choice
-// (0, 1 or 2 states down) of the lane's NS states is packed into one byte, state i at bits 2i, and stored at
-// bp[boff[gb] + t * ceil(S / NS) + lane index] for t >= 1: consecutive lanes, consecutive bytes. score[gb] is the
-// better of v_{T-1}(S-1) and v_{T-1}(S-2) (S-1 on a tie; state 0 for L = 0) and endst[gb] that state; a line marked
+// The max-plus policy: v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), [l_s != l_{s-2}] v_{t-1}(s-2)) + lp_t(s) in float32. Ties
+// are part of the contract: a predecessor replaces the running best only when strictly greater, in the order s, s-1,
+// s-2. The choice (0, 1 or 2 states down) of the lane's NS states is packed into one byte, state i at bits 2i, and
+// stored at bp[boff[gb] + t * ceil(S / NS) + lane index] for t >= 1: consecutive lanes, consecutive bytes. score[gb] is
+// the better of v_{T-1}(S-1) and v_{T-1}(S-2) (S-1 on a tie; state 0 for L = 0) and endst[gb] that state; a line marked
 // T = 0 gets -inf and -1.
+template <int NS_>
+struct CtcMax {
+    static constexpr int NS = NS_;
+    static_assert(NS <= 4, "one byte holds the backpointers of a lane");
+    const int64_t* __restrict__ boff;
+    uint8_t* __restrict__ bp;
+    float* __restrict__ score;
+    int32_t* __restrict__ endst;
+    uint8_t* brow;
+    int stride;                                    // bytes per step: the lanes that hold a state
+    __device__ __forceinline__ void start(int gb, int S, const float (&)[NS]) {
+        stride = (S + NS - 1) / NS;
+        brow = bp + boff[gb] + (int)threadIdx.x;
+    }
+    __device__ __forceinline__ float combine(float best, float la2, float la3, int i, unsigned& code) const {
+        unsigned from = 0;
+        if (la2 > best) { best = la2; from = 1; }
+        if (la3 > best) { best = la3; from = 2; }
+        code |= from << (2 * i);
+        return best;
+    }
+    __device__ __forceinline__ void row(int t, const float (&)[NS], unsigned code) const {
+        if ((int)threadIdx.x < stride) brow[(int64_t)t * stride] = (uint8_t)code;
+    }
+    __device__ __forceinline__ void none(int gb) const {
+        score[gb] = -INFINITY;
+        endst[gb] = -1;
+    }
+    __device__ __forceinline__ void finish(int gb, int L, int S, float last, float prev) const {
+        const bool end = L == 0 || last >= prev;
+        score[gb] = end ? last : prev;
+        endst[gb] = end ? S - 1 : S - 2;
+    }
+};
+
 template <int NS, int PF, int NW>
 __global__ __launch_bounds__(64 * NW) void ctc_viterbi_kernel(const float* __restrict__ emis, const CtcLines m, int b0,
                                                                int W, const int64_t* __restrict__ boff,
                                                                uint8_t* __restrict__ bp, float* __restrict__ score,
                                                                int32_t* __restrict__ endst) {
-    static_assert(NW == 1 || NS >= 2, "a wave boundary hands over two states from one lane");
-    static_assert(NS <= 4, "one byte holds the backpointers of a lane");
-    __shared__ float xb[2][NW][2];                 // [step parity][wave] = {state wave_end-1, state wave_end-2}
-    __shared__ float fin[2];
-    const int b = blockIdx.x, gb = b0 + b, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int T = m.T[gb], L = m.L[gb], S = 2 * L + 1;
-    if (T == 0) {                                  // no alignment (host-side feasibility test); block-uniform
-        if (tid == 0) {
-            score[gb] = -INFINITY;
-            endst[gb] = -1;
-        }
-        return;
-    }
-    const int32_t* ts = m.slot + m.off[gb];
-    int slot[NS];
-    bool skip[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int s = tid * NS + i;
-        const bool lab = (s & 1) && s < S;
-        slot[i] = lab ? ts[s >> 1] : 0;
-        skip[i] = lab && s >= 3 && ts[s >> 1] != ts[(s >> 1) - 1];
-    }
-    const int D = m.D;
-    const float* base = emis + (int64_t)b * W * D;
-    float a[NS];
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int s = tid * NS + i;
-        a[i] = (s == 0 || (s == 1 && S > 1)) ? base[slot[i]] : -INFINITY;
-    }
-    const int stride = (S + NS - 1) / NS;          // bytes per step: the lanes that hold a state
-    const bool own = tid < stride;
-    uint8_t* brow = bp + boff[gb] + tid;
-    auto publish = [&](int parity) {
-        if (NW > 1) {
-            if (lane == 63) {
-                xb[parity][wv][0] = a[NS - 1];
-                xb[parity][wv][1] = a[NS >= 2 ? NS - 2 : 0];
-            }
-            __syncthreads();
-        }
-    };
-    publish(0);
-    float e[PF][NS];
-#pragma unroll
-    for (int k = 0; k < PF; ++k) {
-        const float* r = base + (int64_t)min(1 + k, T - 1) * D;
-#pragma unroll
-        for (int i = 0; i < NS; ++i) e[k][i] = r[slot[i]];
-    }
-    for (int t0 = 1; t0 < T; t0 += PF) {
-#pragma unroll
-        for (int k = 0; k < PF; ++k) {
-            const int t = t0 + k;
-            if (t < T) {                           // (block-uniform)
-                float p1 = __shfl_up(a[NS - 1], 1);
-                float p2 = NS >= 2 ? __shfl_up(a[NS >= 2 ? NS - 2 : 0], 1) : __shfl_up(a[NS - 1], 2);
-                if (lane == 0) {
-                    p1 = wv > 0 ? xb[(t - 1) & 1][wv > 0 ? wv - 1 : 0][0] : -INFINITY;
-                    p2 = wv > 0 ? xb[(t - 1) & 1][wv > 0 ? wv - 1 : 0][1] : -INFINITY;
-                }
-                if (NS == 1 && lane == 1) p2 = -INFINITY;      // (NS == 1 only with NW == 1)
-                unsigned code = 0;
-#pragma unroll
-                for (int i = NS - 1; i >= 0; --i) {      // descending: a[i-1], a[i-2] still hold step t-1
-                    const float la2 = i >= 1 ? a[i >= 1 ? i - 1 : 0] : p1;
-                    const float la3 = skip[i] ? (i >= 2 ? a[i >= 2 ? i - 2 : 0] : (i == 1 ? p1 : p2)) : -INFINITY;
-                    float best = a[i];
-                    unsigned from = 0;
-                    if (la2 > best) { best = la2; from = 1; }
-                    if (la3 > best) { best = la3; from = 2; }
-                    a[i] = best + e[k][i];
-                    code |= from << (2 * i);
-                }
-                if (own) brow[(int64_t)t * stride] = (uint8_t)code;
-                publish(t & 1);
-            }
-            const float* r = base + (int64_t)min(t + PF, T - 1) * D;   // refill the slot just used
-#pragma unroll
-            for (int i = 0; i < NS; ++i) e[k][i] = r[slot[i]];
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < NS; ++i) {
-        const int s = tid * NS + i;
-        if (s == S - 1) fin[0] = a[i];
-        if (s == S - 2) fin[1] = a[i];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        const bool last = L == 0 || fin[0] >= fin[1];
-        score[gb] = last ? fin[0] : fin[1];
-        endst[gb] = last ? S - 1 : S - 2;
-    }
+    ctc_forward_line<PF, NW>(emis, m, b0, W, CtcMax<NS>{boff, bp, score, endst, nullptr, 0});
 }
 
 // One 256-thread workgroup per line. The walk t = T-1 .. 1 is serial and every step's read depends on the one before,
@@ -3660,22 +3647,11 @@ __global__ __launch_bounds__(256) void ctc_backtrace_kernel(const float* __restr
 hipError_t launch_ctc_viterbi(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states,
                               const int64_t* boff, uint8_t* bp, float* score, int32_t* endst, hipStream_t s) {
     if (nb <= 0) return hipSuccess;
-#define CTC_VITERBI(NS, PF, NW)                                                                                        \
-    if (max_states <= 64 * NS * NW) {                                                                                  \
-        static_assert(NS == ctc_viterbi_lane_states(64 * NS * NW), "the back-trace unpacks NS states per byte");  \
-        hipLaunchKernelGGL((ctc_viterbi_kernel<NS, PF, NW>), dim3((unsigned)nb), dim3(64 * NW), 0, s, emis, m, b0, W,  \
-                           boff, bp, score, endst);                                                                    \
-        return hipGetLastError();                                                                                      \
-    }
-    CTC_VITERBI(1, 4, 1)                           // the ladder of launch_ctc_alpha
-    CTC_VITERBI(2, 4, 1)
-    CTC_VITERBI(2, 4, 2)
-    CTC_VITERBI(2, 4, 4)
-    CTC_VITERBI(2, 4, 8)
-    CTC_VITERBI(2, 4, 16)
-    CTC_VITERBI(4, 2, 16)
-#undef CTC_VITERBI
-    return hipErrorInvalidValue;
+    return ctc_launch_rung(max_states, [&](auto r) {
+        using R = decltype(r);
+        hipLaunchKernelGGL((ctc_viterbi_kernel<R::NS, R::PF, R::NW>), dim3((unsigned)nb), dim3(64 * R::NW), 0, s, emis, m, b0,
+                           W, boff, bp, score, endst);
+    });
 }
 
 hipError_t launch_ctc_backtrace(const float* emis, const CtcLines& m, int b0, int nb, int W, int max_states,

@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+import ctc_align_ref as align_ref
+
 pytestmark = pytest.mark.gpu
 
 FACTOR, FLOOR = 4.0, 2e-5
@@ -236,6 +238,29 @@ def test_small_shapes(pkg, crit_none):
         np.testing.assert_allclose(nll[fin], nll64[fin], rtol=1e-5, atol=1e-3)
         assert (nll64[~fin] == 0).all()
         _check_rule(grad, g64, g32, None, str((W, B, C)))
+
+
+def test_every_ladder_instance(pkg, crit_none):
+    """S = 2L + 1 = 41 .. 2201 reaches every bucket of the launch ladder (<= 64, 128, 256, 512, 1024, 2048, 4096) as the
+    batch's largest; the prefixes make each bucket the launched one, since a batch launches the instance of its longest
+    target. A line's loss and gradient do not depend on the rest of the batch, so one torch reference serves all."""
+    W, C = 1200, 64
+    Ls = [20, 50, 100, 200, 400, 900, 1100]
+    Ts = [1000, W, W, 1111, W, W, W]
+    reps = [0.3, 0.3, 0.3, 0.3, 0.3, 0.1, 0.04]
+    rng = np.random.RandomState(5)
+    lines = [align_ref.random_target(rng, C, L, r) for L, r in zip(Ls, reps)]
+    for t, T in zip(lines, Ts):
+        assert len(t) + int((t[1:] == t[:-1]).sum()) <= T   # every line has an alignment
+    logits = (rng.standard_normal((W, len(Ls), C)) * 3).astype(np.float32)
+    tl, il = np.array(Ls, np.int32), np.array(Ts, np.int32)
+    g64, g32, nll64 = _torch_grads(logits, np.concatenate(lines), tl, il)
+    for n in [len(Ls)] + list(range(1, len(Ls))):
+        x, tg = np.ascontiguousarray(logits[:, :n]), np.concatenate(lines[:n]).astype(np.int32)
+        nll, grad = _raw_grad(pkg, crit_none, x, tg, tl[:n], il[:n])
+        np.testing.assert_allclose(nll, nll64[:n], rtol=1e-5, atol=1e-3)
+        _check_rule(grad, g64[:, :n], g32[:, :n], None, "ladder, first %d" % n)
+        np.testing.assert_array_equal(pkg.ctc.loss_logits(crit_none._context(), x, 0, tg, tl[:n], il[:n]), nll)
 
 
 def _autograd_case():
