@@ -178,6 +178,20 @@ class ctc_codec(object):
             full_logp = self._full_logp(logits, on_dev)
         return self.decode_frontend(fe, full_logp)
 
+    def recognize(self, preds):
+        """Greedy decode of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) with per-character spans,
+        confidences and runners-up: returns ``(texts, ctc.Recognition)``, ``texts`` being exactly ``decode``'s greedy
+        strings whatever ``use_beam_search`` says (include/hctr_hip.h ``hctr_recognize_logits``)."""
+        from . import ctc
+        logits, on_dev = self._as_logits(preds)
+        W, B, C = (int(v) for v in logits.shape)
+        if C != len(self.characters):
+            raise ValueError("logits have %d classes, codec has %d" % (C, len(self.characters)))
+        if W == 0:
+            raise ValueError("preds have no steps (W = 0)")
+        rec = ctc.recognize_logits(self._context(), logits, on_dev)
+        return self.labels_to_text(rec.label_lists()), rec
+
     def labels_to_text(self, label_lists):
         chars = self.characters
         return ["".join(chars[i] for i in line) for line in label_lists]

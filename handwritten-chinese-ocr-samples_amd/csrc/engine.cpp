@@ -1118,6 +1118,33 @@ int ctc_prepare(hctr_ctx* c, int B, int W, int C, const int32_t* targets, const 
     return HCTR_OK;
 }
 
+// the context's grow-only CTC scratch with room for `need` bytes. When it has to grow, its first `keep` bytes move to
+// the new block (recognition's kept log-sum-exps); with keep = 0 the old block is freed before the new one is asked for.
+int ctc_reserve(hctr_ctx* c, size_t need, size_t keep = 0) {
+    if (need <= c->ctc_cap) return HCTR_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if (!keep) {
+        if (c->ctc_buf) (void)hipFree(c->ctc_buf);
+        c->ctc_buf = nullptr; c->ctc_cap = 0;
+    }
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, need);
+    if (e != hipSuccess)
+        return fail(c, HCTR_ERR_NOMEM, "hipMalloc(%zu bytes) for the CTC scratch failed: %s", need, hipGetErrorString(e));
+    if (keep) {
+        e = hipMemcpyAsync(p, c->ctc_buf, keep, hipMemcpyDeviceToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) {
+            (void)hipFree(p);
+            return fail(c, HCTR_ERR_HIP, "moving the CTC scratch: %s", hipGetErrorString(e));
+        }
+        (void)hipFree(c->ctc_buf);
+    }
+    c->ctc_buf = (char*)p;
+    c->ctc_cap = need;
+    return HCTR_OK;
+}
+
 // device scratch of a CTC call: the tables (uploaded), nll[B], `emis_floats` emission floats and, for the gradient,
 // `extra_b` more bytes at *extra (256-byte aligned)
 int ctc_scratch(hctr_ctx* c, const CtcHost& h, size_t emis_floats, CtcLines* m, float** nll, float** emis,
@@ -1125,17 +1152,7 @@ int ctc_scratch(hctr_ctx* c, const CtcHost& h, size_t emis_floats, CtcLines* m, 
     const size_t tab_b = align256(h.tab.size() * 4), nll_b = align256((size_t)h.B * 4);
     const size_t emis_b = extra_b ? align256(emis_floats * 4) : emis_floats * 4;
     const size_t need = tab_b + nll_b + emis_b + extra_b;
-    if (need > c->ctc_cap) {
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (c->ctc_buf) (void)hipFree(c->ctc_buf);
-        c->ctc_buf = nullptr; c->ctc_cap = 0;
-        void* p = nullptr;
-        hipError_t e = hipMalloc(&p, need);
-        if (e != hipSuccess)
-            return fail(c, HCTR_ERR_NOMEM, "hipMalloc(%zu bytes) for the CTC scratch failed: %s", need, hipGetErrorString(e));
-        c->ctc_buf = (char*)p;
-        c->ctc_cap = need;
-    }
+    TRY(ctc_reserve(c, need));
     *m = h.lines((const int32_t*)c->ctc_buf);
     *nll = (float*)(c->ctc_buf + tab_b);
     *emis = (float*)(c->ctc_buf + tab_b + nll_b);
@@ -1245,6 +1262,90 @@ int ctc_image_call(hctr_ctx* c, const void* img, int img_dtype, int img_on_devic
     }
     // pageable host tables queued above were staged before hipMemcpyAsync returned
     return synced(c, rc);
+}
+
+// ---------------------------------------------------------------------------------------------
+// greedy recognition (hctr_recognize*)
+// ---------------------------------------------------------------------------------------------
+struct RecOut {              // the caller's host outputs, [B][W] / [B]; any may be null
+    int32_t *labels, *lengths, *span_start, *span_end;
+    float* char_logp;
+    int32_t* alt_label;
+    float *alt_logp, *path_logp, *text_nll;
+};
+
+// One pass of nb lines, [b0, b0 + nb) of the caller's batch, whose logit rows lie at x + (b*sb + t*st) * ld. The CTC
+// scratch holds lse[nb*W] first, which outlives the row figures and the spans; once those are on the host the tables,
+// nll and emissions of the decoded text take their place. h_lab / h_len: where the batch's labels and lengths go on the
+// host (the caller's arrays, or the call's own when text_nll needs them). Returns with the stream drained when
+// text_nll is wanted.
+int rec_pass(hctr_ctx* c, const float* x, int64_t ld, int64_t sb, int64_t st, int C, int b0, int nb, int W,
+             const RecOut& o, int32_t* h_lab, int32_t* h_len) {
+    const size_t n = (size_t)nb, col_b = align256(n * W * 4), line_b = align256(n * 4), lse_b = align256(n * W * 8);
+    TRY(ctc_reserve(c, lse_b + 10 * col_b + 2 * line_b));
+    double* d_lse = (double*)c->ctc_buf;
+    char* q = c->ctc_buf + lse_b;
+    auto col = [&]() { char* r = q; q += col_b; return r; };
+    int32_t *k1 = (int32_t*)col(), *k2 = (int32_t*)col();
+    float *lp1 = (float*)col(), *lp2 = (float*)col();
+    int32_t *d_lab = (int32_t*)col(), *d_st = (int32_t*)col(), *d_en = (int32_t*)col(), *d_alab = (int32_t*)col();
+    float *d_clp = (float*)col(), *d_alp = (float*)col();
+    int32_t* d_len = (int32_t*)q;
+    float* d_plp = (float*)(q + line_b);
+    Prof pf(c);
+    pf.begin("greedy_rowstat");
+    HIP_TRY(c, launch_greedy_rowstat(x, ld, sb, st, C, nb, W, k1, k2, lp1, lp2, d_lse, c->stream));
+    pf.end();
+    pf.begin("greedy_spans");
+    HIP_TRY(c, launch_greedy_spans(k1, k2, lp1, lp2, nb, W, C, d_lab, d_len, d_st, d_en, d_clp, d_alab, d_alp, d_plp,
+                                   c->stream));
+    pf.end();
+    const size_t co = (size_t)b0 * W, cb = n * W * 4;
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIP_TRY(c, fetch(h_lab ? h_lab + co : nullptr, d_lab, cb));
+    HIP_TRY(c, fetch(h_len ? h_len + b0 : nullptr, d_len, n * 4));
+    HIP_TRY(c, fetch(o.span_start ? o.span_start + co : nullptr, d_st, cb));
+    HIP_TRY(c, fetch(o.span_end ? o.span_end + co : nullptr, d_en, cb));
+    HIP_TRY(c, fetch(o.char_logp ? o.char_logp + co : nullptr, d_clp, cb));
+    HIP_TRY(c, fetch(o.alt_label ? o.alt_label + co : nullptr, d_alab, cb));
+    HIP_TRY(c, fetch(o.alt_logp ? o.alt_logp + co : nullptr, d_alp, cb));
+    HIP_TRY(c, fetch(o.path_logp ? o.path_logp + b0 : nullptr, d_plp, n * 4));
+    if (!o.text_nll) return HCTR_OK;
+    std::vector<float> plp(n);                 // a NaN here marks a line with a NaN row
+    HIP_TRY(c, fetch(plp.data(), d_plp, n * 4));
+    // the loss of the decoded text: its tables are built as the loss builds them, on labels that must be on the host
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    std::vector<int32_t> tg, tl((size_t)nb);
+    for (int b = 0; b < nb; ++b) {
+        const int L = h_len[b0 + b];
+        const bool fits = 2 * (int64_t)L + 1 <= kCtcMaxStates;      // a longer text gets NaN, not an error
+        tl[(size_t)b] = fits ? L : 0;
+        if (fits) tg.insert(tg.end(), h_lab + (co + (size_t)b * W), h_lab + (co + (size_t)b * W) + L);
+    }
+    CtcHost h;
+    TRY(ctc_prepare(c, nb, W, C, tg.data(), tl.data(), nullptr, &h));
+    const size_t tab_b = align256(h.tab.size() * 4);
+    TRY(ctc_reserve(c, lse_b + tab_b + line_b + n * W * h.D * 4, lse_b));
+    d_lse = (double*)c->ctc_buf;
+    const CtcLines m = h.lines((const int32_t*)(c->ctc_buf + lse_b));
+    float* d_nll = (float*)(c->ctc_buf + lse_b + tab_b);
+    float* emis = (float*)(c->ctc_buf + lse_b + tab_b + line_b);
+    HIP_TRY(c, hipMemcpyAsync(c->ctc_buf + lse_b, h.tab.data(), h.tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    pf.begin("ctc_emis_gather");
+    HIP_TRY(c, launch_ctc_emis_gather(x, ld, sb, st, m, 0, nb, W, d_lse, emis, c->stream));
+    pf.end();
+    pf.begin("ctc_alpha");
+    HIP_TRY(c, launch_ctc_alpha(emis, m, 0, nb, W, h.max_states, d_nll, nullptr, nullptr, c->stream));
+    pf.end();
+    HIP_TRY(c, hipMemcpyAsync(o.text_nll + b0, d_nll, n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // the recursion's max / min drop a NaN emission, so the loss of a line with a NaN row is no figure: NaN, by contract
+    for (int b = 0; b < nb; ++b)
+        if (tl[(size_t)b] != h_len[b0 + b] || plp[(size_t)b] != plp[(size_t)b])
+            o.text_nll[b0 + b] = std::numeric_limits<float>::quiet_NaN();
+    return HCTR_OK;
 }
 
 }  // namespace
@@ -1637,6 +1738,7 @@ int hctr_decode_greedy_logits(hctr_ctx* c, const float* logits_wbc, int on_devic
         if ((int64_t)W * B == 0) return HCTR_OK;     // reference: zero-length lines produce no output (:85-86)
         if (!logits_wbc || !labels || !lengths) return fail(c, HCTR_ERR_ARG, "NULL pointer");
         HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
         const float* dev = nullptr;
@@ -1647,8 +1749,15 @@ int hctr_decode_greedy_logits(hctr_ctx* c, const float* logits_wbc, int on_devic
         if (rc == HCTR_OK) rc = dev_alloc(c, tmp, &dn, (size_t)B, false);
         if (rc == HCTR_OK) {
             // rows of the WBC tensor are r = t*B + b; the argmax kernel writes idx as [b][t]
+            Prof pf(c);
+            pf.begin("argmax_rows");
             hipError_t e = launch_argmax_rows(dev, C, (int64_t)W * B, C, idx, B, W, c->stream);
-            if (e == hipSuccess) e = launch_ctc_collapse(idx, B, W, C, dl, dn, c->stream);
+            pf.end();
+            if (e == hipSuccess) {
+                pf.begin("ctc_collapse");
+                e = launch_ctc_collapse(idx, B, W, C, dl, dn, c->stream);
+                pf.end();
+            }
             if (e == hipSuccess) e = hipMemcpyAsync(labels, dl, (size_t)W * B * 4, hipMemcpyDeviceToHost, c->stream);
             if (e == hipSuccess) e = hipMemcpyAsync(lengths, dn, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
             if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "decode_greedy_logits: %s", hipGetErrorString(e));
@@ -2067,6 +2176,62 @@ int hctr_ctc_align_logits(hctr_ctx* c, const float* logits_wbc, int on_device, i
             if (e == hipSuccess) e = align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
             if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_align_logits: %s", hipGetErrorString(e));
         }
+        return synced(c, rc);
+    });
+}
+
+int hctr_recognize(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
+                   int32_t* labels, int32_t* lengths, int32_t* span_start, int32_t* span_end, float* char_logp,
+                   int32_t* alt_label, float* alt_logp, float* path_logp, float* text_nll) {
+    return guard(c, [&]() -> int {
+        TRY(check_forward_args(c, img, img_dtype, B, W));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        SplitScope scope(c);
+        c->split = c->mode != 0;              // as hctr_ctc_loss: mode 2's guard certifies argmaxes, not confidences
+        if (!c->wts().built) return fail(c, HCTR_ERR_STATE, "the weight set of this precision mode is not resident");
+        prof_reset(c);
+        const RecOut o{labels, lengths, span_start, span_end, char_logp, alt_label, alt_logp, path_logp, text_nll};
+        std::vector<int32_t> own_lab, own_len;
+        if (text_nll && !labels) own_lab.resize((size_t)B * W);
+        if (text_nll && !lengths) own_len.resize((size_t)B);
+        int32_t* h_lab = labels ? labels : text_nll ? own_lab.data() : nullptr;
+        int32_t* h_len = lengths ? lengths : text_nll ? own_len.data() : nullptr;
+        std::vector<int> all((size_t)B);
+        for (int b = 0; b < B; ++b) all[(size_t)b] = b;
+        const int nbmax = sub_batch(c, B, W, c->split);
+        auto pass = [&](int b0, int nb) -> int {
+            TRY(ensure_workspace(c, nb, W, ws_need(c, HEAD_LOGITS)));
+            TRY(stage_input(c, img, img_dtype, img_on_device, widths, all.data() + b0, nb, W));
+            TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, HEAD_LOGITS, false));
+            return rec_pass(c, c->ws.logits, c->cpad, W, 1, c->num_classes, b0, nb, W, o, h_lab, h_len);
+        };
+        int rc = HCTR_OK;
+        for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax) rc = pass(b0, std::min(nbmax, B - b0));
+        return synced(c, rc);
+    });
+}
+
+int hctr_recognize_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W, int B, int C, int32_t* labels,
+                          int32_t* lengths, int32_t* span_start, int32_t* span_end, float* char_logp, int32_t* alt_label,
+                          float* alt_logp, float* path_logp, float* text_nll) {
+    return guard(c, [&]() -> int {
+        TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
+        const RecOut o{labels, lengths, span_start, span_end, char_logp, alt_label, alt_logp, path_logp, text_nll};
+        std::vector<int32_t> own_lab, own_len;
+        if (text_nll && !labels) own_lab.resize((size_t)B * W);
+        if (text_nll && !lengths) own_len.resize((size_t)B);
+        std::vector<void*> tmp;
+        PoolGuard tmp_guard{tmp};
+        const float* dev = nullptr;
+        int rc = logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev);
+        // rows of the WBC tensor are r = t*B + b
+        if (rc == HCTR_OK)
+            rc = rec_pass(c, dev, C, 1, B, C, 0, B, W, o, labels ? labels : text_nll ? own_lab.data() : nullptr,
+                          lengths ? lengths : text_nll ? own_len.data() : nullptr);
         return synced(c, rc);
     });
 }

@@ -241,6 +241,23 @@ hipError_t launch_ctc_backtrace(const float* emis, const CtcLines& m, int b0, in
                                 const int64_t* boff, const uint8_t* bp, const int32_t* endst, int32_t* path,
                                 int32_t* span_start, int32_t* span_end, float* span_logp, hipStream_t s);
 
+// greedy recognition (hctr_recognize*), rows of logits at x + (b*sb + t*st) * ld for the pass's lines b = 0..nb-1, every
+// one of the W columns; all per-column and per-character arrays are [nb][W]:
+// launch_greedy_rowstat: one read of each row -> k1 (np.argmax), k2 (the first index of the largest logit among the other
+//   classes), lp1 / lp2 = float32(z[k] - lse) and lse, the row's log-sum-exp with launch_ctc_lse's arithmetic, bit for bit;
+// launch_greedy_spans: the greedy collapse of k1 (launch_ctc_collapse's labels and lengths) and per character j its first
+//   column, the column after its run, the ascending-t float32 sum of lp1 over the run, and k2 / lp2 at the run's peak
+//   column (largest lp1, first on ties); path_logp[b] = the sum of lp1 over the line's W columns, in a fixed order;
+// launch_ctc_emis_gather: launch_ctc_lse's emissions, bit for bit, from kept log-sum-exps lse[b*W + t]: D values are read
+//   per row, not the row.
+hipError_t launch_greedy_rowstat(const float* x, int64_t ld, int64_t sb, int64_t st, int C, int nb, int W, int32_t* k1,
+                                 int32_t* k2, float* lp1, float* lp2, double* lse, hipStream_t s);
+hipError_t launch_greedy_spans(const int32_t* k1, const int32_t* k2, const float* lp1, const float* lp2, int nb, int W,
+                               int C, int32_t* labels, int32_t* lengths, int32_t* span_start, int32_t* span_end,
+                               float* char_logp, int32_t* alt_label, float* alt_logp, float* path_logp, hipStream_t s);
+hipError_t launch_ctc_emis_gather(const float* x, int64_t ld, int64_t sb, int64_t st, const CtcLines& m, int b0, int nb,
+                                  int W, const double* lse, float* emis, hipStream_t s);
+
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {
     int64_t src_off;          // byte offset of the image inside the packed source buffer

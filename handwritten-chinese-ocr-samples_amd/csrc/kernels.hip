@@ -3027,27 +3027,24 @@ hipError_t launch_beam_candidates(const int32_t* emit_cnt, const int32_t* emit_l
 // emis[(b*W + t) * D + j]; the alpha recursion reads nothing else. See CtcLines in kernels.h.
 // -------------------------------------------------------------------------------------------
 
-// One 256-thread block per (t, line): log-sum-exp of the row (float32 max, float64 exp-sum and log) in one pass over it,
-// then the slots of D_b as float32(z - lse). Rows t >= T_b are not read. KEEP (the gradient's pass) also keeps the row's
-// log-sum-exp, lse_out[b*W + t]; the arithmetic is the same, so emis is bit-identical either way.
-template <bool KEEP>
-__device__ __forceinline__ void ctc_lse_row(const float* __restrict__ x, int64_t ld, int64_t sb, int64_t st, int C,
-                                            const CtcLines& m, int b0, int W, float* __restrict__ emis,
-                                            double* __restrict__ lse_out) {
+// Log-sum-exp of the row p[0..C) by a 256-thread block (float32 max, float64 exp-sum and log), every thread's result.
+// One pass over the row: eight loads in flight per thread, a running (max, exp-sum) rescaled when the max grows.
+// see(v, c) is handed every element a thread loads, in ascending c (greedy_rowstat_kernel's top-2; the loss passes
+// nothing, and its code is what it was).
+template <class See>
+__device__ __forceinline__ double ctc_row_lse(const float* __restrict__ p, int C, See see) {
     __shared__ float rv[4];
     __shared__ double rd[4];
-    const int64_t r = blockIdx.x;                  // b*W + t
-    const int b = (int)(r / W), t = (int)(r % W), gb = b0 + b;
-    if (t >= m.T[gb]) return;                      // (block-uniform)
-    const float* p = x + ((int64_t)b * sb + (int64_t)t * st) * ld;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    // one pass over the row: eight loads in flight per thread, a running (max, exp-sum) rescaled when the max grows
     float tm = -INFINITY;
     double ts = 0.0;
     for (int c0 = tid; c0 < C; c0 += 8 * 256) {
         float v[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = c0 + k * 256 < C ? p[c0 + k * 256] : -INFINITY;
+#pragma unroll
+        for (int k = 0; k < 8; ++k)
+            if (c0 + k * 256 < C) see(v[k], c0 + k * 256);
         float cm = v[0];
 #pragma unroll
         for (int k = 1; k < 8; ++k) cm = fmaxf(cm, v[k]);
@@ -3067,7 +3064,22 @@ __device__ __forceinline__ void ctc_lse_row(const float* __restrict__ x, int64_t
     __syncthreads();
     mx = fmaxf(fmaxf(rv[0], rv[1]), fmaxf(rv[2], rv[3]));
     const double s = block_sum_d(tm == -INFINITY ? 0.0 : ts * (double)expf(tm - mx), rd);
-    const double lse = (double)mx + log(s);
+    return (double)mx + log(s);
+}
+
+// One 256-thread block per (t, line): log-sum-exp of the row in one pass over it, then the slots of D_b as
+// float32(z - lse). Rows t >= T_b are not read. KEEP (the gradient's pass) also keeps the row's log-sum-exp,
+// lse_out[b*W + t]; the arithmetic is the same, so emis is bit-identical either way.
+template <bool KEEP>
+__device__ __forceinline__ void ctc_lse_row(const float* __restrict__ x, int64_t ld, int64_t sb, int64_t st, int C,
+                                            const CtcLines& m, int b0, int W, float* __restrict__ emis,
+                                            double* __restrict__ lse_out) {
+    const int64_t r = blockIdx.x;                  // b*W + t
+    const int b = (int)(r / W), t = (int)(r % W), gb = b0 + b;
+    if (t >= m.T[gb]) return;                      // (block-uniform)
+    const float* p = x + ((int64_t)b * sb + (int64_t)t * st) * ld;
+    const int tid = threadIdx.x;
+    const double lse = ctc_row_lse(p, C, [](float, int) {});
     const int nd = m.nd[gb];
     const int32_t* cls = m.cls + (int64_t)gb * m.D;
     float* e = emis + ((int64_t)b * W + t) * m.D;
@@ -3661,6 +3673,182 @@ hipError_t launch_ctc_backtrace(const float* emis, const CtcLines& m, int b0, in
     const int ns = ctc_viterbi_lane_states(max_states), sh = ns == 1 ? 0 : ns == 2 ? 1 : 2;
     hipLaunchKernelGGL(ctc_backtrace_kernel, dim3((unsigned)nb), dim3(256), 0, s, emis, m, b0, W, sh, boff, bp, endst, path,
                        span_start, span_end, span_logp);
+    return hipGetLastError();
+}
+
+// -------------------------------------------------------------------------------------------
+// Greedy recognition (hctr_recognize*): the greedy path is itself a CTC path, so its spans need no recursion.
+// greedy_rowstat_kernel reads every row once for argmax, runner-up and log-sum-exp; greedy_spans_kernel collapses a
+// line and sums each character's run; ctc_emis_gather_kernel forms the emissions of the decoded text from the kept
+// log-sum-exp, for the loss's own ctc_alpha ladder.
+// -------------------------------------------------------------------------------------------
+constexpr int kNoIdx = 0x7fffffff;
+
+// np.argmax's order between two (value, class) pairs of distinct classes: NaN counts as the maximum, the lower class
+// wins a tie. The empty pair (-inf, kNoIdx) loses to every real one.
+__device__ __forceinline__ bool np_beats(float a, int ai, float b, int bi) {
+    return np_gt(a, b) || (np_eq(a, b) && ai < bi);
+}
+
+// the best two of the union of two best-two pairs over disjoint classes
+__device__ __forceinline__ void top2_merge(float& bv, int& bi, float& sv, int& si, float obv, int obi, float osv, int osi) {
+    const bool wins = np_beats(obv, obi, bv, bi);
+    const float lv = wins ? bv : obv, kv = wins ? osv : sv;      // the losing best against the winner's own runner-up
+    const int li = wins ? bi : obi, ki = wins ? osi : si;
+    const bool l2 = np_beats(lv, li, kv, ki);
+    sv = l2 ? lv : kv;
+    si = l2 ? li : ki;
+    if (wins) { bv = obv; bi = obi; }
+}
+
+// One 256-thread block per row r = b*W + t of the pass (logits at x + (b*sb + t*st) * ld): ctc_row_lse's pass over the
+// row, which also carries each thread's best two elements. A thread sees its classes in ascending order, so strict
+// comparisons keep the first index; elements equal to -inf never enter, and the row's last thread settles the rows
+// that have fewer than two others.
+__global__ __launch_bounds__(256) void greedy_rowstat_kernel(const float* __restrict__ x, int64_t ld, int64_t sb, int64_t st,
+                                                             int C, int W, int32_t* __restrict__ k1,
+                                                             int32_t* __restrict__ k2, float* __restrict__ lp1,
+                                                             float* __restrict__ lp2, double* __restrict__ lse_out) {
+    __shared__ float wbv[4], wsv[4];
+    __shared__ int wbi[4], wsi[4];
+    const int64_t r = blockIdx.x;
+    const int b = (int)(r / W), t = (int)(r % W);
+    const float* p = x + ((int64_t)b * sb + (int64_t)t * st) * ld;
+    float bv = -INFINITY, sv = -INFINITY;
+    int bi = kNoIdx, si = kNoIdx;
+    const double lse = ctc_row_lse(p, C, [&](float v, int c) {
+        if (!(v <= sv)) {                          // above the runner-up, or a NaN on either side
+            const bool nb = np_gt(v, bv), ns = !nb && np_gt(v, sv);     // (selects: the four stay in registers)
+            sv = nb ? bv : ns ? v : sv;
+            si = nb ? bi : ns ? c : si;
+            bv = nb ? v : bv;
+            bi = nb ? c : bi;
+        }
+    });
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1)
+        top2_merge(bv, bi, sv, si, __shfl_xor(bv, off), __shfl_xor(bi, off), __shfl_xor(sv, off), __shfl_xor(si, off));
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0) { wbv[tid >> 6] = bv; wbi[tid >> 6] = bi; wsv[tid >> 6] = sv; wsi[tid >> 6] = si; }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int w = 1; w < 4; ++w) top2_merge(bv, bi, sv, si, wbv[w], wbi[w], wsv[w], wsi[w]);
+        // what never entered is -inf: the first such class is the answer where fewer than two others exist
+        if (bi == kNoIdx) bi = 0;
+        if (si == kNoIdx) si = bi == 0 ? 1 : 0;
+        k1[r] = bi;
+        k2[r] = si;
+        lp1[r] = (float)((double)bv - lse);
+        lp2[r] = (float)((double)sv - lse);
+        lse_out[r] = lse;
+    }
+}
+
+// One 256-thread block per line over the row figures [b][t]. Wave 0 marks the kept columns (ctc_collapse_kernel's rule
+// and compaction; the previous column is compared raw, so a run may straddle a 64-column chunk) and writes each
+// character's label and first column; then a thread per character walks its run: the ascending-t float32 sum of lp1,
+// the run's end and its peak column (largest lp1, first on ties), whose runner-up it reports. path_logp: per-thread
+// strided sums, an xor tree per wave, the four waves in order.
+__global__ __launch_bounds__(256) void greedy_spans_kernel(const int32_t* __restrict__ k1, const int32_t* __restrict__ k2,
+                                                           const float* __restrict__ lp1, const float* __restrict__ lp2,
+                                                           int W, int C, int32_t* labels, int32_t* lengths,
+                                                           int32_t* span_start, int32_t* __restrict__ span_end,
+                                                           float* __restrict__ char_logp, int32_t* __restrict__ alt_label,
+                                                           float* __restrict__ alt_logp, float* __restrict__ path_logp) {
+    __shared__ int s_n;
+    __shared__ float s_part[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
+    const int64_t o = (int64_t)b * W;
+    const int32_t* p = k1 + o;
+    if (tid < 64) {
+        int base = 0;
+        for (int t0 = 0; t0 < W; t0 += 64) {
+            const int t = t0 + lane;
+            int cur = 0, prev = -1;
+            if (t < W) {
+                cur = p[t];
+                if (t > 0) prev = p[t - 1];
+            }
+            const bool keep = (t < W) && cur != 0 && cur != C - 1 && cur != prev;
+            const unsigned long long m = __ballot(keep);
+            if (keep) {
+                const int j = base + __popcll(m & ((1ull << lane) - 1ull));
+                labels[o + j] = cur;
+                span_start[o + j] = t;
+            }
+            base += __popcll(m);
+        }
+        if (lane == 0) { lengths[b] = base; s_n = base; }
+    }
+    float ps = 0.f;
+    for (int t = tid; t < W; t += 256) ps += lp1[o + t];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) ps += __shfl_xor(ps, off);
+    if (lane == 0) s_part[tid >> 6] = ps;
+    __syncthreads();
+    if (tid == 0) path_logp[b] = (s_part[0] + s_part[1]) + (s_part[2] + s_part[3]);
+    const int n = s_n;
+    for (int j = tid; j < n; j += 256) {
+        const int label = labels[o + j], s = span_start[o + j];
+        float sum = 0.f, pv = lp1[o + s];
+        int pt = s, t = s;
+        for (; t < W && p[t] == label; ++t) {
+            const float v = lp1[o + t];
+            sum += v;
+            if (v > pv) { pv = v; pt = t; }
+        }
+        span_end[o + j] = t;
+        char_logp[o + j] = sum;
+        alt_label[o + j] = k2[o + pt];
+        alt_logp[o + j] = sum != sum ? sum : lp2[o + pt];      // a NaN row in the span: NaN, whichever column peaked
+    }
+    for (int j = n + tid; j < W; j += 256) {                   // past the text: zeros, so whole arrays compare equal
+        labels[o + j] = 0; span_start[o + j] = 0; span_end[o + j] = 0; alt_label[o + j] = 0;
+        char_logp[o + j] = 0.f; alt_logp[o + j] = 0.f;
+    }
+}
+
+// emissions of the decoded text from the kept log-sum-exp: thread per (row r = b*W + t, slot j), D values read per row
+__global__ __launch_bounds__(256) void ctc_emis_gather_kernel(const float* __restrict__ x, int64_t ld, int64_t sb, int64_t st,
+                                                              const CtcLines m, int b0, int64_t rows, int W,
+                                                              const double* __restrict__ lse, float* __restrict__ emis) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t r = i / m.D;
+    const int j = (int)(i % m.D);
+    if (r >= rows) return;
+    const int b = (int)(r / W), t = (int)(r % W), gb = b0 + b;
+    if (t >= m.T[gb] || j >= m.nd[gb]) return;
+    const float* p = x + ((int64_t)b * sb + (int64_t)t * st) * ld;
+    emis[r * m.D + j] = (float)((double)p[m.cls[(int64_t)gb * m.D + j]] - lse[r]);
+}
+
+hipError_t launch_greedy_rowstat(const float* x, int64_t ld, int64_t sb, int64_t st, int C, int nb, int W, int32_t* k1,
+                                 int32_t* k2, float* lp1, float* lp2, double* lse, hipStream_t s) {
+    const int64_t rows = (int64_t)nb * W;
+    if (rows <= 0) return hipSuccess;
+    if (rows > INT32_MAX || C < 2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(greedy_rowstat_kernel, dim3((unsigned)rows), dim3(256), 0, s, x, ld, sb, st, C, W, k1, k2, lp1, lp2,
+                       lse);
+    return hipGetLastError();
+}
+
+hipError_t launch_greedy_spans(const int32_t* k1, const int32_t* k2, const float* lp1, const float* lp2, int nb, int W,
+                               int C, int32_t* labels, int32_t* lengths, int32_t* span_start, int32_t* span_end,
+                               float* char_logp, int32_t* alt_label, float* alt_logp, float* path_logp, hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+    hipLaunchKernelGGL(greedy_spans_kernel, dim3((unsigned)nb), dim3(256), 0, s, k1, k2, lp1, lp2, W, C, labels, lengths,
+                       span_start, span_end, char_logp, alt_label, alt_logp, path_logp);
+    return hipGetLastError();
+}
+
+hipError_t launch_ctc_emis_gather(const float* x, int64_t ld, int64_t sb, int64_t st, const CtcLines& m, int b0, int nb,
+                                  int W, const double* lse, float* emis, hipStream_t s) {
+    const int64_t rows = (int64_t)nb * W, grid = (rows * m.D + 255) / 256;
+    if (rows <= 0) return hipSuccess;
+    if (grid > INT32_MAX) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(ctc_emis_gather_kernel, dim3((unsigned)grid), dim3(256), 0, s, x, ld, sb, st, m, b0, rows, W, lse,
+                       emis);
     return hipGetLastError();
 }
 

@@ -233,6 +233,78 @@ def align_images(ctx, x, dt, on_dev, widths, B, W, targets, target_lengths, inpu
     return CTCAlignment(path, score, st, en, lp, tg, tl)
 
 
+class Recognition(object):
+    """Result of a greedy recognition of B lines of W steps (numpy arrays, on the host; include/hctr_hip.h
+    ``hctr_recognize``): ``labels`` int32 [B, W] and ``lengths`` int32 [B], the decoded text as the greedy decode gives it
+    (a line's first ``lengths[b]`` entries are valid, in every per-character array); ``starts`` / ``ends`` int32 [B, W],
+    each character's pixel-column span; ``logps`` float32 [B, W], the sum of its label's log-probabilities over the span;
+    ``alt_labels`` int32 / ``alt_logps`` float32 [B, W], the runner-up class at the span's peak column and its
+    log-probability there; ``path_logp`` float32 [B], the greedy path's log-probability; ``text_nll`` float32 [B], the
+    CTC loss of the decoded text (NaN for a text of more than 2047 labels)."""
+
+    def __init__(self, labels, lengths, starts, ends, logps, alt_labels, alt_logps, path_logp, text_nll):
+        self.labels, self.lengths = labels, lengths
+        self.starts, self.ends, self.logps = starts, ends, logps
+        self.alt_labels, self.alt_logps = alt_labels, alt_logps
+        self.path_logp, self.text_nll = path_logp, text_nll
+
+    def __len__(self):
+        return len(self.lengths)
+
+    @property
+    def text_posterior(self):
+        """float64 [B]: exp(-text_nll), the probability of the decoded text summed over all its alignments."""
+        return np.exp(-np.asarray(self.text_nll, dtype=np.float64))
+
+    def label_lists(self):
+        return [self.labels[b, :int(self.lengths[b])].copy() for b in range(len(self))]
+
+    def lines(self):
+        """yields per line the list of (label, start, end, confidence, alt_label, alt_prob), one per character: its
+        pixel-column span [start, end), the geometric mean of its probability over the span, exp(logp / (end - start)),
+        and the likeliest substitution with its probability at the span's most confident column."""
+        for b in range(len(self)):
+            out = []
+            for j in range(int(self.lengths[b])):
+                st, en = int(self.starts[b, j]), int(self.ends[b, j])
+                conf = float(np.exp(np.float64(self.logps[b, j]) / (en - st)))
+                out.append((int(self.labels[b, j]), st, en, conf, int(self.alt_labels[b, j]),
+                            float(np.exp(np.float64(self.alt_logps[b, j])))))
+            yield out
+
+
+def _recognize_outputs(B, W):
+    """the output arrays in the order of the C ABI's arguments (and of Recognition's); zeros past a line's length"""
+    i, f = np.int32, np.float32
+    return tuple(np.zeros(shape, dt) for shape, dt in (((B, W), i), ((B,), i), ((B, W), i), ((B, W), i), ((B, W), f),
+                                                       ((B, W), i), ((B, W), f), ((B,), f), ((B,), f)))
+
+
+def recognize_logits(ctx, logits, on_dev):
+    """Recognition of caller logits / log-probs in WBC layout (hctr_recognize_logits)."""
+    if len(logits.shape) != 3:
+        raise ValueError("logits must be [W,B,C]")
+    W, B, C = (int(v) for v in logits.shape)
+    if C < 2:
+        raise ValueError("logits need at least 2 classes, got %d" % C)
+    if B and W < 1:
+        raise ValueError("logits have no steps (W = 0)")
+    out = _recognize_outputs(B, W)
+    if B:
+        _lib.check(_lib.load().hctr_recognize_logits(ctx, _lib.ptr(logits), on_dev, W, B, C, *[_lib.ptr(a) for a in out]),
+                   ctx)
+    return Recognition(*out)
+
+
+def recognize_images(ctx, x, dt, on_dev, widths, B, W):
+    """Recognition of line images (hctr_recognize); x, dt, on_dev, widths as hctr_model._img_args / _widths give them."""
+    out = _recognize_outputs(B, W)
+    if B:
+        _lib.check(_lib.load().hctr_recognize(ctx, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W,
+                                              *[_lib.ptr(a) for a in out]), ctx)
+    return Recognition(*out)
+
+
 _FN = None
 
 

@@ -272,6 +272,17 @@ class hctr_model(object):
         x, dt, on_dev, B, W = self._img_args(input)
         return ctc.align_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, targets, target_lengths, input_lengths)
 
+    def recognize(self, input, widths=None):
+        """Forward + greedy decode with what an OCR interface reports beside the text, the logits never leaving the
+        device: per character its pixel-column span, confidence and likeliest substitution, per line the greedy path's
+        log-probability and the posterior of the decoded text. Returns a ``ctc.Recognition`` (numpy arrays; ``lines()``
+        for (label, start, end, confidence, alt_label, alt_prob) per character, ``label_lists()`` for what ``greedy``
+        returns). In "auto" precision every line is recognised in f16x3 (include/hctr_hip.h ``hctr_recognize``)."""
+        from . import ctc
+        ctx = self._require_ctx()
+        x, dt, on_dev, B, W = self._img_args(input)
+        return ctc.recognize_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W)
+
     # -- precision mode ---------------------------------------------------------------------------
     def set_precision(self, precision):
         """Switch the mode of a loaded model among those whose weight set is resident (all three for a model built

@@ -110,7 +110,9 @@ int hctr_greedy(hctr_ctx* ctx, const void* img, int img_dtype, int img_on_device
                 int32_t* labels, int32_t* lengths);
 
 /* ---- decode of caller-supplied logits: replaces ctc_codec.decode(ndarray) greedy -------------
- * utils/ctc_codec.py:63-99. logits: float32 WBC with C classes (host or device pointer). */
+ * utils/ctc_codec.py:63-99. logits: float32 WBC with C classes (host or device pointer).
+ * Like every entry point that launches kernels it starts a new profile: hctr_last_profile afterwards names its two
+ * launches, argmax_rows and ctc_collapse. */
 int hctr_decode_greedy_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device,
                               int W, int B, int C, int32_t* labels, int32_t* lengths);
 
@@ -225,6 +227,61 @@ int hctr_ctc_align(hctr_ctx* ctx, const void* img, int img_dtype, int img_on_dev
 int hctr_ctc_align_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C,
                           const int32_t* targets, const int32_t* target_lengths, const int32_t* input_lengths,
                           int32_t* path, int32_t* span_start, int32_t* span_end, float* span_logp, float* score);
+
+/* ---- greedy recognition: the decoded text with per-character spans, confidences and runners-up -------------------
+ * What hctr_greedy / hctr_decode_greedy_logits decode, plus the figures the CTC family above gives only for a
+ * transcription the caller already knows - in one pass over the logits, without a Viterbi recursion: the greedy path is
+ * itself a CTC path. The reference has no counterpart. All W columns of every line count, pad columns included, exactly
+ * as the greedy decode takes them; there is no input_lengths.
+ * For row (t, b) with logits z over C classes:
+ *   k1  = the argmax in np.argmax's order (the first maximum wins, a NaN counts as the maximum);
+ *   k2  = the first index of the largest logit among the classes c != k1;
+ *   lse = the row's log-sum-exp with the loss's arithmetic, bit for bit (float32 running max, float64 exp-sum and log);
+ *   lp1 = (float)((double)z[k1] - lse), lp2 likewise for k2.
+ * A column t is kept iff k1 != 0 && k1 != C-1 && k1 != k1[t-1] (the previous column is compared raw, as the greedy
+ * decode does). Character j of line b has the label k1[s_j] of its kept column s_j and the span [s_j, e_j), e_j being the
+ * first t > s_j with k1[t] != label, or W.
+ * Outputs are host pointers and any may be NULL; the per-character arrays are [B][W] like labels, the first lengths[b]
+ * entries of a line valid (the rest are written as zeros):
+ *   labels, lengths:      identical to hctr_decode_greedy_logits on the same logits;
+ *   span_start, span_end: int32, s_j and e_j;
+ *   char_logp:            float32, the sum of lp1[t] over the span, ascending t, in float32 (exp(char_logp / (end - start))
+ *                         is the geometric-mean probability, the confidence, as for hctr_ctc_align's span_logp);
+ *   alt_label, alt_logp:  int32 / float32, k2 and lp2 at the span's peak column (the t with the largest lp1, the first
+ *                         on ties): the likeliest substitution;
+ *   path_logp:            float32 [B], the sum of lp1[t] over all W columns in a fixed order: the greedy path's log-prob;
+ *   text_nll:             float32 [B], the CTC loss of the decoded labels on these logits, bit-identical to
+ *                         hctr_ctc_loss_logits with labels / lengths as targets and input_lengths = NULL
+ *                         (exp(-text_nll) is the posterior of the text; >= exp(path_logp) unless a column decodes to C-1,
+ *                         which the collapse drops but the loss does not take for a blank). A line whose decoded length
+ *                         exceeds the loss's 2047 labels gets NaN, not an error. NULL skips the loss part entirely.
+ * A row holding a NaN: labels as the greedy decode gives them; the float figures of a character whose span holds such a
+ * row, and that line's path_logp / text_nll, are NaN (text_nll's bit-identity with the loss is for the other lines: the
+ * loss's recursion drops a NaN emission); alt_label there is unspecified. A row with +inf, or with nothing but -inf,
+ * has a NaN log-sum-exp and counts as such a row.
+ * No atomics: repeated calls, and host-pointer / device-pointer calls, agree bit for bit.
+ * hctr_recognize runs the forward of img (arguments as hctr_greedy) with the stored-logits head in internal passes,
+ * exactly as hctr_ctc_loss / hctr_ctc_align do: mode 0 f16, mode 1 f16x3, mode 2 EVERY line in f16x3 (the margin
+ * certificate bounds argmax flips, not confidences), hctr_last_guard's figures left as they were. In modes 0 and 1 the
+ * labels equal hctr_greedy's. hctr_recognize_logits takes caller logits or log-probs in WBC layout, host or device
+ * pointer, and needs no weights (a context made for ctc_codec serves). Errors, B == 0 (a no-op) and HCTR_ERR_NOMEM as in
+ * the family: the context stays usable.
+ * Launches (hctr_last_profile): greedy_rowstat (one 256-thread block per row: argmax, runner-up and log-sum-exp in one
+ * read), greedy_spans (one block per line), then for text_nll ctc_emis_gather (the emissions of the decoded text from
+ * the kept log-sum-exps: D values read per row) and ctc_alpha.
+ * Device scratch (the context's grow-only CTC scratch; n = B, or the lines of one pass for images):
+ *   8 * n*W (log-sum-exps) + max(40 * n*W + 8 * n (row figures and spans), the loss's tables + 4 * n + 4 * n*W*D
+ *   (emissions of the decoded text, D = the largest number of distinct classes of a line, blank included)), each array
+ *   rounded up to 256 bytes; plus W*B*C floats for logits passed as a host pointer. D is known only once the text is
+ *   decoded: when the second layout outgrows the block, the log-sum-exps are copied to a larger one, and for the length
+ *   of that copy both blocks exist (a transient peak of old + new bytes, paid by the first call at a larger shape; if
+ *   the larger block cannot be had, HCTR_ERR_NOMEM leaves the old one and the context as they were). */
+int hctr_recognize(hctr_ctx* ctx, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
+                   int32_t* labels, int32_t* lengths, int32_t* span_start, int32_t* span_end, float* char_logp,
+                   int32_t* alt_label, float* alt_logp, float* path_logp, float* text_nll);
+int hctr_recognize_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C,
+                          int32_t* labels, int32_t* lengths, int32_t* span_start, int32_t* span_end, float* char_logp,
+                          int32_t* alt_label, float* alt_logp, float* path_logp, float* text_nll);
 
 /* ---- host prefix beam search: replaces ctc_codec.__cbs_full__/__cbs_skip__ -------------------
  * utils/ctc_codec.py:124-285 (Beam :288-307), float64 accumulators over float32 log-probs.

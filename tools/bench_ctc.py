@@ -21,7 +21,14 @@ the gradient once).
 
 times the forced alignment on the same caller logits and targets (hctr_ctc_align_logits, every output fetched) and, in
 the same run, the loss (hctr_ctc_loss_logits), alternately after warm-up calls of each. --layers adds the device times
-of the align call's launches: the emission pass, the recursion and the back-trace."""
+of the align call's launches: the emission pass, the recursion and the back-trace.
+
+    python tools/bench_ctc.py --recognize [--layers] ...
+
+times the greedy recognition on the same caller logits (hctr_recognize_logits, every output fetched) against the chain
+of three calls it replaces - hctr_decode_greedy_logits, then hctr_ctc_loss_logits and hctr_ctc_align_logits with the
+decoded labels as targets - alternately after warm-up calls of each. --layers adds the device times of every launch of
+both, and greedy_rowstat's time against the sum of the two row passes it fuses (argmax_rows + ctc_lse)."""
 import argparse
 import json
 import os
@@ -44,6 +51,7 @@ def main():
     ap.add_argument("--layers", action="store_true")
     ap.add_argument("--backward", action="store_true")
     ap.add_argument("--align", action="store_true")
+    ap.add_argument("--recognize", action="store_true")
     args = ap.parse_args()
     import torch
     import hctr_amd
@@ -60,6 +68,9 @@ def main():
         return
     if args.align:
         print(json.dumps(align(args, hctr_amd, m, imgs, targets, tl)))
+        return
+    if args.recognize:
+        print(json.dumps(recognize(args, hctr_amd, m, imgs)))
         return
 
     def t_greedy():
@@ -216,6 +227,84 @@ def align(args, hctr_amd, m, imgs, targets, tl):
         m.set_profiling(False)
         rec["loss_only_layers_ms"] = {k: round(v, 4) for k, v in fprof.items()}
         rec["align_layers_ms"] = {k: round(v, 4) for k, v in aprof.items()}
+    return rec
+
+
+def recognize(args, hctr_amd, m, imgs):
+    import torch
+    al = hctr_amd.CTCAligner().attach(m)
+    mod = sys.modules[type(al).__module__]
+    lib, ptr = hctr_amd.load_library(), mod._lib.ptr
+    ctx = al._context()
+    logits = m(imgs)                                             # device tensor [W, lines, C]
+    W, B, C = (int(v) for v in logits.shape)
+    labels, lengths = np.empty((B, W), np.int32), np.empty((B,), np.int32)
+    prof, profiling = {}, [False]
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def keep(name):
+        if profiling[0]:
+            prof[name] = dict(m.last_profile())
+
+    def fused():
+        rec = mod.recognize_logits(ctx, logits, 1)
+        keep("recognize")
+        assert np.isfinite(rec.text_nll).all()
+        return rec
+
+    def chain():
+        rc = lib.hctr_decode_greedy_logits(ctx, ptr(logits), 1, W, B, C, ptr(labels), ptr(lengths))
+        assert rc == 0
+        keep("decode")
+        tg = np.concatenate([labels[b, :lengths[b]] for b in range(B)]).astype(np.int32)
+        nll = mod.loss_logits(ctx, logits, 1, tg, lengths, None)
+        keep("loss")
+        a = mod.align_logits(ctx, logits, 1, tg, lengths, None)
+        keep("align")
+        assert np.isfinite(nll).all() and np.isfinite(a.scores).all()
+        return nll
+
+    fns = (("recognize", fused), ("chain", chain))
+    for _ in range(args.warmup):
+        for _, fn in fns:
+            fn()
+    ms = {k: [] for k, _ in fns}
+    for _ in range(args.steps):
+        for k, fn in fns:
+            ms[k].append(1e3 * timed(fn))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    rec = {"mode": "recognize", "lines": B, "width": W, "classes": C, "precision": args.precision,
+           "mean_text_length": float(lengths.mean()), "max_text_length": int(lengths.max())}
+    for k, v in ms.items():
+        rec[k + "_ms"] = [round(x, 3) for x in v]
+        rec[k + "_ms_median"] = round(med[k], 3)
+    rec["recognize_over_chain"] = round(med["recognize"] / med["chain"], 4)
+    assert fused().text_nll.tobytes() == chain().tobytes()       # the same loss, bit for bit
+    if args.layers:
+        m.set_profiling(True)
+        profiling[0] = True
+        rows = {"greedy_rowstat": [], "argmax_rows": [], "ctc_lse": []}
+        for _ in range(args.steps):                              # alternating, median of each launch
+            fused()
+            chain()
+            rows["greedy_rowstat"].append(prof["recognize"]["greedy_rowstat"])
+            rows["argmax_rows"].append(prof["decode"]["argmax_rows"])
+            rows["ctc_lse"].append(prof["loss"]["ctc_lse"])
+        m.set_profiling(False)
+        profiling[0] = False
+        for k, v in prof.items():
+            rec[k + "_layers_ms"] = {n: round(t, 4) for n, t in v.items()}
+        for k, v in rows.items():
+            rec[k + "_ms_median"] = round(float(np.median(v)), 4)
+        two = float(np.median(rows["argmax_rows"])) + float(np.median(rows["ctc_lse"]))
+        rec["rowstat_over_two_passes"] = round(float(np.median(rows["greedy_rowstat"])) / two, 4)
+        rec["greedy_rowstat_TBps"] = round(4.0 * W * B * C / (1e-3 * float(np.median(rows["greedy_rowstat"]))) / 1e12, 3)
     return rec
 
 
