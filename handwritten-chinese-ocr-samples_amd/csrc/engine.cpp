@@ -240,6 +240,14 @@ R guard(hctr_ctx* c, F&& body) noexcept {
                         hipGetErrorString(_e));                                                   \
     } while (0)
 
+// a launch (or copy) timed under a profile label
+#define PROF_TRY(pf, name, expr) \
+    do {                         \
+        (pf).begin(name);        \
+        HIP_TRY((pf).c, expr);   \
+        (pf).end();              \
+    } while (0)
+
 #define TRY(expr)                   \
     do {                            \
         int _r = (expr);            \
@@ -280,8 +288,8 @@ int logits_on_device(hctr_ctx* c, std::vector<void*>& pool, const float* logits,
     float* up = nullptr;
     TRY(dev_alloc(c, pool, &up, n, false));
     *dev = up;
-    hipError_t e = hipMemcpyAsync(up, logits, n * 4, hipMemcpyHostToDevice, c->stream);
-    return e == hipSuccess ? HCTR_OK : fail(c, HCTR_ERR_HIP, "H2D logits: %s", hipGetErrorString(e));
+    HIP_TRY(c, hipMemcpyAsync(up, logits, n * 4, hipMemcpyHostToDevice, c->stream));
+    return HCTR_OK;
 }
 
 // the end of a call that queued work: wait for the stream; a sync error does not mask an earlier one
@@ -756,14 +764,12 @@ int run_block(hctr_ctx* c, Prof& pf, const std::string& name, const BlockW& bw, 
         c->out_class = 2;
         TRY(run_conv(c, pf, (name + ".conv1").c_str(), bw.conv1, in, t, H, true, false, ws.se_part, false));
         c->out_class = 4;
-        pf.begin((name + ".se_stats").c_str());
-        HIP_TRY(c, launch_se_border(t, ws.B, H, ws.W, ws.Wa, planes, c->split, ws.se_part, tiles1, ws.se_border, c->stream));
-        pf.end();
-        pf.begin((name + ".se_scale").c_str());
-        HIP_TRY(c, launch_se_premean(ws.se_border, t, bw.conv2.w, bw.conv2.bias, ws.B, H, ws.W, ws.Wa, planes,
-                                     bw.conv2.coutPad, c->split, ws.se_mean, bw.se.w1, bw.se.w2, ws.se_scale,
-                                     ws.se_counter, c->stream));
-        pf.end();
+        PROF_TRY(pf, (name + ".se_stats").c_str(), launch_se_border(t, ws.B, H, ws.W, ws.Wa, planes, c->split,
+                                                                    ws.se_part, tiles1, ws.se_border, c->stream));
+        PROF_TRY(pf, (name + ".se_scale").c_str(), launch_se_premean(ws.se_border, t, bw.conv2.w, bw.conv2.bias, ws.B,
+                                                                     H, ws.W, ws.Wa, planes, bw.conv2.coutPad, c->split,
+                                                                     ws.se_mean, bw.se.w1, bw.se.w2, ws.se_scale,
+                                                                     ws.se_counter, c->stream));
         if (fuse_ds)
             TRY(run_conv(c, pf, (name + ".conv2+se+ds").c_str(), bw.conv2, ActDesc{t, H, planes}, o, H, true, false,
                          nullptr, false, ws.se_scale, nullptr, &bw.ds, in.p));
@@ -778,12 +784,10 @@ int run_block(hctr_ctx* c, Prof& pf, const std::string& name, const BlockW& bw, 
     TRY(run_conv(c, pf, (name + ".conv2").c_str(), bw.conv2, ActDesc{t, H, planes}, o, H, false, false,
                  ws.se_part, false));
     const int tiles = tiles_of(bw.conv2);
-    pf.begin((name + ".se_fc").c_str());
-    HIP_TRY(c, launch_se_fc(ws.se_part, tiles, bw.se.w1, bw.se.w2, ws.se_scale, ws.B, planes, inv_hw, c->stream));
-    pf.end();
-    pf.begin((name + ".se_apply").c_str());
-    HIP_TRY(c, launch_se_apply(o, res, ws.se_scale, (int64_t)(H + 2) * ws.Wa * planes, ws.B, planes, c->stream));
-    pf.end();
+    PROF_TRY(pf, (name + ".se_fc").c_str(), launch_se_fc(ws.se_part, tiles, bw.se.w1, bw.se.w2, ws.se_scale, ws.B,
+                                                         planes, inv_hw, c->stream));
+    PROF_TRY(pf, (name + ".se_apply").c_str(), launch_se_apply(o, res, ws.se_scale, (int64_t)(H + 2) * ws.Wa * planes,
+                                                               ws.B, planes, c->stream));
     return HCTR_OK;
 }
 
@@ -849,10 +853,9 @@ int run_forward(hctr_ctx* c, int img_f32, bool have_widths, HeadMode mode = HEAD
         TRY(run_conv(c, pf, "stem+conv0_2+pool", wt.conv0_2, ActDesc{nullptr, 128, 64}, ws.x[1], 64, true, true, nullptr,
                      false, nullptr, nullptr, nullptr, nullptr, img_f32 ? 1 : 0, have_widths));
     } else {
-        pf.begin("stem.conv0_1");
-        HIP_TRY(c, launch_stem(ws.img, img_f32, have_widths ? ws.widths : nullptr, wt.stem_w, wt.stem_b, ws.s0, ws.B,
-                               ws.W, ws.Wa, c->split ? ((c->x3_mask & 8) ? 1 : 2) : 0, c->stream));
-        pf.end();
+        PROF_TRY(pf, "stem.conv0_1", launch_stem(ws.img, img_f32, have_widths ? ws.widths : nullptr, wt.stem_w,
+                                                 wt.stem_b, ws.s0, ws.B, ws.W, ws.Wa,
+                                                 c->split ? ((c->x3_mask & 8) ? 1 : 2) : 0, c->stream));
         TRY(run_conv(c, pf, "conv0_2+pool", wt.conv0_2, ActDesc{ws.s0, 128, 64}, ws.x[1], 64, true, true, nullptr, false));
     }
     int cin = 64;
@@ -888,9 +891,7 @@ int run_forward(hctr_ctx* c, int img_f32, bool have_widths, HeadMode mode = HEAD
     ConvTile htile;
     head_args(c, &a, &htile);
     auto line_guard = [&]() -> int {
-        pf.begin("line_guard");
-        HIP_TRY(c, launch_line_guard(ws.col_margin, ws.col_abs, ws.B, ws.W, ws.line_guard, c->stream));
-        pf.end();
+        PROF_TRY(pf, "line_guard", launch_line_guard(ws.col_margin, ws.col_abs, ws.B, ws.W, ws.line_guard, c->stream));
         return HCTR_OK;
     };
     if (mode == HEAD_ARGMAX || mode == HEAD_BEAM) {
@@ -899,25 +900,21 @@ int run_forward(hctr_ctx* c, int img_f32, bool have_widths, HeadMode mode = HEAD
         a.amax_idx = ws.amax_idx;
         if (guarded) { a.amax_val2 = ws.amax_val2; a.amax_abs = ws.amax_abs; }
         if (mode == HEAD_BEAM) { a.psum = ws.psum; a.blank_logit = ws.blank_logit; }
-        pf.begin(mode == HEAD_BEAM ? "head.linear+partials" : "head.linear+argmax");
-        HIP_TRY(c, launch_conv(a, htile, 1, true, c->stream));
-        pf.end();
+        PROF_TRY(pf, mode == HEAD_BEAM ? "head.linear+partials" : "head.linear+argmax",
+                 launch_conv(a, htile, 1, true, c->stream));
         if (mode == HEAD_BEAM && !guarded) return HCTR_OK;
-        pf.begin("argmax_partials");
-        HIP_TRY(c, launch_argmax_partials(ws.amax_val, ws.amax_idx, a.ntiles * kLinearWN, a.M,
-                                          mode == HEAD_BEAM ? nullptr : ws.colidx, c->stream, a.amax_val2, a.amax_abs,
-                                          guarded ? ws.col_margin : nullptr, guarded ? ws.col_abs : nullptr));
-        pf.end();
+        PROF_TRY(pf, "argmax_partials", launch_argmax_partials(ws.amax_val, ws.amax_idx, a.ntiles * kLinearWN, a.M,
+                                                               mode == HEAD_BEAM ? nullptr : ws.colidx, c->stream,
+                                                               a.amax_val2, a.amax_abs,
+                                                               guarded ? ws.col_margin : nullptr,
+                                                               guarded ? ws.col_abs : nullptr));
         if (guarded) TRY(line_guard());
         return HCTR_OK;
     }
-    pf.begin("head.linear");
-    HIP_TRY(c, launch_conv(a, htile, 1, true, c->stream));
-    pf.end();
+    PROF_TRY(pf, "head.linear", launch_conv(a, htile, 1, true, c->stream));
     if (guarded) {
-        pf.begin("row_guard");
-        HIP_TRY(c, launch_row_guard(ws.logits, c->cpad, a.M, c->num_classes, ws.col_margin, ws.col_abs, c->stream));
-        pf.end();
+        PROF_TRY(pf, "row_guard", launch_row_guard(ws.logits, c->cpad, a.M, c->num_classes, ws.col_margin, ws.col_abs,
+                                                   c->stream));
         TRY(line_guard());
     }
     return HCTR_OK;
@@ -933,45 +930,56 @@ int beam_finish(hctr_ctx* c, int k, bool want_candidates, double thresh, int32_t
     ConvTile htile;
     head_args(c, &a, &htile);
     const int P = a.ntiles * kLinearWN;
-    pf.begin("beam_thresholds");
-    HIP_TRY(c, launch_beam_thresholds(ws.amax_val, ws.psum, P, a.M, k, thresh, want_candidates ? 1 : 0, ws.row_thr,
-                                      ws.emit_cnt, c->stream));
-    pf.end();
+    PROF_TRY(pf, "beam_thresholds", launch_beam_thresholds(ws.amax_val, ws.psum, P, a.M, k, thresh,
+                                                           want_candidates ? 1 : 0, ws.row_thr, ws.emit_cnt,
+                                                           c->stream));
     a.y = nullptr;
     a.row_thr = ws.row_thr; a.emit_cnt = ws.emit_cnt; a.emit_list = ws.emit_list; a.emit_cap = kBeamCap;
     a.esum = ws.esum;
-    pf.begin("head.linear+lists");
-    HIP_TRY(c, launch_conv(a, htile, 1, true, c->stream));
-    pf.end();
+    PROF_TRY(pf, "head.linear+lists", launch_conv(a, htile, 1, true, c->stream));
     HIP_TRY(c, hipMemsetAsync(ws.overflow, 0, 4, c->stream));
-    pf.begin("beam_select");
-    HIP_TRY(c, launch_beam_select(ws.row_thr, ws.emit_cnt, ws.emit_list, kBeamCap, ws.esum, P, ws.blank_logit, ws.B, ws.W,
-                                  k, thresh, d_idx, d_lp, d_bl, d_st, d_cnt, ws.overflow, c->stream));
-    pf.end();
+    PROF_TRY(pf, "beam_select", launch_beam_select(ws.row_thr, ws.emit_cnt, ws.emit_list, kBeamCap, ws.esum, P,
+                                                   ws.blank_logit, ws.B, ws.W, k, thresh, d_idx, d_lp, d_bl, d_st,
+                                                   d_cnt, ws.overflow, c->stream));
+    return HCTR_OK;
+}
+
+struct Batch {              // the caller's line images: [B][128][W] u8 or f32, on the host or the device; widths[B] or null
+    const void* img;
+    int dtype, on_device;
+    const int32_t* widths;
+    int B, W;
+};
+
+// f(first_index, run_length) for every run of consecutive line numbers in lines[0..nb), until one fails
+template <class F>
+int for_runs(const int* lines, int nb, F f) {
+    for (int i = 0; i < nb;) {
+        int j = i + 1;
+        while (j < nb && lines[j] == lines[j - 1] + 1) ++j;
+        TRY(f(i, j - i));
+        i = j;
+    }
     return HCTR_OK;
 }
 
 // Copy the lines `lines[0..nb)` of the caller's batch (and their widths) into the workspace. Runs of consecutive
 // lines become one copy each, so an ordinary pass (a contiguous range) is a single copy.
-int stage_input(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths,
-                const int* lines, int nb, int W) {
+int stage_input(hctr_ctx* c, const Batch& in, const int* lines, int nb) {
     Workspace& ws = c->ws;
-    const size_t esz = img_dtype == HCTR_F32 ? 4 : 1;
-    const size_t per = (size_t)kImgH * W * esz;
-    const hipMemcpyKind kind = img_on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    for (int i = 0; i < nb;) {
-        int j = i + 1;
-        while (j < nb && lines[j] == lines[j - 1] + 1) ++j;
-        HIP_TRY(c, hipMemcpyAsync((char*)ws.img + (size_t)i * per, (const char*)img + (size_t)lines[i] * per,
-                                  per * (size_t)(j - i), kind, c->stream));
-        i = j;
-    }
-    if (widths) {
+    const size_t per = (size_t)kImgH * in.W * (in.dtype == HCTR_F32 ? 4 : 1);
+    const hipMemcpyKind kind = in.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    TRY(for_runs(lines, nb, [&](int i, int n) -> int {
+        HIP_TRY(c, hipMemcpyAsync((char*)ws.img + (size_t)i * per, (const char*)in.img + (size_t)lines[i] * per,
+                                  per * (size_t)n, kind, c->stream));
+        return HCTR_OK;
+    }));
+    if (in.widths) {
         c->h_widths.emplace_back((size_t)nb);
         std::vector<int32_t>& hw = c->h_widths.back();
         for (int i = 0; i < nb; ++i) {
-            const int32_t w = widths[lines[i]];
-            if (w < 1 || w > W) return fail(c, HCTR_ERR_ARG, "widths[%d]=%d outside [1,%d]", lines[i], w, W);
+            const int32_t w = in.widths[lines[i]];
+            if (w < 1 || w > in.W) return fail(c, HCTR_ERR_ARG, "widths[%d]=%d outside [1,%d]", lines[i], w, in.W);
             hw[(size_t)i] = w;
         }
         HIP_TRY(c, hipMemcpyAsync(ws.widths, hw.data(), (size_t)nb * 4, hipMemcpyHostToDevice, c->stream));
@@ -1030,6 +1038,70 @@ struct SplitScope {
     explicit SplitScope(hctr_ctx* ctx) : c(ctx) { c->split = c->mode == 1; }
     ~SplitScope() { c->split = c->mode == 1; }
 };
+
+std::vector<int> line_indices(int B) {
+    std::vector<int> all((size_t)B);
+    for (int b = 0; b < B; ++b) all[(size_t)b] = b;
+    return all;
+}
+
+// ---------------------------------------------------------------------------------------------
+// the passes of a call on line images ("The pass skeleton")
+// ---------------------------------------------------------------------------------------------
+struct Pass {                // one internal pass: the lines lines[0..nb) of the caller's batch
+    const int* lines;
+    int nb;
+    int first, total;        // the pass holds lines [first, first + nb) of its sweep's `total`
+    bool rerun;              // second sweep of a guarded call: the flagged lines, in f16x3
+    float* guard_dst;        // first sweep of a guarded call: where the lines' [nb][2] guard figures go on the host
+};
+
+// Stage the pass's lines and run trunk + head in head mode `hm`; a guard pass also queues its figures' copy back.
+int forward_pass(hctr_ctx* c, const Batch& in, const Pass& p, HeadMode hm) {
+    const bool guard_pass = p.guard_dst != nullptr;
+    TRY(ensure_workspace(c, p.nb, in.W, ws_need(c, hm, guard_pass)));
+    TRY(stage_input(c, in, p.lines, p.nb));
+    TRY(run_forward(c, in.dtype == HCTR_F32, in.widths != nullptr, hm, guard_pass));
+    if (guard_pass)
+        HIP_TRY(c, hipMemcpyAsync(p.guard_dst, c->ws.line_guard, (size_t)p.nb * 8, hipMemcpyDeviceToHost, c->stream));
+    return HCTR_OK;
+}
+
+// which arithmetic a call's lines run in. OWN: the mode's, and in mode 2 guarded - every line in f16, then the lines
+// guard_decide flags once more in f16x3 (argmaxes and what derives from them). EXACT: figures (losses, alignments,
+// confidences) that mode 2's guard does not certify - f16x3 unless the mode is 0, in one sweep.
+enum PassPolicy { PASS_OWN, PASS_EXACT };
+
+// Cut the batch into balanced passes of sub_batch() lines and hand each to pass(const Pass&), which runs forward_pass
+// and queues what follows it. The first failure ends the call. Work may still be queued on return, failure included:
+// the entry ends with synced(). The one exception, which entries may rely on: a guarded call that flags nothing
+// returns drained (the guard figures had to come back).
+template <class PassFn>
+int run_passes(hctr_ctx* c, const Batch& in, PassPolicy policy, PassFn pass) {
+    SplitScope scope(c);
+    if (policy == PASS_EXACT) {
+        c->split = c->mode != 0;
+        if (!c->wts().built) return fail(c, HCTR_ERR_STATE, "the weight set of this precision mode is not resident");
+    } else {
+        guard_clear(c);
+    }
+    prof_reset(c);
+    auto sweep = [&](const std::vector<int>& lines, bool rerun, float* gbuf) -> int {
+        const int n = (int)lines.size(), nbmax = sub_batch(c, n, in.W, c->split);
+        for (int o = 0; o < n; o += nbmax)
+            TRY(pass(Pass{lines.data() + o, std::min(nbmax, n - o), o, n, rerun, gbuf ? gbuf + 2 * (size_t)o : nullptr}));
+        return HCTR_OK;
+    };
+    if (policy == PASS_EXACT || c->mode != 2) return sweep(line_indices(in.B), false, nullptr);
+    // guarded precision: the lines the f16 sweep cannot certify run again in f16x3 at the SAME padded width (a line's
+    // result depends on nothing but its own pixels and W) and replace their rows of every output
+    std::vector<float> gbuf((size_t)2 * in.B);
+    TRY(synced(c, sweep(line_indices(in.B), false, gbuf.data())));
+    const std::vector<int> flagged = guard_decide(c, gbuf, in.B);
+    if (flagged.empty()) return HCTR_OK;
+    c->split = true;
+    return sweep(flagged, true, nullptr);
+}
 
 // ---------------------------------------------------------------------------------------------
 // CTC loss (hctr_ctc_loss*): argument checks, the per-line tables of kernels.h CtcLines, scratch
@@ -1132,11 +1204,14 @@ int ctc_reserve(hctr_ctx* c, size_t need, size_t keep = 0) {
     if (e != hipSuccess)
         return fail(c, HCTR_ERR_NOMEM, "hipMalloc(%zu bytes) for the CTC scratch failed: %s", need, hipGetErrorString(e));
     if (keep) {
-        e = hipMemcpyAsync(p, c->ctc_buf, keep, hipMemcpyDeviceToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
+        auto move = [&]() -> int {
+            HIP_TRY(c, hipMemcpyAsync(p, c->ctc_buf, keep, hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            return HCTR_OK;
+        };
+        if (const int rc = move()) {
             (void)hipFree(p);
-            return fail(c, HCTR_ERR_HIP, "moving the CTC scratch: %s", hipGetErrorString(e));
+            return rc;
         }
         (void)hipFree(c->ctc_buf);
     }
@@ -1197,71 +1272,52 @@ void align_carve(char* extra, AlignDev* a) {
 }
 
 // recursion and back-trace of the pass's lines [b0, b0 + nb) over their emissions
-hipError_t align_launch(hctr_ctx* c, Prof& pf, const float* emis, const CtcLines& m, const CtcHost& h, const AlignDev& a,
-                        int b0, int nb, int W, float* d_score) {
-    pf.begin("ctc_viterbi");
-    hipError_t e = launch_ctc_viterbi(emis, m, b0, nb, W, h.max_states, a.d_boff, a.d_bp, d_score, a.d_end, c->stream);
-    pf.end();
-    if (e != hipSuccess) return e;
-    pf.begin("ctc_backtrace");
-    e = launch_ctc_backtrace(emis, m, b0, nb, W, h.max_states, a.d_boff, a.d_bp, a.d_end, a.d_path, a.d_st, a.d_en, a.d_lp,
-                             c->stream);
-    pf.end();
-    return e;
+int align_launch(hctr_ctx* c, Prof& pf, const float* emis, const CtcLines& m, const CtcHost& h, const AlignDev& a, int b0,
+                 int nb, int W, float* d_score) {
+    PROF_TRY(pf, "ctc_viterbi", launch_ctc_viterbi(emis, m, b0, nb, W, h.max_states, a.d_boff, a.d_bp, d_score, a.d_end,
+                                                   c->stream));
+    PROF_TRY(pf, "ctc_backtrace", launch_ctc_backtrace(emis, m, b0, nb, W, h.max_states, a.d_boff, a.d_bp, a.d_end,
+                                                       a.d_path, a.d_st, a.d_en, a.d_lp, c->stream));
+    return HCTR_OK;
 }
 
-hipError_t align_fetch(hctr_ctx* c, const AlignDev& a, int B, int W, const float* d_score, int32_t* path,
-                       int32_t* span_start, int32_t* span_end, float* span_logp, float* score) {
-    hipError_t e = hipSuccess;
-    if (path) e = hipMemcpyAsync(path, a.d_path, (size_t)B * W * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && span_start && a.total)
-        e = hipMemcpyAsync(span_start, a.d_st, a.total * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && span_end && a.total)
-        e = hipMemcpyAsync(span_end, a.d_en, a.total * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && span_logp && a.total)
-        e = hipMemcpyAsync(span_logp, a.d_lp, a.total * 4, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && score) e = hipMemcpyAsync(score, d_score, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
-    return e;
+int align_fetch(hctr_ctx* c, const AlignDev& a, int B, int W, const float* d_score, int32_t* path, int32_t* span_start,
+                int32_t* span_end, float* span_logp, float* score) {
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIP_TRY(c, fetch(path, a.d_path, (size_t)B * W * 4));
+    HIP_TRY(c, fetch(span_start, a.d_st, a.total * 4));
+    HIP_TRY(c, fetch(span_end, a.d_en, a.total * 4));
+    HIP_TRY(c, fetch(span_logp, a.d_lp, a.total * 4));
+    HIP_TRY(c, fetch(score, d_score, (size_t)B * 4));
+    return HCTR_OK;
 }
 
-// The image path of hctr_ctc_loss / hctr_ctc_align: the lines go through the forward in passes of sub_batch() lines into
-// stored logits and from there into emissions. carve(extra) takes the call's `extra_b` further bytes of scratch;
+// The image path of hctr_ctc_loss / hctr_ctc_align: the lines go through the forward in passes into stored logits and
+// from there into emissions. carve(extra) takes the call's `extra_b` further bytes of scratch;
 // after(pf, m, emis, res, b0, nb) queues what follows the emissions of the pass's lines [b0, b0 + nb), res[B] being the
-// per-line result; fetch(res) queues the copies back (`what` names them in its error).
+// per-line result; fetch(res) queues the copies back.
 template <class Carve, class After, class Fetch>
-int ctc_image_call(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
-                   const CtcHost& h, size_t extra_b, Carve carve, After after, Fetch fetch, const char* what) {
-    SplitScope scope(c);
-    c->split = c->mode != 0;                  // mode 2 takes every line in f16x3: its guard certifies argmaxes, not losses
-    if (!c->wts().built) return fail(c, HCTR_ERR_STATE, "the weight set of this precision mode is not resident");
-    prof_reset(c);
-    const int nbmax = sub_batch(c, B, W, c->split);
+int ctc_image_call(hctr_ctx* c, const Batch& in, const CtcHost& h, size_t extra_b, Carve carve, After after, Fetch fetch) {
     CtcLines m;
     float *res = nullptr, *emis = nullptr;
-    char* extra = nullptr;
-    TRY(ctc_scratch(c, h, (size_t)nbmax * W * h.D, &m, &res, &emis, extra_b, &extra));
-    TRY(carve(extra));
-    std::vector<int> all((size_t)B);
-    for (int b = 0; b < B; ++b) all[(size_t)b] = b;
-    auto pass = [&](int b0, int nb) -> int {
-        TRY(ensure_workspace(c, nb, W, ws_need(c, HEAD_LOGITS)));
-        TRY(stage_input(c, img, img_dtype, img_on_device, widths, all.data() + b0, nb, W));
-        TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, HEAD_LOGITS, false));
-        Prof pf(c);
-        pf.begin("ctc_lse");
-        HIP_TRY(c, launch_ctc_lse(c->ws.logits, c->cpad, W, 1, c->num_classes, m, b0, nb, W, emis, nullptr, c->stream));
-        pf.end();
-        HIP_TRY(c, after(pf, m, emis, res, b0, nb));
-        return HCTR_OK;
-    };
-    int rc = HCTR_OK;
-    for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax) rc = pass(b0, std::min(nbmax, B - b0));
-    if (rc == HCTR_OK) {
-        hipError_t e = fetch(res);
-        if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "D2H %s: %s", what, hipGetErrorString(e));
-    }
-    // pageable host tables queued above were staged before hipMemcpyAsync returned
-    return synced(c, rc);
+    // pageable host tables queued below were staged before hipMemcpyAsync returned
+    return synced(c, [&]() -> int {
+        TRY(run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
+            if (p.first == 0) {               // no later pass is larger: the scratch holds the emissions of one pass
+                char* extra = nullptr;
+                TRY(ctc_scratch(c, h, (size_t)p.nb * in.W * h.D, &m, &res, &emis, extra_b, &extra));
+                TRY(carve(extra));
+            }
+            TRY(forward_pass(c, in, p, HEAD_LOGITS));
+            Prof pf(c);
+            PROF_TRY(pf, "ctc_lse", launch_ctc_lse(c->ws.logits, c->cpad, in.W, 1, c->num_classes, m, p.first, p.nb,
+                                                   in.W, emis, nullptr, c->stream));
+            return after(pf, m, emis, res, p.first, p.nb);
+        }));
+        return fetch(res);
+    }());
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1274,13 +1330,25 @@ struct RecOut {              // the caller's host outputs, [B][W] / [B]; any may
     float *alt_logp, *path_logp, *text_nll;
 };
 
+struct RecCall {             // + where the batch's labels and lengths go on the host: the caller's arrays, or the call's
+    RecOut o;                // own when only text_nll needs them (null when nobody does)
+    std::vector<int32_t> own_lab, own_len;
+    int32_t *h_lab, *h_len;
+    RecCall(const RecOut& out, int B, int W) : o(out) {
+        if (o.text_nll && !o.labels) own_lab.resize((size_t)B * W);
+        if (o.text_nll && !o.lengths) own_len.resize((size_t)B);
+        h_lab = o.labels ? o.labels : o.text_nll ? own_lab.data() : nullptr;
+        h_len = o.lengths ? o.lengths : o.text_nll ? own_len.data() : nullptr;
+    }
+};
+
 // One pass of nb lines, [b0, b0 + nb) of the caller's batch, whose logit rows lie at x + (b*sb + t*st) * ld. The CTC
 // scratch holds lse[nb*W] first, which outlives the row figures and the spans; once those are on the host the tables,
-// nll and emissions of the decoded text take their place. h_lab / h_len: where the batch's labels and lengths go on the
-// host (the caller's arrays, or the call's own when text_nll needs them). Returns with the stream drained when
-// text_nll is wanted.
+// nll and emissions of the decoded text take their place. Returns with the stream drained when text_nll is wanted.
 int rec_pass(hctr_ctx* c, const float* x, int64_t ld, int64_t sb, int64_t st, int C, int b0, int nb, int W,
-             const RecOut& o, int32_t* h_lab, int32_t* h_len) {
+             const RecCall& rc) {
+    const RecOut& o = rc.o;
+    int32_t *const h_lab = rc.h_lab, *const h_len = rc.h_len;
     const size_t n = (size_t)nb, col_b = align256(n * W * 4), line_b = align256(n * 4), lse_b = align256(n * W * 8);
     TRY(ctc_reserve(c, lse_b + 10 * col_b + 2 * line_b));
     double* d_lse = (double*)c->ctc_buf;
@@ -1293,13 +1361,9 @@ int rec_pass(hctr_ctx* c, const float* x, int64_t ld, int64_t sb, int64_t st, in
     int32_t* d_len = (int32_t*)q;
     float* d_plp = (float*)(q + line_b);
     Prof pf(c);
-    pf.begin("greedy_rowstat");
-    HIP_TRY(c, launch_greedy_rowstat(x, ld, sb, st, C, nb, W, k1, k2, lp1, lp2, d_lse, c->stream));
-    pf.end();
-    pf.begin("greedy_spans");
-    HIP_TRY(c, launch_greedy_spans(k1, k2, lp1, lp2, nb, W, C, d_lab, d_len, d_st, d_en, d_clp, d_alab, d_alp, d_plp,
-                                   c->stream));
-    pf.end();
+    PROF_TRY(pf, "greedy_rowstat", launch_greedy_rowstat(x, ld, sb, st, C, nb, W, k1, k2, lp1, lp2, d_lse, c->stream));
+    PROF_TRY(pf, "greedy_spans", launch_greedy_spans(k1, k2, lp1, lp2, nb, W, C, d_lab, d_len, d_st, d_en, d_clp,
+                                                     d_alab, d_alp, d_plp, c->stream));
     const size_t co = (size_t)b0 * W, cb = n * W * 4;
     auto fetch = [&](void* dst, const void* src, size_t bytes) {
         return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
@@ -1333,12 +1397,8 @@ int rec_pass(hctr_ctx* c, const float* x, int64_t ld, int64_t sb, int64_t st, in
     float* d_nll = (float*)(c->ctc_buf + lse_b + tab_b);
     float* emis = (float*)(c->ctc_buf + lse_b + tab_b + line_b);
     HIP_TRY(c, hipMemcpyAsync(c->ctc_buf + lse_b, h.tab.data(), h.tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-    pf.begin("ctc_emis_gather");
-    HIP_TRY(c, launch_ctc_emis_gather(x, ld, sb, st, m, 0, nb, W, d_lse, emis, c->stream));
-    pf.end();
-    pf.begin("ctc_alpha");
-    HIP_TRY(c, launch_ctc_alpha(emis, m, 0, nb, W, h.max_states, d_nll, nullptr, nullptr, c->stream));
-    pf.end();
+    PROF_TRY(pf, "ctc_emis_gather", launch_ctc_emis_gather(x, ld, sb, st, m, 0, nb, W, d_lse, emis, c->stream));
+    PROF_TRY(pf, "ctc_alpha", launch_ctc_alpha(emis, m, 0, nb, W, h.max_states, d_nll, nullptr, nullptr, c->stream));
     HIP_TRY(c, hipMemcpyAsync(o.text_nll + b0, d_nll, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     // the recursion's max / min drop a NaN emission, so the loss of a line with a NaN row is no figure: NaN, by contract
@@ -1610,54 +1670,26 @@ int hctr_forward_logits(hctr_ctx* c, const void* img, int img_dtype, int img_on_
         if (B == 0) return HCTR_OK;
         HIP_TRY(c, hipSetDevice(c->device));
         const int C = c->num_classes;
-        const bool guarded = c->mode == 2;
-        SplitScope scope(c);
-        prof_reset(c);
-        guard_clear(c);
+        const Batch in{img, img_dtype, img_on_device, widths, B, W};
         float* dev_out = out_wbc;
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        if (!out_on_device) TRY(dev_alloc(c, tmp, &dev_out, (size_t)B * W * C, false));
-        std::vector<float> gbuf(guarded ? (size_t)2 * B : 0);
-        // one pass: the lines `lines[0..nb)` -> their rows of the [W][B][C] output
-        auto pass = [&](const int* lines, int nb, bool guard_pass, float* guard_dst) -> int {
-            TRY(ensure_workspace(c, nb, W, ws_need(c, HEAD_LOGITS, guard_pass)));
-            TRY(stage_input(c, img, img_dtype, img_on_device, widths, lines, nb, W));
-            TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, HEAD_LOGITS, guard_pass));
-            for (int i = 0; i < nb;) {             // [nb*W][cpad] -> out[t][line][C], one launch per run of consecutive lines
-                int j = i + 1;
-                while (j < nb && lines[j] == lines[j - 1] + 1) ++j;
-                HIP_TRY(c, launch_logits_to_wbc(c->ws.logits + (size_t)i * W * c->cpad, c->cpad, j - i, W, C, dev_out, B,
-                                                lines[i], c->stream));
-                i = j;
-            }
-            if (guard_pass)
-                HIP_TRY(c, hipMemcpyAsync(guard_dst, c->ws.line_guard, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
+        return synced(c, [&]() -> int {
+            if (!out_on_device) TRY(dev_alloc(c, tmp, &dev_out, (size_t)B * W * C, false));
+            // one pass: the lines' rows of the [W][B][C] output (a re-run overwrites them in stream order)
+            TRY(run_passes(c, in, PASS_OWN, [&](const Pass& p) -> int {
+                TRY(forward_pass(c, in, p, HEAD_LOGITS));
+                // [nb*W][cpad] -> out[t][line][C], one launch per run of consecutive lines
+                return for_runs(p.lines, p.nb, [&](int i, int n) -> int {
+                    HIP_TRY(c, launch_logits_to_wbc(c->ws.logits + (size_t)i * W * c->cpad, c->cpad, n, W, C, dev_out, B,
+                                                    p.lines[i], c->stream));
+                    return HCTR_OK;
+                });
+            }));
+            if (!out_on_device)
+                HIP_TRY(c, hipMemcpyAsync(out_wbc, dev_out, (size_t)B * W * C * 4, hipMemcpyDeviceToHost, c->stream));
             return HCTR_OK;
-        };
-        std::vector<int> all((size_t)B);
-        for (int b = 0; b < B; ++b) all[(size_t)b] = b;
-        int rc = HCTR_OK;
-        const int nbmax = sub_batch(c, B, W, c->split);
-        for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax)
-            rc = pass(all.data() + b0, std::min(nbmax, B - b0), guarded, guarded ? gbuf.data() + 2 * (size_t)b0 : nullptr);
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-        if (rc == HCTR_OK && guarded) {
-            const std::vector<int> flagged = guard_decide(c, gbuf, B);
-            if (!flagged.empty()) {               // the uncertain lines once more, in f16x3, into the same output rows
-                c->split = true;
-                const int nf = (int)flagged.size(), nb3 = sub_batch(c, nf, W, true);
-                for (int o = 0; o < nf && rc == HCTR_OK; o += nb3) rc = pass(flagged.data() + o, std::min(nb3, nf - o), false, nullptr);
-            }
-        }
-        if (rc == HCTR_OK && !out_on_device) {
-            e = hipMemcpyAsync(out_wbc, dev_out, (size_t)B * W * C * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "D2H logits: %s", hipGetErrorString(e));
-        }
-        e = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-        return rc;
+        }());
     });
 }
 
@@ -1669,62 +1701,41 @@ int hctr_greedy(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, 
         if (B == 0) return HCTR_OK;
         HIP_TRY(c, hipSetDevice(c->device));
         const int C = c->num_classes;
-        const bool guarded = c->mode == 2;
-        SplitScope scope(c);
-        prof_reset(c);
-        guard_clear(c);
-        std::vector<float> gbuf(guarded ? (size_t)2 * B : 0);
+        const Batch in{img, img_dtype, img_on_device, widths, B, W};
         const HeadMode hm = c->fuse_argmax ? HEAD_ARGMAX : HEAD_LOGITS;
-        // every pass queues async copies into host buffers: on a failure the stream is still drained before
-        // returning, so nothing is in flight into (or out of) caller memory after an error
-        auto pass = [&](const int* lines, int nb, bool guard_pass, int32_t* lab_dst, int32_t* len_dst, float* guard_dst) -> int {
-            TRY(ensure_workspace(c, nb, W, ws_need(c, hm, guard_pass)));
-            TRY(stage_input(c, img, img_dtype, img_on_device, widths, lines, nb, W));
-            TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, hm, guard_pass));
+        std::vector<int> redo;                     // the lines of the second sweep
+        // a first-sweep pass's lines are consecutive rows of the caller's arrays; the flagged lines of the second sweep
+        // are not, so their labels are staged in the context and scattered, up to each length, once they are on the host
+        int rc = run_passes(c, in, PASS_OWN, [&](const Pass& p) -> int {
+            if (p.rerun && p.first == 0) {
+                redo.assign(p.lines, p.lines + p.total);
+                c->h_labels.resize((size_t)p.total * W);
+                c->h_lengths.resize((size_t)p.total);
+            }
+            TRY(forward_pass(c, in, p, hm));
             Workspace& ws = c->ws;
             Prof pf(c);
             if (!c->fuse_argmax) {
-                pf.begin("argmax_rows");
-                HIP_TRY(c, launch_argmax_rows(ws.logits, c->cpad, (int64_t)nb * W, C, ws.colidx, 0, 0, c->stream));
-                pf.end();
+                PROF_TRY(pf, "argmax_rows",
+                         launch_argmax_rows(ws.logits, c->cpad, (int64_t)p.nb * W, C, ws.colidx, 0, 0, c->stream));
             }
-            pf.begin("ctc_collapse");
-            HIP_TRY(c, launch_ctc_collapse(ws.colidx, nb, W, C, ws.labels, ws.lengths, c->stream));
-            pf.end();
-            HIP_TRY(c, hipMemcpyAsync(lab_dst, ws.labels, (size_t)nb * W * 4, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(len_dst, ws.lengths, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
-            if (guard_pass)
-                HIP_TRY(c, hipMemcpyAsync(guard_dst, ws.line_guard, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
+            PROF_TRY(pf, "ctc_collapse", launch_ctc_collapse(ws.colidx, p.nb, W, C, ws.labels, ws.lengths, c->stream));
+            int32_t* lab_dst = p.rerun ? c->h_labels.data() : labels;
+            int32_t* len_dst = p.rerun ? c->h_lengths.data() : lengths;
+            HIP_TRY(c, hipMemcpyAsync(lab_dst + (size_t)p.first * W, ws.labels, (size_t)p.nb * W * 4, hipMemcpyDeviceToHost,
+                                      c->stream));
+            HIP_TRY(c, hipMemcpyAsync(len_dst + p.first, ws.lengths, (size_t)p.nb * 4, hipMemcpyDeviceToHost, c->stream));
             return HCTR_OK;
-        };
-        std::vector<int> all((size_t)B);
-        for (int b = 0; b < B; ++b) all[(size_t)b] = b;
-        int rc = HCTR_OK;
-        const int nbmax = sub_batch(c, B, W, c->split);
-        for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax)
-            rc = pass(all.data() + b0, std::min(nbmax, B - b0), guarded, labels + (size_t)b0 * W, lengths + b0,
-                      guarded ? gbuf.data() + 2 * (size_t)b0 : nullptr);
-        hipError_t es = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && es != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(es));
-        if (rc != HCTR_OK || !guarded) return rc;
-        // guarded precision: the lines the f16 sweep cannot certify run again in f16x3 at the SAME padded width (a line's
-        // result depends on nothing but its own pixels and W), and their labels replace the f16 ones
-        const std::vector<int> flagged = guard_decide(c, gbuf, B);
-        if (flagged.empty()) return HCTR_OK;
-        c->split = true;
-        const int nf = (int)flagged.size(), nb3 = sub_batch(c, nf, W, true);
-        c->h_labels.resize((size_t)nf * W);
-        c->h_lengths.resize((size_t)nf);
-        for (int o = 0; o < nf && rc == HCTR_OK; o += nb3)
-            rc = pass(flagged.data() + o, std::min(nb3, nf - o), false, c->h_labels.data() + (size_t)o * W,
-                      c->h_lengths.data() + o, nullptr);
-        es = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && es != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(es));
-        if (rc != HCTR_OK) return rc;
-        for (int i = 0; i < nf; ++i) {
-            const int n = c->h_lengths[(size_t)i];
-            lengths[flagged[(size_t)i]] = n;
-            if (n > 0) memcpy(labels + (size_t)flagged[(size_t)i] * W, c->h_labels.data() + (size_t)i * W, (size_t)n * 4);
+        });
+        // every pass queued async copies into host buffers: also after a failure the stream is drained before
+        // returning, so nothing is in flight into (or out of) caller memory. Only a guarded call that flagged nothing
+        // comes back drained (run_passes).
+        if (rc != HCTR_OK || c->mode != 2 || !redo.empty()) rc = synced(c, rc);
+        TRY(rc);
+        for (size_t i = 0; i < redo.size(); ++i) {
+            const int n = c->h_lengths[i];
+            lengths[redo[i]] = n;
+            if (n > 0) memcpy(labels + (size_t)redo[i] * W, c->h_labels.data() + i * W, (size_t)n * 4);
         }
         return HCTR_OK;
     });
@@ -1741,28 +1752,21 @@ int hctr_decode_greedy_logits(hctr_ctx* c, const float* logits_wbc, int on_devic
         prof_reset(c);
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        const float* dev = nullptr;
-        int32_t *idx = nullptr, *dl = nullptr, *dn = nullptr;
-        int rc = logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev);
-        if (rc == HCTR_OK) rc = dev_alloc(c, tmp, &idx, (size_t)W * B, false);
-        if (rc == HCTR_OK) rc = dev_alloc(c, tmp, &dl, (size_t)W * B, false);
-        if (rc == HCTR_OK) rc = dev_alloc(c, tmp, &dn, (size_t)B, false);
-        if (rc == HCTR_OK) {
+        return synced(c, [&]() -> int {
+            const float* dev = nullptr;
+            int32_t *idx = nullptr, *dl = nullptr, *dn = nullptr;
+            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
+            TRY(dev_alloc(c, tmp, &idx, (size_t)W * B, false));
+            TRY(dev_alloc(c, tmp, &dl, (size_t)W * B, false));
+            TRY(dev_alloc(c, tmp, &dn, (size_t)B, false));
             // rows of the WBC tensor are r = t*B + b; the argmax kernel writes idx as [b][t]
             Prof pf(c);
-            pf.begin("argmax_rows");
-            hipError_t e = launch_argmax_rows(dev, C, (int64_t)W * B, C, idx, B, W, c->stream);
-            pf.end();
-            if (e == hipSuccess) {
-                pf.begin("ctc_collapse");
-                e = launch_ctc_collapse(idx, B, W, C, dl, dn, c->stream);
-                pf.end();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(labels, dl, (size_t)W * B * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(lengths, dn, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "decode_greedy_logits: %s", hipGetErrorString(e));
-        }
-        return synced(c, rc);
+            PROF_TRY(pf, "argmax_rows", launch_argmax_rows(dev, C, (int64_t)W * B, C, idx, B, W, c->stream));
+            PROF_TRY(pf, "ctc_collapse", launch_ctc_collapse(idx, B, W, C, dl, dn, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(labels, dl, (size_t)W * B * 4, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(lengths, dn, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+            return HCTR_OK;
+        }());
     });
 }
 
@@ -1789,20 +1793,18 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
         }
         if (k > C) return fail(c, HCTR_ERR_ARG, "k=%d exceeds C=%d", k, C);
         const double thresh = std::log(0.001);        // utils/ctc_codec.py:128
-        const bool guarded = from_img && c->mode == 2;
-        SplitScope scope(c);
-        prof_reset(c);
-        guard_clear(c);
+        const Batch in{img, img_dtype, img_on_device, widths, B, W};
         // candidate lists of one pass (lines in pass order); owner[line] = the pass whose lists are current for the line
         struct PassOut { std::vector<int> lines; std::vector<int64_t> loff; std::vector<int32_t> ci; std::vector<float> cl; };
         std::vector<PassOut> outs;
         std::vector<int> owner((size_t)B, -1);
         std::vector<int32_t> counts((size_t)W * B, 0);
-        std::vector<float> gbuf(guarded ? (size_t)2 * B : 0);
         std::vector<void*>& pool = c->beam_allocs;
         // one pass over the lines `lines[0..nb)`: forward (or the caller's logits), log-softmax + top-k (+ lists), results
         // scattered to the lines' (t, line) rows of the host outputs
-        auto run_pass = [&](const int* lines, int nb, bool guard_pass, float* guard_dst) -> int {
+        auto run_pass = [&](const Pass& p) -> int {
+            const int* lines = p.lines;
+            const int nb = p.nb;
             const int64_t rows = (int64_t)nb * W;
             free_pool(pool);
             const float* rowsrc = nullptr;
@@ -1812,12 +1814,7 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
             // more than kBeamCap list slots (near-uniform logits) is redone through the stored-logits kernels.
             bool fused = from_img && c->fuse_beam && k <= kBeamMaxK && k <= head_parts(c);
             if (from_img) {
-                const HeadMode hm = fused ? HEAD_BEAM : HEAD_LOGITS;
-                TRY(ensure_workspace(c, nb, W, ws_need(c, hm, guard_pass)));
-                TRY(stage_input(c, img, img_dtype, img_on_device, widths, lines, nb, W));
-                TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, hm, guard_pass));
-                if (guard_pass)
-                    HIP_TRY(c, hipMemcpyAsync(guard_dst, c->ws.line_guard, (size_t)nb * 8, hipMemcpyDeviceToHost, c->stream));
+                TRY(forward_pass(c, in, p, fused ? HEAD_BEAM : HEAD_LOGITS));
                 rowsrc = c->ws.logits; ld = c->cpad;
             } else {
                 float *up = nullptr, *rowsbuf = nullptr;
@@ -1852,9 +1849,9 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
                 if (ovf) {                       // redo this pass with stored logits (re-staged: carving may move the arena)
                     fused = false;
                     ++c->beam_fallbacks;
-                    TRY(ensure_workspace(c, nb, W, ws_need(c, HEAD_LOGITS)));
-                    TRY(stage_input(c, img, img_dtype, img_on_device, widths, lines, nb, W));
-                    TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, HEAD_LOGITS));
+                    Pass redo = p;
+                    redo.guard_dst = nullptr;      // (the guard figures came back with the fused forward)
+                    TRY(forward_pass(c, in, redo, HEAD_LOGITS));
                     rowsrc = c->ws.logits;
                     TRY(own_outputs());
                 }
@@ -1863,10 +1860,8 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
             }
             if (!fused) {
                 Prof pf(c);
-                pf.begin("row_topk");
-                const hipError_t e = launch_row_topk(rowsrc, ld, nb, W, C, k, thresh, d_idx, d_lp, d_bl, d_st, d_cnt, c->stream);
-                pf.end();
-                if (e != hipSuccess) return fail(c, HCTR_ERR_HIP, "row_topk: %s (C=%d)", hipGetErrorString(e), C);
+                PROF_TRY(pf, "row_topk", launch_row_topk(rowsrc, ld, nb, W, C, k, thresh, d_idx, d_lp, d_bl, d_st,
+                                                         d_cnt, c->stream));
             }
             // D2H through a pinned staging buffer (grown on demand): a pageable destination is copied in small staged pieces
             const size_t nk = (size_t)rows * k, need_pin = (2 * nk + 2 * (size_t)rows) * 4;
@@ -1924,23 +1919,18 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             return HCTR_OK;
         };
-        std::vector<int> all((size_t)B);
-        for (int b = 0; b < B; ++b) all[(size_t)b] = b;
-        int rc = HCTR_OK;
-        const int nbmax = from_img ? sub_batch(c, B, W, c->split) : B;
-        for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax)
-            rc = run_pass(all.data() + b0, std::min(nbmax, B - b0), guarded, guarded ? gbuf.data() + 2 * (size_t)b0 : nullptr);
-        if (rc == HCTR_OK && guarded) {
-            // guarded precision: lines with a column the f16 sweep cannot certify (same criterion as hctr_greedy) once
-            // more in f16x3; their rows of every output are replaced
-            const std::vector<int> flagged = guard_decide(c, gbuf, B);
-            if (!flagged.empty()) {
-                c->split = true;
-                const int nf = (int)flagged.size(), nb3 = sub_batch(c, nf, W, true);
-                for (int o = 0; o < nf && rc == HCTR_OK; o += nb3) rc = run_pass(flagged.data() + o, std::min(nb3, nf - o), false, nullptr);
-            }
+        // from images: the passes of the mode (lines with a column the f16 sweep cannot certify - same criterion as
+        // hctr_greedy - once more in f16x3, their rows of every output replaced); caller logits: one pass, no forward
+        int rc;
+        if (from_img) {
+            rc = run_passes(c, in, PASS_OWN, run_pass);
+        } else {
+            prof_reset(c);
+            guard_clear(c);
+            const std::vector<int> all = line_indices(B);
+            rc = run_pass(Pass{all.data(), B, 0, B, false, nullptr});
         }
-        (void)hipStreamSynchronize(c->stream);
+        rc = synced(c, rc);
         free_pool(pool);
         if (rc != HCTR_OK || !want_candidates) return rc;
         // merge the per-pass lists into one CSR in (t*B + b) order, held by the context until fetched
@@ -1977,15 +1967,16 @@ int hctr_ctc_loss(hctr_ctx* c, const void* img, int img_dtype, int img_on_device
         CtcHost h;
         TRY(ctc_prepare(c, B, W, c->num_classes, targets, target_lengths, input_lengths, &h));
         return ctc_image_call(
-            c, img, img_dtype, img_on_device, widths, B, W, h, 0, [](char*) { return HCTR_OK; },
-            [&](Prof& pf, const CtcLines& m, const float* emis, float* d_nll, int b0, int nb) {
-                pf.begin("ctc_alpha");
-                hipError_t e = launch_ctc_alpha(emis, m, b0, nb, W, h.max_states, d_nll, nullptr, nullptr, c->stream);
-                pf.end();
-                return e;
+            c, Batch{img, img_dtype, img_on_device, widths, B, W}, h, 0, [](char*) { return HCTR_OK; },
+            [&](Prof& pf, const CtcLines& m, const float* emis, float* d_nll, int b0, int nb) -> int {
+                PROF_TRY(pf, "ctc_alpha", launch_ctc_alpha(emis, m, b0, nb, W, h.max_states, d_nll, nullptr, nullptr,
+                                                           c->stream));
+                return HCTR_OK;
             },
-            [&](const float* d_nll) { return hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream); },
-            "nll");
+            [&](const float* d_nll) -> int {
+                HIP_TRY(c, hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+                return HCTR_OK;
+            });
     });
 }
 
@@ -2000,26 +1991,20 @@ int hctr_ctc_loss_logits(hctr_ctx* c, const float* logits_wbc, int on_device, in
         prof_reset(c);
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        CtcLines m;
-        float *d_nll = nullptr, *emis = nullptr;
-        TRY(ctc_scratch(c, h, (size_t)B * W * h.D, &m, &d_nll, &emis));
-        const float* dev = nullptr;
-        int rc = logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev);
-        if (rc == HCTR_OK) {
+        return synced(c, [&]() -> int {
+            CtcLines m;
+            float *d_nll = nullptr, *emis = nullptr;
+            const float* dev = nullptr;
+            TRY(ctc_scratch(c, h, (size_t)B * W * h.D, &m, &d_nll, &emis));
+            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
             Prof pf(c);
             // rows of the WBC tensor are r = t*B + b
-            pf.begin("ctc_lse");
-            hipError_t e = launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, nullptr, c->stream);
-            pf.end();
-            if (e == hipSuccess) {
-                pf.begin("ctc_alpha");
-                e = launch_ctc_alpha(emis, m, 0, B, W, h.max_states, d_nll, nullptr, nullptr, c->stream);
-                pf.end();
-            }
-            if (e == hipSuccess) e = hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_loss_logits: %s", hipGetErrorString(e));
-        }
-        return synced(c, rc);
+            PROF_TRY(pf, "ctc_lse", launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, nullptr, c->stream));
+            PROF_TRY(pf, "ctc_alpha", launch_ctc_alpha(emis, m, 0, B, W, h.max_states, d_nll, nullptr, nullptr,
+                                                       c->stream));
+            HIP_TRY(c, hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+            return HCTR_OK;
+        }());
     });
 }
 
@@ -2061,56 +2046,38 @@ int hctr_ctc_loss_logits_grad(hctr_ctx* c, const float* logits_wbc, int on_devic
                      gtab_b = align256(gtab.size() * 4);
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        CtcLines m;
-        float *d_nll = nullptr, *emis = nullptr, *dgrad = grad_wbc;
-        char* extra = nullptr;
-        TRY(ctc_scratch(c, h, BW * h.D, &m, &d_nll, &emis, lse_b + aoff_b + wt_b + gtab_b + (size_t)ast_floats * 4 + 16,
-                        &extra));
-        double* d_lse = (double*)extra;
-        int64_t* d_aoff = (int64_t*)(extra + lse_b);
-        float* d_wt = (float*)(extra + lse_b + aoff_b);
-        int32_t* d_soff = (int32_t*)(extra + lse_b + aoff_b + wt_b);
-        int32_t* d_pos = d_soff + (size_t)B * D1;
-        float* d_ast = (float*)(extra + lse_b + aoff_b + wt_b + gtab_b);
-        const size_t n = (size_t)W * B * C;
-        const float* dev = nullptr;
-        int rc = logits_on_device(c, tmp, logits_wbc, on_device, n, &dev);
-        if (rc == HCTR_OK && !grad_on_device) rc = dev_alloc(c, tmp, &dgrad, n, false);
-        if (rc == HCTR_OK) {
-            hipError_t e = hipMemcpyAsync(d_aoff, aoff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(d_wt, wt.data(), (size_t)B * 4, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(d_soff, gtab.data(), gtab.size() * 4, hipMemcpyHostToDevice, c->stream);
+        // the host tables above are pageable: their copies are staged before hipMemcpyAsync returns
+        return synced(c, [&]() -> int {
+            CtcLines m;
+            float *d_nll = nullptr, *emis = nullptr, *dgrad = grad_wbc;
+            char* extra = nullptr;
+            TRY(ctc_scratch(c, h, BW * h.D, &m, &d_nll, &emis, lse_b + aoff_b + wt_b + gtab_b + (size_t)ast_floats * 4 + 16,
+                            &extra));
+            double* d_lse = (double*)extra;
+            int64_t* d_aoff = (int64_t*)(extra + lse_b);
+            float* d_wt = (float*)(extra + lse_b + aoff_b);
+            int32_t* d_soff = (int32_t*)(extra + lse_b + aoff_b + wt_b);
+            int32_t* d_pos = d_soff + (size_t)B * D1;
+            float* d_ast = (float*)(extra + lse_b + aoff_b + wt_b + gtab_b);
+            const size_t n = (size_t)W * B * C;
+            const float* dev = nullptr;
+            TRY(logits_on_device(c, tmp, logits_wbc, on_device, n, &dev));
+            if (!grad_on_device) TRY(dev_alloc(c, tmp, &dgrad, n, false));
+            HIP_TRY(c, hipMemcpyAsync(d_aoff, aoff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d_wt, wt.data(), (size_t)B * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d_soff, gtab.data(), gtab.size() * 4, hipMemcpyHostToDevice, c->stream));
             Prof pf(c);
             // rows of the WBC tensor are r = t*B + b
-            if (e == hipSuccess) {
-                pf.begin("ctc_rowlse");
-                e = launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, d_lse, c->stream);
-                pf.end();
-            }
-            if (e == hipSuccess) {
-                pf.begin("ctc_alpha_store");
-                e = launch_ctc_alpha(emis, m, 0, B, W, h.max_states, d_nll, d_aoff, d_ast, c->stream);
-                pf.end();
-            }
-            if (e == hipSuccess) {
-                pf.begin("ctc_beta");
-                e = launch_ctc_beta(emis, m, B, W, h.max_states, d_nll, d_aoff, d_ast, c->stream);
-                pf.end();
-            }
-            if (e == hipSuccess) {
-                pf.begin("ctc_grad_rows");
-                e = launch_ctc_grad_rows(dev, C, B, W, m, d_lse, d_nll, d_wt, d_aoff, d_ast, d_soff, d_pos, dgrad,
-                                         c->stream);
-                pf.end();
-            }
-            if (e == hipSuccess && nll) e = hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e == hipSuccess && !grad_on_device)
-                e = hipMemcpyAsync(grad_wbc, dgrad, n * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_loss_logits_grad: %s", hipGetErrorString(e));
-        }
-        // the host tables above are pageable: their copies were staged before hipMemcpyAsync returned
-        return synced(c, rc);
+            PROF_TRY(pf, "ctc_rowlse", launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, d_lse, c->stream));
+            PROF_TRY(pf, "ctc_alpha_store", launch_ctc_alpha(emis, m, 0, B, W, h.max_states, d_nll, d_aoff, d_ast,
+                                                             c->stream));
+            PROF_TRY(pf, "ctc_beta", launch_ctc_beta(emis, m, B, W, h.max_states, d_nll, d_aoff, d_ast, c->stream));
+            PROF_TRY(pf, "ctc_grad_rows", launch_ctc_grad_rows(dev, C, B, W, m, d_lse, d_nll, d_wt, d_aoff, d_ast,
+                                                               d_soff, d_pos, dgrad, c->stream));
+            if (nll) HIP_TRY(c, hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+            if (!grad_on_device) HIP_TRY(c, hipMemcpyAsync(grad_wbc, dgrad, n * 4, hipMemcpyDeviceToHost, c->stream));
+            return HCTR_OK;
+        }());
     });
 }
 
@@ -2126,7 +2093,7 @@ int hctr_ctc_align(hctr_ctx* c, const void* img, int img_dtype, int img_on_devic
         AlignDev a;
         align_layout(h, W, &a);
         return ctc_image_call(
-            c, img, img_dtype, img_on_device, widths, B, W, h, a.bytes() + 16,
+            c, Batch{img, img_dtype, img_on_device, widths, B, W}, h, a.bytes() + 16,
             [&](char* extra) -> int {
                 align_carve(extra, &a);
                 HIP_TRY(c, hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
@@ -2137,8 +2104,7 @@ int hctr_ctc_align(hctr_ctx* c, const void* img, int img_dtype, int img_on_devic
             },
             [&](const float* d_score) {
                 return align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
-            },
-            "alignment");
+            });
     });
 }
 
@@ -2156,27 +2122,21 @@ int hctr_ctc_align_logits(hctr_ctx* c, const float* logits_wbc, int on_device, i
         align_layout(h, W, &a);
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        CtcLines m;
-        float *d_score = nullptr, *emis = nullptr;
-        char* extra = nullptr;
-        TRY(ctc_scratch(c, h, (size_t)B * W * h.D, &m, &d_score, &emis, a.bytes() + 16, &extra));
-        align_carve(extra, &a);
-        const float* dev = nullptr;
-        int rc = logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev);
-        if (rc == HCTR_OK) {
-            hipError_t e = hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream);
+        return synced(c, [&]() -> int {
+            CtcLines m;
+            float *d_score = nullptr, *emis = nullptr;
+            char* extra = nullptr;
+            const float* dev = nullptr;
+            TRY(ctc_scratch(c, h, (size_t)B * W * h.D, &m, &d_score, &emis, a.bytes() + 16, &extra));
+            align_carve(extra, &a);
+            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
+            HIP_TRY(c, hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
             Prof pf(c);
-            if (e == hipSuccess) {
-                // rows of the WBC tensor are r = t*B + b
-                pf.begin("ctc_lse");
-                e = launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, nullptr, c->stream);
-                pf.end();
-            }
-            if (e == hipSuccess) e = align_launch(c, pf, emis, m, h, a, 0, B, W, d_score);
-            if (e == hipSuccess) e = align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
-            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "ctc_align_logits: %s", hipGetErrorString(e));
-        }
-        return synced(c, rc);
+            // rows of the WBC tensor are r = t*B + b
+            PROF_TRY(pf, "ctc_lse", launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, nullptr, c->stream));
+            TRY(align_launch(c, pf, emis, m, h, a, 0, B, W, d_score));
+            return align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
+        }());
     });
 }
 
@@ -2187,28 +2147,13 @@ int hctr_recognize(hctr_ctx* c, const void* img, int img_dtype, int img_on_devic
         TRY(check_forward_args(c, img, img_dtype, B, W));
         if (B == 0) return HCTR_OK;
         HIP_TRY(c, hipSetDevice(c->device));
-        SplitScope scope(c);
-        c->split = c->mode != 0;              // as hctr_ctc_loss: mode 2's guard certifies argmaxes, not confidences
-        if (!c->wts().built) return fail(c, HCTR_ERR_STATE, "the weight set of this precision mode is not resident");
-        prof_reset(c);
-        const RecOut o{labels, lengths, span_start, span_end, char_logp, alt_label, alt_logp, path_logp, text_nll};
-        std::vector<int32_t> own_lab, own_len;
-        if (text_nll && !labels) own_lab.resize((size_t)B * W);
-        if (text_nll && !lengths) own_len.resize((size_t)B);
-        int32_t* h_lab = labels ? labels : text_nll ? own_lab.data() : nullptr;
-        int32_t* h_len = lengths ? lengths : text_nll ? own_len.data() : nullptr;
-        std::vector<int> all((size_t)B);
-        for (int b = 0; b < B; ++b) all[(size_t)b] = b;
-        const int nbmax = sub_batch(c, B, W, c->split);
-        auto pass = [&](int b0, int nb) -> int {
-            TRY(ensure_workspace(c, nb, W, ws_need(c, HEAD_LOGITS)));
-            TRY(stage_input(c, img, img_dtype, img_on_device, widths, all.data() + b0, nb, W));
-            TRY(run_forward(c, img_dtype == HCTR_F32, widths != nullptr, HEAD_LOGITS, false));
-            return rec_pass(c, c->ws.logits, c->cpad, W, 1, c->num_classes, b0, nb, W, o, h_lab, h_len);
-        };
-        int rc = HCTR_OK;
-        for (int b0 = 0; b0 < B && rc == HCTR_OK; b0 += nbmax) rc = pass(b0, std::min(nbmax, B - b0));
-        return synced(c, rc);
+        const Batch in{img, img_dtype, img_on_device, widths, B, W};
+        const RecCall rc({labels, lengths, span_start, span_end, char_logp, alt_label, alt_logp, path_logp, text_nll}, B, W);
+        // PASS_EXACT as hctr_ctc_loss: mode 2's guard certifies argmaxes, not confidences
+        return synced(c, run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
+            TRY(forward_pass(c, in, p, HEAD_LOGITS));
+            return rec_pass(c, c->ws.logits, c->cpad, W, 1, c->num_classes, p.first, p.nb, W, rc);
+        }));
     });
 }
 
@@ -2220,19 +2165,14 @@ int hctr_recognize_logits(hctr_ctx* c, const float* logits_wbc, int on_device, i
         if (B == 0) return HCTR_OK;
         HIP_TRY(c, hipSetDevice(c->device));
         prof_reset(c);
-        const RecOut o{labels, lengths, span_start, span_end, char_logp, alt_label, alt_logp, path_logp, text_nll};
-        std::vector<int32_t> own_lab, own_len;
-        if (text_nll && !labels) own_lab.resize((size_t)B * W);
-        if (text_nll && !lengths) own_len.resize((size_t)B);
+        const RecCall rc({labels, lengths, span_start, span_end, char_logp, alt_label, alt_logp, path_logp, text_nll}, B, W);
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        const float* dev = nullptr;
-        int rc = logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev);
-        // rows of the WBC tensor are r = t*B + b
-        if (rc == HCTR_OK)
-            rc = rec_pass(c, dev, C, 1, B, C, 0, B, W, o, labels ? labels : text_nll ? own_lab.data() : nullptr,
-                          lengths ? lengths : text_nll ? own_len.data() : nullptr);
-        return synced(c, rc);
+        return synced(c, [&]() -> int {
+            const float* dev = nullptr;
+            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
+            return rec_pass(c, dev, C, 1, B, C, 0, B, W, rc);      // rows of the WBC tensor are r = t*B + b
+        }());
     });
 }
 
@@ -2261,16 +2201,15 @@ int hctr_log_softmax(hctr_ctx* c, const float* logits_wbc, int on_device, int W,
         HIP_TRY(c, hipSetDevice(c->device));
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        const float* dev = nullptr;
-        float* y = nullptr;
-        int rc = logits_on_device(c, tmp, logits_wbc, on_device, (size_t)rows * C, &dev);
-        if (rc == HCTR_OK) rc = dev_alloc(c, tmp, &y, (size_t)rows * C, false);
-        if (rc == HCTR_OK) {
-            hipError_t e = launch_log_softmax_rows(dev, rows, C, y, c->stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(out_host, y, (size_t)rows * C * 4, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "log_softmax: %s", hipGetErrorString(e));
-        }
-        return synced(c, rc);
+        return synced(c, [&]() -> int {
+            const float* dev = nullptr;
+            float* y = nullptr;
+            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)rows * C, &dev));
+            TRY(dev_alloc(c, tmp, &y, (size_t)rows * C, false));
+            HIP_TRY(c, launch_log_softmax_rows(dev, rows, C, y, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(out_host, y, (size_t)rows * C * 4, hipMemcpyDeviceToHost, c->stream));
+            return HCTR_OK;
+        }());
     });
 }
 
@@ -2318,26 +2257,19 @@ int hctr_resize_lines(hctr_ctx* c, const uint8_t* packed_src, int64_t packed_byt
         HIP_TRY(c, hipSetDevice(c->device));
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        uint8_t *src = nullptr, *dst = nullptr;
-        ResizeLine* dl = nullptr;
-        int rc = dev_alloc(c, tmp, &src, (size_t)std::max<int64_t>(packed_bytes, 1), false);
-        if (rc == HCTR_OK) rc = dev_alloc(c, tmp, &dl, (size_t)n, false);
-        const size_t out_bytes = (size_t)n * out_height * out_W;
-        if (rc == HCTR_OK && !out_on_device) rc = dev_alloc(c, tmp, &dst, out_bytes, false);
-        if (rc == HCTR_OK) {
-            uint8_t* target = out_on_device ? out : dst;
-            hipError_t e = hipMemcpyAsync(src, packed_src, (size_t)packed_bytes, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess)
-                e = hipMemcpyAsync(dl, lines.data(), sizeof(ResizeLine) * (size_t)n, hipMemcpyHostToDevice, c->stream);
-            if (e == hipSuccess) e = launch_resize_lines(src, dl, n, target, out_height, out_W, c->stream);
-            if (e == hipSuccess && !out_on_device)
-                e = hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, c->stream);
-            if (e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "resize_lines: %s", hipGetErrorString(e));
-        }
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (rc == HCTR_OK && e != hipSuccess) rc = fail(c, HCTR_ERR_HIP, "stream sync: %s", hipGetErrorString(e));
-        free_pool(tmp);
-        return rc;
+        return synced(c, [&]() -> int {
+            uint8_t *src = nullptr, *dst = out;
+            ResizeLine* dl = nullptr;
+            const size_t out_bytes = (size_t)n * out_height * out_W;
+            TRY(dev_alloc(c, tmp, &src, (size_t)std::max<int64_t>(packed_bytes, 1), false));
+            TRY(dev_alloc(c, tmp, &dl, (size_t)n, false));
+            if (!out_on_device) TRY(dev_alloc(c, tmp, &dst, out_bytes, false));
+            HIP_TRY(c, hipMemcpyAsync(src, packed_src, (size_t)packed_bytes, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(dl, lines.data(), sizeof(ResizeLine) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, launch_resize_lines(src, dl, n, dst, out_height, out_W, c->stream));
+            if (!out_on_device) HIP_TRY(c, hipMemcpyAsync(out, dst, out_bytes, hipMemcpyDeviceToHost, c->stream));
+            return HCTR_OK;
+        }());
     });
 }
 

@@ -135,6 +135,77 @@ def test_guard_thresholds_and_mode_switching(pkg, synth, auto_random, state_dict
         m.set_guard(LOGIT_RTOL, LOGIT_ATOL)
 
 
+def _runs(idx):
+    """number of runs of consecutive integers in a sorted index list"""
+    return sum(1 for i, v in enumerate(idx) if i == 0 or v != idx[i - 1] + 1)
+
+
+def test_partly_flagged_batch_in_several_passes_equals_one_pass(pkg, synth, auto_random, state_dict):
+    """Auto mode with a guard cut that flags a NON-CONTIGUOUS part of 7 lines, in a context whose passes hold 4 lines
+    (f16) / 2 lines (f16x3): logits, greedy labels and both beam front ends (fused, k = 5; stored logits, k = 33 >
+    kBeamMaxK) equal the one-pass context's bit for bit, and every line's logits are its own mode's."""
+    m = auto_random
+    imgs = synth.make_line_images(7, 150, 79)
+    m.set_precision("auto")
+    m.greedy(imgs)
+    mg = m.last_guard()["min_margin"].astype(np.float64)
+    srt = np.sort(mg)
+    cut = None
+    for i in reversed(range(6)):                      # the 6 cuts between consecutive sorted margins, largest set first
+        mid = 0.5 * (srt[i] + srt[i + 1])
+        fl = [b for b in range(7) if not mg[b] > mid]
+        if srt[i] < mid < srt[i + 1] and len(fl) < 7 and _runs(fl) >= 2:
+            cut = mid
+            break
+    print("min_margin", mg.tolist(), "cut", cut)
+    assert cut is not None, mg.tolist()
+    ms, old_cols = None, os.environ.get("HCTR_MAX_COLS")
+    try:
+        os.environ["HCTR_MAX_COLS"] = "1000"          # (read at context creation)
+        ms = pkg.hctr_model(synth.DEFAULT_VOCAB + 2, precision="auto").cuda(0)
+        ms.load_state_dict(state_dict)
+        assert ms.lines_per_pass(7, 150, False) == 4 and ms.lines_per_pass(7, 150, True) == 2
+        m.set_guard(0.0, cut / 2)
+        ms.set_guard(0.0, cut / 2)
+
+        def flags_of(mod):
+            g = mod.last_guard()
+            assert g["lines"] == 7 and 0 < g["flagged"] < 7, g["flagged"]
+            return g["flags"].copy()
+
+        lg1, lgs = m(imgs), ms(imgs)
+        f1, fs = flags_of(m), flags_of(ms)
+        assert np.array_equal(f1, fs) and _runs([b for b in range(7) if f1[b]]) >= 2, (f1, fs)
+        assert np.array_equal(lgs, lg1)
+        lab1, labs = m.greedy(imgs), ms.greedy(imgs)
+        assert np.array_equal(flags_of(m), f1) and np.array_equal(flags_of(ms), f1)
+        assert [x.tolist() for x in labs] == [x.tolist() for x in lab1]
+        for k in (5, 33):                             # fused front end; stored logits (k > kBeamMaxK = 32)
+            fe1 = m.beam_frontend(imgs, k=k, want_candidates=True)
+            fes = ms.beam_frontend(imgs, k=k, want_candidates=True)
+            assert np.array_equal(flags_of(m), f1) and np.array_equal(flags_of(ms), f1)
+            for key in ("topk_idx", "topk_logp", "blank_logp", "cand_off"):
+                assert np.array_equal(fes[key], fe1[key]), (k, key)
+            n = int(fe1["cand_off"][-1])
+            assert n > 0
+            for key in ("cand_idx", "cand_logp"):
+                assert np.array_equal(fes[key][:n], fe1[key][:n]), (k, key)
+        # flagged lines carry the f16x3 logits, the others the f16 ones, bit for bit
+        m.set_precision("f16")
+        lg16 = m(imgs)
+        m.set_precision("f16x3")
+        lg3 = m(imgs)
+        for b, f in enumerate(f1):
+            assert np.array_equal(lg1[:, b], lg3[:, b] if f else lg16[:, b]), (b, f)
+    finally:
+        os.environ.pop("HCTR_MAX_COLS", None)
+        if old_cols is not None:
+            os.environ["HCTR_MAX_COLS"] = old_cols
+        m.set_precision("auto")
+        m.set_guard(LOGIT_RTOL, LOGIT_ATOL)
+        del ms
+
+
 def test_auto_mode_config2_trained_checkpoint_equals_the_real_reference(pkg, synth, auto_trained):
     """BASELINE configs[1] (64 x 1x128x2000), trained-like checkpoint: auto-mode text == the REAL reference's (fp32 CPU)
     for all 64 lines, with only a handful of lines run twice; the guard's margins agree with the reference's own margins
