@@ -9,6 +9,9 @@ Public surface = the reference's surface for this path:
   ctc_codec    drop-in for utils/ctc_codec.py:14                (engine-backed)
   CTCLoss      drop-in for the criterion of main.py:205           (engine-backed, with backward())
   CTCAligner   forced alignment: character spans and confidences  (engine-backed; no counterpart)
+  Evaluation   result of hctr_model.evaluate / ctc_codec.evaluate: edit distance, CER / CR / AR, error counts and the
+               character alignment against the truth              (engine-backed; reference: editdistance.eval)
+  edit_distance  per-line Levenshtein distance of two lists of strings or label sequences, on the device
   Recognition  result of hctr_model.recognize / ctc_codec.recognize: the greedy text with per-character spans,
                confidences and runners-up                          (engine-backed; no counterpart)
 plus ``synth`` (deterministic synthetic checkpoints / line images) and ``build`` / ``load_library``.
@@ -16,7 +19,21 @@ plus ``synth`` (deterministic synthetic checkpoints / line images) and ``build``
 from . import preprocess, synth  # noqa: F401
 from ._lib import build, load as load_library  # noqa: F401
 from .codec import ArpaLM, ToyBigramLM, ZeroLM, ctc_codec  # noqa: F401
-from .ctc import CTCAligner, CTCAlignment, CTCLoss, Recognition  # noqa: F401
+from .ctc import CTCAligner, CTCAlignment, CTCLoss, Evaluation, Recognition  # noqa: F401
 from .model import hctr_model  # noqa: F401
 
-__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "Recognition", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]
+_EDIT_BOUND = None
+
+
+def edit_distance(hyps, refs, device=0):
+    """Per-line Levenshtein distance (int32 array) of two equally long lists of strings or of int sequences, computed
+    on the GPU (include/hctr_hip.h ``hctr_edit_distance``). Strings are compared by code point: ``editdistance.eval``
+    on each pair, exactly. A distance between label sequences of a ``ctc_codec`` equals the distance between the
+    strings they stand for when the codec's ``chars_list`` has no duplicate entries."""
+    global _EDIT_BOUND
+    from . import ctc
+    if _EDIT_BOUND is None or _EDIT_BOUND._device != int(device):
+        _EDIT_BOUND = ctc._EngineBound().cuda(device)
+    return ctc.edit_distance_sequences(_EDIT_BOUND._context(), list(hyps), list(refs), maps=False).edits
+
+__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "Recognition", "Evaluation", "edit_distance", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]

@@ -192,6 +192,30 @@ class ctc_codec(object):
         rec = ctc.recognize_logits(self._context(), logits, on_dev)
         return self.labels_to_text(rec.label_lists()), rec
 
+    def evaluate(self, preds, truths, maps=True):
+        """Score decoded text against the truth strings on the device: returns ``(texts, ctc.Evaluation)``.
+        ``preds`` is what ``decode`` takes - then the greedy decode is scored in label space against ``encode(truths)``
+        without the labels visiting the host (include/hctr_hip.h ``hctr_evaluate_logits``) - or a list of strings from
+        any decoder, beam search included, scored on code points (``hctr_edit_distance``), which is
+        ``editdistance.eval(pre, tru)`` exactly, also for characters outside the vocabulary. The two coincide when
+        ``chars_list`` has no duplicate entries and every truth character is in it (a truth character outside it is
+        encoded as <unknown>, which no decode produces: one error either way, but two different unknown characters
+        are equal in label space only)."""
+        from . import ctc
+        truths = list(truths)
+        if isinstance(preds, (list, tuple)) and all(isinstance(p, str) for p in preds):
+            texts = list(preds)
+            return texts, ctc.edit_distance_sequences(self._context(), texts, truths, maps)
+        logits, on_dev = self._as_logits(preds)
+        W, B, C = (int(v) for v in logits.shape)
+        if C != len(self.characters):
+            raise ValueError("logits have %d classes, codec has %d" % (C, len(self.characters)))
+        if W == 0:
+            raise ValueError("preds have no steps (W = 0)")
+        tg, tl = self.encode(truths)
+        ev = ctc.evaluate_logits(self._context(), logits, on_dev, tg, tl, maps)
+        return self.labels_to_text([ev.labels[b, :ev.lengths[b]] for b in range(B)]), ev
+
     def labels_to_text(self, label_lists):
         chars = self.characters
         return ["".join(chars[i] for i in line) for line in label_lists]

@@ -1408,6 +1408,184 @@ int rec_pass(hctr_ctx* c, const float* x, int64_t ld, int64_t sb, int64_t st, in
     return HCTR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// greedy decode of line images (hctr_greedy, hctr_evaluate)
+// ---------------------------------------------------------------------------------------------
+// The passes of hctr_greedy: forward, argmax, collapse, labels and lengths copied to the host arrays (which may be null).
+// A first-sweep pass's lines are consecutive rows of the caller's arrays; the flagged lines of the second sweep are not,
+// so their labels are staged in the context and scattered by greedy_scatter once they are on the host. `redo` receives
+// the lines of the second sweep. after(pf, p) queues what a caller adds behind a pass's collapse, on ws.labels / lengths.
+template <class After>
+int greedy_passes(hctr_ctx* c, const Batch& in, int32_t* labels, int32_t* lengths, std::vector<int>* redo, After after) {
+    const int C = c->num_classes, W = in.W;
+    const HeadMode hm = c->fuse_argmax ? HEAD_ARGMAX : HEAD_LOGITS;
+    return run_passes(c, in, PASS_OWN, [&](const Pass& p) -> int {
+        if (p.rerun && p.first == 0) {
+            redo->assign(p.lines, p.lines + p.total);
+            c->h_labels.resize((size_t)p.total * W);
+            c->h_lengths.resize((size_t)p.total);
+        }
+        TRY(forward_pass(c, in, p, hm));
+        Workspace& ws = c->ws;
+        Prof pf(c);
+        if (!c->fuse_argmax) {
+            PROF_TRY(pf, "argmax_rows",
+                     launch_argmax_rows(ws.logits, c->cpad, (int64_t)p.nb * W, C, ws.colidx, 0, 0, c->stream));
+        }
+        PROF_TRY(pf, "ctc_collapse", launch_ctc_collapse(ws.colidx, p.nb, W, C, ws.labels, ws.lengths, c->stream));
+        int32_t* lab_dst = p.rerun ? c->h_labels.data() : labels;
+        int32_t* len_dst = p.rerun ? c->h_lengths.data() : lengths;
+        if (labels)
+            HIP_TRY(c, hipMemcpyAsync(lab_dst + (size_t)p.first * W, ws.labels, (size_t)p.nb * W * 4, hipMemcpyDeviceToHost,
+                                      c->stream));
+        if (lengths)
+            HIP_TRY(c, hipMemcpyAsync(len_dst + p.first, ws.lengths, (size_t)p.nb * 4, hipMemcpyDeviceToHost, c->stream));
+        return after(pf, p);
+    });
+}
+
+// the re-run lines' labels, up to each length, into the caller's rows (the stream is drained)
+void greedy_scatter(hctr_ctx* c, const std::vector<int>& redo, int W, int32_t* labels, int32_t* lengths) {
+    for (size_t i = 0; i < redo.size() && lengths; ++i) {
+        const int n = c->h_lengths[i];
+        lengths[redo[i]] = n;
+        if (n > 0 && labels) memcpy(labels + (size_t)redo[i] * W, c->h_labels.data() + i * W, (size_t)n * 4);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// edit distance (hctr_edit_distance, hctr_evaluate*)
+// ---------------------------------------------------------------------------------------------
+struct EditOut {             // the caller's host outputs; any may be null
+    int32_t *edits, *counts, *ref_map, *hyp_map;
+    bool maps() const { return counts || ref_map || hyp_map; }
+};
+
+// One call's references, its scratch layout and its device pointers. The scratch, in the context's CTC block:
+// tab | edits[B] | line_of[B] | counts[B][4] | ref_map[sum L] | hyp_map[B][stride] | boff[B] | user | backpointers,
+// counts to boff and the backpointers only with maps; the backpointers hold the `pass_lines` largest lines, which bounds every pass.
+struct EditCall {
+    std::vector<int32_t> tab;             // L[B] | off[B] | ref[sum L], uploaded as one block
+    std::vector<int64_t> line_bytes;      // [B] backpointer bytes of each line at its bound on H (maps only)
+    std::vector<std::vector<int64_t>> boffs;      // per pass: sources of queued copies, kept until the call ends
+    int B = 0, stride = 0, max_len = 0;
+    size_t total = 0;
+    bool maps = false;
+    EditLines m{};
+    int32_t *d_edits = nullptr, *d_counts = nullptr, *d_rmap = nullptr, *d_hmap = nullptr, *d_line_of = nullptr;
+    int64_t* d_boff = nullptr;
+    char* d_user = nullptr;
+    uint8_t* d_bp = nullptr;
+    size_t bp_cap = 0;
+};
+
+// argument checks and the tables. hyp_bound[b] (null: `stride` for every line) bounds the line's hypothesis length
+int edit_prepare(hctr_ctx* c, int B, int stride, const int32_t* ref, const int32_t* ref_lengths, const int32_t* hyp_bound,
+                 bool maps, EditCall* e) {
+    if (!ref_lengths) return fail(c, HCTR_ERR_ARG, "ref_lengths is NULL");
+    const int limit = kEditMaxRows - 1;
+    int64_t total = 0;
+    int max_len = 0;
+    for (int b = 0; b < B; ++b) {
+        const int L = ref_lengths[b];
+        if (L < 0 || L > limit) return fail(c, HCTR_ERR_ARG, "ref_lengths[%d]=%d outside [0,%d]", b, L, limit);
+        total += L;
+        max_len = std::max(max_len, L);
+    }
+    if (total > 0 && !ref) return fail(c, HCTR_ERR_ARG, "ref is NULL");
+    if (total > INT32_MAX) return fail(c, HCTR_ERR_ARG, "too many reference symbols (%lld)", (long long)total);
+    e->B = B; e->stride = stride; e->max_len = max_len; e->total = (size_t)total; e->maps = maps;
+    e->tab.assign(2 * (size_t)B + (size_t)total, 0);
+    int64_t o = 0;
+    for (int b = 0; b < B; ++b) {
+        e->tab[(size_t)b] = ref_lengths[b];
+        e->tab[(size_t)B + b] = (int32_t)o;
+        o += ref_lengths[b];
+    }
+    if (total) memcpy(e->tab.data() + 2 * (size_t)B, ref, (size_t)total * 4);
+    if (maps) {
+        const int ns = edit_lane_rows(max_len);
+        e->line_bytes.assign((size_t)B, 0);
+        for (int b = 0; b < B; ++b) {
+            const int64_t L = ref_lengths[b], H = hyp_bound ? hyp_bound[b] : stride, lanes = (L + ns - 1) / ns;
+            e->line_bytes[(size_t)b] = L > 0 && H > 0 ? (H + lanes - 1) * lanes : 0;
+        }
+    }
+    return HCTR_OK;
+}
+
+// the scratch, with `user_b` bytes at d_user, and the tables' upload
+int edit_scratch(hctr_ctx* c, EditCall* e, int pass_lines, size_t user_b) {
+    const size_t B = (size_t)e->B;
+    const size_t tab_b = align256(e->tab.size() * 4), line_b = align256(B * 4);
+    size_t need = tab_b + 2 * line_b + align256(user_b), bp_b = 0;
+    const size_t cnt_b = align256(B * 16), rmap_b = align256(e->total * 4), hmap_b = align256(B * e->stride * 4),
+                 boff_b = align256(B * 8);
+    if (e->maps) {
+        std::vector<int64_t> big(e->line_bytes);
+        const size_t n = std::min((size_t)std::max(pass_lines, 1), big.size());
+        std::partial_sort(big.begin(), big.begin() + (std::ptrdiff_t)n, big.end(), std::greater<int64_t>());
+        for (size_t i = 0; i < n; ++i) bp_b += (size_t)big[i];
+        need += cnt_b + rmap_b + hmap_b + boff_b + align256(bp_b);
+    }
+    TRY(ctc_reserve(c, need));
+    char* q = c->ctc_buf;
+    auto take = [&](size_t bytes) { char* r = q; q += bytes; return r; };
+    const int32_t* d_tab = (const int32_t*)take(tab_b);
+    e->m = EditLines{d_tab, d_tab + B, d_tab + 2 * B};
+    e->d_edits = (int32_t*)take(line_b);
+    e->d_line_of = (int32_t*)take(line_b);
+    if (e->maps) {
+        e->d_counts = (int32_t*)take(cnt_b);
+        e->d_rmap = (int32_t*)take(rmap_b);
+        e->d_hmap = (int32_t*)take(hmap_b);
+        e->d_boff = (int64_t*)take(boff_b);
+    }
+    e->d_user = take(align256(user_b));
+    e->d_bp = e->maps ? (uint8_t*)q : nullptr;
+    e->bp_cap = bp_b;
+    HIP_TRY(c, hipMemcpyAsync(c->ctc_buf, e->tab.data(), e->tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return HCTR_OK;
+}
+
+// The kernels on the pass's lines lines[0..nb) of the batch, whose hypotheses lie at d_hyp[nb][stride] / d_hlen[nb]:
+// d_line_of (the same numbers on the device) or, for consecutive lines, null.
+int edit_launch(hctr_ctx* c, Prof& pf, EditCall* e, const int* lines, const int32_t* d_line_of, int nb,
+                const int32_t* d_hyp, const int32_t* d_hlen) {
+    const int b0 = lines[0];
+    if (!e->maps) {
+        PROF_TRY(pf, "edit_distance", launch_edit_distance(e->m, b0, d_line_of, nb, d_hyp, d_hlen, e->stride, e->max_len,
+                                                           nullptr, nullptr, e->d_edits, c->stream));
+        return HCTR_OK;
+    }
+    e->boffs.emplace_back((size_t)nb);
+    std::vector<int64_t>& boff = e->boffs.back();
+    int64_t bytes = 0;
+    for (int b = 0; b < nb; ++b) {
+        boff[(size_t)b] = bytes;
+        bytes += e->line_bytes[(size_t)lines[b]];
+    }
+    if ((size_t)bytes > e->bp_cap) return fail(c, HCTR_ERR_STATE, "a pass of %d lines exceeds the backpointer scratch", nb);
+    HIP_TRY(c, hipMemcpyAsync(e->d_boff, boff.data(), (size_t)nb * 8, hipMemcpyHostToDevice, c->stream));
+    PROF_TRY(pf, "edit_distance", launch_edit_distance(e->m, b0, d_line_of, nb, d_hyp, d_hlen, e->stride, e->max_len,
+                                                       e->d_boff, e->d_bp, e->d_edits, c->stream));
+    PROF_TRY(pf, "edit_backtrace", launch_edit_backtrace(e->m, b0, d_line_of, nb, d_hyp, d_hlen, e->stride, e->max_len,
+                                                         e->d_boff, e->d_bp, e->d_counts, e->d_rmap, e->d_hmap,
+                                                         c->stream));
+    return HCTR_OK;
+}
+
+int edit_fetch(hctr_ctx* c, const EditCall& e, const EditOut& o) {
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIP_TRY(c, fetch(o.edits, e.d_edits, (size_t)e.B * 4));
+    HIP_TRY(c, fetch(o.counts, e.d_counts, (size_t)e.B * 16));
+    HIP_TRY(c, fetch(o.ref_map, e.d_rmap, e.total * 4));
+    HIP_TRY(c, fetch(o.hyp_map, e.d_hmap, (size_t)e.B * e.stride * 4));
+    return HCTR_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1700,43 +1878,15 @@ int hctr_greedy(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, 
         if (!labels || !lengths) return fail(c, HCTR_ERR_ARG, "labels/lengths is NULL");
         if (B == 0) return HCTR_OK;
         HIP_TRY(c, hipSetDevice(c->device));
-        const int C = c->num_classes;
         const Batch in{img, img_dtype, img_on_device, widths, B, W};
-        const HeadMode hm = c->fuse_argmax ? HEAD_ARGMAX : HEAD_LOGITS;
         std::vector<int> redo;                     // the lines of the second sweep
-        // a first-sweep pass's lines are consecutive rows of the caller's arrays; the flagged lines of the second sweep
-        // are not, so their labels are staged in the context and scattered, up to each length, once they are on the host
-        int rc = run_passes(c, in, PASS_OWN, [&](const Pass& p) -> int {
-            if (p.rerun && p.first == 0) {
-                redo.assign(p.lines, p.lines + p.total);
-                c->h_labels.resize((size_t)p.total * W);
-                c->h_lengths.resize((size_t)p.total);
-            }
-            TRY(forward_pass(c, in, p, hm));
-            Workspace& ws = c->ws;
-            Prof pf(c);
-            if (!c->fuse_argmax) {
-                PROF_TRY(pf, "argmax_rows",
-                         launch_argmax_rows(ws.logits, c->cpad, (int64_t)p.nb * W, C, ws.colidx, 0, 0, c->stream));
-            }
-            PROF_TRY(pf, "ctc_collapse", launch_ctc_collapse(ws.colidx, p.nb, W, C, ws.labels, ws.lengths, c->stream));
-            int32_t* lab_dst = p.rerun ? c->h_labels.data() : labels;
-            int32_t* len_dst = p.rerun ? c->h_lengths.data() : lengths;
-            HIP_TRY(c, hipMemcpyAsync(lab_dst + (size_t)p.first * W, ws.labels, (size_t)p.nb * W * 4, hipMemcpyDeviceToHost,
-                                      c->stream));
-            HIP_TRY(c, hipMemcpyAsync(len_dst + p.first, ws.lengths, (size_t)p.nb * 4, hipMemcpyDeviceToHost, c->stream));
-            return HCTR_OK;
-        });
+        int rc = greedy_passes(c, in, labels, lengths, &redo, [](Prof&, const Pass&) { return HCTR_OK; });
         // every pass queued async copies into host buffers: also after a failure the stream is drained before
         // returning, so nothing is in flight into (or out of) caller memory. Only a guarded call that flagged nothing
         // comes back drained (run_passes).
         if (rc != HCTR_OK || c->mode != 2 || !redo.empty()) rc = synced(c, rc);
         TRY(rc);
-        for (size_t i = 0; i < redo.size(); ++i) {
-            const int n = c->h_lengths[i];
-            lengths[redo[i]] = n;
-            if (n > 0) memcpy(labels + (size_t)redo[i] * W, c->h_labels.data() + i * W, (size_t)n * 4);
-        }
+        greedy_scatter(c, redo, W, labels, lengths);
         return HCTR_OK;
     });
 }
@@ -2172,6 +2322,105 @@ int hctr_recognize_logits(hctr_ctx* c, const float* logits_wbc, int on_device, i
             const float* dev = nullptr;
             TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
             return rec_pass(c, dev, C, 1, B, C, 0, B, W, rc);      // rows of the WBC tensor are r = t*B + b
+        }());
+    });
+}
+
+int hctr_edit_distance(hctr_ctx* c, const int32_t* hyp, const int32_t* hyp_lengths, int hyp_stride, const int32_t* ref,
+                       const int32_t* ref_lengths, int B, int32_t* edits, int32_t* counts, int32_t* ref_map,
+                       int32_t* hyp_map) {
+    return guard(c, [&]() -> int {
+        if (!c) return HCTR_ERR_ARG;
+        if (B < 0 || hyp_stride < 0) return fail(c, HCTR_ERR_ARG, "bad shape B=%d hyp_stride=%d", B, hyp_stride);
+        if (B == 0) return HCTR_OK;
+        if (!hyp || !hyp_lengths) return fail(c, HCTR_ERR_ARG, "hyp/hyp_lengths is NULL");
+        for (int b = 0; b < B; ++b)
+            if (hyp_lengths[b] < 0 || hyp_lengths[b] > hyp_stride)
+                return fail(c, HCTR_ERR_ARG, "hyp_lengths[%d]=%d outside [0,%d]", b, hyp_lengths[b], hyp_stride);
+        const EditOut out{edits, counts, ref_map, hyp_map};
+        EditCall e;
+        TRY(edit_prepare(c, B, hyp_stride, ref, ref_lengths, hyp_lengths, out.maps(), &e));
+        HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
+        return synced(c, [&]() -> int {
+            const size_t hyp_b = align256((size_t)B * hyp_stride * 4);
+            TRY(edit_scratch(c, &e, B, hyp_b + (size_t)B * 4));
+            int32_t *d_hyp = (int32_t*)e.d_user, *d_hlen = (int32_t*)(e.d_user + hyp_b);
+            if (hyp_stride)
+                HIP_TRY(c, hipMemcpyAsync(d_hyp, hyp, (size_t)B * hyp_stride * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d_hlen, hyp_lengths, (size_t)B * 4, hipMemcpyHostToDevice, c->stream));
+            const std::vector<int> lines = line_indices(B);
+            Prof pf(c);
+            TRY(edit_launch(c, pf, &e, lines.data(), nullptr, B, d_hyp, d_hlen));
+            return edit_fetch(c, e, out);
+        }());
+    });
+}
+
+int hctr_evaluate(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
+                  const int32_t* targets, const int32_t* target_lengths, int32_t* labels, int32_t* lengths, int32_t* edits,
+                  int32_t* counts, int32_t* ref_map, int32_t* hyp_map) {
+    return guard(c, [&]() -> int {
+        TRY(check_forward_args(c, img, img_dtype, B, W));
+        if (B == 0) return HCTR_OK;
+        if (labels && !lengths) return fail(c, HCTR_ERR_ARG, "labels without lengths");
+        const EditOut out{edits, counts, ref_map, hyp_map};
+        EditCall e;
+        TRY(edit_prepare(c, B, W, targets, target_lengths, nullptr, out.maps(), &e));
+        HIP_TRY(c, hipSetDevice(c->device));
+        const Batch in{img, img_dtype, img_on_device, widths, B, W};
+        std::vector<int> redo;
+        bool reserved = false;
+        // the edit kernels of a pass read the decoded labels where the collapse left them; a re-run pass names its lines
+        // through line_of, and its results replace the first sweep's in the device arrays, which come back once
+        int rc = greedy_passes(c, in, labels, lengths, &redo, [&](Prof& pf, const Pass& p) -> int {
+            if (!reserved) {
+                TRY(edit_scratch(c, &e, sub_batch(c, B, W, c->mode == 1), 0));
+                reserved = true;
+            }
+            if (p.rerun && p.first == 0)
+                HIP_TRY(c, hipMemcpyAsync(e.d_line_of, p.lines, (size_t)p.total * 4, hipMemcpyHostToDevice, c->stream));
+            return edit_launch(c, pf, &e, p.lines, p.rerun ? e.d_line_of + p.first : nullptr, p.nb, c->ws.labels,
+                               c->ws.lengths);
+        });
+        if (rc == HCTR_OK) rc = edit_fetch(c, e, out);
+        TRY(synced(c, rc));
+        greedy_scatter(c, redo, W, labels, lengths);
+        return HCTR_OK;
+    });
+}
+
+int hctr_evaluate_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W, int B, int C, const int32_t* targets,
+                         const int32_t* target_lengths, int32_t* labels, int32_t* lengths, int32_t* edits, int32_t* counts,
+                         int32_t* ref_map, int32_t* hyp_map) {
+    return guard(c, [&]() -> int {
+        TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
+        if (B == 0) return HCTR_OK;
+        const EditOut out{edits, counts, ref_map, hyp_map};
+        EditCall e;
+        TRY(edit_prepare(c, B, W, targets, target_lengths, nullptr, out.maps(), &e));
+        for (size_t j = 0; j < e.total; ++j)              // hctr_ctc_loss_logits' check of the ids
+            if (targets[j] < 1 || targets[j] > C - 1)
+                return fail(c, HCTR_ERR_ARG, "target id %d (position %zu) outside [1,%d]", targets[j], j, C - 1);
+        HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
+        std::vector<void*> tmp;
+        PoolGuard tmp_guard{tmp};
+        return synced(c, [&]() -> int {
+            const float* dev = nullptr;
+            const size_t col_b = align256((size_t)W * B * 4);
+            TRY(edit_scratch(c, &e, B, 2 * col_b + (size_t)B * 4));
+            int32_t *idx = (int32_t*)e.d_user, *dl = (int32_t*)(e.d_user + col_b), *dn = (int32_t*)(e.d_user + 2 * col_b);
+            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
+            Prof pf(c);
+            // rows of the WBC tensor are r = t*B + b; the argmax kernel writes idx as [b][t]
+            PROF_TRY(pf, "argmax_rows", launch_argmax_rows(dev, C, (int64_t)W * B, C, idx, B, W, c->stream));
+            PROF_TRY(pf, "ctc_collapse", launch_ctc_collapse(idx, B, W, C, dl, dn, c->stream));
+            if (labels) HIP_TRY(c, hipMemcpyAsync(labels, dl, (size_t)W * B * 4, hipMemcpyDeviceToHost, c->stream));
+            if (lengths) HIP_TRY(c, hipMemcpyAsync(lengths, dn, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+            const std::vector<int> lines = line_indices(B);
+            TRY(edit_launch(c, pf, &e, lines.data(), nullptr, B, dl, dn));
+            return edit_fetch(c, e, out);
         }());
     });
 }

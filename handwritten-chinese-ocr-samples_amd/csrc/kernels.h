@@ -258,6 +258,31 @@ hipError_t launch_greedy_spans(const int32_t* k1, const int32_t* k2, const float
 hipError_t launch_ctc_emis_gather(const float* x, int64_t ld, int64_t sb, int64_t st, const CtcLines& m, int b0, int nb,
                                   int W, const double* lse, float* emis, hipStream_t s);
 
+// ---- edit distance (hctr_edit_distance, hctr_evaluate*): the references on the device, indexed by the line's place gb
+// in the caller's batch; the hypotheses hyp[b][stride] / hlen[b], the backpointer offsets boff[b] and the launch's lines
+// are the pass's own, b = 0..nb-1, line gb = line_of ? line_of[b] : b0 + b ----
+// kernels.hip's instance ladder of the sweep: the reference rows of its last rung, and the rows per lane of the rung
+// max_len launches
+extern const int kEditMaxRows;
+int edit_lane_rows(int max_len);
+struct EditLines {
+    const int32_t* L;       // [B] reference length
+    const int32_t* off;     // [B] offset of the line's reference in ref
+    const int32_t* ref;     // [sum L] reference symbols, any int32 values
+};
+// launch_edit_distance: edits[gb] = D[L][H]; max_len = the longest reference of the launch's lines. bp (else null: the
+//   distance-only instance, same arithmetic) keeps the 2-bit backpointers (0 diagonal, 1 deletion, 2 insertion; row i of
+//   a lane at bits 2i) of step d = j - 1 + k of lane k = (row - 1) / NS at bp[boff[b] + d * lanes + k], lanes =
+//   ceil(L / NS), NS = edit_lane_rows(max_len): (H + lanes - 1) * lanes bytes for the line;
+// launch_edit_backtrace: counts[gb][4] = {hits, substitutions, deletions, insertions}, ref_map[off[gb] + i] = position
+//   in the hypothesis (-1 deleted), hyp_map[gb * stride + j] = position in the reference (-1 inserted, 0 for j >= H).
+hipError_t launch_edit_distance(const EditLines& m, int b0, const int32_t* line_of, int nb, const int32_t* hyp,
+                                const int32_t* hlen, int stride, int max_len, const int64_t* boff, uint8_t* bp,
+                                int32_t* edits, hipStream_t s);
+hipError_t launch_edit_backtrace(const EditLines& m, int b0, const int32_t* line_of, int nb, const int32_t* hyp,
+                                 const int32_t* hlen, int stride, int max_len, const int64_t* boff, const uint8_t* bp,
+                                 int32_t* counts, int32_t* ref_map, int32_t* hyp_map, hipStream_t s);
+
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {
     int64_t src_off;          // byte offset of the image inside the packed source buffer

@@ -3852,4 +3852,226 @@ hipError_t launch_ctc_emis_gather(const float* x, int64_t ld, int64_t sb, int64_
     return hipGetLastError();
 }
 
+// -------------------------------------------------------------------------------------------
+// Edit distance (hctr_edit_distance, hctr_evaluate*): the Levenshtein recursion of a hypothesis h_1..h_H against a
+// reference r_1..r_L, D[i][j] = min(D[i-1][j-1] + (r_i != h_j), D[i-1][j] + 1, D[i][j-1] + 1), all int32 and exact.
+// edit_distance_kernel sweeps it lane-skewed and, with STORE, keeps 2-bit backpointers; edit_backtrace_kernel walks
+// them back from (L, H) and writes the counts and the two maps.
+// -------------------------------------------------------------------------------------------
+
+// The instances (NS reference rows per lane, NW wave64s per line); a batch launches the first whose 64 * NS * NW rows
+// hold its longest reference. As in HCTR_CTC_LADDER a long reference spreads over more waves before it takes more rows
+// per lane; the last rung takes four rows, because every lane in use is one more step of the skewed sweep.
+#define HCTR_EDIT_LADDER(X) X(1, 1) X(2, 1) X(2, 2) X(2, 4) X(2, 8) X(4, 8)
+constexpr int kEditPF = 4;                         // hypothesis symbols in flight per lane
+
+// The sweep: thread k owns the rows k*NS + 1 .. k*NS + NS and keeps their D[row][j-1] in registers. At step d it works
+// on column j = d - k + 1 (when 1 <= j <= H). D[k*NS][j], the row above its first, is what thread k-1 finished at step
+// d-1: it arrives over __shfl_up, across a wave boundary through xb[step parity][wave] with one barrier per step (none
+// for a one-wave line); the value that arrived a step earlier is D[k*NS][j-1]. Thread 0 takes j and j-1. A thread
+// outside its columns keeps its registers, so after the H + lanes - 1 steps every row holds D[row][H]. Rows beyond L
+// compute figures nobody reads: a row depends on the rows above it only.
+// STORE: the backpointer of a cell by the contract's tie order (0 diagonal, 1 deletion, 2 insertion), the NS cells of
+// a thread in one byte (row i at bits 2i), at bp[boff[b] + d * lanes + k], lanes = ceil(L / NS): the bytes one step
+// stores are consecutive, although its threads work on different columns.
+template <int NS, int NW, bool STORE>
+__global__ __launch_bounds__(64 * NW) void edit_distance_kernel(const EditLines m, int b0,
+                                                                 const int32_t* __restrict__ line_of,
+                                                                 const int32_t* __restrict__ hyp,
+                                                                 const int32_t* __restrict__ hlen, int stride,
+                                                                 const int64_t* __restrict__ boff,
+                                                                 uint8_t* __restrict__ bp, int32_t* __restrict__ edits) {
+    static_assert(NS <= 4, "one byte holds the backpointers of a lane");
+    __shared__ int xb[2][NW];
+    const int b = blockIdx.x, gb = line_of ? line_of[b] : b0 + b, tid = threadIdx.x;
+    const int L = m.L[gb], H = hlen[b];
+    const int32_t* __restrict__ r = m.ref + m.off[gb];
+    const int32_t* __restrict__ h = hyp + (int64_t)b * stride;
+    const int lanes = (L + NS - 1) / NS;
+    int left[NS], rs[NS];
+#pragma unroll
+    for (int i = 0; i < NS; ++i) {
+        const int row = tid * NS + i + 1;
+        left[i] = row;                             // D[row][0]
+        rs[i] = row <= L ? r[row - 1] : 0;
+    }
+    int diag0 = tid * NS;                          // D[k*NS][j-1] of the thread's next column
+    const int nsteps = (L > 0 && H > 0) ? H + lanes - 1 : 0;     // (block-uniform)
+    uint8_t* brow = nullptr;
+    if (STORE) brow = bp + boff[b] + tid;
+    if (NW > 1) {
+        if ((tid & 63) == 63) xb[1][tid >> 6] = left[NS - 1];      // "step -1"; never read by a thread in its columns
+        __syncthreads();
+    }
+    int e[kEditPF];
+#pragma unroll
+    for (int k = 0; k < kEditPF; ++k) e[k] = nsteps ? h[min(max(k - tid, 0), H - 1)] : 0;
+    for (int d0 = 0; d0 < nsteps; d0 += kEditPF) {
+#pragma unroll
+        for (int k = 0; k < kEditPF; ++k) {
+            const int d = d0 + k;
+            if (d < nsteps) {                      // (block-uniform)
+                const int j = d - tid + 1;
+                int top = __shfl_up(left[NS - 1], 1);
+                if (NW > 1 && (tid & 63) == 0 && tid > 0) top = xb[(d - 1) & 1][(tid >> 6) - 1];
+                if (tid == 0) top = j;
+                if (j >= 1 && j <= H) {
+                    const int hs = e[k];
+                    int up = top, dg = diag0;
+                    unsigned code = 0;
+#pragma unroll
+                    for (int i = 0; i < NS; ++i) {
+                        const int sub = dg + (rs[i] != hs ? 1 : 0), del = up + 1, ins = left[i] + 1;
+                        const int v = min(sub, min(del, ins));
+                        if (STORE) code |= (v == sub ? 0u : v == del ? 1u : 2u) << (2 * i);
+                        dg = left[i];
+                        left[i] = v;
+                        up = v;
+                    }
+                    diag0 = top;
+                    if (STORE && tid < lanes) brow[(int64_t)d * lanes] = (uint8_t)code;
+                }
+                if (NW > 1) {
+                    if ((tid & 63) == 63) xb[d & 1][tid >> 6] = left[NS - 1];
+                    __syncthreads();
+                }
+            }
+            if (nsteps) e[k] = h[min(max(d + kEditPF - tid, 0), H - 1)];      // refill the slot just used
+        }
+    }
+    if (L == 0) {
+        if (tid == 0) edits[gb] = H;
+    } else if (tid == (L - 1) / NS) {
+#pragma unroll
+        for (int i = 0; i < NS; ++i)
+            if (i == (L - 1) % NS) edits[gb] = left[i];
+    }
+}
+
+// One 256-thread workgroup per line, as ctc_backtrace_kernel: the walk from (L, H) is serial, so the backpointers are
+// staged in LDS a (kEditWin + 1)^2 window of cells at a time - a step lowers i, j or both by one, so the walk stays in
+// the window [i0 - kEditWin, i0] x [j0 - kEditWin, j0] for more than kEditWin steps. All threads load the window
+// (independent byte loads), then every thread walks it on LDS broadcasts with the same scalar state and thread 0
+// stores the maps. On the border j = 0 what is left of the reference is deleted, on i = 0 what is left of the
+// hypothesis inserted. Deletions and insertions are counted in the walk; the substitutions afterwards in parallel from
+// hyp_map (int32 sums, so the order does not matter), and hits = L - S - D. hyp_map past H is zeroed.
+// sh = log2 of the sweep instance's rows per lane.
+constexpr int kEditWin = 32;
+__global__ __launch_bounds__(256) void edit_backtrace_kernel(const EditLines m, int b0, const int32_t* __restrict__ line_of,
+                                                             const int32_t* __restrict__ hyp,
+                                                             const int32_t* __restrict__ hlen, int stride, int sh,
+                                                             const int64_t* __restrict__ boff,
+                                                             const uint8_t* __restrict__ bp, int32_t* __restrict__ counts,
+                                                             int32_t* ref_map, int32_t* hyp_map) {
+    constexpr int WC = kEditWin + 1;
+    __shared__ uint8_t win[WC][WC + 3];            // [column][lane byte]; at most WC lanes at one row per lane
+    __shared__ int s_sub[4];
+    const int b = blockIdx.x, gb = line_of ? line_of[b] : b0 + b, tid = threadIdx.x;
+    const int L = m.L[gb], H = hlen[b];
+    const int32_t* __restrict__ r = m.ref + m.off[gb];
+    const int32_t* __restrict__ h = hyp + (int64_t)b * stride;
+    int32_t* rm = ref_map + m.off[gb];
+    int32_t* hm = hyp_map + (int64_t)gb * stride;
+    const int lanes = (L + (1 << sh) - 1) >> sh, smask = (1 << sh) - 1;
+    const uint8_t* rows = bp + boff[b];
+    int i = L, j = H, ndel = 0, nins = 0;
+    while (i > 0 && j > 0) {                       // (block-uniform)
+        const int ilo = max(i - kEditWin, 1), jlo = max(j - kEditWin, 1);
+        const int klo = (ilo - 1) >> sh, kn = ((i - 1) >> sh) - klo + 1, jn = j - jlo + 1;
+        for (int idx = tid; idx < jn * kn; idx += 256) {
+            const int jj = jlo + idx / kn, k = klo + idx % kn;
+            win[jj - jlo][k - klo] = rows[(int64_t)(jj - 1 + k) * lanes + k];
+        }
+        __syncthreads();
+        while (i >= ilo && j >= jlo) {
+            const int k = (i - 1) >> sh;
+            const int from = (win[j - jlo][k - klo] >> (2 * ((i - 1) & smask))) & 3;
+            if (tid == 0) {
+                if (from != 2) rm[i - 1] = from == 0 ? j - 1 : -1;
+                if (from != 1) hm[j - 1] = from == 0 ? i - 1 : -1;
+            }
+            ndel += from == 1;
+            nins += from == 2;
+            i = __builtin_amdgcn_readfirstlane(i - (from != 2));
+            j = __builtin_amdgcn_readfirstlane(j - (from != 1));
+        }
+        __syncthreads();                           // the window is loaded again
+    }
+    ndel += i;
+    nins += j;
+    for (int t = tid; t < i; t += 256) rm[t] = -1;
+    for (int t = tid; t < j; t += 256) hm[t] = -1;
+    for (int t = H + tid; t < stride; t += 256) hm[t] = 0;
+    __syncthreads();                               // thread 0's hyp_map, read below
+    int nsub = 0;
+    for (int t = tid; t < H; t += 256) {
+        const int at = hm[t];
+        if (at >= 0 && r[at] != h[t]) ++nsub;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) nsub += __shfl_xor(nsub, off);
+    if ((tid & 63) == 0) s_sub[tid >> 6] = nsub;
+    __syncthreads();
+    if (tid == 0) {
+        nsub = s_sub[0] + s_sub[1] + s_sub[2] + s_sub[3];
+        int32_t* c = counts + (int64_t)gb * 4;
+        c[0] = L - nsub - ndel;
+        c[1] = nsub;
+        c[2] = ndel;
+        c[3] = nins;
+    }
+}
+
+template <int NS_, int NW_>
+struct EditRung {
+    static constexpr int NS = NS_, NW = NW_;
+};
+// visit(EditRung<NS, NW>) of the rung that a longest reference of max_len launches; false beyond the ladder
+template <class F>
+bool edit_rung(int max_len, F visit) {
+#define EDIT_RUNG(NS, NW)              \
+    if (max_len <= 64 * NS * NW) {     \
+        visit(EditRung<NS, NW>{});     \
+        return true;                   \
+    }
+    HCTR_EDIT_LADDER(EDIT_RUNG)
+#undef EDIT_RUNG
+    return false;
+}
+int edit_lane_rows(int max_len) {
+    int ns = 0;
+    edit_rung(max_len, [&](auto r) { ns = decltype(r)::NS; });
+    return ns;
+}
+#define EDIT_RUNG_ROWS(NS, NW) , 64 * NS * NW
+const int kEditMaxRows = std::max({0 HCTR_EDIT_LADDER(EDIT_RUNG_ROWS)});
+#undef EDIT_RUNG_ROWS
+
+hipError_t launch_edit_distance(const EditLines& m, int b0, const int32_t* line_of, int nb, const int32_t* hyp,
+                                const int32_t* hlen, int stride, int max_len, const int64_t* boff, uint8_t* bp,
+                                int32_t* edits, hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+    const bool ok = edit_rung(max_len, [&](auto r) {
+        using R = decltype(r);
+        if (bp)
+            hipLaunchKernelGGL((edit_distance_kernel<R::NS, R::NW, true>), dim3((unsigned)nb), dim3(64 * R::NW), 0, s, m, b0,
+                               line_of, hyp, hlen, stride, boff, bp, edits);
+        else
+            hipLaunchKernelGGL((edit_distance_kernel<R::NS, R::NW, false>), dim3((unsigned)nb), dim3(64 * R::NW), 0, s, m,
+                               b0, line_of, hyp, hlen, stride, nullptr, nullptr, edits);
+    });
+    return ok ? hipGetLastError() : hipErrorInvalidValue;
+}
+
+hipError_t launch_edit_backtrace(const EditLines& m, int b0, const int32_t* line_of, int nb, const int32_t* hyp,
+                                 const int32_t* hlen, int stride, int max_len, const int64_t* boff, const uint8_t* bp,
+                                 int32_t* counts, int32_t* ref_map, int32_t* hyp_map, hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+    const int ns = edit_lane_rows(max_len);
+    if (!ns) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(edit_backtrace_kernel, dim3((unsigned)nb), dim3(256), 0, s, m, b0, line_of, hyp, hlen, stride,
+                       ns == 1 ? 0 : ns == 2 ? 1 : 2, boff, bp, counts, ref_map, hyp_map);
+    return hipGetLastError();
+}
+
 }  // namespace hctr

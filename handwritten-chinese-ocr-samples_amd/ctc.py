@@ -305,6 +305,170 @@ def recognize_images(ctx, x, dt, on_dev, widths, B, W):
     return Recognition(*out)
 
 
+class Evaluation(object):
+    """Result of scoring B decoded lines against their transcriptions (numpy arrays, on the host; include/hctr_hip.h
+    ``hctr_edit_distance``): ``edits`` int32 [B], the Levenshtein distance of each line; ``counts`` int32 [B, 4] =
+    (hits, substitutions, deletions, insertions); ``ref_map`` int32 [sum L], per reference character the position in
+    the line's hypothesis it is aligned with (-1: deleted); ``hyp_map`` int32 [B, stride], per decoded character the
+    position in the line's reference (-1: inserted; zeros past a line's length); ``labels`` int32 [B, stride] /
+    ``lengths`` int32 [B], the hypotheses; ``targets`` int32 [sum L] / ``target_lengths`` int32 [B], the references;
+    ``offsets`` int64 [B + 1], where each line's reference begins. ``counts``, ``ref_map`` and ``hyp_map`` are None
+    after a distance-only call (``maps=False``); ``labels`` may be None when only the distances were asked for."""
+
+    def __init__(self, edits, counts, ref_map, hyp_map, labels, lengths, targets, target_lengths):
+        self.edits, self.counts, self.ref_map, self.hyp_map = edits, counts, ref_map, hyp_map
+        self.labels, self.lengths = labels, lengths
+        self.targets = targets
+        self.target_lengths = np.asarray(target_lengths, np.int32)
+        self.offsets = np.concatenate([[0], np.cumsum(self.target_lengths.astype(np.int64))]).astype(np.int64)
+
+    def __len__(self):
+        return len(self.edits)
+
+    def _need_counts(self):
+        if self.counts is None:
+            raise ValueError("a distance-only Evaluation (maps=False) has no counts or maps")
+
+    @property
+    def total_edits(self):
+        return int(np.asarray(self.edits, np.int64).sum())
+
+    @property
+    def total_chars(self):
+        return int(self.offsets[-1])
+
+    @property
+    def totals(self):
+        """(hits, substitutions, deletions, insertions) over all lines"""
+        self._need_counts()
+        return tuple(int(v) for v in np.asarray(self.counts, np.int64).reshape(-1, 4).sum(axis=0))
+
+    @property
+    def cer(self):
+        """sum(edits) / sum(L): the reference's CER (test.py:285); NaN without a reference character"""
+        n = self.total_chars
+        return self.total_edits / n if n else float("nan")
+
+    @property
+    def cr(self):
+        """correct rate (N - D - S) / N"""
+        _, s, d, _ = self.totals
+        n = self.total_chars
+        return (n - d - s) / n if n else float("nan")
+
+    @property
+    def ar(self):
+        """accurate rate (N - D - S - I) / N = 1 - cer"""
+        _, s, d, i = self.totals
+        n = self.total_chars
+        return (n - d - s - i) / n if n else float("nan")
+
+    def lines(self):
+        """yields per line the list of (ref_symbol, hyp_symbol, ref_pos, hyp_pos) along the alignment, in reading order:
+        a hit or a substitution has both, a deletion (ref_symbol, None, i, -1), an insertion (None, hyp_symbol, -1, j).
+        Between two aligned pairs the insertions come first, then the deletions."""
+        self._need_counts()
+        for b in range(len(self)):
+            o, L, H = int(self.offsets[b]), int(self.target_lengths[b]), int(self.lengths[b])
+            out, i = [], 0
+            for j in range(H):
+                at = int(self.hyp_map[b, j])
+                if at < 0:
+                    out.append((None, int(self.labels[b, j]), -1, j))
+                    continue
+                for k in range(i, at):
+                    out.append((int(self.targets[o + k]), None, k, -1))
+                out.append((int(self.targets[o + at]), int(self.labels[b, j]), at, j))
+                i = at + 1
+            for k in range(i, L):
+                out.append((int(self.targets[o + k]), None, k, -1))
+            yield out
+
+    def confusions(self):
+        """{(ref_symbol, hyp_symbol): count} of the substitutions, built on the host from the maps"""
+        self._need_counts()
+        out = {}
+        for b in range(len(self)):
+            o, L = int(self.offsets[b]), int(self.target_lengths[b])
+            rm = np.asarray(self.ref_map[o:o + L])
+            pos = np.flatnonzero(rm >= 0)
+            r, h = np.asarray(self.targets[o:o + L])[pos], np.asarray(self.labels[b])[rm[pos]]
+            for x, y in zip(r[r != h].tolist(), h[r != h].tolist()):
+                out[(x, y)] = out.get((x, y), 0) + 1
+        return out
+
+
+def _edit_outputs(B, stride, total, maps):
+    """edits, counts, ref_map, hyp_map in the order of the C ABI's arguments (None: the distance-only call)"""
+    if not maps:
+        return np.zeros((B,), np.int32), None, None, None
+    return (np.zeros((B,), np.int32), np.zeros((B, 4), np.int32), np.zeros((total,), np.int32),
+            np.zeros((B, stride), np.int32))
+
+
+def edit_distance_labels(ctx, labels, lengths, targets, target_lengths, maps=True):
+    """Evaluation of hypotheses ``labels`` int32 [B, stride] / ``lengths`` [B] against concatenated ``targets`` /
+    ``target_lengths`` [B] (hctr_edit_distance); the symbols are arbitrary int32 values."""
+    labels = np.ascontiguousarray(labels, dtype=np.int32)
+    lengths = np.ascontiguousarray(lengths, dtype=np.int32).reshape(-1)
+    B = int(lengths.size)
+    if labels.ndim != 2 or labels.shape[0] != B:
+        raise ValueError("labels must be [B, stride] with one row per length")
+    tg, tl = normalize_targets(targets, target_lengths, B)
+    out = _edit_outputs(B, int(labels.shape[1]), int(tg.size), maps)
+    if B:
+        _lib.check(_lib.load().hctr_edit_distance(ctx, _lib.ptr(labels), _lib.ptr(lengths), int(labels.shape[1]),
+                                                  _lib.ptr(tg), _lib.ptr(tl), B, *[_lib.ptr(a) for a in out]), ctx)
+    return Evaluation(*out, labels, lengths, tg, tl)
+
+
+def pad_sequences(seqs):
+    """(int32 [B, stride], int32 [B]) from a list of strings (their code points) or of int sequences"""
+    rows = [np.fromiter((ord(ch) for ch in s), np.int64, len(s)) if isinstance(s, str)
+            else np.asarray(s, dtype=np.int64).reshape(-1) for s in seqs]
+    n = np.array([r.size for r in rows], np.int32)
+    out = np.zeros((len(rows), max(1, int(n.max()) if len(rows) else 1)), np.int32)
+    for b, r in enumerate(rows):
+        out[b, :r.size] = r
+    return out, n
+
+
+def edit_distance_sequences(ctx, hyps, refs, maps=True):
+    """Evaluation of two equally long lists of strings or int sequences, line by line (hctr_edit_distance). Strings
+    are compared by code point, which is ``editdistance.eval`` on the strings, exactly."""
+    if len(hyps) != len(refs):
+        raise ValueError("%d hypotheses but %d references" % (len(hyps), len(refs)))
+    lab, n = pad_sequences(hyps)
+    ref, tl = pad_sequences(refs)
+    tg = np.concatenate([ref[b, :tl[b]] for b in range(len(refs))] + [np.zeros((0,), np.int32)]).astype(np.int32)
+    return edit_distance_labels(ctx, lab, n, tg, tl, maps)
+
+
+def evaluate_logits(ctx, logits, on_dev, targets, target_lengths, maps=True):
+    """Evaluation of the greedy decode of caller logits / log-probs in WBC layout (hctr_evaluate_logits)."""
+    W, B, C = (int(v) for v in logits.shape)
+    tg, tl = normalize_targets(targets, target_lengths, B)
+    labels, lengths = np.zeros((B, W), np.int32), np.zeros((B,), np.int32)
+    out = _edit_outputs(B, W, int(tg.size), maps)
+    if B:
+        _lib.check(_lib.load().hctr_evaluate_logits(ctx, _lib.ptr(logits), on_dev, W, B, C, _lib.ptr(tg), _lib.ptr(tl),
+                                                    _lib.ptr(labels), _lib.ptr(lengths), *[_lib.ptr(a) for a in out]),
+                   ctx)
+    return Evaluation(*out, labels, lengths, tg, tl)
+
+
+def evaluate_images(ctx, x, dt, on_dev, widths, B, W, targets, target_lengths, maps=True):
+    """Evaluation of line images (hctr_evaluate); x, dt, on_dev, widths as hctr_model._img_args / _widths give them."""
+    tg, tl = normalize_targets(targets, target_lengths, B)
+    labels, lengths = np.zeros((B, W), np.int32), np.zeros((B,), np.int32)
+    out = _edit_outputs(B, W, int(tg.size), maps)
+    if B:
+        _lib.check(_lib.load().hctr_evaluate(ctx, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, _lib.ptr(tg),
+                                             _lib.ptr(tl), _lib.ptr(labels), _lib.ptr(lengths),
+                                             *[_lib.ptr(a) for a in out]), ctx)
+    return Evaluation(*out, labels, lengths, tg, tl)
+
+
 _FN = None
 
 

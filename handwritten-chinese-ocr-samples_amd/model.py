@@ -283,6 +283,20 @@ class hctr_model(object):
         x, dt, on_dev, B, W = self._img_args(input)
         return ctc.recognize_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W)
 
+    def evaluate(self, input, targets, target_lengths, widths=None, maps=True):
+        """Forward + greedy decode + edit distance against the transcriptions, the decoded labels never leaving the
+        device between decode and scoring: the reference's ``editdistance.eval(pre, tru)`` per line (test.py:275) in
+        label space. Decodes exactly as ``greedy`` does, in every precision mode. ``targets`` / ``target_lengths`` as
+        ``ctc_loss`` takes them. Returns a ``ctc.Evaluation``: ``edits``, ``cer``, and with ``maps=True`` the counts of
+        hits / substitutions / deletions / insertions, ``cr`` / ``ar``, the character alignment (``ref_map``,
+        ``hyp_map``) and ``confusions()``; ``maps=False`` takes the distance-only path. Label-space and string-space
+        distances coincide when the codec's ``chars_list`` has no duplicate entries and no truth character is outside
+        it (include/hctr_hip.h ``hctr_evaluate``)."""
+        from . import ctc
+        ctx = self._require_ctx()
+        x, dt, on_dev, B, W = self._img_args(input)
+        return ctc.evaluate_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, targets, target_lengths, maps)
+
     # -- precision mode ---------------------------------------------------------------------------
     def set_precision(self, precision):
         """Switch the mode of a loaded model among those whose weight set is resident (all three for a model built

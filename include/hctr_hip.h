@@ -283,6 +283,63 @@ int hctr_recognize_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device,
                           int32_t* labels, int32_t* lengths, int32_t* span_start, int32_t* span_end, float* char_logp,
                           int32_t* alt_label, float* alt_logp, float* path_logp, float* text_nll);
 
+/* ---- evaluation: edit distance of a decoded text against its transcription, on the device -----
+ * The reference's figure of merit, editdistance.eval(pre, tru) per line and CER = total edits / total characters
+ * (test.py:266-285, main.py:506), with the breakdown its paper reports: substitutions, deletions, insertions and which
+ * reference character went with which decoded character. Everything is int32 and exact.
+ * For a reference r_1..r_L and a hypothesis h_1..h_H (int32 symbols of any value, compared with ==):
+ *   D[i][0] = i, D[0][j] = j, D[i][j] = min(D[i-1][j-1] + (r_i != h_j), D[i-1][j] + 1, D[i][j-1] + 1);  edits = D[L][H].
+ * The path is walked back from (L, H), ties decided in this order (part of the contract): the diagonal if i > 0, j > 0
+ * and D[i][j] == D[i-1][j-1] + (r_i != h_j) - a hit when the symbols are equal, else a substitution; else a deletion
+ * (r_i has no counterpart) if i > 0 and D[i][j] == D[i-1][j] + 1; else an insertion (h_j is spurious).
+ * hctr_edit_distance: hyp is [B][hyp_stride] with the first hyp_lengths[b] entries of a line valid (the layout
+ * hctr_greedy returns, hyp_stride = W); ref holds the lines' symbols back to back, ref_lengths[b] each (what
+ * codec.encode returns). All pointers are host pointers. Outputs, any may be NULL:
+ *   edits:   int32 [B];
+ *   counts:  int32 [B][4] = {hits, substitutions, deletions, insertions}; hits + S + D = L, hits + S + I = H,
+ *            S + D + I = edits;
+ *   ref_map: int32 [sum L], in the order of ref: the 0-based position in the line's hypothesis the reference character
+ *            is aligned with (hit or substitution), -1 for a deletion;
+ *   hyp_map: int32 [B][hyp_stride]: the 0-based position in the line's reference, -1 for an insertion; entries beyond
+ *            hyp_lengths[b] are written as zeros.
+ * With counts, ref_map and hyp_map all NULL the distance-only instance runs and no backpointer scratch is taken; edits
+ * is the same either way. Limits: every ref_lengths[b] in [0, 2047] (the family's limit), hyp_lengths[b] in
+ * [0, hyp_stride]; anything else, a NULL hyp, hyp_lengths or ref_lengths (or ref where sum L > 0) with B > 0, is
+ * HCTR_ERR_ARG with a message naming the line. B == 0 is a no-op. Needs no weights (a context made for ctc_codec
+ * serves) and knows nothing of classes.
+ * hctr_evaluate takes img .. W as hctr_greedy does and decodes exactly as hctr_greedy decodes - the mode's own
+ * arithmetic, in mode 2 the guard sweep and the f16x3 re-run of the flagged lines; labels / lengths (either may be
+ * NULL, labels only together with lengths) are identical to hctr_greedy's in all three modes and hctr_last_guard
+ * advances as it does there. targets / target_lengths are the references (ids are not checked against the classes
+ * here: they are compared, never used as an index). They are uploaded once; inside each pass, after ctc_collapse, the
+ * edit kernels run on the pass's decoded labels where they lie on the device, and the results of re-run lines replace
+ * the first sweep's. The maps' hyp_stride is W.
+ * hctr_evaluate_logits is hctr_decode_greedy_logits on caller logits (WBC, host or device pointer) plus the same
+ * stage; it needs no weights, and its targets follow hctr_ctc_loss_logits' check: ids in [1, C-1].
+ * No atomics: repeated calls agree bit for bit. HCTR_ERR_NOMEM leaves the context usable.
+ * Launches (hctr_last_profile): edit_distance (one workgroup per line: the lane-skewed sweep, lane k on reference rows
+ * k*NS+1 .. k*NS+NS and, at step d, on hypothesis column d - k + 1, H + ceil(L/NS) - 1 steps; instances NS x waves of
+ * 1x1, 2x1, 2x2, 2x4, 2x8, 4x8, the first whose 64*NS*waves rows hold the longest reference of the call) and, unless
+ * distance-only, edit_backtrace (one 256-thread workgroup per line); hctr_evaluate* after their decode's launches.
+ * Device scratch (the context's grow-only CTC scratch; n = B, for hctr_evaluate the lines of one pass):
+ *   8 * B + 4 * sum L (references) + 8 * B (edits, re-run line numbers), and unless distance-only 16 * B + 4 * sum L +
+ *   4 * B * hyp_stride + 8 * B (counts, maps, backpointer offsets) plus the backpointers of the n lines that need most:
+ *   per line (H + lanes - 1) * lanes bytes with lanes = ceil(L / NS) - about L*H/NS, L*H/4 at the last instance - where
+ *   H is hyp_lengths[b], for hctr_evaluate* W (the decoded length is known on the device only); hctr_edit_distance adds
+ *   4 * B * hyp_stride + 4 * B for the hypotheses, hctr_evaluate_logits 8 * W*B + 4 * B for its decode (and W*B*C floats
+ *   for logits passed as a host pointer). Each array is rounded up to 256 bytes. */
+int hctr_edit_distance(hctr_ctx* ctx, const int32_t* hyp, const int32_t* hyp_lengths, int hyp_stride,
+                       const int32_t* ref, const int32_t* ref_lengths, int B,
+                       int32_t* edits, int32_t* counts, int32_t* ref_map, int32_t* hyp_map);
+int hctr_evaluate(hctr_ctx* ctx, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
+                  const int32_t* targets, const int32_t* target_lengths,
+                  int32_t* labels, int32_t* lengths,
+                  int32_t* edits, int32_t* counts, int32_t* ref_map, int32_t* hyp_map);
+int hctr_evaluate_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C,
+                         const int32_t* targets, const int32_t* target_lengths,
+                         int32_t* labels, int32_t* lengths,
+                         int32_t* edits, int32_t* counts, int32_t* ref_map, int32_t* hyp_map);
+
 /* ---- host prefix beam search: replaces ctc_codec.__cbs_full__/__cbs_skip__ -------------------
  * utils/ctc_codec.py:124-285 (Beam :288-307), float64 accumulators over float32 log-probs.
  * The language model stays behind callbacks, as in the reference (kenlm / transformer objects are

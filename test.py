@@ -222,11 +222,15 @@ def benchmark(model, codec, args):
         chunk = [(n, pp.truncate_label(tru, fw, int(imgs.shape[2]))) for (n, tru), fw in zip(chunk, full)]
         t0 = time.time()
         result = recognise(model, codec, imgs, widths)
+        # editdistance.eval(pre, tru) of every line (test.py:275) in one call on the device, whatever decoded them
+        _, ev = codec.evaluate(result, [tru for _, tru in chunk], maps=args.test_verbose)
         for j, (pre, (_, tru)) in enumerate(zip(result, chunk)):
             if args.test_verbose:
                 print("TEST [{0}/{1}]\nTEST PRE {2}\nTEST TRU {3}".format(j, i // args.batch_size, pre, tru))
-            total += edit_distance(pre, tru)
             nchars += len(tru)
+        total += ev.total_edits
+        if args.test_verbose:
+            print("TEST [{0}] S {2} D {3} I {4}".format(i // args.batch_size, *ev.totals))
         if nchars == 0:
             raise ValueError("Number of label characters should not be 0.")
         cer = total * 1.0 / nchars

@@ -28,7 +28,18 @@ of the align call's launches: the emission pass, the recursion and the back-trac
 times the greedy recognition on the same caller logits (hctr_recognize_logits, every output fetched) against the chain
 of three calls it replaces - hctr_decode_greedy_logits, then hctr_ctc_loss_logits and hctr_ctc_align_logits with the
 decoded labels as targets - alternately after warm-up calls of each. --layers adds the device times of every launch of
-both, and greedy_rowstat's time against the sum of the two row passes it fuses (argmax_rows + ctc_lse)."""
+both, and greedy_rowstat's time against the sum of the two row passes it fuses (argmax_rows + ctc_lse).
+
+    python tools/bench_ctc.py --evaluate [--host-lines 4] ...
+
+times the edit distance on the device against the host loop it replaces (test.py's edit_distance, the pure-Python
+two-row recursion) on the same label sequences, at two shapes: "short", font lines under the trained-like head with their
+own texts as truths (a few dozen characters a line, what a trained model decodes), and "long", the random-head batch,
+whose lines decode to about a thousand labels, against their own decode with a tenth of the labels altered. Per shape:
+hctr_edit_distance distance-only and with counts and maps, the host loop, hctr_model.evaluate (distance-only and with
+maps) and hctr_model.greedy followed by the host loop - alternately, after warm-up calls of each, medians. The host loop
+of the long shape takes about a second per line: it is timed once on the first --host-lines lines and scaled to the
+batch (reported as such)."""
 import argparse
 import json
 import os
@@ -52,6 +63,8 @@ def main():
     ap.add_argument("--backward", action="store_true")
     ap.add_argument("--align", action="store_true")
     ap.add_argument("--recognize", action="store_true")
+    ap.add_argument("--evaluate", action="store_true")
+    ap.add_argument("--host-lines", type=int, default=4)
     args = ap.parse_args()
     import torch
     import hctr_amd
@@ -71,6 +84,9 @@ def main():
         return
     if args.recognize:
         print(json.dumps(recognize(args, hctr_amd, m, imgs)))
+        return
+    if args.evaluate:
+        print(json.dumps(evaluate(args, hctr_amd, m, imgs, labels)))
         return
 
     def t_greedy():
@@ -305,6 +321,124 @@ def recognize(args, hctr_amd, m, imgs):
         two = float(np.median(rows["argmax_rows"])) + float(np.median(rows["ctc_lse"]))
         rec["rowstat_over_two_passes"] = round(float(np.median(rows["greedy_rowstat"])) / two, 4)
         rec["greedy_rowstat_TBps"] = round(4.0 * W * B * C / (1e-3 * float(np.median(rows["greedy_rowstat"]))) / 1e12, 3)
+    return rec
+
+
+def evaluate(args, hctr_amd, m, imgs, labels):
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("hctr_test_cli", os.path.join(ROOT, "test.py"))
+    cli = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cli)
+    s = hctr_amd.synth
+    C = s.DEFAULT_VOCAB + 2
+    mod = sys.modules[hctr_amd.CTCLoss.__module__]
+    rng = np.random.RandomState(7)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return 1e3 * (time.perf_counter() - t0), out
+
+    def shape(name, model, images, widths, truths, host_lines):
+        """truths: list of int label lists; the hypotheses are the model's greedy decode of images"""
+        ctx = model._ctx
+        hyps = [v.tolist() for v in model.greedy(images, widths=widths)]
+        lab, n = mod.pad_sequences(hyps)
+        tl = np.array([len(t) for t in truths], np.int32)
+        tg = np.concatenate([np.asarray(t, np.int32) for t in truths]).astype(np.int32)
+        nh = len(hyps) if host_lines <= 0 else min(host_lines, len(hyps))
+
+        def host(k=nh):
+            return [cli.edit_distance(hyps[b], truths[b]) for b in range(k)]
+
+        fns = {"edit_distance_only": lambda: mod.edit_distance_labels(ctx, lab, n, tg, tl, maps=False).edits,
+               "edit_distance_maps": lambda: mod.edit_distance_labels(ctx, lab, n, tg, tl).edits,
+               "evaluate_only": lambda: model.evaluate(images, tg, tl, widths=widths, maps=False).edits,
+               "evaluate_maps": lambda: model.evaluate(images, tg, tl, widths=widths).edits,
+               "greedy": lambda: model.greedy(images, widths=widths)}
+        if nh == len(hyps):
+            fns["host_loop"] = host
+        for _ in range(args.warmup):
+            for fn in fns.values():
+                fn()
+        ms = {k: [] for k in fns}
+        outs = {}
+        for _ in range(args.steps):
+            for k, fn in fns.items():
+                t, outs[k] = timed(fn)
+                ms[k].append(t)
+        rec = {"lines": len(hyps), "mean_hyp_length": float(n.mean()), "mean_ref_length": float(tl.mean()),
+               "cells": int((n.astype(np.int64) * tl).sum())}
+        for k, v in ms.items():
+            rec[k + "_ms"] = [round(x, 3) for x in v]
+            rec[k + "_ms_median"] = round(float(np.median(v)), 3)
+        if nh == len(hyps):
+            want, host_ms = outs["host_loop"], float(np.median(ms["host_loop"]))
+        else:
+            t, want = timed(host)
+            host_ms = t * float((n.astype(np.int64) * tl).sum()) / float((n[:nh].astype(np.int64) * tl[:nh]).sum())
+            rec["host_loop_ms_measured_on_%d_lines" % nh] = round(t, 3)
+            rec["host_loop_ms_scaled_by_cells"] = round(host_ms, 3)
+        for k in ("edit_distance_only", "edit_distance_maps", "evaluate_only", "evaluate_maps"):
+            assert outs[k][:nh].tolist() == want, k
+        rec["host_loop_over_edit_distance_only"] = round(host_ms / float(np.median(ms["edit_distance_only"])), 3)
+        rec["host_loop_over_edit_distance_maps"] = round(host_ms / float(np.median(ms["edit_distance_maps"])), 3)
+        rec["greedy_plus_host_loop_ms"] = round(float(np.median(ms["greedy"])) + host_ms, 3)
+        rec["greedy_plus_host_loop_over_evaluate_only"] = round(
+            rec["greedy_plus_host_loop_ms"] / float(np.median(ms["evaluate_only"])), 3)
+        rec["greedy_plus_host_loop_over_evaluate_maps"] = round(
+            rec["greedy_plus_host_loop_ms"] / float(np.median(ms["evaluate_maps"])), 3)
+        model.set_profiling(True)
+        model.evaluate(images, tg, tl, widths=widths)
+        rec["evaluate_maps_layers_ms"] = {k: round(v, 4) for k, v in dict(model.last_profile()).items() if "edit" in k or "ctc" in k}
+        model.set_profiling(False)
+        return rec
+
+    def altered(lab):
+        out = [int(v) for v in lab]
+        for i in np.flatnonzero(rng.rand(len(out)) < 0.1)[::-1]:
+            kind = rng.randint(3)
+            if kind == 0:
+                out[i] = int(rng.randint(1, C - 1))
+            elif kind == 1:
+                del out[i]
+            else:
+                out.insert(i, int(rng.randint(1, C - 1)))
+        return out
+
+    rec = {"mode": "evaluate", "width": args.width, "precision": args.precision}
+    rec["long"] = shape("long", m, imgs, None, [altered(v) for v in labels], args.host_lines)
+    del m
+    mt = hctr_amd.hctr_model(C, precision=args.precision).cuda(0)
+    mt.load_state_dict(s.make_state_dict(C, seed=0, head="trained"))
+    font, boxes = s.make_font_lines(args.lines, args.width, 11, with_truth=True)
+    codec = hctr_amd.ctc_codec(s.characters())
+    truths = [codec.encode([s.font_truth_text(bx, args.width)])[0].tolist() for bx in boxes]
+    rec["short"] = shape("short", mt, torch.from_numpy(font).cuda(0), None, truths, 0)
+    # the entry alone at the shape the reference's -bm loop sees: `lines` lines of exactly 40 characters
+    refs = [rng.randint(1, C - 1, 40).tolist() for _ in range(args.lines)]
+    hyps = [altered(r) for r in refs]
+    lab, n = mod.pad_sequences(hyps)
+    tl = np.full(args.lines, 40, np.int32)
+    tg = np.asarray(refs, np.int32).reshape(-1)
+    fns = {"edit_distance_only": lambda: mod.edit_distance_labels(mt._ctx, lab, n, tg, tl, maps=False).edits.tolist(),
+           "edit_distance_maps": lambda: mod.edit_distance_labels(mt._ctx, lab, n, tg, tl).edits.tolist(),
+           "host_loop": lambda: [cli.edit_distance(h, r) for h, r in zip(hyps, refs)]}
+    for _ in range(args.warmup):
+        for fn in fns.values():
+            fn()
+    ms, outs = {k: [] for k in fns}, {}
+    for _ in range(max(args.steps, 20)):
+        for k, fn in fns.items():
+            t, outs[k] = timed(fn)
+            ms[k].append(t)
+    assert outs["edit_distance_only"] == outs["edit_distance_maps"] == outs["host_loop"]
+    rec["lines40"] = {k + "_ms_median": round(float(np.median(v)), 4) for k, v in ms.items()}
+    rec["lines40"].update({k + "_ms_min": round(float(np.min(v)), 4) for k, v in ms.items()})
+    rec["lines40"]["lines"] = args.lines
     return rec
 
 
