@@ -14,12 +14,14 @@ Public surface = the reference's surface for this path:
   edit_distance  per-line Levenshtein distance of two lists of strings or label sequences, on the device
   Recognition  result of hctr_model.recognize / ctc_codec.recognize: the greedy text with per-character spans,
                confidences and runners-up                          (engine-backed; no counterpart)
+  NBest        result of hctr_model.nbest / ctc_codec.nbest: the N best texts of a line with their log-probabilities,
+               by the device prefix beam search without a language model (engine-backed)
 plus ``synth`` (deterministic synthetic checkpoints / line images) and ``build`` / ``load_library``.
 """
 from . import preprocess, synth  # noqa: F401
 from ._lib import build, load as load_library  # noqa: F401
 from .codec import ArpaLM, ToyBigramLM, ZeroLM, ctc_codec  # noqa: F401
-from .ctc import CTCAligner, CTCAlignment, CTCLoss, Evaluation, Recognition  # noqa: F401
+from .ctc import CTCAligner, CTCAlignment, CTCLoss, Evaluation, NBest, Recognition  # noqa: F401
 from .model import hctr_model  # noqa: F401
 
 _EDIT_BOUND = None
@@ -36,4 +38,4 @@ def edit_distance(hyps, refs, device=0):
         _EDIT_BOUND = ctc._EngineBound().cuda(device)
     return ctc.edit_distance_sequences(_EDIT_BOUND._context(), list(hyps), list(refs), maps=False).edits
 
-__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "Recognition", "Evaluation", "edit_distance", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]
+__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "Recognition", "Evaluation", "NBest", "edit_distance", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]

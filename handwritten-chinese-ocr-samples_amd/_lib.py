@@ -171,6 +171,9 @@ SIGNATURES = [
     ("hctr_edit_distance", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP]),
     ("hctr_evaluate", _I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_evaluate_logits", _I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_nbest_topk", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, ctypes.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_nbest_logits", _I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, ctypes.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_nbest", _I, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, ctypes.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_beam_search", _I, [ctypes.POINTER(BeamParams), _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                               _VP, _VP, _VP]),
     ("hctr_ngram_load", _I, [ctypes.c_char_p, ctypes.POINTER(_VP)]),

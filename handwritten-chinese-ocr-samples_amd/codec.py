@@ -192,6 +192,22 @@ class ctc_codec(object):
         rec = ctc.recognize_logits(self._context(), logits, on_dev)
         return self.labels_to_text(rec.label_lists()), rec
 
+    def nbest(self, preds, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None):
+        """The ``n`` best texts of every line of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) with
+        their log-probabilities, by the device prefix beam search without a language model (include/hctr_hip.h
+        ``hctr_nbest_logits``; arguments as ``hctr_model.nbest``). Returns a ``ctc.NBest`` with ``.texts`` added: per
+        line the list of its hypotheses' strings, best first. ``decode`` and ``set_beam_search`` are not involved."""
+        from . import ctc
+        logits, on_dev = self._as_logits(preds)
+        W, B, C = (int(v) for v in logits.shape)
+        if C != len(self.characters):
+            raise ValueError("logits have %d classes, codec has %d" % (C, len(self.characters)))
+        if W == 0:
+            raise ValueError("preds have no steps (W = 0)")
+        res = ctc.nbest_logits(self._context(), logits, on_dev, n, beam, min(int(depth), C), len_bonus, input_lengths)
+        res.texts = [self.labels_to_text(line) for line in res.label_lists()]
+        return res
+
     def evaluate(self, preds, truths, maps=True):
         """Score decoded text against the truth strings on the device: returns ``(texts, ctc.Evaluation)``.
         ``preds`` is what ``decode`` takes - then the greedy decode is scored in label space against ``encode(truths)``

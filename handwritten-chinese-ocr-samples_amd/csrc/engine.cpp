@@ -1586,6 +1586,164 @@ int edit_fetch(hctr_ctx* c, const EditCall& e, const EditOut& o) {
     return HCTR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// the beam front end of one pass (hctr_beam_frontend, hctr_nbest*) and the prefix beam search on its lists (hctr_nbest*)
+// ---------------------------------------------------------------------------------------------
+struct BeamLists {           // one pass's lists on the device, rows r = t*nb + b: k classes / log-probs, blank log-prob,
+    int32_t *idx = nullptr, *cnt = nullptr;      // (row max, log-sum) pairs, candidate counts
+    float *lp = nullptr, *bl = nullptr, *st = nullptr;
+    const float* rowsrc = nullptr;               // the logit rows [nb*W][ld] the lists were taken from (not when fused)
+    int64_t ld = 0;
+    bool fused = false;                          // the lists came out of the head GEMM's epilogues (ws.emit_* hold them)
+};
+
+// Log-softmax + top-k of the pass's lines: the forward of `in` (or, with in == null, the caller's logits in WBC layout,
+// one pass of all lines), then the fused front end or the stored-logits kernels. Temporaries live in c->beam_allocs,
+// which the next pass (or the caller, at the end of its call) frees.
+int beam_lists_pass(hctr_ctx* c, const Batch* in, const Pass& p, const float* logits_wbc, int logits_on_device, int W,
+                    int C, int k, bool want_candidates, double thresh, BeamLists* out) {
+    std::vector<void*>& pool = c->beam_allocs;
+    const int nb = p.nb;
+    const int64_t rows = (int64_t)nb * W;
+    const bool from_img = in != nullptr;
+    free_pool(pool);
+    const float* rowsrc = nullptr;
+    int64_t ld = 0;
+    // fused front end (default): the logits are never stored; the head GEMM runs twice with reducing epilogues
+    // (kernels.h ConvArgs). Not for k beyond the part count / kBeamMaxK, and a pass in which some row needed
+    // more than kBeamCap list slots (near-uniform logits) is redone through the stored-logits kernels.
+    bool fused = from_img && c->fuse_beam && k <= kBeamMaxK && k <= head_parts(c);
+    if (from_img) {
+        TRY(forward_pass(c, *in, p, fused ? HEAD_BEAM : HEAD_LOGITS));
+        rowsrc = c->ws.logits; ld = c->cpad;
+    } else {
+        float *up = nullptr, *rowsbuf = nullptr;
+        const float* dev = logits_wbc;
+        if (!logits_on_device) {
+            TRY(dev_alloc(c, pool, &up, (size_t)rows * C, false));
+            HIP_TRY(c, hipMemcpyAsync(up, logits_wbc, (size_t)rows * C * 4, hipMemcpyHostToDevice, c->stream));
+            dev = up;
+        }
+        TRY(dev_alloc(c, pool, &rowsbuf, (size_t)rows * C, false));
+        HIP_TRY(c, launch_wbc_to_rows(dev, nb, W, C, rowsbuf, C, c->stream));
+        rowsrc = rowsbuf; ld = C;
+    }
+    // device outputs (rows r = t*nb + b): inside the arena on the fused path (no allocation per pass)
+    int32_t *d_idx = nullptr, *d_cnt = nullptr;
+    float *d_lp = nullptr, *d_bl = nullptr, *d_st = nullptr;
+    auto own_outputs = [&]() -> int {
+        TRY(dev_alloc(c, pool, &d_idx, (size_t)rows * k, false));
+        TRY(dev_alloc(c, pool, &d_lp, (size_t)rows * k, false));
+        TRY(dev_alloc(c, pool, &d_bl, (size_t)rows, false));
+        TRY(dev_alloc(c, pool, &d_st, (size_t)rows * 2, false));
+        TRY(dev_alloc(c, pool, &d_cnt, (size_t)rows, false));
+        return HCTR_OK;
+    };
+    if (fused) {
+        const Workspace& w0 = c->ws;
+        d_idx = w0.bm_idx; d_lp = w0.bm_lp; d_bl = w0.bm_bl; d_st = w0.bm_st; d_cnt = w0.bm_cnt;
+        TRY(beam_finish(c, k, want_candidates, thresh, d_idx, d_lp, d_bl, d_st, d_cnt));
+        int32_t ovf = 0;
+        HIP_TRY(c, hipMemcpyAsync(&ovf, c->ws.overflow, 4, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (ovf) {                       // redo this pass with stored logits (re-staged: carving may move the arena)
+            fused = false;
+            ++c->beam_fallbacks;
+            Pass redo = p;
+            redo.guard_dst = nullptr;      // (the guard figures came back with the fused forward)
+            TRY(forward_pass(c, *in, redo, HEAD_LOGITS));
+            rowsrc = c->ws.logits;
+            TRY(own_outputs());
+        }
+    } else {
+        TRY(own_outputs());
+    }
+    if (!fused) {
+        Prof pf(c);
+        PROF_TRY(pf, "row_topk", launch_row_topk(rowsrc, ld, nb, W, C, k, thresh, d_idx, d_lp, d_bl, d_st,
+                                                 d_cnt, c->stream));
+    }
+    out->idx = d_idx; out->cnt = d_cnt; out->lp = d_lp; out->bl = d_bl; out->st = d_st;
+    out->rowsrc = rowsrc; out->ld = ld; out->fused = fused;
+    return HCTR_OK;
+}
+
+struct NbestOut {            // the caller's host outputs, [B][nbest][W] / [B][nbest] / [B]; any may be null
+    int32_t *labels, *lengths;
+    double *logp, *score;
+    int32_t* count;
+};
+
+struct NbestCall {
+    int B = 0, W = 0, C = 0, k = 0, beam = 0, nbest = 0;
+    double len_bonus = 0.0;
+    NbestOut o{};
+    std::vector<int32_t> T;       // [B] steps of each line
+    // device (the context's CTC scratch): T of the whole batch, the rest for the lines of one pass
+    int32_t *d_T = nullptr, *d_lab = nullptr, *d_len = nullptr, *d_cnt = nullptr;
+    double *d_logp = nullptr, *d_score = nullptr;
+    int2* d_hist = nullptr;
+};
+
+int nbest_prepare(hctr_ctx* c, int B, int W, int C, int k, int beam, int nbest, double len_bonus,
+                  const int32_t* input_lengths, const NbestOut& o, NbestCall* n) {
+    if (nbest < 1 || nbest > beam || beam > kBeamMaxK)
+        return fail(c, HCTR_ERR_ARG, "need 1 <= nbest <= beam <= %d, got nbest=%d beam=%d", kBeamMaxK, nbest, beam);
+    if (k < 1 || k > C || k > kBeamMaxK)
+        return fail(c, HCTR_ERR_ARG, "need 1 <= k <= min(C, %d), got k=%d C=%d", kBeamMaxK, k, C);
+    if (len_bonus != len_bonus) return fail(c, HCTR_ERR_ARG, "len_bonus is NaN");
+    if (o.labels && !o.lengths) return fail(c, HCTR_ERR_ARG, "labels needs lengths");
+    n->B = B; n->W = W; n->C = C; n->k = k; n->beam = beam; n->nbest = nbest; n->len_bonus = len_bonus; n->o = o;
+    n->T.assign((size_t)B, W);
+    for (int b = 0; b < B && input_lengths; ++b) {
+        const int Tb = input_lengths[b];
+        if (Tb < 1 || Tb > W) return fail(c, HCTR_ERR_ARG, "input_lengths[%d]=%d outside [1,%d]", b, Tb, W);
+        n->T[(size_t)b] = Tb;
+    }
+    return HCTR_OK;
+}
+
+// scratch for passes of at most `lines` lines; uploads T
+int nbest_scratch(hctr_ctx* c, NbestCall* n, int lines) {
+    const size_t ln = (size_t)lines * n->nbest;
+    const size_t T_b = align256((size_t)n->B * 4), hist_b = align256((size_t)lines * n->W * n->beam * sizeof(int2)),
+                 lab_b = align256(ln * n->W * 4), i32_b = align256(ln * 4), f64_b = align256(ln * 8),
+                 cnt_b = align256((size_t)lines * 4);
+    TRY(ctc_reserve(c, T_b + hist_b + lab_b + i32_b + 2 * f64_b + cnt_b));
+    char* q = c->ctc_buf;
+    n->d_T = (int32_t*)q; q += T_b;
+    n->d_hist = (int2*)q; q += hist_b;
+    n->d_lab = (int32_t*)q; q += lab_b;
+    n->d_logp = (double*)q; q += f64_b;
+    n->d_score = (double*)q; q += f64_b;
+    n->d_len = (int32_t*)q; q += i32_b;
+    n->d_cnt = (int32_t*)q;
+    HIP_TRY(c, hipMemcpyAsync(n->d_T, n->T.data(), (size_t)n->B * 4, hipMemcpyHostToDevice, c->stream));
+    return HCTR_OK;
+}
+
+// the search of the pass's lines [b0, b0 + nb) on their lists (rows r = t*nb + b), results queued to the caller's rows
+int nbest_launch(hctr_ctx* c, const NbestCall& n, const int32_t* d_idx, const float* d_lp, int b0, int nb) {
+    const size_t ln = (size_t)nb * n.nbest;
+    Prof pf(c);
+    if (n.o.labels) HIP_TRY(c, hipMemsetAsync(n.d_lab, 0, ln * n.W * 4, c->stream));
+    PROF_TRY(pf, "prefix_beam", launch_prefix_beam(d_idx, d_lp, nb, n.W, n.k, n.C, n.beam, n.nbest, n.len_bonus,
+                                                   n.d_T + b0, n.d_hist, n.d_len, n.d_logp, n.d_score, n.d_cnt, c->stream));
+    if (n.o.labels)
+        PROF_TRY(pf, "prefix_backtrace", launch_prefix_backtrace(n.d_hist, n.d_T + b0, nb, n.W, n.beam, n.nbest, n.d_len,
+                                                                 n.d_cnt, n.d_lab, c->stream));
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    const size_t lo = (size_t)b0 * n.nbest;
+    HIP_TRY(c, fetch(n.o.labels ? n.o.labels + lo * n.W : nullptr, n.d_lab, ln * n.W * 4));
+    HIP_TRY(c, fetch(n.o.lengths ? n.o.lengths + lo : nullptr, n.d_len, ln * 4));
+    HIP_TRY(c, fetch(n.o.logp ? n.o.logp + lo : nullptr, n.d_logp, ln * 8));
+    HIP_TRY(c, fetch(n.o.score ? n.o.score + lo : nullptr, n.d_score, ln * 8));
+    HIP_TRY(c, fetch(n.o.count ? n.o.count + b0 : nullptr, n.d_cnt, (size_t)nb * 4));
+    return HCTR_OK;
+}
+
 }  // namespace
 
 // =============================================================================================
@@ -1949,70 +2107,21 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
         std::vector<PassOut> outs;
         std::vector<int> owner((size_t)B, -1);
         std::vector<int32_t> counts((size_t)W * B, 0);
-        std::vector<void*>& pool = c->beam_allocs;
         // one pass over the lines `lines[0..nb)`: forward (or the caller's logits), log-softmax + top-k (+ lists), results
         // scattered to the lines' (t, line) rows of the host outputs
+        std::vector<void*>& pool = c->beam_allocs;
         auto run_pass = [&](const Pass& p) -> int {
             const int* lines = p.lines;
             const int nb = p.nb;
             const int64_t rows = (int64_t)nb * W;
-            free_pool(pool);
-            const float* rowsrc = nullptr;
-            int64_t ld = 0;
-            // fused front end (default): the logits are never stored; the head GEMM runs twice with reducing epilogues
-            // (kernels.h ConvArgs). Not for k beyond the part count / kBeamMaxK, and a pass in which some row needed
-            // more than kBeamCap list slots (near-uniform logits) is redone through the stored-logits kernels.
-            bool fused = from_img && c->fuse_beam && k <= kBeamMaxK && k <= head_parts(c);
-            if (from_img) {
-                TRY(forward_pass(c, in, p, fused ? HEAD_BEAM : HEAD_LOGITS));
-                rowsrc = c->ws.logits; ld = c->cpad;
-            } else {
-                float *up = nullptr, *rowsbuf = nullptr;
-                const float* dev = logits_wbc;
-                if (!logits_on_device) {
-                    TRY(dev_alloc(c, pool, &up, (size_t)rows * C, false));
-                    HIP_TRY(c, hipMemcpyAsync(up, logits_wbc, (size_t)rows * C * 4, hipMemcpyHostToDevice, c->stream));
-                    dev = up;
-                }
-                TRY(dev_alloc(c, pool, &rowsbuf, (size_t)rows * C, false));
-                HIP_TRY(c, launch_wbc_to_rows(dev, nb, W, C, rowsbuf, C, c->stream));
-                rowsrc = rowsbuf; ld = C;
-            }
-            // device outputs (rows r = t*nb + b): inside the arena on the fused path (no allocation per pass)
-            int32_t *d_idx = nullptr, *d_cnt = nullptr;
-            float *d_lp = nullptr, *d_bl = nullptr, *d_st = nullptr;
-            auto own_outputs = [&]() -> int {
-                TRY(dev_alloc(c, pool, &d_idx, (size_t)rows * k, false));
-                TRY(dev_alloc(c, pool, &d_lp, (size_t)rows * k, false));
-                TRY(dev_alloc(c, pool, &d_bl, (size_t)rows, false));
-                TRY(dev_alloc(c, pool, &d_st, (size_t)rows * 2, false));
-                TRY(dev_alloc(c, pool, &d_cnt, (size_t)rows, false));
-                return HCTR_OK;
-            };
-            if (fused) {
-                const Workspace& w0 = c->ws;
-                d_idx = w0.bm_idx; d_lp = w0.bm_lp; d_bl = w0.bm_bl; d_st = w0.bm_st; d_cnt = w0.bm_cnt;
-                TRY(beam_finish(c, k, want_candidates != 0, thresh, d_idx, d_lp, d_bl, d_st, d_cnt));
-                int32_t ovf = 0;
-                HIP_TRY(c, hipMemcpyAsync(&ovf, c->ws.overflow, 4, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                if (ovf) {                       // redo this pass with stored logits (re-staged: carving may move the arena)
-                    fused = false;
-                    ++c->beam_fallbacks;
-                    Pass redo = p;
-                    redo.guard_dst = nullptr;      // (the guard figures came back with the fused forward)
-                    TRY(forward_pass(c, in, redo, HEAD_LOGITS));
-                    rowsrc = c->ws.logits;
-                    TRY(own_outputs());
-                }
-            } else {
-                TRY(own_outputs());
-            }
-            if (!fused) {
-                Prof pf(c);
-                PROF_TRY(pf, "row_topk", launch_row_topk(rowsrc, ld, nb, W, C, k, thresh, d_idx, d_lp, d_bl, d_st,
-                                                         d_cnt, c->stream));
-            }
+            BeamLists L;
+            TRY(beam_lists_pass(c, from_img ? &in : nullptr, p, logits_wbc, logits_on_device, W, C, k, want_candidates != 0,
+                                thresh, &L));
+            const bool fused = L.fused;
+            const float* rowsrc = L.rowsrc;
+            const int64_t ld = L.ld;
+            int32_t *d_idx = L.idx, *d_cnt = L.cnt;
+            float *d_lp = L.lp, *d_bl = L.bl, *d_st = L.st;
             // D2H through a pinned staging buffer (grown on demand): a pageable destination is copied in small staged pieces
             const size_t nk = (size_t)rows * k, need_pin = (2 * nk + 2 * (size_t)rows) * 4;
             if (c->pin_cap < need_pin) {
@@ -2104,6 +2213,91 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
         }
         if (num_candidates) *num_candidates = tot;
         return HCTR_OK;
+    });
+}
+
+int hctr_nbest_topk(hctr_ctx* c, const int32_t* topk_idx, const float* topk_logp, int W, int B, int C, int k, int beam,
+                    int nbest, double len_bonus, const int32_t* input_lengths, int32_t* labels, int32_t* lengths,
+                    double* logp, double* score, int32_t* count) {
+    return guard(c, [&]() -> int {
+        TRY(check_logits_args(c, W, B, C, topk_idx && topk_logp));
+        NbestCall n;
+        TRY(nbest_prepare(c, B, W, C, k, beam, nbest, len_bonus, input_lengths, NbestOut{labels, lengths, logp, score, count},
+                          &n));
+        if (B == 0) return HCTR_OK;
+        // the lists are the caller's: classes in [0, C) and distinct within a row, as the front end produces them
+        const size_t rows = (size_t)W * B;
+        for (size_t r = 0; r < rows; ++r) {
+            const int32_t* row = topk_idx + r * k;
+            for (int j = 0; j < k; ++j) {
+                bool bad = row[j] < 0 || row[j] >= C;
+                for (int i = 0; i < j && !bad; ++i) bad = row[i] == row[j];
+                if (bad)
+                    return fail(c, HCTR_ERR_ARG, "topk_idx row (t=%zu, b=%zu) entry %d: class %d outside [0,%d) or repeated",
+                                r / B, r % B, j, row[j], C);
+            }
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
+        std::vector<void*> tmp;
+        PoolGuard tmp_guard{tmp};
+        return synced(c, [&]() -> int {
+            int32_t* d_idx = nullptr;
+            float* d_lp = nullptr;
+            TRY(nbest_scratch(c, &n, B));
+            TRY(dev_alloc(c, tmp, &d_idx, rows * k, false));
+            TRY(dev_alloc(c, tmp, &d_lp, rows * k, false));
+            HIP_TRY(c, hipMemcpyAsync(d_idx, topk_idx, rows * k * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d_lp, topk_logp, rows * k * 4, hipMemcpyHostToDevice, c->stream));
+            return nbest_launch(c, n, d_idx, d_lp, 0, B);
+        }());
+    });
+}
+
+int hctr_nbest_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W, int B, int C, int k, int beam, int nbest,
+                      double len_bonus, const int32_t* input_lengths, int32_t* labels, int32_t* lengths, double* logp,
+                      double* score, int32_t* count) {
+    return guard(c, [&]() -> int {
+        TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
+        NbestCall n;
+        TRY(nbest_prepare(c, B, W, C, k, beam, nbest, len_bonus, input_lengths, NbestOut{labels, lengths, logp, score, count},
+                          &n));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
+        const std::vector<int> all = line_indices(B);
+        const int rc = synced(c, [&]() -> int {
+            BeamLists L;
+            TRY(nbest_scratch(c, &n, B));
+            TRY(beam_lists_pass(c, nullptr, Pass{all.data(), B, 0, B, false, nullptr}, logits_wbc, on_device, W, C, k, false,
+                                std::log(0.001), &L));
+            return nbest_launch(c, n, L.idx, L.lp, 0, B);
+        }());
+        free_pool(c->beam_allocs);
+        return rc;
+    });
+}
+
+int hctr_nbest(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W, int k,
+               int beam, int nbest, double len_bonus, const int32_t* input_lengths, int32_t* labels, int32_t* lengths,
+               double* logp, double* score, int32_t* count) {
+    return guard(c, [&]() -> int {
+        TRY(check_forward_args(c, img, img_dtype, B, W));
+        NbestCall n;
+        TRY(nbest_prepare(c, B, W, c->num_classes, k, beam, nbest, len_bonus, input_lengths,
+                          NbestOut{labels, lengths, logp, score, count}, &n));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        const Batch in{img, img_dtype, img_on_device, widths, B, W};
+        // inside each pass the search runs on the front end's lists where they lie; only its results go to the host
+        const int rc = synced(c, run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
+            if (p.first == 0) TRY(nbest_scratch(c, &n, p.nb));      // no later pass is larger
+            BeamLists L;
+            TRY(beam_lists_pass(c, &in, p, nullptr, 0, W, n.C, k, false, std::log(0.001), &L));
+            return nbest_launch(c, n, L.idx, L.lp, p.first, p.nb);
+        }));
+        free_pool(c->beam_allocs);
+        return rc;
     });
 }
 

@@ -283,6 +283,19 @@ hipError_t launch_edit_backtrace(const EditLines& m, int b0, const int32_t* line
                                  const int32_t* hlen, int stride, int max_len, const int64_t* boff, const uint8_t* bp,
                                  int32_t* counts, int32_t* ref_map, int32_t* hyp_map, hipStream_t s);
 
+// ---- prefix beam search without a language model (hctr_nbest*) on the front end's lists where they lie: idx / lp hold
+// k classes (descending float32 log-probs) per row r = t*nb + b of the launch's lines b = 0..nb-1; T[b] in [1, W] steps
+// of line b count. 1 <= nbest <= beam <= kBeamMaxK, k <= kBeamMaxK (the instance ladder in kernels.hip) ----
+// launch_prefix_beam: per line the first nbest hypotheses of the final list, [nb][nbest]: len, logp = logaddexp(pb, pnb),
+//   score = logp + len * len_bonus (0, -inf, -inf beyond cnt[b] = the number returned), and the history
+//   hist[(b*W + t) * beam + place] = {parent place, appended label or -1} of every kept place of every step;
+// launch_prefix_backtrace: labels[nb][nbest][W] (zero on entry) from that history, the first len entries of each.
+hipError_t launch_prefix_beam(const int32_t* idx, const float* lp, int nb, int W, int k, int C, int beam, int nbest,
+                              double len_bonus, const int32_t* T, int2* hist, int32_t* len, double* logp, double* score,
+                              int32_t* cnt, hipStream_t s);
+hipError_t launch_prefix_backtrace(const int2* hist, const int32_t* T, int nb, int W, int beam, int nbest,
+                                   const int32_t* len, const int32_t* cnt, int32_t* labels, hipStream_t s);
+
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {
     int64_t src_off;          // byte offset of the image inside the packed source buffer

@@ -4074,4 +4074,283 @@ hipError_t launch_edit_backtrace(const EditLines& m, int b0, const int32_t* line
     return hipGetLastError();
 }
 
+
+// -------------------------------------------------------------------------------------------
+// Prefix beam search without a language model (hctr_nbest*): the search of utils/ctc_codec.py:212-285 with a zero LM,
+// as csrc/beam_search.cpp's beam_step restates it, on the front end's per-row lists (k classes, descending float32
+// log-probs) where they lie on the device. One workgroup per line, sequential over the line's steps; all state in LDS.
+//
+// A step turns the ordered list of n <= beam hypotheses (pb, pnb, length, last label, fingerprint) into at most
+// n * (k + 1) entries, one SLOT each: slot i < n is hypothesis i's own prefix, slot n + i * k + j its extension by the
+// row's class j (the own entries, which carry the two-term merges, share one round of the threads). An extension can only coincide with a prefix already in the list (two extensions of different
+// prefixes of equal length differ in their parents), so entries are merged by looking the extension up among the n
+// hypotheses: the extension's slot goes unused and the prefix's own slot takes its mass and the smaller first-touch key.
+// Hence pb' has at most one contribution and pnb' at most two, and logaddexp of two terms is symmetric: no atomics and
+// no ordering question. The first-touch key of a slot is (i * k + j) * 2 + {0 own, 1 extension} of the first pair that
+// touched it (the own entry of hypothesis i is first touched by the row's first usable class j0). Keys are unique, so
+// (total descending, key ascending) is a total order - Python's stable sort over dict insertion order - and a slot's
+// place in the next list is the number of slots that beat it (rank by counting, all-pairs on LDS broadcasts). Totals
+// are compared as order-preserving integers, NaN last, so the ranks are a permutation whatever the inputs hold.
+//
+// Identity: a hypothesis carries (length, 64-bit fingerprint of its labels, fingerprint of its parent prefix); the
+// fingerprint of prefix + c is beam_mix(fingerprint(prefix), c), a bijection of its first argument. Hypothesis m IS the
+// extension of hypothesis p by c iff len_m = len_p + 1, last_m = c and parent_m = fingerprint_p; a false match needs
+// two different label strings of equal length in one list with equal fingerprints (DESIGN.md 4f has the bound).
+//
+// History: per step and kept place one {parent place, appended label or -1}, hist[(b*W + t) * beam + place];
+// prefix_backtrace_kernel walks it, one lane per returned hypothesis. Two barriers per step (entries -> ranks -> next
+// list); the next row's k classes are loaded before the step's arithmetic and stored to LDS behind it.
+// Float64 throughout; logaddexp is numpy's formula (npy_logaddexp), as in beam_search.cpp.
+// -------------------------------------------------------------------------------------------
+
+// The instances (beam, k, wave64s per line); a call launches the first that holds its beam and k. The arithmetic does
+// not depend on the rung: it sizes the LDS arrays and the threads over which the slots are spread.
+#define HCTR_BEAM_LADDER(X) X(10, 10, 1) X(16, 16, 4) X(32, 32, 4)
+
+// numpy's formula - x + log1p(exp(y - x)) for x > y, y + log1p(exp(x - y)) otherwise - without its branches, which
+// lanes of one wave would take both ways: the larger argument plus log1p(exp(-|x - y|)), the same operands bit for bit
+__device__ __forceinline__ double beam_logaddexp(double x, double y) {
+    if (x == y) return x + 0.693147180559945309417232121458176568;      // (also -inf, -inf: no inf - inf)
+    return fmax(x, y) + log1p(exp(-fabs(x - y)));  // NaN in, NaN out (fmax drops one NaN, exp(NaN) brings it back)
+}
+
+// total() of the reference with a zero LM: log-prob + len * len_bonus, the product rounded on its own as Python does
+__device__ __forceinline__ double beam_total(double logp, int len, double len_bonus) {
+#pragma clang fp contract(off)
+    const double pt = (double)len * len_bonus;
+    return logp + pt;
+}
+
+// order-preserving integer image of a total: larger double <-> larger integer, -0 = +0, NaN below -inf; never 0
+__device__ __forceinline__ unsigned long long beam_ord(double t) {
+    if (t != t) return 1ull;
+    if (t == 0.0) t = 0.0;
+    const unsigned long long u = (unsigned long long)__double_as_longlong(t);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ unsigned long long beam_mix(unsigned long long h, int c) {
+    unsigned long long z = h + (unsigned long long)(unsigned)(c + 1) * 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// what the ranking reads of a slot, one 16-byte LDS load: the total's integer image and the first-touch key
+struct alignas(16) BeamSortKey {
+    unsigned long long ord;
+    unsigned key, pad;
+};
+
+template <int BEAM, int K, int NW>
+__global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __restrict__ idx, const float* __restrict__ lp,
+                                                              int nb, int W, int k, int unk, int beam, int nbest,
+                                                              double len_bonus, const int32_t* __restrict__ Tl,
+                                                              int2* __restrict__ hist, int32_t* __restrict__ o_len,
+                                                              double* __restrict__ o_logp, double* __restrict__ o_score,
+                                                              int32_t* __restrict__ o_cnt) {
+    constexpr int NT = 64 * NW, SLOTS = BEAM * (K + 1);
+    constexpr double NINF = -__builtin_huge_val();
+    // the list, double-buffered: place r of step t's list is written while step t's slots still read the old one
+    __shared__ double h_pb[2][BEAM], h_pnb[2][BEAM], h_tot[2][BEAM];
+    __shared__ unsigned long long h_hash[2][BEAM], h_par[2][BEAM];
+    __shared__ int h_len[2][BEAM], h_last[2][BEAM];
+    __shared__ BeamSortKey e_sort[SLOTS];          // ord 0 = the slot holds no entry
+    __shared__ double e_pb[SLOTS], e_pnb[SLOTS], e_tot[SLOTS];
+    __shared__ int r_cls[2][K];
+    __shared__ double r_lp[2][K];
+    __shared__ int r_meta[2][2];                   // {the row's first usable class j0, the place of the blank}, -1 = none
+    __shared__ int s_n[2], s_valid[NW];
+    const int b = blockIdx.x, tid = threadIdx.x, k1 = k + 1;
+    const int T = Tl[b];
+    int2* __restrict__ hb = hist + (int64_t)b * W * beam;
+
+    // a row's classes into LDS (wave 0; every lane of it takes part in the ballots)
+    auto put_row = [&](int buf, bool have, int c, float l) {
+        const unsigned long long usable = __ballot(have && (unsigned)c < (unsigned)unk);
+        const unsigned long long blank = __ballot(have && c == 0);
+        if (have) { r_cls[buf][tid] = c; r_lp[buf][tid] = (double)l; }
+        if (tid == 0) {
+            r_meta[buf][0] = usable ? __ffsll((long long)usable) - 1 : -1;
+            r_meta[buf][1] = blank ? __ffsll((long long)blank) - 1 : -1;
+        }
+    };
+    if (tid < 64) {
+        const bool have = T > 0 && tid < k;
+        const int64_t a = (int64_t)b * k + tid;
+        put_row(0, have, have ? idx[a] : 0, have ? lp[a] : 0.f);
+    }
+    if (tid == 0) {                                // [((), 0, -inf)]
+        h_pb[0][0] = 0.0; h_pnb[0][0] = NINF; h_tot[0][0] = 0.0;
+        h_hash[0][0] = 0x243F6A8885A308D3ull; h_par[0][0] = 0ull;
+        h_len[0][0] = 0; h_last[0][0] = -1;
+        s_n[0] = 1;
+    }
+    __syncthreads();
+    int cur = 0;
+    for (int t = 0; t < T; ++t, cur ^= 1) {
+        const int nxt = cur ^ 1, n = s_n[cur];
+        if (n == 0) break;                         // (block-uniform) every class of some row was <unknown>: nothing is left
+        const bool pre = t + 1 < T && tid < k;
+        int pc = 0;
+        float pl = 0.f;
+        if (pre) {
+            const int64_t a = ((int64_t)(t + 1) * nb + b) * k + tid;
+            pc = idx[a];
+            pl = lp[a];
+        }
+        const int j0 = r_meta[cur][0], jb = r_meta[cur][1], E = n * k1;
+        // entries
+        int nvalid = 0;                            // valid entries of this wave's slots (wave-uniform)
+        for (int e0 = 0; e0 < E; e0 += NT) {       // (block-uniform trips: the ballot below counts whole waves)
+            const int e = e0 + tid;
+            const bool in = e < E;
+            // (a lane past the last slot idles through the cheap side, the extension of hypothesis 0 by class 0)
+            const int i = !in ? 0 : e < n ? e : (e - n) / k, jj = !in ? 1 : e < n ? 0 : e - n - i * k + 1;
+            const int leni = h_len[cur][i], lasti = h_last[cur][i];
+            bool valid;
+            unsigned key;
+            double pb = NINF, pnb = NINF, tot;
+            if (jj == 0) {                         // the prefix's own entry
+                valid = j0 >= 0;
+                key = (unsigned)(i * k + max(j0, 0)) * 2u;
+                if (jb >= 0) pb = h_tot[cur][i] + r_lp[cur][jb];
+                int jt = -1;
+#pragma unroll 4
+                for (int j = 0; j < k; ++j)        // (independent LDS loads: unrolled, they overlap)
+                    if (r_cls[cur][j] == lasti) jt = j;
+                if (jt >= 0 && lasti > 0 && lasti < unk) {
+                    const double l = r_lp[cur][jt];
+                    const unsigned long long want = h_par[cur][i];
+                    int p = -1;                    // the hypothesis whose extension by the last label this prefix is
+#pragma unroll 4
+                    for (int q = 0; q < n; ++q)
+                        if (h_len[cur][q] == leni - 1 && h_hash[cur][q] == want) p = q;
+                    double ext = NINF;
+                    if (p >= 0) {
+                        ext = (h_last[cur][p] != lasti ? h_tot[cur][p] : h_pb[cur][p]) + l;
+                        key = min(key, (unsigned)(p * k + jt) * 2u + 1u);
+                    }
+                    pnb = beam_logaddexp(h_pnb[cur][i] + l, ext);
+                }
+                tot = beam_logaddexp(pb, pnb);
+            } else {                               // the extension by class j
+                const int j = jj - 1, c = r_cls[cur][j];
+                valid = c > 0 && c < unk;
+                key = (unsigned)(i * k + j) * 2u + 1u;
+                if (valid) {
+                    const unsigned long long mine = h_hash[cur][i];
+#pragma unroll 4
+                    for (int m = 0; m < n; ++m)    // already in the list: its own slot takes this mass
+                        if (h_len[cur][m] == leni + 1 && h_last[cur][m] == c && h_par[cur][m] == mine) valid = false;
+                }
+                pnb = (c != lasti ? h_tot[cur][i] : h_pb[cur][i]) + r_lp[cur][j];
+                tot = pnb;                         // logaddexp(-inf, x) = x
+            }
+            valid = valid && in;
+            nvalid += __popcll(__ballot(valid));
+            if (in) {
+                e_sort[e] = BeamSortKey{valid ? beam_ord(beam_total(tot, leni + (jj ? 1 : 0), len_bonus)) : 0ull, key, 0u};
+                e_pb[e] = pb; e_pnb[e] = pnb; e_tot[e] = tot;
+            }
+        }
+        if ((tid & 63) == 0) s_valid[tid >> 6] = nvalid;
+        __syncthreads();
+        // ranks; the first `beam` become the next list
+        for (int e = tid; e < E; e += NT) {
+            const unsigned long long ord = e_sort[e].ord;
+            const unsigned key = e_sort[e].key;
+            int rank = 0;
+#pragma unroll 8
+            for (int f = 0; f < E; ++f) {          // (broadcast loads, eight in flight)
+                const BeamSortKey o = e_sort[f];
+                rank += (o.ord > ord) || (o.ord == ord && o.key < key);
+            }
+            if (e == 0) {
+                int cnt = 0;
+                for (int w = 0; w < NW; ++w) cnt += s_valid[w];
+                s_n[nxt] = min(cnt, beam);
+            }
+            if (ord != 0ull && rank < beam) {
+                const int i = e < n ? e : (e - n) / k, jj = e < n ? 0 : e - n - i * k + 1;
+                const int c = jj ? r_cls[cur][jj - 1] : -1;
+                const unsigned long long hi = h_hash[cur][i];
+                h_pb[nxt][rank] = e_pb[e]; h_pnb[nxt][rank] = e_pnb[e]; h_tot[nxt][rank] = e_tot[e];
+                h_len[nxt][rank] = h_len[cur][i] + (jj ? 1 : 0);
+                h_last[nxt][rank] = jj ? c : h_last[cur][i];
+                h_hash[nxt][rank] = jj ? beam_mix(hi, c) : hi;
+                h_par[nxt][rank] = jj ? hi : h_par[cur][i];
+                hb[(int64_t)t * beam + rank] = make_int2(i, c);
+            }
+        }
+        if (tid < 64) put_row(nxt, pre, pc, pl);
+        __syncthreads();
+    }
+    const int n = s_n[cur];
+    if (tid < nbest) {
+        const bool have = tid < n;
+        const int len = have ? h_len[cur][tid] : 0;
+        const double logp = have ? h_tot[cur][tid] : NINF;
+        const int64_t o = (int64_t)b * nbest + tid;
+        o_len[o] = len;
+        o_logp[o] = logp;
+        o_score[o] = have ? beam_total(logp, len, len_bonus) : NINF;
+    }
+    if (tid == 0) o_cnt[b] = min(n, nbest);
+}
+
+// labels of the returned hypotheses, one lane each: from the last step back, place to parent place, the appended labels
+// filling the text from its end. The labels array is zero on entry. Places and positions are clamped, so a history
+// left unspecified by a NaN row is walked without leaving the line's arrays.
+__global__ __launch_bounds__(64) void prefix_backtrace_kernel(const int2* __restrict__ hist, const int32_t* __restrict__ Tl,
+                                                              int W, int beam, int nbest,
+                                                              const int32_t* __restrict__ o_len,
+                                                              const int32_t* __restrict__ o_cnt,
+                                                              int32_t* __restrict__ labels) {
+    const int b = blockIdx.x, s = threadIdx.x;
+    if (s >= min(o_cnt[b], nbest)) return;
+    const int2* __restrict__ hb = hist + (int64_t)b * W * beam;
+    int32_t* __restrict__ out = labels + ((int64_t)b * nbest + s) * W;
+    int pos = min(max(o_len[(int64_t)b * nbest + s], 0), W), place = s;
+    for (int t = min(Tl[b], W) - 1; t >= 0 && pos > 0; --t) {
+        const int2 h = hb[(int64_t)t * beam + place];
+        if (h.y >= 0) out[--pos] = h.y;
+        place = (int)min((unsigned)h.x, (unsigned)(beam - 1));
+    }
+}
+
+template <int BEAM_, int K_, int NW_>
+struct BeamRung {
+    static constexpr int BEAM = BEAM_, K = K_, NW = NW_;
+};
+#define BEAM_RUNG_MAX(BEAM, K, NW) , BEAM
+constexpr int kBeamLadderMax = std::max({0 HCTR_BEAM_LADDER(BEAM_RUNG_MAX)});
+#undef BEAM_RUNG_MAX
+static_assert(kBeamLadderMax == kBeamMaxK, "the last rung holds the documented limits of hctr_nbest*");
+
+hipError_t launch_prefix_beam(const int32_t* idx, const float* lp, int nb, int W, int k, int C, int beam, int nbest,
+                              double len_bonus, const int32_t* T, int2* hist, int32_t* len, double* logp, double* score,
+                              int32_t* cnt, hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+    if (k < 1 || beam < 1 || nbest < 1 || nbest > beam || C < 2 || W < 1) return hipErrorInvalidValue;
+#define BEAM_RUNG(BEAM, K, NW)                                                                                       \
+    if (beam <= BEAM && k <= K) {                                                                                    \
+        hipLaunchKernelGGL((prefix_beam_kernel<BEAM, K, NW>), dim3((unsigned)nb), dim3(64 * NW), 0, s, idx, lp, nb, W, k,   \
+                           C - 1, beam, nbest, len_bonus, T, hist, len, logp, score, cnt);                           \
+        return hipGetLastError();                                                                                    \
+    }
+    HCTR_BEAM_LADDER(BEAM_RUNG)
+#undef BEAM_RUNG
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_prefix_backtrace(const int2* hist, const int32_t* T, int nb, int W, int beam, int nbest,
+                                   const int32_t* len, const int32_t* cnt, int32_t* labels, hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+    if (beam < 1 || nbest < 1 || nbest > 64) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(prefix_backtrace_kernel, dim3((unsigned)nb), dim3(64), 0, s, hist, T, W, beam, nbest, len, cnt,
+                       labels);
+    return hipGetLastError();
+}
+
 }  // namespace hctr

@@ -469,6 +469,86 @@ def evaluate_images(ctx, x, dt, on_dev, widths, B, W, targets, target_lengths, m
     return Evaluation(*out, labels, lengths, tg, tl)
 
 
+class NBest(object):
+    """Result of the device prefix beam search over B lines (numpy arrays, on the host; include/hctr_hip.h
+    ``hctr_nbest*``): ``labels`` int32 [B, n, W] and ``lengths`` int32 [B, n], line b's hypotheses best first (the first
+    ``lengths[b, i]`` entries of a hypothesis are valid, the rest zeros); ``logps`` float64 [B, n], the log-probability of
+    each text over the alignments the pruned search kept; ``scores`` float64 [B, n], what the search ranked by
+    (``logp + length * len_bonus``); ``counts`` int32 [B], how many hypotheses a line really has (unused slots have
+    length 0 and -inf)."""
+
+    def __init__(self, labels, lengths, logps, scores, counts):
+        self.labels, self.lengths, self.logps, self.scores, self.counts = labels, lengths, logps, scores, counts
+
+    def __len__(self):
+        return len(self.counts)
+
+    def label_lists(self):
+        """per line the list of its hypotheses' label arrays, best first"""
+        return [[self.labels[b, i, :int(self.lengths[b, i])].copy() for i in range(int(self.counts[b]))]
+                for b in range(len(self))]
+
+    def lines(self):
+        """yields per line the list of (labels, logp, score), best first"""
+        for b in range(len(self)):
+            yield [(self.labels[b, i, :int(self.lengths[b, i])].copy(), float(self.logps[b, i]), float(self.scores[b, i]))
+                   for i in range(int(self.counts[b]))]
+
+    def posteriors(self):
+        """float64 [B, n]: each hypothesis's share of the probability mass of its line's list, softmax of ``logps``
+        over the hypotheses returned (0 for unused slots; a line without a hypothesis is all zeros)."""
+        lp = np.asarray(self.logps, np.float64)
+        out = np.zeros(lp.shape, np.float64)
+        for b in range(len(self)):
+            n = int(self.counts[b])
+            row = lp[b, :n]
+            if n and np.isfinite(row.max()):
+                e = np.exp(row - row.max())
+                out[b, :n] = e / e.sum()
+        return out
+
+
+def _nbest_args(B, W, n, beam, depth, len_bonus, input_lengths):
+    n, beam, depth = int(n), int(beam), int(depth)
+    il = normalize_input_lengths(input_lengths, B)
+    out = (np.zeros((B, n, W), np.int32), np.zeros((B, n), np.int32), np.full((B, n), -np.inf, np.float64),
+           np.full((B, n), -np.inf, np.float64), np.zeros((B,), np.int32))
+    return n, beam, depth, ctypes.c_double(float(len_bonus)), il, out
+
+
+def nbest_topk(ctx, topk_idx, topk_logp, C, n=5, beam=10, len_bonus=0.0, input_lengths=None):
+    """NBest of front-end lists ``topk_idx`` int32 / ``topk_logp`` float32 [W, B, k] over ``C`` classes
+    (hctr_nbest_topk): the search alone."""
+    idx = np.ascontiguousarray(topk_idx, dtype=np.int32)
+    lp = np.ascontiguousarray(topk_logp, dtype=np.float32)
+    if idx.ndim != 3 or idx.shape != lp.shape:
+        raise ValueError("topk_idx and topk_logp must both be [W,B,k]")
+    W, B, k = (int(v) for v in idx.shape)
+    n, beam, _, bonus, il, out = _nbest_args(B, W, n, beam, k, len_bonus, input_lengths)
+    _lib.check(_lib.load().hctr_nbest_topk(ctx, _lib.ptr(idx), _lib.ptr(lp), W, B, int(C), k, beam, n, bonus,
+                                           _lib.ptr(il), *[_lib.ptr(a) for a in out]), ctx)
+    return NBest(*out)
+
+
+def nbest_logits(ctx, logits, on_dev, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None):
+    """NBest of caller logits / log-probs in WBC layout (hctr_nbest_logits): top-``depth`` per column, then the search."""
+    if len(logits.shape) != 3:
+        raise ValueError("logits must be [W,B,C]")
+    W, B, C = (int(v) for v in logits.shape)
+    n, beam, depth, bonus, il, out = _nbest_args(B, W, n, beam, depth, len_bonus, input_lengths)
+    _lib.check(_lib.load().hctr_nbest_logits(ctx, _lib.ptr(logits), on_dev, W, B, C, depth, beam, n, bonus,
+                                             _lib.ptr(il), *[_lib.ptr(a) for a in out]), ctx)
+    return NBest(*out)
+
+
+def nbest_images(ctx, x, dt, on_dev, widths, B, W, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None):
+    """NBest of line images (hctr_nbest); x, dt, on_dev, widths as hctr_model._img_args / _widths give them."""
+    n, beam, depth, bonus, il, out = _nbest_args(B, W, n, beam, depth, len_bonus, input_lengths)
+    _lib.check(_lib.load().hctr_nbest(ctx, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, depth, beam, n, bonus,
+                                      _lib.ptr(il), *[_lib.ptr(a) for a in out]), ctx)
+    return NBest(*out)
+
+
 _FN = None
 
 

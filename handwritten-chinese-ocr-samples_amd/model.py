@@ -297,6 +297,20 @@ class hctr_model(object):
         x, dt, on_dev, B, W = self._img_args(input)
         return ctc.evaluate_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, targets, target_lengths, maps)
 
+    def nbest(self, input, n=5, beam=10, depth=10, len_bonus=0.0, widths=None, input_lengths=None):
+        """Forward + CTC prefix beam search without a language model, on the device: the ``n`` best texts of every line
+        with their log-probabilities, what rescoring with any language model starts from. ``beam`` hypotheses are kept
+        per step over the ``depth`` likeliest classes of each pixel column (the reference's beam_size / search_depth,
+        at most 32 each); ``len_bonus`` is added per character to what the search ranks by. No top-k array visits the
+        host. ``input_lengths`` None = all W columns of every line. Returns a ``ctc.NBest`` (numpy arrays;
+        ``label_lists()``, ``lines()``, ``posteriors()``). In "auto" precision every line runs in f16x3
+        (include/hctr_hip.h ``hctr_nbest``)."""
+        from . import ctc
+        ctx = self._require_ctx()
+        x, dt, on_dev, B, W = self._img_args(input)
+        return ctc.nbest_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, n, beam, depth, len_bonus,
+                                input_lengths)
+
     # -- precision mode ---------------------------------------------------------------------------
     def set_precision(self, precision):
         """Switch the mode of a loaded model among those whose weight set is resident (all three for a model built

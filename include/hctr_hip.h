@@ -340,6 +340,75 @@ int hctr_evaluate_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device, 
                          int32_t* labels, int32_t* lengths,
                          int32_t* edits, int32_t* counts, int32_t* ref_map, int32_t* hyp_map);
 
+/* ---- N-best texts with scores: the CTC prefix beam search without a language model, on the device -------------
+ * The search of utils/ctc_codec.py:212-285 (__context_beam_search__) with a language model that scores everything 0 -
+ * what hctr_beam_search does per step with builtin_lm == 1 - run where the front end's lists lie, over a caller-chosen
+ * number of steps and without the greedy end-step / empty-line rules of __cbs_full__; it returns the first nbest
+ * hypotheses of the final list with their log-probabilities instead of one string. An N-best list is what rescoring with
+ * any language model needs (N calls per line); an LM-scored search itself stays on the host (hctr_beam_search).
+ * Input per row (t, b): k classes in descending log-prob order (ties: lower index first), distinct, with float32
+ * log-probs - hctr_beam_frontend's topk_idx / topk_logp. Line b runs T_b = input_lengths[b] steps, in [1, W]; NULL = W
+ * for every line (all columns count, pad columns included, as in hctr_greedy and hctr_recognize).
+ * Per line the state is an ordered list of at most `beam` hypotheses (prefix, pb, pnb) in float64, at first
+ * [((), 0, -inf)]. Step t:
+ *   1. pairs (i, j) are taken in lexicographic order, hypothesis i in list order, candidate j in list order; candidates
+ *      with class >= C-1 (<unknown>) are skipped;
+ *   2. with tot = logaddexp(pb, pnb), tail = the prefix's last label (or none) and the candidate's class c and log-prob
+ *      l (widened to float64), the pair touches the entry of prefix and
+ *        c == 0:     pb'(prefix) (+)= tot + l;
+ *        c != tail:  touches prefix+c, pnb'(prefix+c) (+)= tot + l;
+ *        c == tail:  touches prefix+c, pnb'(prefix+c) (+)= pb + l and pnb'(prefix) (+)= pnb + l;
+ *      (+)= is logaddexp into an accumulator that starts at -inf (numpy's formula; logaddexp(-inf, -inf) = -inf, never
+ *      NaN); entries are keyed by the label string, equal strings are one entry;
+ *   3. the entries stand in first-touch order: an entry's position is that of the first pair that touched it, within a
+ *      pair the prefix's own entry before the extension (Python dict insertion order, the gen vector of beam_step);
+ *   4. they are sorted STABLY, descending, by total = logaddexp(pb', pnb') + len(prefix) * len_bonus and the first `beam`
+ *      survive; an entry whose total is -inf sorts last but may survive if there is room;
+ *   5. the blank takes part only when it is among the row's k classes (the reference's rule).
+ * After T_b steps the first nbest hypotheses are the result, in that order; the tie rule of 3-4 is part of the contract.
+ * Identity by label string is decided with a fingerprint (length, 64-bit hash of the labels) per hypothesis: two
+ * different strings of one length in one list are taken for equal with probability 2^-64 per pair, below 1e-11 for a
+ * whole call of 64 lines x 2000 steps at beam 32 - "equal strings", with that bound.
+ * Outputs are host pointers; any may be NULL, except that labels needs lengths:
+ *   labels  int32 [B][nbest][W]: the first lengths entries of a hypothesis valid, the rest zeros;
+ *   lengths int32 [B][nbest];
+ *   logp    float64 [B][nbest]: logaddexp(pb, pnb), the log-prob of the text over the alignments the pruned search kept,
+ *           a lower bound of -nll of that text;
+ *   score   float64 [B][nbest]: total;
+ *   count   int32 [B]: hypotheses returned, below nbest when fewer exist, 0 when every candidate of some step was
+ *           <unknown> (no error here, unlike hctr_beam_search's HCTR_ERR_EMPTY_LINE). Unused slots: length 0, logp and
+ *           score -inf.
+ * Limits: 1 <= nbest <= beam <= 32, 1 <= k <= min(C, 32) (the reference's defaults are 10 / 10); input_lengths outside
+ * [1, W], a NaN len_bonus, labels without lengths, and for hctr_nbest_topk a class outside [0, C) or repeated in its
+ * row: HCTR_ERR_ARG with a message. B == 0 is a no-op. A row holding a NaN leaves that line's outputs unspecified; the
+ * call returns and the other lines are unaffected. No atomics: repeated calls, and host-pointer / device-pointer calls,
+ * agree bit for bit. HCTR_ERR_NOMEM leaves the context usable.
+ * hctr_nbest_topk takes the caller's lists, [W][B][k] host arrays: the search alone; needs no weights.
+ * hctr_nbest_logits takes logits (or log-probs) in WBC layout, host or device pointer, and runs hctr_beam_frontend's
+ *   stored-logits front end (wbc_to_rows, row_topk) and the search on its device lists; needs no weights.
+ * hctr_nbest runs the forward of img (arguments as hctr_greedy) in internal passes with the front end hctr_beam_frontend
+ *   uses - the fused head epilogues where they apply, stored logits + row_topk otherwise and when a row list overflows -
+ *   and inside each pass the search on the pass's lists where they lie; no top-k array goes to the host. Mode 0 is f16,
+ *   mode 1 f16x3; mode 2 runs EVERY line in f16x3 (the margin certificate bounds argmax flips, not beam scores) and
+ *   leaves hctr_last_guard's figures as they were, exactly as hctr_ctc_loss / hctr_ctc_align do.
+ * Launches (hctr_last_profile), after the front end's own: prefix_beam (one workgroup per line, sequential over its
+ * steps, the list in LDS; instances (beam, k) <= (10, 10) on one wave64, (16, 16) and (32, 32) on four) and, when labels
+ * are wanted, prefix_backtrace (one lane per returned hypothesis).
+ * Device scratch (the context's grow-only CTC scratch; n = B, for hctr_nbest the lines of one pass): 4 * B (steps) +
+ * 8 * n*W*beam (per step and place: parent place and appended label; 64 lines of 2000 steps at beam 32: 32 MB) +
+ * 4 * n*nbest*W (labels) + 20 * n*nbest + 4 * n, each array rounded up to 256 bytes; hctr_nbest_topk adds 8 * W*B*k for
+ * the lists, hctr_nbest_logits W*B*C floats for the rows (as many again for logits passed as a host pointer) and
+ * 4 * W*B * (2k + 4) for the lists. */
+int hctr_nbest_topk(hctr_ctx* ctx, const int32_t* topk_idx, const float* topk_logp, int W, int B, int C, int k,
+                    int beam, int nbest, double len_bonus, const int32_t* input_lengths,
+                    int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count);
+int hctr_nbest_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C, int k,
+                      int beam, int nbest, double len_bonus, const int32_t* input_lengths,
+                      int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count);
+int hctr_nbest(hctr_ctx* ctx, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
+               int k, int beam, int nbest, double len_bonus, const int32_t* input_lengths,
+               int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count);
+
 /* ---- host prefix beam search: replaces ctc_codec.__cbs_full__/__cbs_skip__ -------------------
  * utils/ctc_codec.py:124-285 (Beam :288-307), float64 accumulators over float32 log-probs.
  * The language model stays behind callbacks, as in the reference (kenlm / transformer objects are

@@ -39,7 +39,17 @@ whose lines decode to about a thousand labels, against their own decode with a t
 hctr_edit_distance distance-only and with counts and maps, the host loop, hctr_model.evaluate (distance-only and with
 maps) and hctr_model.greedy followed by the host loop - alternately, after warm-up calls of each, medians. The host loop
 of the long shape takes about a second per line: it is timed once on the first --host-lines lines and scaled to the
-batch (reported as such)."""
+batch (reported as such).
+
+    python tools/bench_ctc.py --nbest ...
+
+times the device prefix beam search (hctr_nbest: forward, front end and search on the device, N-best labels and scores
+fetched) against the path it spares LM-free callers - hctr_beam_frontend with its top-k copy to the host, then the host
+search hctr_beam_search(builtin_lm = 1) on 16 threads on those lists - at beam 10 / depth 10, len_bonus 5.8, each line
+over the host search's own number of steps (the reference's end step), alternately after warm-up calls of each, medians.
+Three figures: the device search alone (its two launches' device time, and the wall time of hctr_nbest_topk on the same
+lists, which adds their upload), the front end + D2H + host search, and the front end alone. The 1-best texts of the two
+searches are compared."""
 import argparse
 import json
 import os
@@ -64,6 +74,7 @@ def main():
     ap.add_argument("--align", action="store_true")
     ap.add_argument("--recognize", action="store_true")
     ap.add_argument("--evaluate", action="store_true")
+    ap.add_argument("--nbest", action="store_true")
     ap.add_argument("--host-lines", type=int, default=4)
     args = ap.parse_args()
     import torch
@@ -87,6 +98,9 @@ def main():
         return
     if args.evaluate:
         print(json.dumps(evaluate(args, hctr_amd, m, imgs, labels)))
+        return
+    if args.nbest:
+        print(json.dumps(nbest(args, hctr_amd, m, imgs)))
         return
 
     def t_greedy():
@@ -322,6 +336,66 @@ def recognize(args, hctr_amd, m, imgs):
         rec["rowstat_over_two_passes"] = round(float(np.median(rows["greedy_rowstat"])) / two, 4)
         rec["greedy_rowstat_TBps"] = round(4.0 * W * B * C / (1e-3 * float(np.median(rows["greedy_rowstat"]))) / 1e12, 3)
     return rec
+
+
+def nbest(args, hctr_amd, m, imgs):
+    import torch
+    from hctr_amd import package
+    ctc = sys.modules[package.__name__ + ".ctc"]
+    B, W = int(imgs.shape[0]), int(imgs.shape[-1])
+    C, k, beam, n, bonus = int(m.noutput), 10, 10, 5, 5.8
+    codec = hctr_amd.ctc_codec(hctr_amd.synth.characters()).attach(m)
+    codec.set_beam_search(ngram_path="zero", use_tfm_pred=False, len_bonus=bonus, beam_size=beam, search_depth=k)
+    codec.num_threads = 16
+    fe = m.beam_frontend(imgs, k)
+    top1 = fe["topk_idx"][:, :, 0]
+    ends = np.empty(B, np.int32)
+    for b in range(B):                                             # the reference's end step: last greedy character + 4
+        t = top1[:, b]
+        keep = (t != 0) & (t != C - 1)
+        keep[1:] &= t[1:] != t[:-1]
+        ends[b] = min(int(np.flatnonzero(keep)[-1]) + 4, W)
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    calls = {"nbest_images": lambda: m.nbest(imgs, n=n, beam=beam, depth=k, len_bonus=bonus, input_lengths=ends),
+             "frontend": lambda: m.beam_frontend(imgs, k),
+             "host_search": lambda: codec.decode_frontend(fe),
+             "nbest_topk": lambda: ctc.nbest_topk(m._ctx, fe["topk_idx"], fe["topk_logp"], C, n, beam, bonus, ends)}
+    for _ in range(args.warmup):
+        for f in calls.values():
+            f()
+    ms = {name: [] for name in calls}
+    out = {}
+    for _ in range(args.steps):
+        for name, f in calls.items():
+            dt, out[name] = timed(f)
+            ms[name].append(1e3 * dt)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    m.set_profiling(True)
+    calls["nbest_images"]()
+    prof = dict(m.last_profile())
+    m.set_profiling(False)
+    search_dev = prof.get("prefix_beam", 0.0) + prof.get("prefix_backtrace", 0.0)
+    one_best = codec.labels_to_text([line[0] for line in out["nbest_topk"].label_lists()])
+    return {"mode": "nbest", "lines": B, "width": W, "classes": C, "precision": args.precision, "beam": beam, "depth": k,
+            "nbest": n, "host_threads": 16, "mean_steps": float(ends.mean()),
+            "device_search_ms": round(search_dev, 3),
+            "device_search_launches_ms": {key: round(prof.get(key, 0.0), 4) for key in ("prefix_beam", "prefix_backtrace")},
+            "nbest_topk_call_ms_median": round(med["nbest_topk"], 3),
+            "frontend_d2h_host_search_ms_median": round(med["frontend"] + med["host_search"], 3),
+            "host_search_ms_median": round(med["host_search"], 3),
+            "frontend_alone_ms_median": round(med["frontend"], 3),
+            "nbest_images_call_ms_median": round(med["nbest_images"], 3),
+            "nbest_images_device_ms": round(sum(prof.values()), 3),
+            "ms": {name: [round(v, 3) for v in vals] for name, vals in ms.items()},
+            "one_best_equals_host_search": one_best == out["host_search"],
+            "mean_text_length": float(np.mean([len(t) for t in one_best]))}
 
 
 def evaluate(args, hctr_amd, m, imgs, labels):
