@@ -25,9 +25,12 @@ ERR_ARG, ERR_HIP, ERR_STATE, ERR_KEY, ERR_SHAPE, ERR_EMPTY_LINE, ERR_NOMEM = -1,
 U8, F32, I64 = 0, 1, 2
 
 
+def _headers():
+    return [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "ngram_lm.h"), os.path.join(CSRC, "lm_flat.h"), HEADER]
+
+
 def _deps():
-    return [os.path.join(CSRC, s) for s, _ in SOURCES] + [os.path.join(CSRC, "kernels.h"),
-                                                          os.path.join(CSRC, "ngram_lm.h"), HEADER]
+    return [os.path.join(CSRC, s) for s, _ in SOURCES] + _headers()
 
 
 def source_hash():
@@ -100,7 +103,7 @@ def _build_locked(verbose):
         # an object is reused when its source, the headers and its command line are unchanged
         import hashlib
         h = hashlib.sha256(repr(cmd).encode())
-        for d in [os.path.join(CSRC, src), os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "ngram_lm.h"), HEADER]:
+        for d in [os.path.join(CSRC, src)] + _headers():
             with open(d, "rb") as f:
                 h.update(f.read())
         tag, tagfile = h.hexdigest(), obj + ".tag"
@@ -174,6 +177,16 @@ SIGNATURES = [
     ("hctr_nbest_topk", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, ctypes.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_nbest_logits", _I, [_VP, _VP, _I, _I, _I, _I, _I, _I, _I, ctypes.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_nbest", _I, [_VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, ctypes.c_double, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_lm_build", _I, [_VP, _VP, _I, ctypes.POINTER(_VP)]),
+    ("hctr_lm_order", _I, [_VP]),
+    ("hctr_lm_word_logp", ctypes.c_double, [_VP, _VP, _I, ctypes.c_int32]),
+    ("hctr_lm_free", None, [_VP]),
+    ("hctr_nbest_lm_topk", _I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _VP, _VP, _VP,
+                                _VP, _VP, _VP, _VP]),
+    ("hctr_nbest_lm_logits", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _VP, _VP,
+                                  _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_nbest_lm", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _VP, _VP, _VP,
+                           _VP, _VP, _VP, _VP]),
     ("hctr_beam_search", _I, [ctypes.POINTER(BeamParams), _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                               _VP, _VP, _VP]),
     ("hctr_ngram_load", _I, [ctypes.c_char_p, ctypes.POINTER(_VP)]),
@@ -181,6 +194,7 @@ SIGNATURES = [
     ("hctr_ngram_order", _I, [_VP]),
     ("hctr_ngram_word_id", ctypes.c_int32, [_VP, ctypes.c_char_p]),
     ("hctr_ngram_score", ctypes.c_double, [_VP, ctypes.c_char_p, _I, _I]),
+    ("hctr_ngram_word_logp", ctypes.c_double, [_VP, _VP, _I, ctypes.c_int32]),
     ("hctr_ngram_last_error", ctypes.c_char_p, []),
     ("hctr_comm_unique_id", _I, [_VP]),
     ("hctr_comm_create", _I, [ctypes.POINTER(_VP), _VP, _I, _I, _I]),

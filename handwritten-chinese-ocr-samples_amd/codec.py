@@ -60,6 +60,7 @@ class ArpaLM(object):
         if rc != 0:
             raise OSError("cannot load ARPA model: %s" % lib.hctr_ngram_last_error().decode("utf-8", "replace"))
         self._h = h
+        self._flat = {}
         self.path = str(arpa_path)
         self.order = lib.hctr_ngram_order(h)
 
@@ -69,8 +70,35 @@ class ArpaLM(object):
     def word_id(self, token):
         return int(_lib.load().hctr_ngram_word_id(self._h, token.encode("utf-8")))
 
+    def label_words(self, label_chars):
+        """int32 [C]: the LM word id of every label of a codec (``ctc_codec.characters``). A character the model does
+        not know, and the multi-character entries <blank> / <unknown>, take <unk>'s id as kenlm's vocabulary does (-1
+        when the model has no <unk>): the mapping ``ctc_codec.decode_frontend`` gives the host search."""
+        unk = self.word_id("<unk>")
+        return np.array([(self.word_id(c) if self.word_id(c) >= 0 else unk) if len(c) == 1 else unk
+                         for c in label_chars], dtype=np.int32)
+
+    def flat(self, label_chars):
+        """The ``hctr_lm`` handle of this model for a codec's characters (``hctr_lm_build``): the flat table the device
+        search probes, with ``label_words(label_chars)`` inside. Built once per character list and kept with the model."""
+        key = tuple(label_chars)
+        h = self._flat.get(key)
+        if h is None:
+            lib = _lib.load()
+            words = self.label_words(label_chars)
+            h = ctypes.c_void_p()
+            rc = lib.hctr_lm_build(self._h, _lib.ptr(words), len(words), ctypes.byref(h))
+            if rc != 0:
+                raise (MemoryError if rc == _lib.ERR_NOMEM else ValueError)(
+                    "cannot build the flat n-gram table: %s" % lib.hctr_ngram_last_error().decode("utf-8", "replace"))
+            self._flat[key] = h
+        return h
+
     def __del__(self):
         try:
+            for h in getattr(self, "_flat", {}).values():
+                _lib.load().hctr_lm_free(h)
+            self._flat = {}
             if getattr(self, "_h", None):
                 _lib.load().hctr_ngram_free(self._h)
                 self._h = None
@@ -192,11 +220,15 @@ class ctc_codec(object):
         rec = ctc.recognize_logits(self._context(), logits, on_dev)
         return self.labels_to_text(rec.label_lists()), rec
 
-    def nbest(self, preds, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None):
+    def nbest(self, preds, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None, lm=None, lm_panelty=2.0):
         """The ``n`` best texts of every line of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) with
         their log-probabilities, by the device prefix beam search without a language model (include/hctr_hip.h
         ``hctr_nbest_logits``; arguments as ``hctr_model.nbest``). Returns a ``ctc.NBest`` with ``.texts`` added: per
-        line the list of its hypotheses' strings, best first. ``decode`` and ``set_beam_search`` are not involved."""
+        line the list of its hypotheses' strings, best first. ``decode`` and ``set_beam_search`` are not involved.
+        With ``lm`` (an ``ArpaLM``) the search is the reference's n-gram-scored one, on the device
+        (``hctr_nbest_lm_logits``): every step ranks by ``logp + lm_score(prefix + greedy suffix) * lm_panelty + length *
+        len_bonus`` over the reference's end steps, ``.lm_scores`` holds the n-gram score of each text, and a line whose
+        greedy text is empty returns no hypothesis (the reference's defaults are lm_panelty 2, len_bonus 5.8)."""
         from . import ctc
         logits, on_dev = self._as_logits(preds)
         W, B, C = (int(v) for v in logits.shape)
@@ -204,7 +236,9 @@ class ctc_codec(object):
             raise ValueError("logits have %d classes, codec has %d" % (C, len(self.characters)))
         if W == 0:
             raise ValueError("preds have no steps (W = 0)")
-        res = ctc.nbest_logits(self._context(), logits, on_dev, n, beam, min(int(depth), C), len_bonus, input_lengths)
+        flat = None if lm is None else lm.flat(self.characters)
+        res = ctc.nbest_logits(self._context(), logits, on_dev, n, beam, min(int(depth), C), len_bonus, input_lengths,
+                               lm=flat, lm_panelty=lm_panelty)
         res.texts = [self.labels_to_text(line) for line in res.label_lists()]
         return res
 

@@ -194,6 +194,11 @@ struct hctr_ctx {
     // CTC loss scratch (hctr_ctc_loss*): per-line tables, per-line results and the emission rows; grows, never shrinks
     char* ctc_buf = nullptr;
     size_t ctc_cap = 0;
+    // device copy of the most recently used hctr_lm (hctr_nbest_lm*): its table and label -> word map, recognised by
+    // the serial number stored in the object (0 = none)
+    LmSlot* lm_slots = nullptr;
+    int32_t* lm_words = nullptr;
+    uint64_t lm_serial = 0;
 };
 
 namespace {
@@ -1683,7 +1688,50 @@ struct NbestCall {
     int32_t *d_T = nullptr, *d_lab = nullptr, *d_len = nullptr, *d_cnt = nullptr;
     double *d_logp = nullptr, *d_score = nullptr;
     int2* d_hist = nullptr;
+    // the LM-scored search (hctr_nbest_lm*): lm == null is the zero-LM search, with none of the below
+    const hctr_lm* lm = nullptr;
+    double lm_panelty = 0.0;
+    double* o_lm = nullptr;       // the caller's [B][nbest], may be null
+    int32_t *d_end = nullptr, *d_wid = nullptr;
+    int4* d_suf = nullptr;
+    double* d_lm = nullptr;
 };
+
+// the extra arguments of hctr_nbest_lm*
+int nbest_lm_prepare(hctr_ctx* c, NbestCall* n, const hctr_lm* lm, double lm_panelty, double* lm_score) {
+    if (!lm) return fail(c, HCTR_ERR_ARG, "lm is NULL");
+    if (lm_panelty != lm_panelty) return fail(c, HCTR_ERR_ARG, "lm_panelty is NaN");
+    if (lm->C != n->C) return fail(c, HCTR_ERR_ARG, "lm was built for %d classes, the call has %d", lm->C, n->C);
+    n->lm = lm; n->lm_panelty = lm_panelty; n->o_lm = lm_score;
+    return HCTR_OK;
+}
+
+// the context's device copy of the call's model: uploaded when the context holds another one (or none)
+int lm_on_device(hctr_ctx* c, const hctr_lm* lm) {
+    if (c->lm_serial == lm->serial) return HCTR_OK;
+    c->lm_serial = 0;
+    if (c->lm_slots) (void)hipFree(c->lm_slots);
+    if (c->lm_words) (void)hipFree(c->lm_words);
+    c->lm_slots = nullptr; c->lm_words = nullptr;
+    const size_t slot_b = lm->slots.size() * sizeof(LmSlot), word_b = lm->label_words.size() * 4;
+    void *ps = nullptr, *pw = nullptr;
+    hipError_t e = hipMalloc(&ps, slot_b);
+    if (e == hipSuccess) {
+        e = hipMalloc(&pw, word_b);
+        if (e != hipSuccess) (void)hipFree(ps);
+    }
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, HCTR_ERR_NOMEM, "no device memory for the n-gram table (%zu bytes): %s", slot_b + word_b,
+                    hipGetErrorString(e));
+    }
+    c->lm_slots = (LmSlot*)ps; c->lm_words = (int32_t*)pw;
+    HIP_TRY(c, hipMemcpyAsync(ps, lm->slots.data(), slot_b, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(pw, lm->label_words.data(), word_b, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the model is the caller's: it may be freed after this call)
+    c->lm_serial = lm->serial;
+    return HCTR_OK;
+}
 
 int nbest_prepare(hctr_ctx* c, int B, int W, int C, int k, int beam, int nbest, double len_bonus,
                   const int32_t* input_lengths, const NbestOut& o, NbestCall* n) {
@@ -1709,7 +1757,9 @@ int nbest_scratch(hctr_ctx* c, NbestCall* n, int lines) {
     const size_t T_b = align256((size_t)n->B * 4), hist_b = align256((size_t)lines * n->W * n->beam * sizeof(int2)),
                  lab_b = align256(ln * n->W * 4), i32_b = align256(ln * 4), f64_b = align256(ln * 8),
                  cnt_b = align256((size_t)lines * 4);
-    TRY(ctc_reserve(c, T_b + hist_b + lab_b + i32_b + 2 * f64_b + cnt_b));
+    const size_t suf_b = align256((size_t)lines * n->W * sizeof(int4)), wid_b = align256((size_t)lines * n->W * n->k * 4);
+    TRY(ctc_reserve(c, T_b + hist_b + lab_b + i32_b + 2 * f64_b + cnt_b + (n->lm ? cnt_b + suf_b + wid_b + f64_b : 0)));
+    if (n->lm) TRY(lm_on_device(c, n->lm));
     char* q = c->ctc_buf;
     n->d_T = (int32_t*)q; q += T_b;
     n->d_hist = (int2*)q; q += hist_b;
@@ -1717,7 +1767,13 @@ int nbest_scratch(hctr_ctx* c, NbestCall* n, int lines) {
     n->d_logp = (double*)q; q += f64_b;
     n->d_score = (double*)q; q += f64_b;
     n->d_len = (int32_t*)q; q += i32_b;
-    n->d_cnt = (int32_t*)q;
+    n->d_cnt = (int32_t*)q; q += cnt_b;
+    if (n->lm) {
+        n->d_suf = (int4*)q; q += suf_b;
+        n->d_lm = (double*)q; q += f64_b;
+        n->d_wid = (int32_t*)q; q += wid_b;
+        n->d_end = (int32_t*)q;
+    }
     HIP_TRY(c, hipMemcpyAsync(n->d_T, n->T.data(), (size_t)n->B * 4, hipMemcpyHostToDevice, c->stream));
     return HCTR_OK;
 }
@@ -1727,10 +1783,23 @@ int nbest_launch(hctr_ctx* c, const NbestCall& n, const int32_t* d_idx, const fl
     const size_t ln = (size_t)nb * n.nbest;
     Prof pf(c);
     if (n.o.labels) HIP_TRY(c, hipMemsetAsync(n.d_lab, 0, ln * n.W * 4, c->stream));
-    PROF_TRY(pf, "prefix_beam", launch_prefix_beam(d_idx, d_lp, nb, n.W, n.k, n.C, n.beam, n.nbest, n.len_bonus,
-                                                   n.d_T + b0, n.d_hist, n.d_len, n.d_logp, n.d_score, n.d_cnt, c->stream));
+    const int32_t* d_steps = n.d_T + b0;
+    if (n.lm) {
+        PROF_TRY(pf, "beam_lm_prepass", launch_beam_lm_prepass(d_idx, nb, n.W, n.k, n.C, n.d_T + b0, c->lm_words, n.d_wid,
+                                                               n.d_suf, n.d_end, c->stream));
+        BeamLm lm;
+        lm.table = LmView{c->lm_slots, (uint32_t)n.lm->slots.size() - 1u, n.lm->order, n.lm->unk};
+        lm.wid = n.d_wid; lm.suffix = n.d_suf; lm.lm_panelty = n.lm_panelty; lm.bos = n.lm->bos; lm.o_lm = n.d_lm;
+        d_steps = n.d_end;
+        PROF_TRY(pf, "prefix_beam_lm", launch_prefix_beam_lm(d_idx, d_lp, nb, n.W, n.k, n.C, n.beam, n.nbest, n.len_bonus,
+                                                             d_steps, lm, n.d_hist, n.d_len, n.d_logp, n.d_score, n.d_cnt,
+                                                             c->stream));
+    } else {
+        PROF_TRY(pf, "prefix_beam", launch_prefix_beam(d_idx, d_lp, nb, n.W, n.k, n.C, n.beam, n.nbest, n.len_bonus,
+                                                       d_steps, n.d_hist, n.d_len, n.d_logp, n.d_score, n.d_cnt, c->stream));
+    }
     if (n.o.labels)
-        PROF_TRY(pf, "prefix_backtrace", launch_prefix_backtrace(n.d_hist, n.d_T + b0, nb, n.W, n.beam, n.nbest, n.d_len,
+        PROF_TRY(pf, "prefix_backtrace", launch_prefix_backtrace(n.d_hist, d_steps, nb, n.W, n.beam, n.nbest, n.d_len,
                                                                  n.d_cnt, n.d_lab, c->stream));
     auto fetch = [&](void* dst, const void* src, size_t bytes) {
         return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
@@ -1741,6 +1810,7 @@ int nbest_launch(hctr_ctx* c, const NbestCall& n, const int32_t* d_idx, const fl
     HIP_TRY(c, fetch(n.o.logp ? n.o.logp + lo : nullptr, n.d_logp, ln * 8));
     HIP_TRY(c, fetch(n.o.score ? n.o.score + lo : nullptr, n.d_score, ln * 8));
     HIP_TRY(c, fetch(n.o.count ? n.o.count + b0 : nullptr, n.d_cnt, (size_t)nb * 4));
+    if (n.lm) HIP_TRY(c, fetch(n.o_lm ? n.o_lm + lo : nullptr, n.d_lm, ln * 8));
     return HCTR_OK;
 }
 
@@ -1819,6 +1889,8 @@ void hctr_destroy(hctr_ctx* c) {
     free_pool(c->wallocs);
     free_pool(c->beam_allocs);
     if (c->ctc_buf) (void)hipFree(c->ctc_buf);
+    if (c->lm_slots) (void)hipFree(c->lm_slots);
+    if (c->lm_words) (void)hipFree(c->lm_words);
     if (c->stamp_buf) (void)hipFree(c->stamp_buf);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -2216,14 +2288,22 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
     });
 }
 
-int hctr_nbest_topk(hctr_ctx* c, const int32_t* topk_idx, const float* topk_logp, int W, int B, int C, int k, int beam,
-                    int nbest, double len_bonus, const int32_t* input_lengths, int32_t* labels, int32_t* lengths,
-                    double* logp, double* score, int32_t* count) {
+// The three N-best entry points, each with and without an n-gram model: `lm` (null or the three extra arguments of
+// hctr_nbest_lm*) is all that tells the two apart.
+struct NbestLmArgs {
+    const hctr_lm* lm;
+    double lm_panelty;
+    double* lm_score;
+};
+
+static int nbest_topk_impl(hctr_ctx* c, const NbestLmArgs* lm, const int32_t* topk_idx, const float* topk_logp, int W, int B,
+                           int C, int k, int beam, int nbest, double len_bonus, const int32_t* input_lengths,
+                           const NbestOut& o) {
     return guard(c, [&]() -> int {
         TRY(check_logits_args(c, W, B, C, topk_idx && topk_logp));
         NbestCall n;
-        TRY(nbest_prepare(c, B, W, C, k, beam, nbest, len_bonus, input_lengths, NbestOut{labels, lengths, logp, score, count},
-                          &n));
+        TRY(nbest_prepare(c, B, W, C, k, beam, nbest, len_bonus, input_lengths, o, &n));
+        if (lm) TRY(nbest_lm_prepare(c, &n, lm->lm, lm->lm_panelty, lm->lm_score));
         if (B == 0) return HCTR_OK;
         // the lists are the caller's: classes in [0, C) and distinct within a row, as the front end produces them
         const size_t rows = (size_t)W * B;
@@ -2254,14 +2334,14 @@ int hctr_nbest_topk(hctr_ctx* c, const int32_t* topk_idx, const float* topk_logp
     });
 }
 
-int hctr_nbest_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W, int B, int C, int k, int beam, int nbest,
-                      double len_bonus, const int32_t* input_lengths, int32_t* labels, int32_t* lengths, double* logp,
-                      double* score, int32_t* count) {
+static int nbest_logits_impl(hctr_ctx* c, const NbestLmArgs* lm, const float* logits_wbc, int on_device, int W, int B, int C,
+                             int k, int beam, int nbest, double len_bonus, const int32_t* input_lengths,
+                             const NbestOut& o) {
     return guard(c, [&]() -> int {
         TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
         NbestCall n;
-        TRY(nbest_prepare(c, B, W, C, k, beam, nbest, len_bonus, input_lengths, NbestOut{labels, lengths, logp, score, count},
-                          &n));
+        TRY(nbest_prepare(c, B, W, C, k, beam, nbest, len_bonus, input_lengths, o, &n));
+        if (lm) TRY(nbest_lm_prepare(c, &n, lm->lm, lm->lm_panelty, lm->lm_score));
         if (B == 0) return HCTR_OK;
         HIP_TRY(c, hipSetDevice(c->device));
         prof_reset(c);
@@ -2278,14 +2358,14 @@ int hctr_nbest_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W
     });
 }
 
-int hctr_nbest(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W, int k,
-               int beam, int nbest, double len_bonus, const int32_t* input_lengths, int32_t* labels, int32_t* lengths,
-               double* logp, double* score, int32_t* count) {
+static int nbest_images_impl(hctr_ctx* c, const NbestLmArgs* lm, const void* img, int img_dtype, int img_on_device,
+                             const int32_t* widths, int B, int W, int k, int beam, int nbest, double len_bonus,
+                             const int32_t* input_lengths, const NbestOut& o) {
     return guard(c, [&]() -> int {
         TRY(check_forward_args(c, img, img_dtype, B, W));
         NbestCall n;
-        TRY(nbest_prepare(c, B, W, c->num_classes, k, beam, nbest, len_bonus, input_lengths,
-                          NbestOut{labels, lengths, logp, score, count}, &n));
+        TRY(nbest_prepare(c, B, W, c->num_classes, k, beam, nbest, len_bonus, input_lengths, o, &n));
+        if (lm) TRY(nbest_lm_prepare(c, &n, lm->lm, lm->lm_panelty, lm->lm_score));
         if (B == 0) return HCTR_OK;
         HIP_TRY(c, hipSetDevice(c->device));
         const Batch in{img, img_dtype, img_on_device, widths, B, W};
@@ -2299,6 +2379,53 @@ int hctr_nbest(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, c
         free_pool(c->beam_allocs);
         return rc;
     });
+}
+
+int hctr_nbest_topk(hctr_ctx* c, const int32_t* topk_idx, const float* topk_logp, int W, int B, int C, int k, int beam,
+                    int nbest, double len_bonus, const int32_t* input_lengths, int32_t* labels, int32_t* lengths,
+                    double* logp, double* score, int32_t* count) {
+    return nbest_topk_impl(c, nullptr, topk_idx, topk_logp, W, B, C, k, beam, nbest, len_bonus, input_lengths,
+                           NbestOut{labels, lengths, logp, score, count});
+}
+
+int hctr_nbest_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W, int B, int C, int k, int beam, int nbest,
+                      double len_bonus, const int32_t* input_lengths, int32_t* labels, int32_t* lengths, double* logp,
+                      double* score, int32_t* count) {
+    return nbest_logits_impl(c, nullptr, logits_wbc, on_device, W, B, C, k, beam, nbest, len_bonus, input_lengths,
+                             NbestOut{labels, lengths, logp, score, count});
+}
+
+int hctr_nbest(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W, int k,
+               int beam, int nbest, double len_bonus, const int32_t* input_lengths, int32_t* labels, int32_t* lengths,
+               double* logp, double* score, int32_t* count) {
+    return nbest_images_impl(c, nullptr, img, img_dtype, img_on_device, widths, B, W, k, beam, nbest, len_bonus,
+                             input_lengths, NbestOut{labels, lengths, logp, score, count});
+}
+
+int hctr_nbest_lm_topk(hctr_ctx* c, const hctr_lm* lm, const int32_t* topk_idx, const float* topk_logp, int W, int B, int C,
+                       int k, int beam, int nbest, double lm_panelty, double len_bonus, const int32_t* input_lengths,
+                       int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count, double* lm_score) {
+    const NbestLmArgs a{lm, lm_panelty, lm_score};
+    return nbest_topk_impl(c, &a, topk_idx, topk_logp, W, B, C, k, beam, nbest, len_bonus, input_lengths,
+                           NbestOut{labels, lengths, logp, score, count});
+}
+
+int hctr_nbest_lm_logits(hctr_ctx* c, const hctr_lm* lm, const float* logits_wbc, int on_device, int W, int B, int C, int k,
+                         int beam, int nbest, double lm_panelty, double len_bonus, const int32_t* input_lengths,
+                         int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count,
+                         double* lm_score) {
+    const NbestLmArgs a{lm, lm_panelty, lm_score};
+    return nbest_logits_impl(c, &a, logits_wbc, on_device, W, B, C, k, beam, nbest, len_bonus, input_lengths,
+                             NbestOut{labels, lengths, logp, score, count});
+}
+
+int hctr_nbest_lm(hctr_ctx* c, const hctr_lm* lm, const void* img, int img_dtype, int img_on_device, const int32_t* widths,
+                  int B, int W, int k, int beam, int nbest, double lm_panelty, double len_bonus,
+                  const int32_t* input_lengths, int32_t* labels, int32_t* lengths, double* logp, double* score,
+                  int32_t* count, double* lm_score) {
+    const NbestLmArgs a{lm, lm_panelty, lm_score};
+    return nbest_images_impl(c, &a, img, img_dtype, img_on_device, widths, B, W, k, beam, nbest, len_bonus, input_lengths,
+                             NbestOut{labels, lengths, logp, score, count});
 }
 
 int hctr_ctc_loss(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "lm_flat.h"
+
 namespace hctr {
 
 typedef _Float16 half_t;
@@ -295,6 +297,27 @@ hipError_t launch_prefix_beam(const int32_t* idx, const float* lp, int nb, int W
                               int32_t* cnt, hipStream_t s);
 hipError_t launch_prefix_backtrace(const int2* hist, const int32_t* T, int nb, int W, int beam, int nbest,
                                    const int32_t* len, const int32_t* cnt, int32_t* labels, hipStream_t s);
+
+// ---- the same search scored by an n-gram model (hctr_nbest_lm*; lm_flat.h has the table and the lookup) ----
+// launch_beam_lm_prepass: from the lists and T[b] (the columns of line b that count) the word ids of every list entry
+//   (wid, laid out as idx; words[C] = label -> word id), suffix[b * W + t] = the first <= 4 greedy entries with a stamp
+//   > t as word ids (-2 = no more) and end[b] = min(last greedy stamp + 4, T[b]), 0 for an empty greedy text;
+// launch_prefix_beam_lm: launch_prefix_beam over end[b] steps with every entry ranked by log-prob + (n-gram score of
+//   prefix + suffix) * lm_panelty + len * len_bonus; score is that total, o_lm[nb][nbest] the n-gram score of the text
+//   (-inf beyond cnt[b]); a line with end[b] = 0 returns cnt[b] = 0. launch_prefix_backtrace then takes end as its T.
+struct BeamLm {
+    LmView table{};               // device slots
+    const int32_t* wid = nullptr;
+    const int4* suffix = nullptr;
+    double lm_panelty = 0.0;
+    int32_t bos = -1;
+    double* o_lm = nullptr;
+};
+hipError_t launch_beam_lm_prepass(const int32_t* idx, int nb, int W, int k, int C, const int32_t* T, const int32_t* words,
+                                  int32_t* wid, int4* suffix, int32_t* end, hipStream_t s);
+hipError_t launch_prefix_beam_lm(const int32_t* idx, const float* lp, int nb, int W, int k, int C, int beam, int nbest,
+                                 double len_bonus, const int32_t* end, const BeamLm& lm, int2* hist, int32_t* len,
+                                 double* logp, double* score, int32_t* cnt, hipStream_t s);
 
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {

@@ -4136,20 +4136,35 @@ __device__ __forceinline__ unsigned long long beam_mix(unsigned long long h, int
     return z ^ (z >> 31);
 }
 
+// total() with the n-gram model: pt = s * lm_panelty + len * len_bonus, each product rounded on its own, then log-prob + pt
+__device__ __forceinline__ double beam_total_lm(double logp, double s, int len, double lm_panelty, double len_bonus) {
+#pragma clang fp contract(off)
+    const double pt = s * lm_panelty + (double)len * len_bonus;
+    return logp + pt;
+}
+
 // what the ranking reads of a slot, one 16-byte LDS load: the total's integer image and the first-touch key
 struct alignas(16) BeamSortKey {
     unsigned long long ord;
     unsigned key, pad;
 };
 
-template <int BEAM, int K, int NW>
+// LM = true is the search of hctr_nbest_lm* (DESIGN.md 4g): the same steps, slots, merges, keys and ranks; besides, a
+// hypothesis carries the n-gram score of its prefix (float64, summed left to right) and its last word ids in the fixed
+// form of lm_word_logp, an extension adds one term to its parent's, and every valid entry is ranked by its log-prob +
+// (score of prefix + the step's suffix) * lm_panelty + len * len_bonus. Tl holds the end steps of the pre-pass, 0 for a
+// line without a greedy text, which returns nothing. With LM = false none of it is compiled.
+template <int BEAM, int K, int NW, bool LM>
 __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __restrict__ idx, const float* __restrict__ lp,
                                                               int nb, int W, int k, int unk, int beam, int nbest,
                                                               double len_bonus, const int32_t* __restrict__ Tl,
                                                               int2* __restrict__ hist, int32_t* __restrict__ o_len,
                                                               double* __restrict__ o_logp, double* __restrict__ o_score,
-                                                              int32_t* __restrict__ o_cnt) {
+                                                              int32_t* __restrict__ o_cnt, const BeamLm lm) {
     constexpr int NT = 64 * NW, SLOTS = BEAM * (K + 1);
+    constexpr int LB = LM ? BEAM : 1, LS = LM ? SLOTS : 1, LK = LM ? K : 1, NCX = kLmMaxOrder - 1;
+    __shared__ double h_lm[2][LB], e_lm[LS];       // n-gram score of a hypothesis' / an entry's prefix
+    __shared__ int h_cx[2][LB][NCX], r_w[2][LK];   // its context; the word ids of the row's classes
     constexpr double NINF = -__builtin_huge_val();
     // the list, double-buffered: place r of step t's list is written while step t's slots still read the old one
     __shared__ double h_pb[2][BEAM], h_pnb[2][BEAM], h_tot[2][BEAM];
@@ -4166,10 +4181,13 @@ __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __r
     int2* __restrict__ hb = hist + (int64_t)b * W * beam;
 
     // a row's classes into LDS (wave 0; every lane of it takes part in the ballots)
-    auto put_row = [&](int buf, bool have, int c, float l) {
+    auto put_row = [&](int buf, bool have, int c, float l, int w) {
         const unsigned long long usable = __ballot(have && (unsigned)c < (unsigned)unk);
         const unsigned long long blank = __ballot(have && c == 0);
         if (have) { r_cls[buf][tid] = c; r_lp[buf][tid] = (double)l; }
+        if constexpr (LM) {
+            if (have) r_w[buf][tid] = w;
+        }
         if (tid == 0) {
             r_meta[buf][0] = usable ? __ffsll((long long)usable) - 1 : -1;
             r_meta[buf][1] = blank ? __ffsll((long long)blank) - 1 : -1;
@@ -4178,13 +4196,23 @@ __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __r
     if (tid < 64) {
         const bool have = T > 0 && tid < k;
         const int64_t a = (int64_t)b * k + tid;
-        put_row(0, have, have ? idx[a] : 0, have ? lp[a] : 0.f);
+        int w = -1;
+        if constexpr (LM) w = have ? lm.wid[a] : -1;
+        put_row(0, have, have ? idx[a] : 0, have ? lp[a] : 0.f, w);
     }
     if (tid == 0) {                                // [((), 0, -inf)]
         h_pb[0][0] = 0.0; h_pnb[0][0] = NINF; h_tot[0][0] = 0.0;
         h_hash[0][0] = 0x243F6A8885A308D3ull; h_par[0][0] = 0ull;
         h_len[0][0] = 0; h_last[0][0] = -1;
         s_n[0] = 1;
+        if constexpr (LM) {                        // score 0 in the <s> context
+            h_lm[0][0] = 0.0;
+            for (int q = 0; q < NCX; ++q) h_cx[0][0][q] = q == NCX - 1 ? lm.bos : -1;
+        }
+    }
+    int4 sfx = make_int4(-2, -2, -2, -2);          // the step's suffix as word ids, -2 = no more
+    if constexpr (LM) {
+        if (T > 0) sfx = lm.suffix[(int64_t)b * W];
     }
     __syncthreads();
     int cur = 0;
@@ -4192,12 +4220,17 @@ __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __r
         const int nxt = cur ^ 1, n = s_n[cur];
         if (n == 0) break;                         // (block-uniform) every class of some row was <unknown>: nothing is left
         const bool pre = t + 1 < T && tid < k;
-        int pc = 0;
+        int pc = 0, pw = -1;
         float pl = 0.f;
         if (pre) {
             const int64_t a = ((int64_t)(t + 1) * nb + b) * k + tid;
             pc = idx[a];
             pl = lp[a];
+            if constexpr (LM) pw = lm.wid[a];
+        }
+        int4 sfx_next = sfx;
+        if constexpr (LM) {
+            if (t + 1 < T) sfx_next = lm.suffix[(int64_t)b * W + t + 1];
         }
         const int j0 = r_meta[cur][0], jb = r_meta[cur][1], E = n * k1;
         // entries
@@ -4249,8 +4282,33 @@ __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __r
             }
             valid = valid && in;
             nvalid += __popcll(__ballot(valid));
+            double total = 0.0;
+            if constexpr (LM) {
+                if (valid) {
+                    int cx[NCX];
+#pragma unroll
+                    for (int q = 0; q < NCX; ++q) cx[q] = h_cx[cur][i][q];
+                    double sc = h_lm[cur][i];
+                    if (jj) {
+                        const int w = r_w[cur][jj - 1];
+                        sc += lm_word_logp(lm.table, cx, w);
+                        lm_roll(cx, w);
+                    }
+                    e_lm[e] = sc;
+                    int4 rest = sfx;
+#pragma unroll 1
+                    for (int q = 0; q < 4 && rest.x != -2; ++q) {
+                        sc += lm_word_logp(lm.table, cx, rest.x);
+                        lm_roll(cx, rest.x);
+                        rest = make_int4(rest.y, rest.z, rest.w, -2);
+                    }
+                    total = beam_total_lm(tot, sc, leni + (jj ? 1 : 0), lm.lm_panelty, len_bonus);
+                }
+            } else {
+                total = beam_total(tot, leni + (jj ? 1 : 0), len_bonus);
+            }
             if (in) {
-                e_sort[e] = BeamSortKey{valid ? beam_ord(beam_total(tot, leni + (jj ? 1 : 0), len_bonus)) : 0ull, key, 0u};
+                e_sort[e] = BeamSortKey{valid ? beam_ord(total) : 0ull, key, 0u};
                 e_pb[e] = pb; e_pnb[e] = pnb; e_tot[e] = tot;
             }
         }
@@ -4280,13 +4338,21 @@ __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __r
                 h_last[nxt][rank] = jj ? c : h_last[cur][i];
                 h_hash[nxt][rank] = jj ? beam_mix(hi, c) : hi;
                 h_par[nxt][rank] = jj ? hi : h_par[cur][i];
+                if constexpr (LM) {
+                    h_lm[nxt][rank] = e_lm[e];
+                    const int w = jj ? r_w[cur][jj - 1] : -1;
+#pragma unroll
+                    for (int q = 0; q < NCX; ++q)
+                        h_cx[nxt][rank][q] = !jj ? h_cx[cur][i][q] : q + 1 < NCX ? h_cx[cur][i][q + 1] : w;
+                }
                 hb[(int64_t)t * beam + rank] = make_int2(i, c);
             }
         }
-        if (tid < 64) put_row(nxt, pre, pc, pl);
+        if (tid < 64) put_row(nxt, pre, pc, pl, pw);
+        sfx = sfx_next;
         __syncthreads();
     }
-    const int n = s_n[cur];
+    const int n = LM && T == 0 ? 0 : s_n[cur];
     if (tid < nbest) {
         const bool have = tid < n;
         const int len = have ? h_len[cur][tid] : 0;
@@ -4294,7 +4360,13 @@ __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __r
         const int64_t o = (int64_t)b * nbest + tid;
         o_len[o] = len;
         o_logp[o] = logp;
-        o_score[o] = have ? beam_total(logp, len, len_bonus) : NINF;
+        if constexpr (LM) {
+            const double sc = have ? h_lm[cur][tid] : NINF;
+            o_score[o] = have ? beam_total_lm(logp, sc, len, lm.lm_panelty, len_bonus) : NINF;
+            lm.o_lm[o] = sc;
+        } else {
+            o_score[o] = have ? beam_total(logp, len, len_bonus) : NINF;
+        }
     }
     if (tid == 0) o_cnt[b] = min(n, nbest);
 }
@@ -4319,6 +4391,54 @@ __global__ __launch_bounds__(64) void prefix_backtrace_kernel(const int2* __rest
     }
 }
 
+// Pre-pass of the LM-scored search, one workgroup per line over its first L = Tl[b] columns: the LM word id of every
+// class of the line's lists (wid, laid out as idx); the greedy line of utils/ctc_codec.py:188-195 - the top-1 class of
+// column t is kept when it is not blank, not <unknown> and not the top-1 class of column t - 1 - and from it, per step
+// t, the first <= 4 kept entries with a stamp > t as word ids (suffix[b * W + t], -2 = no more) and the end step
+// min(last stamp + 4, L), 0 when nothing was kept. The suffixes come from one backward walk (thread 0, a window of four)
+// through 256-column chunks staged in LDS; everything else is spread over the threads.
+__global__ __launch_bounds__(256) void beam_lm_prepass_kernel(const int32_t* __restrict__ idx, int nb, int W, int k, int C,
+                                                              const int32_t* __restrict__ Tl,
+                                                              const int32_t* __restrict__ words, int32_t* __restrict__ wid,
+                                                              int4* __restrict__ suffix, int32_t* __restrict__ end) {
+    __shared__ int s_w[256];                       // word id of the chunk's kept entries, -2 = column not kept
+    __shared__ int4 s_suf[256];
+    const int b = blockIdx.x, tid = threadIdx.x, unk = C - 1;
+    const int L = min(max(Tl[b], 0), W);
+    for (int e = tid; e < L * k; e += 256) {
+        const int t = e / k, j = e - t * k;
+        const int64_t a = ((int64_t)t * nb + b) * k + j;
+        const int c = idx[a];
+        wid[a] = (unsigned)c < (unsigned)C ? words[c] : -1;
+    }
+    int4 win = make_int4(-2, -2, -2, -2);
+    int last = -1;
+    for (int base = L > 0 ? ((L - 1) / 256) * 256 : -1; base >= 0; base -= 256) {
+        const int t = base + tid;
+        int w = -2;
+        if (t < L) {
+            const int c = idx[((int64_t)t * nb + b) * k];
+            const int prev = t > 0 ? idx[((int64_t)(t - 1) * nb + b) * k] : -1;
+            if (c != 0 && c != unk && c != prev) w = (unsigned)c < (unsigned)C ? words[c] : -1;
+        }
+        s_w[tid] = w;
+        __syncthreads();
+        if (tid == 0) {
+            for (int u = 255; u >= 0; --u) {
+                s_suf[u] = win;
+                const int wu = s_w[u];
+                if (wu != -2) {
+                    if (last < 0) last = base + u;
+                    win = make_int4(wu, win.x, win.y, win.z);
+                }
+            }
+        }
+        __syncthreads();
+        if (t < L) suffix[(int64_t)b * W + t] = s_suf[tid];
+    }
+    if (tid == 0) end[b] = last < 0 ? 0 : min(last + 4, L);
+}
+
 template <int BEAM_, int K_, int NW_>
 struct BeamRung {
     static constexpr int BEAM = BEAM_, K = K_, NW = NW_;
@@ -4335,8 +4455,35 @@ hipError_t launch_prefix_beam(const int32_t* idx, const float* lp, int nb, int W
     if (k < 1 || beam < 1 || nbest < 1 || nbest > beam || C < 2 || W < 1) return hipErrorInvalidValue;
 #define BEAM_RUNG(BEAM, K, NW)                                                                                       \
     if (beam <= BEAM && k <= K) {                                                                                    \
-        hipLaunchKernelGGL((prefix_beam_kernel<BEAM, K, NW>), dim3((unsigned)nb), dim3(64 * NW), 0, s, idx, lp, nb, W, k,   \
-                           C - 1, beam, nbest, len_bonus, T, hist, len, logp, score, cnt);                           \
+        hipLaunchKernelGGL((prefix_beam_kernel<BEAM, K, NW, false>), dim3((unsigned)nb), dim3(64 * NW), 0, s, idx, lp, nb, \
+                           W, k, C - 1, beam, nbest, len_bonus, T, hist, len, logp, score, cnt, BeamLm{});          \
+        return hipGetLastError();                                                                                    \
+    }
+    HCTR_BEAM_LADDER(BEAM_RUNG)
+#undef BEAM_RUNG
+    return hipErrorInvalidValue;
+}
+
+hipError_t launch_beam_lm_prepass(const int32_t* idx, int nb, int W, int k, int C, const int32_t* T, const int32_t* words,
+                                  int32_t* wid, int4* suffix, int32_t* end, hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+    if (k < 1 || C < 2 || W < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(beam_lm_prepass_kernel, dim3((unsigned)nb), dim3(256), 0, s, idx, nb, W, k, C, T, words, wid, suffix,
+                       end);
+    return hipGetLastError();
+}
+
+hipError_t launch_prefix_beam_lm(const int32_t* idx, const float* lp, int nb, int W, int k, int C, int beam, int nbest,
+                                 double len_bonus, const int32_t* end, const BeamLm& lm, int2* hist, int32_t* len,
+                                 double* logp, double* score, int32_t* cnt, hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+    if (k < 1 || beam < 1 || nbest < 1 || nbest > beam || C < 2 || W < 1) return hipErrorInvalidValue;
+    if (!lm.table.slots || lm.table.order < 1 || lm.table.order > kLmMaxOrder || !lm.wid || !lm.suffix || !lm.o_lm)
+        return hipErrorInvalidValue;
+#define BEAM_RUNG(BEAM, K, NW)                                                                                       \
+    if (beam <= BEAM && k <= K) {                                                                                    \
+        hipLaunchKernelGGL((prefix_beam_kernel<BEAM, K, NW, true>), dim3((unsigned)nb), dim3(64 * NW), 0, s, idx, lp, nb,  \
+                           W, k, C - 1, beam, nbest, len_bonus, end, hist, len, logp, score, cnt, lm);               \
         return hipGetLastError();                                                                                    \
     }
     HCTR_BEAM_LADDER(BEAM_RUNG)

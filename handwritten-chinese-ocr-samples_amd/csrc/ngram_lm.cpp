@@ -9,9 +9,11 @@
 // has none, kenlm's unknown_missing_logprob). Parity with the real kenlm binary is UNPINNED (module
 // absent here); the scorer is pinned by oracle/ctc_ref.py's ArpaRef and hand-computed cases.
 #include "ngram_lm.h"
+#include "lm_flat.h"
 
 #include "../../include/hctr_hip.h"
 
+#include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -206,5 +208,89 @@ static double ngram_score_impl(const hctr_ngram* lm, const char* sentence_utf8, 
     if (eos && lm->eos >= 0) total += hctr::ngram_word_logp(lm, ctx.data(), (int)ctx.size(), lm->eos);
     return total;
 }
+
+double hctr_ngram_word_logp(const hctr_ngram* lm, const int32_t* ctx, int nctx, int32_t word) {
+    if (!lm || nctx < 0 || (nctx > 0 && !ctx)) return std::numeric_limits<double>::quiet_NaN();
+    try {
+        return hctr::ngram_word_logp(lm, ctx, nctx, word);
+    } catch (...) {
+        return std::numeric_limits<double>::quiet_NaN();
+    }
+}
+
+// ---- the flat table (lm_flat.h): hctr_lm_build copies every n-gram of every order into one open-addressing table ----
+static int lm_build_impl(const hctr_ngram* lm, const int32_t* label_words, int C, hctr_lm** out) {
+    if (lm->order > hctr::kLmMaxOrder) {
+        g_ngram_error = "hctr_lm_build: the model has order " + std::to_string(lm->order) + ", the flat table holds up to " +
+                        std::to_string(hctr::kLmMaxOrder);
+        return HCTR_ERR_ARG;
+    }
+    const int32_t nwords = (int32_t)lm->words.size();
+    for (int c = 0; c < C; ++c)
+        if (label_words[c] < -1 || label_words[c] >= nwords) {
+            g_ngram_error = "hctr_lm_build: label_words[" + std::to_string(c) + "] is not a word id of the model";
+            return HCTR_ERR_ARG;
+        }
+    static std::atomic<uint64_t> serial{0};
+    std::unique_ptr<hctr_lm> h(new hctr_lm());
+    h->order = lm->order; h->C = C; h->bos = lm->bos; h->unk = lm->unk;
+    h->serial = ++serial;
+    h->label_words.assign(label_words, label_words + C);
+    size_t total = 0;
+    for (const auto& tab : lm->tables) total += tab.size();
+    size_t cap = 16;
+    while (cap < 2 * total) cap <<= 1;
+    if (cap > ((size_t)1 << 31)) { g_ngram_error = "hctr_lm_build: the model has too many n-grams"; return HCTR_ERR_ARG; }
+    hctr::LmSlot empty;
+    for (int i = 0; i < hctr::kLmMaxOrder; ++i) empty.ids[i] = i == 0 ? hctr::kLmEmpty : -1;
+    empty.logp = 0.f; empty.backoff = 0.f;
+    h->slots.assign(cap, empty);
+    const uint32_t mask = (uint32_t)(cap - 1);
+    for (size_t n = 0; n < lm->tables.size(); ++n)
+        for (const auto& kv : lm->tables[n]) {
+            hctr::LmKey key;
+            for (int i = 0; i < hctr::kLmMaxOrder; ++i) key.w[i] = -1;
+            memcpy(key.w, kv.first.data(), (n + 1) * 4);
+            uint32_t at = hctr::lm_hash(key.w, (int)n + 1) & mask;
+            while (h->slots[at].ids[0] != hctr::kLmEmpty) at = (at + 1) & mask;
+            hctr::LmSlot& s = h->slots[at];
+            for (int i = 0; i < hctr::kLmMaxOrder; ++i) s.ids[i] = key.w[i];
+            s.logp = kv.second.logp; s.backoff = kv.second.backoff;
+        }
+    *out = h.release();
+    return HCTR_OK;
+}
+
+int hctr_lm_build(const hctr_ngram* lm, const int32_t* label_words, int C, hctr_lm** out) {
+    if (out) *out = nullptr;
+    if (!lm || !label_words || !out || C < 2) {
+        try { g_ngram_error = "hctr_lm_build: lm / label_words / out is NULL or C < 2"; } catch (...) {}
+        return HCTR_ERR_ARG;
+    }
+    try {
+        return lm_build_impl(lm, label_words, C, out);
+    } catch (const std::bad_alloc&) {
+        try { g_ngram_error = "out of host memory while building the flat n-gram table"; } catch (...) {}
+        return HCTR_ERR_NOMEM;
+    } catch (...) {
+        try { g_ngram_error = "unexpected C++ exception while building the flat n-gram table"; } catch (...) {}
+        return HCTR_ERR_STATE;
+    }
+}
+
+int hctr_lm_order(const hctr_lm* lm) { return lm ? lm->order : 0; }
+
+double hctr_lm_word_logp(const hctr_lm* lm, const int32_t* ctx, int nctx, int32_t word) {
+    if (!lm || nctx < 0 || (nctx > 0 && !ctx)) return std::numeric_limits<double>::quiet_NaN();
+    int32_t cx[hctr::kLmMaxOrder - 1];
+    const int have = hctr::kLmMaxOrder - 1;
+    for (int i = 0; i < have; ++i) {               // right-aligned, -1 in front of a shorter context
+        const int src = nctx - have + i;
+        cx[i] = src >= 0 ? ctx[src] : -1;
+    }
+    return hctr::lm_word_logp(lm->view(), cx, word);
+}
+
+void hctr_lm_free(hctr_lm* lm) { delete lm; }
 
 }  // extern "C"

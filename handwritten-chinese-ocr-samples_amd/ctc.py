@@ -475,10 +475,12 @@ class NBest(object):
     ``lengths[b, i]`` entries of a hypothesis are valid, the rest zeros); ``logps`` float64 [B, n], the log-probability of
     each text over the alignments the pruned search kept; ``scores`` float64 [B, n], what the search ranked by
     (``logp + length * len_bonus``); ``counts`` int32 [B], how many hypotheses a line really has (unused slots have
-    length 0 and -inf)."""
+    length 0 and -inf). ``lm_scores`` is None without a language model; with one (``hctr_nbest_lm*``) it is float64
+    [B, n], the n-gram log10 score of each text, and ``scores`` is ``logp + lm_score * lm_panelty + length * len_bonus``."""
 
-    def __init__(self, labels, lengths, logps, scores, counts):
+    def __init__(self, labels, lengths, logps, scores, counts, lm_scores=None):
         self.labels, self.lengths, self.logps, self.scores, self.counts = labels, lengths, logps, scores, counts
+        self.lm_scores = lm_scores
 
     def __len__(self):
         return len(self.counts)
@@ -516,34 +518,60 @@ def _nbest_args(B, W, n, beam, depth, len_bonus, input_lengths):
     return n, beam, depth, ctypes.c_double(float(len_bonus)), il, out
 
 
-def nbest_topk(ctx, topk_idx, topk_logp, C, n=5, beam=10, len_bonus=0.0, input_lengths=None):
+def _lm_args(lm, lm_panelty, out):
+    """the extra arguments of hctr_nbest_lm*: ``lm`` is an ``hctr_lm`` handle (``codec.ArpaLM.flat``)"""
+    lm_scores = np.full(out[2].shape, -np.inf, np.float64)
+    return lm, ctypes.c_double(float(lm_panelty)), lm_scores
+
+
+def nbest_topk(ctx, topk_idx, topk_logp, C, n=5, beam=10, len_bonus=0.0, input_lengths=None, lm=None, lm_panelty=2.0):
     """NBest of front-end lists ``topk_idx`` int32 / ``topk_logp`` float32 [W, B, k] over ``C`` classes
-    (hctr_nbest_topk): the search alone."""
+    (hctr_nbest_topk): the search alone. With ``lm`` (an ``hctr_lm`` handle, ``codec.ArpaLM.flat``) the search is the
+    n-gram-scored one over the reference's own end steps (hctr_nbest_lm_topk), ranking by
+    ``logp + lm_score * lm_panelty + length * len_bonus``; ``lm_scores`` is then filled."""
     idx = np.ascontiguousarray(topk_idx, dtype=np.int32)
     lp = np.ascontiguousarray(topk_logp, dtype=np.float32)
     if idx.ndim != 3 or idx.shape != lp.shape:
         raise ValueError("topk_idx and topk_logp must both be [W,B,k]")
     W, B, k = (int(v) for v in idx.shape)
     n, beam, _, bonus, il, out = _nbest_args(B, W, n, beam, k, len_bonus, input_lengths)
+    if lm is not None:
+        lm, pen, lms = _lm_args(lm, lm_panelty, out)
+        _lib.check(_lib.load().hctr_nbest_lm_topk(ctx, lm, _lib.ptr(idx), _lib.ptr(lp), W, B, int(C), k, beam, n, pen, bonus,
+                                                  _lib.ptr(il), *[_lib.ptr(a) for a in out + (lms,)]), ctx)
+        return NBest(*out, lm_scores=lms)
     _lib.check(_lib.load().hctr_nbest_topk(ctx, _lib.ptr(idx), _lib.ptr(lp), W, B, int(C), k, beam, n, bonus,
                                            _lib.ptr(il), *[_lib.ptr(a) for a in out]), ctx)
     return NBest(*out)
 
 
-def nbest_logits(ctx, logits, on_dev, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None):
-    """NBest of caller logits / log-probs in WBC layout (hctr_nbest_logits): top-``depth`` per column, then the search."""
+def nbest_logits(ctx, logits, on_dev, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None, lm=None, lm_panelty=2.0):
+    """NBest of caller logits / log-probs in WBC layout (hctr_nbest_logits): top-``depth`` per column, then the search;
+    ``lm`` / ``lm_panelty`` as in ``nbest_topk`` (hctr_nbest_lm_logits)."""
     if len(logits.shape) != 3:
         raise ValueError("logits must be [W,B,C]")
     W, B, C = (int(v) for v in logits.shape)
     n, beam, depth, bonus, il, out = _nbest_args(B, W, n, beam, depth, len_bonus, input_lengths)
+    if lm is not None:
+        lm, pen, lms = _lm_args(lm, lm_panelty, out)
+        _lib.check(_lib.load().hctr_nbest_lm_logits(ctx, lm, _lib.ptr(logits), on_dev, W, B, C, depth, beam, n, pen, bonus,
+                                                    _lib.ptr(il), *[_lib.ptr(a) for a in out + (lms,)]), ctx)
+        return NBest(*out, lm_scores=lms)
     _lib.check(_lib.load().hctr_nbest_logits(ctx, _lib.ptr(logits), on_dev, W, B, C, depth, beam, n, bonus,
                                              _lib.ptr(il), *[_lib.ptr(a) for a in out]), ctx)
     return NBest(*out)
 
 
-def nbest_images(ctx, x, dt, on_dev, widths, B, W, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None):
-    """NBest of line images (hctr_nbest); x, dt, on_dev, widths as hctr_model._img_args / _widths give them."""
+def nbest_images(ctx, x, dt, on_dev, widths, B, W, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None, lm=None,
+                 lm_panelty=2.0):
+    """NBest of line images (hctr_nbest); x, dt, on_dev, widths as hctr_model._img_args / _widths give them; ``lm`` /
+    ``lm_panelty`` as in ``nbest_topk`` (hctr_nbest_lm)."""
     n, beam, depth, bonus, il, out = _nbest_args(B, W, n, beam, depth, len_bonus, input_lengths)
+    if lm is not None:
+        lm, pen, lms = _lm_args(lm, lm_panelty, out)
+        _lib.check(_lib.load().hctr_nbest_lm(ctx, lm, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, depth, beam, n, pen,
+                                             bonus, _lib.ptr(il), *[_lib.ptr(a) for a in out + (lms,)]), ctx)
+        return NBest(*out, lm_scores=lms)
     _lib.check(_lib.load().hctr_nbest(ctx, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, depth, beam, n, bonus,
                                       _lib.ptr(il), *[_lib.ptr(a) for a in out]), ctx)
     return NBest(*out)

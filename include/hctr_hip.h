@@ -345,7 +345,8 @@ int hctr_evaluate_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device, 
  * what hctr_beam_search does per step with builtin_lm == 1 - run where the front end's lists lie, over a caller-chosen
  * number of steps and without the greedy end-step / empty-line rules of __cbs_full__; it returns the first nbest
  * hypotheses of the final list with their log-probabilities instead of one string. An N-best list is what rescoring with
- * any language model needs (N calls per line); an LM-scored search itself stays on the host (hctr_beam_search).
+ * any language model needs (N calls per line); the n-gram-scored search on the device is hctr_nbest_lm* below, every
+ * other LM-scored search stays on the host (hctr_beam_search).
  * Input per row (t, b): k classes in descending log-prob order (ties: lower index first), distinct, with float32
  * log-probs - hctr_beam_frontend's topk_idx / topk_logp. Line b runs T_b = input_lengths[b] steps, in [1, W]; NULL = W
  * for every line (all columns count, pad columns included, as in hctr_greedy and hctr_recognize).
@@ -435,13 +436,16 @@ typedef int (*hctr_lm_next_cb)(void* user, int n, const int32_t* ids, const int3
  * hctr_ngram_score == kenlm.Model.score(sentence, bos, eos): log10 probability of a whitespace-
  * separated UTF-8 sentence (Katz back-off, OOV -> <unk>). hctr_ngram_word_id maps a token to the
  * model's word id (-1 = out of vocabulary) so the beam search can score label sequences natively
- * (hctr_beam_params.builtin_lm == 3, .ngram, .label_words). Parity with the kenlm binary: unpinned. */
+ * (hctr_beam_params.builtin_lm == 3, .ngram, .label_words). hctr_ngram_word_logp is one term of that score, log10
+ * P(word | ctx): ctx holds the previous word ids, most recent last, only the last order - 1 count; word -1 = out of
+ * vocabulary (NaN for a NULL lm or ctx). Parity with the kenlm binary: unpinned. */
 typedef struct hctr_ngram hctr_ngram;
 int hctr_ngram_load(const char* arpa_path, hctr_ngram** out);
 void hctr_ngram_free(hctr_ngram* lm);
 int hctr_ngram_order(const hctr_ngram* lm);
 int32_t hctr_ngram_word_id(const hctr_ngram* lm, const char* word_utf8);
 double hctr_ngram_score(const hctr_ngram* lm, const char* sentence_utf8, int bos, int eos);
+double hctr_ngram_word_logp(const hctr_ngram* lm, const int32_t* ctx, int nctx, int32_t word);
 const char* hctr_ngram_last_error(void);
 
 typedef struct {
@@ -465,6 +469,60 @@ int hctr_beam_search(const hctr_beam_params* p, int W, int B, int C, int k,
                      const int64_t* cand_off, const int32_t* cand_idx, const float* cand_logp,
                      const float* full_logp_wbc,
                      int32_t* out_labels, int32_t* out_lengths, int32_t* line_status);
+
+/* ---- N-best texts with n-gram LM scores: the reference's LM-scored prefix beam search, on the device ------------
+ * __cbs_full__ of utils/ctc_codec.py:183-285 with an ARPA n-gram model (what hctr_beam_search does with builtin_lm == 3)
+ * run where the front end's lists lie, returning the first nbest hypotheses of the final list with their scores.
+ * hctr_lm is a flat, pointer-free image of an hctr_ngram for one label set: one open-addressing table of 32-byte slots
+ * (six word ids, logp, back-off; power-of-two capacity, load <= 0.5, linear probing; a probe compares every word id, so
+ * lookups are exact) plus the label -> word map. hctr_lm_build is host only and needs no GPU: label_words[C] maps each
+ * label to an LM word id, -1 = out of vocabulary, as hctr_beam_params.label_words does; it is copied. A model of order
+ * above 6, or a label_words entry that is no word id of the model: HCTR_ERR_ARG with a message through
+ * hctr_ngram_last_error; allocation failure: HCTR_ERR_NOMEM; no exception crosses the ABI. hctr_lm_word_logp is
+ * log10 P(word | ctx) over the flat table - ctx: the previous word ids, most recent last, only the last order - 1 count;
+ * word -1 = OOV - by the routine the device search runs, compiled for the host, bit-equal to the string-keyed scorer
+ * behind hctr_ngram_score; it lets the table be checked without a GPU. The hctr_ngram may be freed after the build.
+ * The search is the one of hctr_nbest* (steps 1-5 there, the same tie rule, fingerprints and limits) with three
+ * additions, each as hctr_beam_search(builtin_lm = 3) has it:
+ *   * the greedy line: over the first L_b = input_lengths[b] columns (NULL: W) the top-1 class of each row's list,
+ *     keeping entries that are not blank, not <unknown> (C-1) and not a repeat of the previous column, with their time
+ *     stamps. The line runs end_b = min(last stamp + 4, L_b) steps; at step t the SUFFIX is the first <= 4 greedy labels
+ *     with a stamp > t. Computed on the device. A line whose greedy text is empty returns count[b] = 0 (the host search
+ *     reports HCTR_ERR_EMPTY_LINE for it); the other lines are unaffected and the call returns HCTR_OK;
+ *   * every hypothesis carries the n-gram score of its prefix - a float64 running sum, left to right from the <s>
+ *     context, one log10 P(word | last order-1 words) term per label - and its last order-1 word ids;
+ *   * every entry of a step is ranked by total = logaddexp(pb', pnb') + pt, pt = s * lm_panelty + len * len_bonus with
+ *     each product rounded on its own, s = the prefix's score plus one term per suffix word in order.
+ * At the last step the suffix is empty, so the score that decides the final order is that of the text itself.
+ * Outputs as hctr_nbest* (logp = logaddexp(pb, pnb), score = total) plus
+ *   lm_score float64 [B][nbest]: the n-gram log10 score of the text (bos, no eos) before lm_panelty; -inf in unused slots.
+ * Limits and argument errors as hctr_nbest*; also HCTR_ERR_ARG for a NULL lm, a NaN lm_panelty and an lm built for a
+ * different C. A context uploads the table (and the label map) on first use and keeps the device copy of the most
+ * recently used hctr_lm, recognised by a serial number stored in the object, not by its address; it is replaced when
+ * another model is used and freed with the context. An upload that does not fit is HCTR_ERR_NOMEM and leaves the context
+ * usable. hctr_lm_free does not touch any context; a freed model's device copy stays until replaced.
+ * Launches after the front end's own: beam_lm_prepass (one workgroup per line: word ids of the lists, the per-step
+ * suffixes, the end step), prefix_beam_lm (the instances of prefix_beam) and prefix_backtrace.
+ * Device scratch: that of the matching hctr_nbest* entry, plus 16 * n*W (per-step suffixes) + 4 * n*W*k (word ids of
+ * the lists) + 4 * n (end steps) + 8 * n*nbest (lm_score) in the CTC scratch, plus, held by the context,
+ * 32 * capacity + 4 * C bytes for the table, capacity = the power of two >= 2 * the model's n-gram count. */
+typedef struct hctr_lm hctr_lm;
+int hctr_lm_build(const hctr_ngram* lm, const int32_t* label_words, int C, hctr_lm** out);
+int hctr_lm_order(const hctr_lm* lm);
+double hctr_lm_word_logp(const hctr_lm* lm, const int32_t* ctx, int nctx, int32_t word);
+void hctr_lm_free(hctr_lm* lm);
+int hctr_nbest_lm_topk(hctr_ctx* ctx, const hctr_lm* lm, const int32_t* topk_idx, const float* topk_logp, int W, int B,
+                       int C, int k, int beam, int nbest, double lm_panelty, double len_bonus,
+                       const int32_t* input_lengths, int32_t* labels, int32_t* lengths, double* logp, double* score,
+                       int32_t* count, double* lm_score);
+int hctr_nbest_lm_logits(hctr_ctx* ctx, const hctr_lm* lm, const float* logits_wbc, int on_device, int W, int B, int C,
+                         int k, int beam, int nbest, double lm_panelty, double len_bonus, const int32_t* input_lengths,
+                         int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count,
+                         double* lm_score);
+int hctr_nbest_lm(hctr_ctx* ctx, const hctr_lm* lm, const void* img, int img_dtype, int img_on_device,
+                  const int32_t* widths, int B, int W, int k, int beam, int nbest, double lm_panelty, double len_bonus,
+                  const int32_t* input_lengths, int32_t* labels, int32_t* lengths, double* logp, double* score,
+                  int32_t* count, double* lm_score);
 
 /* ---- line preprocessing on the device: replaces read_resize_image / pil_loader -----------------
  * test.py:207-216 (cv2.cvtColor BGR2GRAY + cv2.resize(src, (tw, 128), interpolation=cv2.INTER_AREA)) and

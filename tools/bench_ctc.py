@@ -49,7 +49,16 @@ search hctr_beam_search(builtin_lm = 1) on 16 threads on those lists - at beam 1
 over the host search's own number of steps (the reference's end step), alternately after warm-up calls of each, medians.
 Three figures: the device search alone (its two launches' device time, and the wall time of hctr_nbest_topk on the same
 lists, which adds their upload), the front end + D2H + host search, and the front end alone. The 1-best texts of the two
-searches are compared."""
+searches are compared.
+
+    python tools/bench_ctc.py --nbest-lm ...
+
+times the n-gram-scored device search (hctr_nbest_lm*) on the same batch against the host search it restates,
+hctr_beam_search(builtin_lm = 3) on 16 threads on the same lists, at beam 10 / depth 10, lm_panelty 2, len_bonus 5.8. The
+model is an ARPA file the tool writes itself: order 5 over the synthetic vocabulary, deterministic, about 330 000
+n-grams (a 32 MB table, so the probes miss L2). Calls alternate after warm-up calls of each, medians; the device time of
+the search's launches (pre-pass, search, backtrace) and of the zero-LM prefix_beam over the same end steps come from
+profiled calls of the same run; the lines whose 1-best differs from the host search's are counted."""
 import argparse
 import json
 import os
@@ -75,6 +84,7 @@ def main():
     ap.add_argument("--recognize", action="store_true")
     ap.add_argument("--evaluate", action="store_true")
     ap.add_argument("--nbest", action="store_true")
+    ap.add_argument("--nbest-lm", action="store_true")
     ap.add_argument("--host-lines", type=int, default=4)
     args = ap.parse_args()
     import torch
@@ -101,6 +111,9 @@ def main():
         return
     if args.nbest:
         print(json.dumps(nbest(args, hctr_amd, m, imgs)))
+        return
+    if args.nbest_lm:
+        print(json.dumps(nbest_lm(args, hctr_amd, m, imgs)))
         return
 
     def t_greedy():
@@ -396,6 +409,108 @@ def nbest(args, hctr_amd, m, imgs):
             "ms": {name: [round(v, 3) for v in vals] for name, vals in ms.items()},
             "one_best_equals_host_search": one_best == out["host_search"],
             "mean_text_length": float(np.mean([len(t) for t in one_best]))}
+
+
+def write_bench_arpa(path, chars, order=5, counts=(0, 100000, 100000, 70000, 50000), seed=5):
+    """Deterministic ARPA model over ``chars`` (+ <unk>, <s>, </s>): every unigram, and counts[n-1] random n-grams of each
+    higher order, each an n-gram of the order below plus one word. Returns the number of n-grams."""
+    rng = np.random.RandomState(seed)
+    words = ["<unk>", "<s>", "</s>"] + list(chars)
+    V = len(words)
+    grams = [[(i,) for i in range(V)]]
+    for n in range(2, order + 1):
+        prev = [g for g in grams[-1] if g[-1] != 2]                # (nothing follows </s>)
+        pick = rng.randint(0, len(prev), counts[n - 1])
+        tail = rng.randint(2, V, counts[n - 1])                    # (<unk> and <s> end no n-gram here)
+        grams.append(sorted(set(prev[int(i)] + (int(w),) for i, w in zip(pick, tail))))
+    with open(path, "w", encoding="utf-8") as f:
+        f.write("\\data\\\n" + "".join("ngram %d=%d\n" % (n + 1, len(g)) for n, g in enumerate(grams)))
+        for n, gs in enumerate(grams, 1):
+            f.write("\n\\%d-grams:\n" % n)
+            p = -0.2 - (5.0 - 0.8 * n) * rng.rand(len(gs))
+            bo = -0.1 - 0.6 * rng.rand(len(gs))
+            for g, pv, bv in zip(gs, p, bo):
+                text = " ".join(words[i] for i in g)
+                f.write("%.6f\t%s\t%.6f\n" % (pv, text, bv) if n < order and g[-1] != 2 else "%.6f\t%s\n" % (pv, text))
+        f.write("\n\\end\\\n")
+    return sum(len(g) for g in grams)
+
+
+def nbest_lm(args, hctr_amd, m, imgs):
+    import tempfile
+    import torch
+    from hctr_amd import package
+    ctc = sys.modules[package.__name__ + ".ctc"]
+    B, W = int(imgs.shape[0]), int(imgs.shape[-1])
+    C, k, beam, n, pen, bonus = int(m.noutput), 10, 10, 5, 2.0, 5.8
+    chars = hctr_amd.synth.characters()
+    codec = hctr_amd.ctc_codec(chars).attach(m)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "bench5.arpa")
+        ngrams = write_bench_arpa(path, chars)
+        codec.set_beam_search(ngram_path=path, use_tfm_pred=False, lm_panelty=pen, len_bonus=bonus, beam_size=beam,
+                              search_depth=k)                      # (an .arpa path: the native ArpaLM, read here)
+    lm = codec.ngram
+    codec.num_threads = 16
+    flat = lm.flat(codec.characters)
+    fe = m.beam_frontend(imgs, k)
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    def lm_topk():
+        return ctc.nbest_topk(m._ctx, fe["topk_idx"], fe["topk_logp"], C, n, beam, bonus, None, lm=flat, lm_panelty=pen)
+
+    calls = {"nbest_lm_images": lambda: m.nbest(imgs, n=n, beam=beam, depth=k, len_bonus=bonus, lm=lm, lm_panelty=pen,
+                                                codec=codec),
+             "host_search": lambda: codec.decode_frontend(fe),
+             "nbest_lm_topk": lm_topk}
+    for _ in range(args.warmup):
+        for f in calls.values():
+            f()
+    ms = {name: [] for name in calls}
+    out = {}
+    for _ in range(args.steps):
+        for name, f in calls.items():
+            dt, out[name] = timed(f)
+            ms[name].append(1e3 * dt)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    m.set_profiling(True)
+    lm_topk()
+    prof = dict(m.last_profile())
+    top1 = fe["topk_idx"][:, :, 0]
+    ends = np.empty(B, np.int32)
+    for b in range(B):                                             # the reference's end step: last greedy character + 4
+        t = top1[:, b]
+        keep = (t != 0) & (t != C - 1)
+        keep[1:] &= t[1:] != t[:-1]
+        ends[b] = min(int(np.flatnonzero(keep)[-1]) + 4, W)
+    ctc.nbest_topk(m._ctx, fe["topk_idx"], fe["topk_logp"], C, n, beam, bonus, ends)
+    zero = dict(m.last_profile())
+    m.set_profiling(False)
+    names = ("beam_lm_prepass", "prefix_beam_lm", "prefix_backtrace")
+    one_best = codec.labels_to_text([line[0] if line else [] for line in out["nbest_lm_topk"].label_lists()])
+    differ = sum(a != b for a, b in zip(one_best, out["host_search"]))
+    same_entries = all(getattr(out["nbest_lm_topk"], f).tobytes() == getattr(out["nbest_lm_images"], f).tobytes()
+                       for f in ("labels", "lengths", "logps", "scores", "counts", "lm_scores"))
+    return {"mode": "nbest-lm", "lines": B, "width": W, "classes": C, "precision": args.precision, "beam": beam, "depth": k,
+            "nbest": n, "lm_order": lm.order, "lm_ngrams": ngrams, "lm_panelty": pen, "len_bonus": bonus,
+            "host_threads": 16, "mean_steps": float(ends.mean()),
+            "device_search_ms": round(sum(prof.get(key, 0.0) for key in names), 3),
+            "device_search_launches_ms": {key: round(prof.get(key, 0.0), 4) for key in names},
+            "zero_lm_prefix_beam_ms": round(zero.get("prefix_beam", 0.0), 3),
+            "nbest_lm_topk_call_ms_median": round(med["nbest_lm_topk"], 3),
+            "nbest_lm_images_call_ms_median": round(med["nbest_lm_images"], 3),
+            "host_search_ms_median": round(med["host_search"], 3),
+            "ms": {name: [round(v, 3) for v in vals] for name, vals in ms.items()},
+            "one_best_lines_differing_from_host_search": int(differ),
+            "images_entry_equals_topk_entry": bool(same_entries),
+            "mean_text_length": float(np.mean([len(t) for t in one_best])),
+            "mean_lm_score": float(np.mean(out["nbest_lm_topk"].lm_scores[:, 0]))}
 
 
 def evaluate(args, hctr_amd, m, imgs, labels):
