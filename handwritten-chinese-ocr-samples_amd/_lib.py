@@ -187,6 +187,13 @@ SIGNATURES = [
                                   _VP, _VP, _VP, _VP, _VP]),
     ("hctr_nbest_lm", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _VP, _VP, _VP,
                            _VP, _VP, _VP, _VP]),
+    # ctx, lm, top1, blank, cand_off, cand_idx, cand_logp, W, B, C, beam, nbest, lm_panelty, len_bonus, input_lengths, 8 outputs
+    ("hctr_nbest_skip_lists", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double,
+                                   _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_nbest_skip_logits", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _VP, _VP, _VP,
+                                    _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_nbest_skip", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _VP, _VP, _VP,
+                             _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_beam_search", _I, [ctypes.POINTER(BeamParams), _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                               _VP, _VP, _VP]),
     ("hctr_ngram_load", _I, [ctypes.c_char_p, ctypes.POINTER(_VP)]),

@@ -220,7 +220,8 @@ class ctc_codec(object):
         rec = ctc.recognize_logits(self._context(), logits, on_dev)
         return self.labels_to_text(rec.label_lists()), rec
 
-    def nbest(self, preds, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None, lm=None, lm_panelty=2.0):
+    def nbest(self, preds, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None, lm=None, lm_panelty=2.0,
+              skip_search=False):
         """The ``n`` best texts of every line of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) with
         their log-probabilities, by the device prefix beam search without a language model (include/hctr_hip.h
         ``hctr_nbest_logits``; arguments as ``hctr_model.nbest``). Returns a ``ctc.NBest`` with ``.texts`` added: per
@@ -228,7 +229,11 @@ class ctc_codec(object):
         With ``lm`` (an ``ArpaLM``) the search is the reference's n-gram-scored one, on the device
         (``hctr_nbest_lm_logits``): every step ranks by ``logp + lm_score(prefix + greedy suffix) * lm_panelty + length *
         len_bonus`` over the reference's end steps, ``.lm_scores`` holds the n-gram score of each text, and a line whose
-        greedy text is empty returns no hypothesis (the reference's defaults are lm_panelty 2, len_bonus 5.8)."""
+        greedy text is empty returns no hypothesis (the reference's defaults are lm_panelty 2, len_bonus 5.8).
+        ``skip_search=True`` is the reference's skip variant of that search (``test.py -ss``; ``hctr_nbest_skip_logits``): a
+        column with one class above probability 0.001 updates the hypotheses in place, the others rank the classes above
+        that threshold (``depth`` is not used); ``lm`` None is then the zero LM. ``.status`` and ``.ranked`` are filled, and
+        the list is returned as it stands (``ctc.NBest``)."""
         from . import ctc
         logits, on_dev = self._as_logits(preds)
         W, B, C = (int(v) for v in logits.shape)
@@ -237,6 +242,11 @@ class ctc_codec(object):
         if W == 0:
             raise ValueError("preds have no steps (W = 0)")
         flat = None if lm is None else lm.flat(self.characters)
+        if skip_search:
+            res = ctc.nbest_skip_logits(self._context(), logits, on_dev, n, beam, len_bonus, input_lengths, lm=flat,
+                                        lm_panelty=lm_panelty)
+            res.texts = [self.labels_to_text(line) for line in res.label_lists()]
+            return res
         res = ctc.nbest_logits(self._context(), logits, on_dev, n, beam, min(int(depth), C), len_bonus, input_lengths,
                                lm=flat, lm_panelty=lm_panelty)
         res.texts = [self.labels_to_text(line) for line in res.label_lists()]

@@ -1695,6 +1695,10 @@ struct NbestCall {
     int32_t *d_end = nullptr, *d_wid = nullptr;
     int4* d_suf = nullptr;
     double* d_lm = nullptr;
+    // the skip search (hctr_nbest_skip*): lm may be null (the zero LM); the pre-pass outputs and lm_score exist either way
+    bool skip = false;
+    int32_t *o_status = nullptr, *o_ranked = nullptr;      // the caller's [B], may be null
+    int32_t *d_status = nullptr, *d_ranked = nullptr;
 };
 
 // the extra arguments of hctr_nbest_lm*
@@ -1758,7 +1762,9 @@ int nbest_scratch(hctr_ctx* c, NbestCall* n, int lines) {
                  lab_b = align256(ln * n->W * 4), i32_b = align256(ln * 4), f64_b = align256(ln * 8),
                  cnt_b = align256((size_t)lines * 4);
     const size_t suf_b = align256((size_t)lines * n->W * sizeof(int4)), wid_b = align256((size_t)lines * n->W * n->k * 4);
-    TRY(ctc_reserve(c, T_b + hist_b + lab_b + i32_b + 2 * f64_b + cnt_b + (n->lm ? cnt_b + suf_b + wid_b + f64_b : 0)));
+    const bool pre = n->lm || n->skip, wids = n->lm && !n->skip;
+    TRY(ctc_reserve(c, T_b + hist_b + lab_b + i32_b + 2 * f64_b + cnt_b + (pre ? cnt_b + suf_b + f64_b : 0) +
+                           (wids ? wid_b : 0) + (n->skip ? 2 * cnt_b : 0)));
     if (n->lm) TRY(lm_on_device(c, n->lm));
     char* q = c->ctc_buf;
     n->d_T = (int32_t*)q; q += T_b;
@@ -1768,11 +1774,15 @@ int nbest_scratch(hctr_ctx* c, NbestCall* n, int lines) {
     n->d_score = (double*)q; q += f64_b;
     n->d_len = (int32_t*)q; q += i32_b;
     n->d_cnt = (int32_t*)q; q += cnt_b;
-    if (n->lm) {
+    if (pre) {
         n->d_suf = (int4*)q; q += suf_b;
         n->d_lm = (double*)q; q += f64_b;
-        n->d_wid = (int32_t*)q; q += wid_b;
-        n->d_end = (int32_t*)q;
+        if (wids) { n->d_wid = (int32_t*)q; q += wid_b; }
+        n->d_end = (int32_t*)q; q += cnt_b;
+    }
+    if (n->skip) {
+        n->d_status = (int32_t*)q; q += cnt_b;
+        n->d_ranked = (int32_t*)q;
     }
     HIP_TRY(c, hipMemcpyAsync(n->d_T, n->T.data(), (size_t)n->B * 4, hipMemcpyHostToDevice, c->stream));
     return HCTR_OK;
@@ -1812,6 +1822,71 @@ int nbest_launch(hctr_ctx* c, const NbestCall& n, const int32_t* d_idx, const fl
     HIP_TRY(c, fetch(n.o.count ? n.o.count + b0 : nullptr, n.d_cnt, (size_t)nb * 4));
     if (n.lm) HIP_TRY(c, fetch(n.o_lm ? n.o_lm + lo : nullptr, n.d_lm, ln * 8));
     return HCTR_OK;
+}
+
+// the extra arguments of hctr_nbest_skip*: lm == null is the zero LM, lm_panelty then unused
+int nbest_skip_prepare(hctr_ctx* c, NbestCall* n, const hctr_lm* lm, double lm_panelty, double* lm_score, int32_t* status,
+                       int32_t* ranked) {
+    if (lm) TRY(nbest_lm_prepare(c, n, lm, lm_panelty, lm_score));
+    n->skip = true; n->o_lm = lm_score; n->o_status = status; n->o_ranked = ranked;
+    return HCTR_OK;
+}
+
+// the skip search of the pass's lines [b0, b0 + nb) on device lists, rows r = t*nb + b: the top-1 classes at top1[r * ks],
+// the blank log-probs, and the candidates in the padded layout (kernels.h); results queued to the caller's rows
+int skip_launch(hctr_ctx* c, const NbestCall& n, const int32_t* d_top1, int ks, const float* d_bl, const int32_t* d_cc,
+                const int32_t* d_ci, const float* d_cl, int b0, int nb) {
+    const size_t ln = (size_t)nb * n.nbest;
+    Prof pf(c);
+    if (n.o.labels) HIP_TRY(c, hipMemsetAsync(n.d_lab, 0, ln * n.W * 4, c->stream));
+    PROF_TRY(pf, "beam_lm_prepass", launch_beam_lm_prepass(d_top1, nb, n.W, ks, n.C, n.d_T + b0, n.lm ? c->lm_words : nullptr,
+                                                           nullptr, n.d_suf, n.d_end, c->stream));
+    BeamLm lm;
+    if (n.lm) {
+        lm.table = LmView{c->lm_slots, (uint32_t)n.lm->slots.size() - 1u, n.lm->order, n.lm->unk};
+        lm.bos = n.lm->bos;
+    }
+    lm.suffix = n.d_suf; lm.lm_panelty = n.lm_panelty; lm.o_lm = n.d_lm;
+    PROF_TRY(pf, "prefix_beam_skip", launch_prefix_beam_skip(d_cc, d_ci, d_cl, d_bl, nb, n.W, n.C, n.beam, n.nbest,
+                                                             n.len_bonus, n.d_end, n.lm ? c->lm_words : nullptr, lm, n.d_hist,
+                                                             n.d_len, n.d_logp, n.d_score, n.d_cnt, n.d_status, n.d_ranked,
+                                                             c->stream));
+    if (n.o.labels)
+        PROF_TRY(pf, "prefix_backtrace", launch_prefix_backtrace(n.d_hist, n.d_end, nb, n.W, n.beam, n.nbest, n.d_len,
+                                                                 n.d_cnt, n.d_lab, c->stream));
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    const size_t lo = (size_t)b0 * n.nbest;
+    HIP_TRY(c, fetch(n.o.labels ? n.o.labels + lo * n.W : nullptr, n.d_lab, ln * n.W * 4));
+    HIP_TRY(c, fetch(n.o.lengths ? n.o.lengths + lo : nullptr, n.d_len, ln * 4));
+    HIP_TRY(c, fetch(n.o.logp ? n.o.logp + lo : nullptr, n.d_logp, ln * 8));
+    HIP_TRY(c, fetch(n.o.score ? n.o.score + lo : nullptr, n.d_score, ln * 8));
+    HIP_TRY(c, fetch(n.o.count ? n.o.count + b0 : nullptr, n.d_cnt, (size_t)nb * 4));
+    HIP_TRY(c, fetch(n.o_lm ? n.o_lm + lo : nullptr, n.d_lm, ln * 8));
+    HIP_TRY(c, fetch(n.o_status ? n.o_status + b0 : nullptr, n.d_status, (size_t)nb * 4));
+    HIP_TRY(c, fetch(n.o_ranked ? n.o_ranked + b0 : nullptr, n.d_ranked, (size_t)nb * 4));
+    return HCTR_OK;
+}
+
+// the skip search on the lists of one front-end pass (made with k = 1 and candidates wanted): the candidates go to the
+// padded layout where the counts already lie - no count visits the host - and the search follows in stream order
+int skip_on_lists(hctr_ctx* c, const NbestCall& n, const BeamLists& L, int b0, int nb) {
+    const size_t rows = (size_t)nb * n.W;
+    int32_t* d_ci = nullptr;
+    float* d_cl = nullptr;
+    TRY(dev_alloc(c, c->beam_allocs, &d_ci, rows * kBeamMaxK, false));
+    TRY(dev_alloc(c, c->beam_allocs, &d_cl, rows * kBeamMaxK, false));
+    const double thresh = std::log(0.001);
+    {
+        Prof pf(c);
+        PROF_TRY(pf, "skip_candidates",
+                 L.fused ? launch_beam_candidates(c->ws.emit_cnt, c->ws.emit_list, kBeamCap, L.st, nb, n.W, thresh, nullptr,
+                                                  kBeamMaxK, d_ci, d_cl, c->stream)
+                         : launch_row_candidates(L.rowsrc, L.ld, nb, n.W, n.C, thresh, L.st, nullptr, kBeamMaxK, d_ci, d_cl,
+                                                 c->stream));
+    }
+    return skip_launch(c, n, L.idx, 1, L.bl, L.cnt, d_ci, d_cl, b0, nb);
 }
 
 }  // namespace
@@ -2240,9 +2315,9 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
             TRY(dev_alloc(c, pool, &d_ci, (size_t)std::max<int64_t>(tot, 1), false));
             TRY(dev_alloc(c, pool, &d_cl, (size_t)std::max<int64_t>(tot, 1), false));
             HIP_TRY(c, hipMemcpyAsync(d_off, po.loff.data(), (size_t)(rows + 1) * 8, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, fused ? launch_beam_candidates(c->ws.emit_cnt, c->ws.emit_list, kBeamCap, d_st, nb, W, thresh, d_off, d_ci,
-                                                      d_cl, c->stream)
-                             : launch_row_candidates(rowsrc, ld, nb, W, C, thresh, d_st, d_off, d_ci, d_cl, c->stream));
+            HIP_TRY(c, fused ? launch_beam_candidates(c->ws.emit_cnt, c->ws.emit_list, kBeamCap, d_st, nb, W, thresh, d_off, 0,
+                                                      d_ci, d_cl, c->stream)
+                             : launch_row_candidates(rowsrc, ld, nb, W, C, thresh, d_st, d_off, 0, d_ci, d_cl, c->stream));
             if (tot) {
                 HIP_TRY(c, hipMemcpyAsync(po.ci.data(), d_ci, (size_t)tot * 4, hipMemcpyDeviceToHost, c->stream));
                 HIP_TRY(c, hipMemcpyAsync(po.cl.data(), d_cl, (size_t)tot * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2426,6 +2501,114 @@ int hctr_nbest_lm(hctr_ctx* c, const hctr_lm* lm, const void* img, int img_dtype
     const NbestLmArgs a{lm, lm_panelty, lm_score};
     return nbest_images_impl(c, &a, img, img_dtype, img_on_device, widths, B, W, k, beam, nbest, len_bonus, input_lengths,
                              NbestOut{labels, lengths, logp, score, count});
+}
+
+int hctr_nbest_skip_lists(hctr_ctx* c, const hctr_lm* lm, const int32_t* top1_idx, const float* blank_logp,
+                          const int64_t* cand_off, const int32_t* cand_idx, const float* cand_logp, int W, int B, int C,
+                          int beam, int nbest, double lm_panelty, double len_bonus, const int32_t* input_lengths,
+                          int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count, double* lm_score,
+                          int32_t* status, int32_t* ranked) {
+    return guard(c, [&]() -> int {
+        TRY(check_logits_args(c, W, B, C, top1_idx && blank_logp && cand_off));
+        NbestCall n;
+        TRY(nbest_prepare(c, B, W, C, 1, beam, nbest, len_bonus, input_lengths, NbestOut{labels, lengths, logp, score, count},
+                          &n));
+        TRY(nbest_skip_prepare(c, &n, lm, lm_panelty, lm_score, status, ranked));
+        if (B == 0) return HCTR_OK;
+        // the lists are the caller's: offsets that do not decrease, classes in [0, C) and strictly ascending within a row
+        const size_t rows = (size_t)W * B;
+        if (cand_off[0] < 0) return fail(c, HCTR_ERR_ARG, "cand_off[0]=%lld is negative", (long long)cand_off[0]);
+        for (size_t r = 0; r < rows; ++r)
+            if (cand_off[r + 1] < cand_off[r])
+                return fail(c, HCTR_ERR_ARG, "cand_off decreases at row (t=%zu, b=%zu)", r / B, r % B);
+        if (cand_off[rows] > cand_off[0] && (!cand_idx || !cand_logp)) return fail(c, HCTR_ERR_ARG, "NULL candidate lists");
+        std::vector<int32_t> pci(rows * kBeamMaxK, 0), pcnt(rows);
+        std::vector<float> pcl(rows * kBeamMaxK, 0.f);
+        for (size_t r = 0; r < rows; ++r) {
+            if (top1_idx[r] < 0 || top1_idx[r] >= C)
+                return fail(c, HCTR_ERR_ARG, "top1_idx (t=%zu, b=%zu): class %d outside [0,%d)", r / B, r % B, top1_idx[r], C);
+            const int64_t o = cand_off[r], m = cand_off[r + 1] - o;
+            for (int64_t j = 0; j < m; ++j) {
+                const int32_t cls = cand_idx[o + j];
+                if (cls < 0 || cls >= C || (j > 0 && cls <= cand_idx[o + j - 1]))
+                    return fail(c, HCTR_ERR_ARG, "cand_idx row (t=%zu, b=%zu) entry %lld: class %d outside [0,%d) or not "
+                                "above the one before it", r / B, r % B, (long long)j, cls, C);
+                if (j < kBeamMaxK) { pci[r * kBeamMaxK + j] = cls; pcl[r * kBeamMaxK + j] = cand_logp[o + j]; }
+            }
+            pcnt[r] = (int32_t)std::min<int64_t>(m, INT32_MAX);
+        }
+        HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
+        std::vector<void*> tmp;
+        PoolGuard tmp_guard{tmp};
+        return synced(c, [&]() -> int {
+            int32_t *d_top1 = nullptr, *d_cc = nullptr, *d_ci = nullptr;
+            float *d_bl = nullptr, *d_cl = nullptr;
+            TRY(nbest_scratch(c, &n, B));
+            TRY(dev_alloc(c, tmp, &d_top1, rows, false));
+            TRY(dev_alloc(c, tmp, &d_bl, rows, false));
+            TRY(dev_alloc(c, tmp, &d_cc, rows, false));
+            TRY(dev_alloc(c, tmp, &d_ci, rows * kBeamMaxK, false));
+            TRY(dev_alloc(c, tmp, &d_cl, rows * kBeamMaxK, false));
+            HIP_TRY(c, hipMemcpyAsync(d_top1, top1_idx, rows * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d_bl, blank_logp, rows * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d_cc, pcnt.data(), rows * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d_ci, pci.data(), rows * kBeamMaxK * 4, hipMemcpyHostToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(d_cl, pcl.data(), rows * kBeamMaxK * 4, hipMemcpyHostToDevice, c->stream));
+            return skip_launch(c, n, d_top1, 1, d_bl, d_cc, d_ci, d_cl, 0, B);
+        }());
+    });
+}
+
+int hctr_nbest_skip_logits(hctr_ctx* c, const hctr_lm* lm, const float* logits_wbc, int on_device, int W, int B, int C,
+                           int beam, int nbest, double lm_panelty, double len_bonus, const int32_t* input_lengths,
+                           int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count, double* lm_score,
+                           int32_t* status, int32_t* ranked) {
+    return guard(c, [&]() -> int {
+        TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
+        NbestCall n;
+        TRY(nbest_prepare(c, B, W, C, 1, beam, nbest, len_bonus, input_lengths, NbestOut{labels, lengths, logp, score, count},
+                          &n));
+        TRY(nbest_skip_prepare(c, &n, lm, lm_panelty, lm_score, status, ranked));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
+        const std::vector<int> all = line_indices(B);
+        const int rc = synced(c, [&]() -> int {
+            BeamLists L;
+            TRY(nbest_scratch(c, &n, B));
+            TRY(beam_lists_pass(c, nullptr, Pass{all.data(), B, 0, B, false, nullptr}, logits_wbc, on_device, W, C, 1, true,
+                                std::log(0.001), &L));
+            return skip_on_lists(c, n, L, 0, B);
+        }());
+        free_pool(c->beam_allocs);
+        return rc;
+    });
+}
+
+int hctr_nbest_skip(hctr_ctx* c, const hctr_lm* lm, const void* img, int img_dtype, int img_on_device, const int32_t* widths,
+                    int B, int W, int beam, int nbest, double lm_panelty, double len_bonus, const int32_t* input_lengths,
+                    int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count, double* lm_score,
+                    int32_t* status, int32_t* ranked) {
+    return guard(c, [&]() -> int {
+        TRY(check_forward_args(c, img, img_dtype, B, W));
+        NbestCall n;
+        TRY(nbest_prepare(c, B, W, c->num_classes, 1, beam, nbest, len_bonus, input_lengths,
+                          NbestOut{labels, lengths, logp, score, count}, &n));
+        TRY(nbest_skip_prepare(c, &n, lm, lm_panelty, lm_score, status, ranked));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        const Batch in{img, img_dtype, img_on_device, widths, B, W};
+        // inside each pass the front end's lists stay where they lie, the candidate counts included
+        const int rc = synced(c, run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
+            if (p.first == 0) TRY(nbest_scratch(c, &n, p.nb));      // no later pass is larger
+            BeamLists L;
+            TRY(beam_lists_pass(c, &in, p, nullptr, 0, W, n.C, 1, true, std::log(0.001), &L));
+            return skip_on_lists(c, n, L, p.first, p.nb);
+        }));
+        free_pool(c->beam_allocs);
+        return rc;
+    });
 }
 
 int hctr_ctc_loss(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,

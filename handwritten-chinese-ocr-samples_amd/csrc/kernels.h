@@ -165,9 +165,10 @@ hipError_t launch_beam_select(const float* row_thr, const int32_t* emit_cnt, con
                               const double* esum, int P, const float* blank_logit, int B, int W, int k,
                               double cand_thresh, int32_t* topk_idx, float* topk_logp, float* blank_logp,
                               float* stats, int32_t* cand_count, int32_t* overflow, hipStream_t s);
-// candidate lists (ascending class order, log-prob > cand_thresh) out of the per-row lists, to cand_off[r] (r = t*B + b)
+// candidate lists (ascending class order, log-prob > cand_thresh) out of the per-row lists, to cand_off[r] (r = t*B + b);
+// cand_off == null: the padded layout of the skip search, row r at r * pad, candidates beyond the first pad dropped
 hipError_t launch_beam_candidates(const int32_t* emit_cnt, const int32_t* emit_list, int cap, const float* stats,
-                                  int B, int W, double cand_thresh, const int64_t* cand_off, int32_t* cand_idx,
+                                  int B, int W, double cand_thresh, const int64_t* cand_off, int pad, int32_t* cand_idx,
                                   float* cand_logp, hipStream_t s);
 
 // raw per-column indices [B][W] (row m = b*W + t) -> collapsed labels [B][W] + lengths [B]
@@ -182,12 +183,13 @@ hipError_t launch_wbc_to_rows(const float* wbc, int B, int W, int C, float* rows
                               hipStream_t s);
 
 // log-softmax + top-k (+ count of candidates above thresh) per (t,b) row of [B*W][ld]; outputs are
-// indexed r = t*B + b. stats receives (row max, log-sum) pairs for launch_row_candidates.
+// indexed r = t*B + b. stats receives (row max, log-sum) pairs for launch_row_candidates (cand_off / pad as
+// launch_beam_candidates takes them).
 hipError_t launch_row_topk(const float* logits, int64_t ld, int B, int W, int C, int k, double thresh,
                            int32_t* topk_idx, float* topk_logp, float* blank_logp, float* stats,
                            int32_t* cand_count, hipStream_t s);
 hipError_t launch_row_candidates(const float* logits, int64_t ld, int B, int W, int C, double thresh,
-                                 const float* stats, const int64_t* cand_off, int32_t* cand_idx,
+                                 const float* stats, const int64_t* cand_off, int pad, int32_t* cand_idx,
                                  float* cand_logp, hipStream_t s);
 
 // contiguous rows [rows][C] -> float32 log-softmax per row
@@ -318,6 +320,21 @@ hipError_t launch_beam_lm_prepass(const int32_t* idx, int nb, int W, int k, int 
 hipError_t launch_prefix_beam_lm(const int32_t* idx, const float* lp, int nb, int W, int k, int C, int beam, int nbest,
                                  double len_bonus, const int32_t* end, const BeamLm& lm, int2* hist, int32_t* len,
                                  double* logp, double* score, int32_t* cnt, hipStream_t s);
+
+// ---- the skip search (hctr_nbest_skip*): __cbs_skip__ on the thresholded candidate lists in the padded layout - row
+// r = t*nb + b has cnt[r] candidates, the first min(cnt[r], kBeamMaxK) of them in ascending class order at
+// ci / cl[r * kBeamMaxK ..], and its blank log-prob at bl[r] ----
+// launch_beam_lm_prepass serves it with k = 1 lists of the top-1 classes; its wid may be null (no word ids of the lists
+//   are written) and so may words (the zero LM: the suffixes are then unspecified and unread).
+// launch_prefix_beam_skip: over end[b] steps, rows with one candidate update the list in place, the others are ranked
+//   steps over the row's candidates; outputs as launch_prefix_beam_lm (lm.o_lm always written: 0 in used slots for the
+//   zero LM, which is lm.table.slots == null and needs no words / suffix) plus status[nb] (0 ok, 1 empty greedy text, 2
+//   the list emptied, 3 a row beyond kBeamMaxK candidates: not searched) and ranked[nb] (rows with cnt != 1 among the
+//   end[b] steps). words[C] = label -> word id on the device. launch_prefix_backtrace takes end as its T.
+hipError_t launch_prefix_beam_skip(const int32_t* cnt, const int32_t* ci, const float* cl, const float* bl, int nb, int W,
+                                   int C, int beam, int nbest, double len_bonus, const int32_t* end, const int32_t* words,
+                                   const BeamLm& lm, int2* hist, int32_t* len, double* logp, double* score,
+                                   int32_t* o_cnt, int32_t* status, int32_t* ranked, hipStream_t s);
 
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {

@@ -2777,17 +2777,19 @@ hipError_t launch_row_topk(const float* logits, int64_t ld, int B, int W, int C,
 
 __global__ __launch_bounds__(64) void row_candidates_kernel(const float* __restrict__ x, int64_t ld, int B, int W,
                                                             int C, double thresh, const float* __restrict__ stats,
-                                                            const int64_t* __restrict__ cand_off,
+                                                            const int64_t* __restrict__ cand_off, int pad,
                                                             int32_t* __restrict__ cand_idx,
                                                             float* __restrict__ cand_logp) {
     // ascending class order, like np.where (utils/ctc_codec.py:144). stats[2r], stats[2r+1] are the
     // row max and log-sum from row_topk, so the float32 log-prob is recomputed bit-identically.
+    // cand_off == null: the padded layout, row r at r * pad, candidates beyond the first pad dropped.
     const int64_t r = blockIdx.x;
     const int t = (int)(r / B), b = (int)(r % B);
     const float* p = x + ((int64_t)b * W + t) * ld;
     const float mx = stats[2 * r], logs = stats[2 * r + 1];
     const int lane = threadIdx.x;
-    int64_t base = cand_off[r];
+    const int64_t row0 = cand_off ? cand_off[r] : r * pad;
+    int64_t base = row0;
     for (int c0 = 0; c0 < C; c0 += 64) {
         const int c = c0 + lane;
         float lp = 0.f;
@@ -2797,8 +2799,8 @@ __global__ __launch_bounds__(64) void row_candidates_kernel(const float* __restr
             keep = (double)lp > thresh;
         }
         const unsigned long long m = __ballot(keep);
-        if (keep) {
-            const int64_t o = base + __popcll(m & ((1ull << lane) - 1ull));
+        const int64_t o = base + __popcll(m & ((1ull << lane) - 1ull));
+        if (keep && (cand_off || o - row0 < pad)) {
             cand_idx[o] = c;
             cand_logp[o] = lp;
         }
@@ -2837,11 +2839,12 @@ hipError_t launch_log_softmax_rows(const float* x, int64_t rows, int C, float* y
 }
 
 hipError_t launch_row_candidates(const float* logits, int64_t ld, int B, int W, int C, double thresh,
-                                 const float* stats, const int64_t* cand_off, int32_t* cand_idx,
+                                 const float* stats, const int64_t* cand_off, int pad, int32_t* cand_idx,
                                  float* cand_logp, hipStream_t s) {
     if ((int64_t)B * W == 0) return hipSuccess;
+    if (!cand_off && pad < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(row_candidates_kernel, dim3((unsigned)((int64_t)B * W)), dim3(64), 0, s, logits, ld, B, W, C,
-                       thresh, stats, cand_off, cand_idx, cand_logp);
+                       thresh, stats, cand_off, pad, cand_idx, cand_logp);
     return hipGetLastError();
 }
 
@@ -2979,12 +2982,13 @@ hipError_t launch_beam_select(const float* row_thr, const int32_t* emit_cnt, con
 }
 
 // one wave per row: the listed classes whose log-prob exceeds the threshold, in ascending class order (np.where,
-// utils/ctc_codec.py:144), written to the row's CSR slot
+// utils/ctc_codec.py:144), written to the row's CSR slot - or, with cand_off == null, to r * pad, the first pad of them
 __global__ __launch_bounds__(256) void beam_candidates_kernel(const int32_t* __restrict__ emit_cnt,
                                                               const int32_t* __restrict__ emit_list, int cap,
                                                               const float* __restrict__ stats, int B, int W,
                                                               double cand_thresh, const int64_t* __restrict__ cand_off,
-                                                              int32_t* __restrict__ cand_idx, float* __restrict__ cand_logp) {
+                                                              int pad, int32_t* __restrict__ cand_idx,
+                                                              float* __restrict__ cand_logp) {
     const int lane = threadIdx.x & 63;
     const int64_t M = (int64_t)B * W;
     const int64_t m = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -2995,7 +2999,7 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const int32_t* __r
     const int n = cnt < cap ? cnt : cap;
     const float gmax = stats[2 * r], logs = stats[2 * r + 1];
     const int32_t* e = emit_list + (int64_t)m * cap * 2;
-    const int64_t base = cand_off[r];
+    const int64_t base = cand_off ? cand_off[r] : r * pad;
     for (int i = lane; i < n; i += 64) {
         const int cls = e[2 * i];
         const float lp = (__builtin_bit_cast(float, e[2 * i + 1]) - gmax) - logs;
@@ -3005,18 +3009,20 @@ __global__ __launch_bounds__(256) void beam_candidates_kernel(const int32_t* __r
             const float lu = (__builtin_bit_cast(float, e[2 * u + 1]) - gmax) - logs;
             rank += ((double)lu > cand_thresh && e[2 * u] < cls) ? 1 : 0;
         }
+        if (!cand_off && rank >= pad) continue;
         cand_idx[base + rank] = cls;
         cand_logp[base + rank] = lp;
     }
 }
 
 hipError_t launch_beam_candidates(const int32_t* emit_cnt, const int32_t* emit_list, int cap, const float* stats,
-                                  int B, int W, double cand_thresh, const int64_t* cand_off, int32_t* cand_idx,
+                                  int B, int W, double cand_thresh, const int64_t* cand_off, int pad, int32_t* cand_idx,
                                   float* cand_logp, hipStream_t s) {
     const int64_t M = (int64_t)B * W;
     if (M <= 0) return hipSuccess;
+    if (!cand_off && pad < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(beam_candidates_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, emit_cnt, emit_list, cap, stats,
-                       B, W, cand_thresh, cand_off, cand_idx, cand_logp);
+                       B, W, cand_thresh, cand_off, pad, cand_idx, cand_logp);
     return hipGetLastError();
 }
 
@@ -4405,7 +4411,7 @@ __global__ __launch_bounds__(256) void beam_lm_prepass_kernel(const int32_t* __r
     __shared__ int4 s_suf[256];
     const int b = blockIdx.x, tid = threadIdx.x, unk = C - 1;
     const int L = min(max(Tl[b], 0), W);
-    for (int e = tid; e < L * k; e += 256) {
+    for (int e = tid; wid && e < L * k; e += 256) {
         const int t = e / k, j = e - t * k;
         const int64_t a = ((int64_t)t * nb + b) * k + j;
         const int c = idx[a];
@@ -4419,7 +4425,7 @@ __global__ __launch_bounds__(256) void beam_lm_prepass_kernel(const int32_t* __r
         if (t < L) {
             const int c = idx[((int64_t)t * nb + b) * k];
             const int prev = t > 0 ? idx[((int64_t)(t - 1) * nb + b) * k] : -1;
-            if (c != 0 && c != unk && c != prev) w = (unsigned)c < (unsigned)C ? words[c] : -1;
+            if (c != 0 && c != unk && c != prev) w = words && (unsigned)c < (unsigned)C ? words[c] : -1;
         }
         s_w[tid] = w;
         __syncthreads();
@@ -4498,6 +4504,399 @@ hipError_t launch_prefix_backtrace(const int2* hist, const int32_t* T, int nb, i
     hipLaunchKernelGGL(prefix_backtrace_kernel, dim3((unsigned)nb), dim3(64), 0, s, hist, T, W, beam, nbest, len, cnt,
                        labels);
     return hipGetLastError();
+}
+
+// -------------------------------------------------------------------------------------------
+// The skip search (hctr_nbest_skip*): __cbs_skip__ of utils/ctc_codec.py:124-181 on the front end's
+// thresholded candidate lists in the padded layout - row r = t*nb + b holds cnt[r] classes in ascending order at
+// ci / cl[r * kBeamMaxK ..], its blank log-prob at bl[r]. A sibling of prefix_beam_kernel: the same list, slots, merges,
+// keys, ranks and history; one workgroup per line over the end[b] steps of the pre-pass.
+//
+// A step whose row has ONE candidate updates every hypothesis in place. A run of such steps is wave 0's alone, one lane
+// per hypothesis with its state in registers: lane j of the wave fetches step t + j's (count, class, log-prob, blank
+// log-prob, word id), a ballot finds where the run ends, and the steps are taken from the lanes by broadcast - one
+// round of memory latency per 64 steps, no LDS traffic and no barrier inside the run; the other waves wait at the one
+// barrier behind it. A step costs at most one logaddexp and, when it appends, one lm_word_logp. Its history record is
+// {same place, appended label or -1}, so prefix_backtrace_kernel walks it like any other.
+//
+// A step with m != 1 candidates is prefix_beam_kernel's step with k := m (the candidates in class order, so are the
+// first-touch keys), behind one more phase of wave 0: the row goes to LDS and, when an in-place step has appended a
+// label since the last ranked step, the list is FOLDED - hypotheses of equal (length, fingerprint) become the first of
+// them with pb = logaddexp over their pb in list order and pnb likewise, the rest close up (an in-place step never
+// merges, so "a" with pb finite and "aa" become "aa", "aa"; the reference's dict sums them in this step, since equal
+// texts see the same candidates and spread the same terms). h_src keeps each survivor's place before the fold for the
+// step's history record. After the fold the texts are distinct and the one-lookup merges hold again.
+//
+// A line with a row of more than kBeamMaxK candidates inside its end step is not searched (status 3); m = 0 empties
+// the list (status 2); the result is the first nbest of the final list as it stands - after a trailing run of in-place
+// steps unsorted and possibly with a text twice. LM = false is the zero LM: no table, no word ids, lm_score 0.
+// -------------------------------------------------------------------------------------------
+template <int BEAM, int NW, bool LM>
+__global__ __launch_bounds__(64 * NW) void prefix_beam_skip_kernel(
+    const int32_t* __restrict__ cnt, const int32_t* __restrict__ ci, const float* __restrict__ cl,
+    const float* __restrict__ bl, int nb, int W, int unk, int beam, int nbest, double len_bonus,
+    const int32_t* __restrict__ Tl, const int32_t* __restrict__ words, int2* __restrict__ hist,
+    int32_t* __restrict__ o_len, double* __restrict__ o_logp, double* __restrict__ o_score, int32_t* __restrict__ o_cnt,
+    int32_t* __restrict__ o_status, int32_t* __restrict__ o_ranked, const BeamLm lm) {
+    constexpr int K = kBeamMaxK, NT = 64 * NW, SLOTS = BEAM * (K + 1);
+    constexpr int LB = LM ? BEAM : 1, LS = LM ? SLOTS : 1, LK = LM ? K : 1, NCX = kLmMaxOrder - 1;
+    constexpr double NINF = -__builtin_huge_val();
+    __shared__ double h_lm[2][LB], e_lm[LS];
+    __shared__ int h_cx[2][LB][NCX], r_w[LK];
+    __shared__ double h_pb[2][BEAM], h_pnb[2][BEAM], h_tot[2][BEAM];
+    __shared__ unsigned long long h_hash[2][BEAM], h_par[2][BEAM];
+    __shared__ int h_len[2][BEAM], h_last[2][BEAM], h_src[BEAM];
+    __shared__ BeamSortKey e_sort[SLOTS];          // ord 0 = the slot holds no entry
+    __shared__ double e_pb[SLOTS], e_pnb[SLOTS], e_tot[SLOTS];
+    __shared__ int r_cls[K];
+    __shared__ double r_lp[K];
+    __shared__ int r_meta[2];                      // {the row's first usable class j0, the place of the blank}, -1 = none
+    __shared__ int s_n[2], s_valid[NW], s_scan[NW][2], s_run[2];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int T = min(max(Tl[b], 0), W);
+    int2* __restrict__ hb = hist + (int64_t)b * W * beam;
+
+    // the line's rows once: how many of its steps are ranked ones, and whether one of them is beyond the cap
+    int ranked = 0, big = 0;
+    for (int t = tid; t < T; t += NT) {
+        const int m = cnt[(int64_t)t * nb + b];
+        ranked += m != 1;
+        big |= m > K;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        ranked += __shfl_xor(ranked, off);
+        big |= __shfl_xor(big, off);
+    }
+    if ((tid & 63) == 0) { s_scan[tid >> 6][0] = ranked; s_scan[tid >> 6][1] = big; }
+    if (tid == 0) {                                // [((), 0, -inf)]
+        h_pb[0][0] = 0.0; h_pnb[0][0] = NINF; h_tot[0][0] = 0.0;
+        h_hash[0][0] = 0x243F6A8885A308D3ull; h_par[0][0] = 0ull;
+        h_len[0][0] = 0; h_last[0][0] = -1;
+        s_n[0] = 1;
+        if constexpr (LM) {                        // score 0 in the <s> context
+            h_lm[0][0] = 0.0;
+            for (int q = 0; q < NCX; ++q) h_cx[0][0][q] = q == NCX - 1 ? lm.bos : -1;
+        }
+    }
+    __syncthreads();
+    ranked = 0; big = 0;
+    for (int w = 0; w < NW; ++w) { ranked += s_scan[w][0]; big |= s_scan[w][1]; }
+    int status = T == 0 ? 1 : big ? 3 : 0;
+    const int Te = status ? 0 : T;                 // (block-uniform)
+
+    int cur = 0, t = 0;
+    bool dirty = false;                            // an in-place step has appended a label since the last ranked step
+    while (t < Te) {
+        const int nxt = cur ^ 1;
+        int n = s_n[cur];
+        if (n == 0) break;                         // (block-uniform) a row without a usable candidate: nothing is left
+        const int m = cnt[(int64_t)t * nb + b];
+        if (m == 1) {
+            // ---- a run of in-place steps: wave 0, hypothesis tid in registers ----
+            if (tid < 64) {
+                const bool live = tid < n;
+                const int hi = live ? tid : 0;     // (a lane past the list idles through hypothesis 0's arithmetic)
+                double pb = h_pb[cur][hi], pnb = h_pnb[cur][hi], tot = h_tot[cur][hi];
+                unsigned long long hash = h_hash[cur][hi], par = h_par[cur][hi];
+                int len = h_len[cur][hi], last = h_last[cur][hi];
+                double sc = 0.0;
+                int cx[NCX];
+                if constexpr (LM) {
+                    sc = h_lm[cur][hi];
+#pragma unroll
+                    for (int q = 0; q < NCX; ++q) cx[q] = h_cx[cur][hi][q];
+                }
+                bool app = false;
+                int t2 = t;
+                for (bool more = true; more;) {
+                    const int tj = t2 + tid;
+                    const bool in = tj < Te;
+                    const int64_t r = (int64_t)(in ? tj : t2) * nb + b;
+                    const int mj = in ? cnt[r] : 0;
+                    const int cj = ci[r * K];
+                    const float lj = cl[r * K], l0j = bl[r];
+                    int wj = -1;
+                    if constexpr (LM) wj = mj == 1 && (unsigned)cj <= (unsigned)unk ? words[cj] : -1;
+                    const unsigned long long stop = __ballot(mj != 1);
+                    const int run = stop ? __ffsll((long long)stop) - 1 : 64;
+                    for (int j = 0; j < run; ++j) {
+                        const int c = __shfl(cj, j);
+                        const double l = (double)__shfl(lj, j), l0 = (double)__shfl(l0j, j);
+                        const int w = __shfl(wj, j);
+                        int label = -1;
+                        if (c == 0) {
+                            pb = tot + l;
+                            tot = beam_logaddexp(pb, pnb);
+                        } else if (c > 0 && c < unk) {
+                            const bool rep = c == last;
+                            if (rep && pb == NINF) {       // the repeat read as the same character: pb first, from the old pnb
+                                pb = tot + l0;
+                                pnb = pnb + l;
+                                tot = beam_logaddexp(pb, pnb);
+                            } else {
+                                pnb = (rep ? pb : tot) + l;
+                                pb = NINF;
+                                tot = pnb;
+                                label = c;
+                                par = hash;
+                                hash = beam_mix(hash, c);
+                                ++len;
+                                last = c;
+                                if constexpr (LM) {
+                                    sc += lm_word_logp(lm.table, cx, w);
+                                    lm_roll(cx, w);
+                                }
+                            }
+                        }
+                        app = app || label >= 0;
+                        if (live) hb[(int64_t)(t2 + j) * beam + tid] = make_int2(tid, label);
+                    }
+                    t2 += run;
+                    more = run == 64 && t2 < Te;
+                }
+                if (live) {
+                    h_pb[cur][tid] = pb; h_pnb[cur][tid] = pnb; h_tot[cur][tid] = tot;
+                    h_hash[cur][tid] = hash; h_par[cur][tid] = par;
+                    h_len[cur][tid] = len; h_last[cur][tid] = last;
+                    if constexpr (LM) {
+                        h_lm[cur][tid] = sc;
+#pragma unroll
+                        for (int q = 0; q < NCX; ++q) h_cx[cur][tid][q] = cx[q];
+                    }
+                }
+                const bool any = __any(app && live);
+                if (tid == 0) { s_run[0] = t2; s_run[1] = any; }
+            }
+            __syncthreads();
+            t = s_run[0];
+            dirty = dirty || s_run[1] != 0;
+            continue;
+        }
+        // ---- a ranked step. Phase 0 (wave 0): the row into LDS; the fold ----
+        const bool fold = dirty;
+        if (tid < 64) {
+            const bool have = tid < m;
+            const int64_t a = ((int64_t)t * nb + b) * K + tid;
+            const int c = have ? ci[a] : 0;
+            const unsigned long long usable = __ballot(have && (unsigned)c < (unsigned)unk);
+            const unsigned long long blank = __ballot(have && c == 0);
+            if (have) { r_cls[tid] = c; r_lp[tid] = (double)cl[a]; }
+            if constexpr (LM) {
+                if (have) r_w[tid] = (unsigned)c <= (unsigned)unk ? words[c] : -1;
+            }
+            if (tid == 0) {
+                r_meta[0] = usable ? __ffsll((long long)usable) - 1 : -1;
+                r_meta[1] = blank ? __ffsll((long long)blank) - 1 : -1;
+            }
+            if (fold) {
+                const bool live = tid < n;
+                const int i = live ? tid : 0;
+                const int leni = h_len[cur][i];
+                const unsigned long long hashi = h_hash[cur][i];
+                double pb = h_pb[cur][i], pnb = h_pnb[cur][i];
+                int first = i;
+                for (int q = 0; q < n; ++q) {
+                    if (q == i || h_len[cur][q] != leni || h_hash[cur][q] != hashi) continue;
+                    if (q < first) first = q;
+                    if (q > i) { pb = beam_logaddexp(pb, h_pb[cur][q]); pnb = beam_logaddexp(pnb, h_pnb[cur][q]); }
+                }
+                const bool keep = live && first == i;
+                const unsigned long long km = __ballot(keep);
+                if (keep) {
+                    const int pos = __popcll(km & ((1ull << tid) - 1ull));
+                    h_pb[nxt][pos] = pb; h_pnb[nxt][pos] = pnb; h_tot[nxt][pos] = beam_logaddexp(pb, pnb);
+                    h_hash[nxt][pos] = hashi; h_par[nxt][pos] = h_par[cur][i];
+                    h_len[nxt][pos] = leni; h_last[nxt][pos] = h_last[cur][i];
+                    h_src[pos] = i;
+                    if constexpr (LM) {
+                        h_lm[nxt][pos] = h_lm[cur][i];
+#pragma unroll
+                        for (int q = 0; q < NCX; ++q) h_cx[nxt][pos][q] = h_cx[cur][i][q];
+                    }
+                }
+                if (tid == 0) s_n[nxt] = __popcll(km);
+            }
+        }
+        __syncthreads();
+        if (fold) {
+            cur ^= 1;
+            n = s_n[cur];
+        }
+        const int out = cur ^ 1, k = m, k1 = m + 1;
+        int4 sfx = make_int4(-2, -2, -2, -2);      // the step's suffix as word ids, -2 = no more
+        if constexpr (LM) sfx = lm.suffix[(int64_t)b * W + t];
+        const int j0 = r_meta[0], jb = r_meta[1], E = n * k1;
+        // entries (prefix_beam_kernel's, with k = m)
+        int nvalid = 0;                            // valid entries of this wave's slots (wave-uniform)
+        for (int e0 = 0; e0 < E; e0 += NT) {       // (block-uniform trips: the ballot below counts whole waves)
+            const int e = e0 + tid;
+            const bool in = e < E;
+            const int i = !in ? 0 : e < n ? e : (e - n) / k, jj = !in ? (k ? 1 : 0) : e < n ? 0 : e - n - i * k + 1;
+            const int leni = h_len[cur][i], lasti = h_last[cur][i];
+            bool valid;
+            unsigned key;
+            double pb = NINF, pnb = NINF, tot;
+            if (jj == 0) {                         // the prefix's own entry
+                valid = j0 >= 0;
+                key = (unsigned)(i * k + max(j0, 0)) * 2u;
+                if (jb >= 0) pb = h_tot[cur][i] + r_lp[jb];
+                int jt = -1;
+#pragma unroll 4
+                for (int j = 0; j < k; ++j)
+                    if (r_cls[j] == lasti) jt = j;
+                if (jt >= 0 && lasti > 0 && lasti < unk) {
+                    const double l = r_lp[jt];
+                    const unsigned long long want = h_par[cur][i];
+                    int p = -1;                    // the hypothesis whose extension by the last label this prefix is
+#pragma unroll 4
+                    for (int q = 0; q < n; ++q)
+                        if (h_len[cur][q] == leni - 1 && h_hash[cur][q] == want) p = q;
+                    double ext = NINF;
+                    if (p >= 0) {
+                        ext = (h_last[cur][p] != lasti ? h_tot[cur][p] : h_pb[cur][p]) + l;
+                        key = min(key, (unsigned)(p * k + jt) * 2u + 1u);
+                    }
+                    pnb = beam_logaddexp(h_pnb[cur][i] + l, ext);
+                }
+                tot = beam_logaddexp(pb, pnb);
+            } else {                               // the extension by class j
+                const int j = jj - 1, c = r_cls[j];
+                valid = c > 0 && c < unk;
+                key = (unsigned)(i * k + j) * 2u + 1u;
+                if (valid) {
+                    const unsigned long long mine = h_hash[cur][i];
+#pragma unroll 4
+                    for (int q = 0; q < n; ++q)    // already in the list: its own slot takes this mass
+                        if (h_len[cur][q] == leni + 1 && h_last[cur][q] == c && h_par[cur][q] == mine) valid = false;
+                }
+                pnb = (c != lasti ? h_tot[cur][i] : h_pb[cur][i]) + r_lp[j];
+                tot = pnb;                         // logaddexp(-inf, x) = x
+            }
+            valid = valid && in;
+            nvalid += __popcll(__ballot(valid));
+            double total = 0.0;
+            if constexpr (LM) {
+                if (valid) {
+                    int cx[NCX];
+#pragma unroll
+                    for (int q = 0; q < NCX; ++q) cx[q] = h_cx[cur][i][q];
+                    double sc = h_lm[cur][i];
+                    if (jj) {
+                        const int w = r_w[jj - 1];
+                        sc += lm_word_logp(lm.table, cx, w);
+                        lm_roll(cx, w);
+                    }
+                    e_lm[e] = sc;
+                    int4 rest = sfx;
+#pragma unroll 1
+                    for (int q = 0; q < 4 && rest.x != -2; ++q) {
+                        sc += lm_word_logp(lm.table, cx, rest.x);
+                        lm_roll(cx, rest.x);
+                        rest = make_int4(rest.y, rest.z, rest.w, -2);
+                    }
+                    total = beam_total_lm(tot, sc, leni + (jj ? 1 : 0), lm.lm_panelty, len_bonus);
+                }
+            } else {
+                total = beam_total(tot, leni + (jj ? 1 : 0), len_bonus);
+            }
+            if (in) {
+                e_sort[e] = BeamSortKey{valid ? beam_ord(total) : 0ull, key, 0u};
+                e_pb[e] = pb; e_pnb[e] = pnb; e_tot[e] = tot;
+            }
+        }
+        if ((tid & 63) == 0) s_valid[tid >> 6] = nvalid;
+        __syncthreads();
+        // ranks; the first `beam` become the next list
+        for (int e = tid; e < E; e += NT) {
+            const unsigned long long ord = e_sort[e].ord;
+            const unsigned key = e_sort[e].key;
+            int rank = 0;
+#pragma unroll 8
+            for (int f = 0; f < E; ++f) {          // (broadcast loads, eight in flight)
+                const BeamSortKey o = e_sort[f];
+                rank += (o.ord > ord) || (o.ord == ord && o.key < key);
+            }
+            if (e == 0) {
+                int c2 = 0;
+                for (int w = 0; w < NW; ++w) c2 += s_valid[w];
+                s_n[out] = min(c2, beam);
+            }
+            if (ord != 0ull && rank < beam) {
+                const int i = e < n ? e : (e - n) / k, jj = e < n ? 0 : e - n - i * k + 1;
+                const int c = jj ? r_cls[jj - 1] : -1;
+                const unsigned long long hi = h_hash[cur][i];
+                h_pb[out][rank] = e_pb[e]; h_pnb[out][rank] = e_pnb[e]; h_tot[out][rank] = e_tot[e];
+                h_len[out][rank] = h_len[cur][i] + (jj ? 1 : 0);
+                h_last[out][rank] = jj ? c : h_last[cur][i];
+                h_hash[out][rank] = jj ? beam_mix(hi, c) : hi;
+                h_par[out][rank] = jj ? hi : h_par[cur][i];
+                if constexpr (LM) {
+                    h_lm[out][rank] = e_lm[e];
+                    const int w = jj ? r_w[jj - 1] : -1;
+#pragma unroll
+                    for (int q = 0; q < NCX; ++q)
+                        h_cx[out][rank][q] = !jj ? h_cx[cur][i][q] : q + 1 < NCX ? h_cx[cur][i][q + 1] : w;
+                }
+                hb[(int64_t)t * beam + rank] = make_int2(fold ? h_src[i] : i, c);
+            }
+        }
+        __syncthreads();
+        cur = out;
+        dirty = false;
+        ++t;
+    }
+    const int n = status ? 0 : s_n[cur];
+    if (!status && n == 0) status = 2;
+    if (tid < nbest) {
+        const bool have = tid < n;
+        const int len = have ? h_len[cur][tid] : 0;
+        const double logp = have ? h_tot[cur][tid] : NINF;
+        const int64_t o = (int64_t)b * nbest + tid;
+        o_len[o] = len;
+        o_logp[o] = logp;
+        if constexpr (LM) {
+            const double sc = have ? h_lm[cur][tid] : NINF;
+            o_score[o] = have ? beam_total_lm(logp, sc, len, lm.lm_panelty, len_bonus) : NINF;
+            lm.o_lm[o] = sc;
+        } else {
+            o_score[o] = have ? beam_total(logp, len, len_bonus) : NINF;
+            lm.o_lm[o] = have ? 0.0 : NINF;
+        }
+    }
+    if (tid == 0) {
+        o_cnt[b] = min(n, nbest);
+        o_status[b] = status;
+        o_ranked[b] = ranked;
+    }
+}
+
+// the instances (beam, wave64s per line), every one with kBeamMaxK candidates per ranked step: 330, 528 and 1056 slots
+#define HCTR_SKIP_LADDER(X) X(10, 1) X(16, 4) X(32, 4)
+
+hipError_t launch_prefix_beam_skip(const int32_t* cnt, const int32_t* ci, const float* cl, const float* bl, int nb, int W,
+                                   int C, int beam, int nbest, double len_bonus, const int32_t* end, const int32_t* words,
+                                   const BeamLm& lm, int2* hist, int32_t* len, double* logp, double* score,
+                                   int32_t* o_cnt, int32_t* status, int32_t* ranked, hipStream_t s) {
+    if (nb <= 0) return hipSuccess;
+    if (beam < 1 || nbest < 1 || nbest > beam || C < 2 || W < 1 || !lm.o_lm) return hipErrorInvalidValue;
+    const bool use_lm = lm.table.slots != nullptr;
+    if (use_lm && (lm.table.order < 1 || lm.table.order > kLmMaxOrder || !lm.suffix || !words)) return hipErrorInvalidValue;
+#define SKIP_RUNG(BEAM, NW)                                                                                             \
+    if (beam <= BEAM) {                                                                                                 \
+        if (use_lm)                                                                                                     \
+            hipLaunchKernelGGL((prefix_beam_skip_kernel<BEAM, NW, true>), dim3((unsigned)nb), dim3(64 * NW), 0, s, cnt, ci, \
+                               cl, bl, nb, W, C - 1, beam, nbest, len_bonus, end, words, hist, len, logp, score, o_cnt,  \
+                               status, ranked, lm);                                                                     \
+        else                                                                                                            \
+            hipLaunchKernelGGL((prefix_beam_skip_kernel<BEAM, NW, false>), dim3((unsigned)nb), dim3(64 * NW), 0, s, cnt, \
+                               ci, cl, bl, nb, W, C - 1, beam, nbest, len_bonus, end, words, hist, len, logp, score,     \
+                               o_cnt, status, ranked, lm);                                                              \
+        return hipGetLastError();                                                                                       \
+    }
+    HCTR_SKIP_LADDER(SKIP_RUNG)
+#undef SKIP_RUNG
+    return hipErrorInvalidValue;
 }
 
 }  // namespace hctr

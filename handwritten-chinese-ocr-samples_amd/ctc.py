@@ -476,11 +476,15 @@ class NBest(object):
     each text over the alignments the pruned search kept; ``scores`` float64 [B, n], what the search ranked by
     (``logp + length * len_bonus``); ``counts`` int32 [B], how many hypotheses a line really has (unused slots have
     length 0 and -inf). ``lm_scores`` is None without a language model; with one (``hctr_nbest_lm*``) it is float64
-    [B, n], the n-gram log10 score of each text, and ``scores`` is ``logp + lm_score * lm_panelty + length * len_bonus``."""
+    [B, n], the n-gram log10 score of each text, and ``scores`` is ``logp + lm_score * lm_panelty + length * len_bonus``.
+    ``status`` and ``ranked`` are None except for the skip search (``hctr_nbest_skip*``): int32 [B], per line 0 ok / 1
+    empty greedy text / 2 list emptied by a row without usable candidates / 3 a row beyond 32 candidates (not searched),
+    and how many of the line's steps were ranked ones (the others updated the list in place). A skip search returns the
+    final list as it stands: after trailing in-place steps it need not be sorted and may hold a text twice."""
 
-    def __init__(self, labels, lengths, logps, scores, counts, lm_scores=None):
+    def __init__(self, labels, lengths, logps, scores, counts, lm_scores=None, status=None, ranked=None):
         self.labels, self.lengths, self.logps, self.scores, self.counts = labels, lengths, logps, scores, counts
-        self.lm_scores = lm_scores
+        self.lm_scores, self.status, self.ranked = lm_scores, status, ranked
 
     def __len__(self):
         return len(self.counts)
@@ -575,6 +579,63 @@ def nbest_images(ctx, x, dt, on_dev, widths, B, W, n=5, beam=10, depth=10, len_b
     _lib.check(_lib.load().hctr_nbest(ctx, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, depth, beam, n, bonus,
                                       _lib.ptr(il), *[_lib.ptr(a) for a in out]), ctx)
     return NBest(*out)
+
+
+def _skip_args(lm, lm_panelty, out, B):
+    lms = np.full(out[2].shape, -np.inf, np.float64)
+    return lm, ctypes.c_double(float(lm_panelty)), out + (lms, np.zeros((B,), np.int32), np.zeros((B,), np.int32))
+
+
+def _skip_result(out):
+    return NBest(*out[:5], lm_scores=out[5], status=out[6], ranked=out[7])
+
+
+def nbest_skip_lists(ctx, top1_idx, blank_logp, cand_off, cand_idx, cand_logp, C, n=5, beam=10, len_bonus=0.0,
+                     input_lengths=None, lm=None, lm_panelty=2.0):
+    """NBest by the reference's skip search on front-end lists (hctr_nbest_skip_lists): ``top1_idx`` int32 / ``blank_logp``
+    float32 [W, B] and the CSR candidate lists ``cand_off`` int64 [W*B + 1], ``cand_idx`` int32, ``cand_logp`` float32
+    (row t*B + b, classes ascending) as ``codec.beam_frontend_call(..., want_candidates=True)`` returns them. ``lm`` is an
+    ``hctr_lm`` handle (``codec.ArpaLM.flat``) or None, the zero LM."""
+    top1 = np.ascontiguousarray(top1_idx, dtype=np.int32)
+    bl = np.ascontiguousarray(blank_logp, dtype=np.float32)
+    if top1.ndim != 2 or top1.shape != bl.shape:
+        raise ValueError("top1_idx and blank_logp must both be [W,B]")
+    W, B = (int(v) for v in top1.shape)
+    off = np.ascontiguousarray(cand_off, dtype=np.int64)
+    if off.shape != (W * B + 1,):
+        raise ValueError("cand_off must be [W*B + 1]")
+    ci = np.ascontiguousarray(cand_idx, dtype=np.int32)
+    cl = np.ascontiguousarray(cand_logp, dtype=np.float32)
+    if ci.ndim != 1 or ci.shape != cl.shape or (off.size and ci.size < int(off.max())):
+        raise ValueError("cand_idx and cand_logp must be flat and hold cand_off's last offset")
+    n, beam, _, bonus, il, out = _nbest_args(B, W, n, beam, 1, len_bonus, input_lengths)
+    lm, pen, out = _skip_args(lm, lm_panelty, out, B)
+    _lib.check(_lib.load().hctr_nbest_skip_lists(ctx, lm, _lib.ptr(top1), _lib.ptr(bl), _lib.ptr(off), _lib.ptr(ci),
+                                                 _lib.ptr(cl), W, B, int(C), beam, n, pen, bonus, _lib.ptr(il),
+                                                 *[_lib.ptr(a) for a in out]), ctx)
+    return _skip_result(out)
+
+
+def nbest_skip_logits(ctx, logits, on_dev, n=5, beam=10, len_bonus=0.0, input_lengths=None, lm=None, lm_panelty=2.0):
+    """NBest by the skip search of caller logits / log-probs in WBC layout (hctr_nbest_skip_logits)"""
+    if len(logits.shape) != 3:
+        raise ValueError("logits must be [W,B,C]")
+    W, B, C = (int(v) for v in logits.shape)
+    n, beam, _, bonus, il, out = _nbest_args(B, W, n, beam, 1, len_bonus, input_lengths)
+    lm, pen, out = _skip_args(lm, lm_panelty, out, B)
+    _lib.check(_lib.load().hctr_nbest_skip_logits(ctx, lm, _lib.ptr(logits), on_dev, W, B, C, beam, n, pen, bonus,
+                                                  _lib.ptr(il), *[_lib.ptr(a) for a in out]), ctx)
+    return _skip_result(out)
+
+
+def nbest_skip_images(ctx, x, dt, on_dev, widths, B, W, n=5, beam=10, len_bonus=0.0, input_lengths=None, lm=None,
+                      lm_panelty=2.0):
+    """NBest by the skip search of line images (hctr_nbest_skip); x, dt, on_dev, widths as in ``nbest_images``"""
+    n, beam, _, bonus, il, out = _nbest_args(B, W, n, beam, 1, len_bonus, input_lengths)
+    lm, pen, out = _skip_args(lm, lm_panelty, out, B)
+    _lib.check(_lib.load().hctr_nbest_skip(ctx, lm, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, beam, n, pen, bonus,
+                                           _lib.ptr(il), *[_lib.ptr(a) for a in out]), ctx)
+    return _skip_result(out)
 
 
 _FN = None

@@ -298,7 +298,7 @@ class hctr_model(object):
         return ctc.evaluate_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, targets, target_lengths, maps)
 
     def nbest(self, input, n=5, beam=10, depth=10, len_bonus=0.0, widths=None, input_lengths=None, lm=None,
-              lm_panelty=2.0, codec=None):
+              lm_panelty=2.0, codec=None, skip_search=False):
         """Forward + CTC prefix beam search without a language model, on the device: the ``n`` best texts of every line
         with their log-probabilities, what rescoring with any language model starts from. ``beam`` hypotheses are kept
         per step over the ``depth`` likeliest classes of each pixel column (the reference's beam_size / search_depth,
@@ -308,7 +308,10 @@ class hctr_model(object):
         (include/hctr_hip.h ``hctr_nbest``).
         With ``lm`` (a ``codec.ArpaLM``) the search is the reference's n-gram-scored one (``hctr_nbest_lm``, arguments
         as ``ctc_codec.nbest``); ``codec``, the ``ctc_codec`` whose characters the classes are, is then required - it
-        maps labels to the model's words - and ``.texts`` is filled from it whenever it is given."""
+        maps labels to the model's words - and ``.texts`` is filled from it whenever it is given.
+        ``skip_search=True`` takes the reference's skip variant (``hctr_nbest_skip``, as ``ctc_codec.nbest`` describes it):
+        ``depth`` is not used, ``lm`` None is the zero LM, ``.status`` and ``.ranked`` are filled, and no list visits the
+        host between the front end and the search."""
         from . import ctc
         ctx = self._require_ctx()
         x, dt, on_dev, B, W = self._img_args(input)
@@ -317,6 +320,12 @@ class hctr_model(object):
             if codec is None:
                 raise ValueError("nbest with a language model needs codec= (the ctc_codec of this model's classes)")
             flat = lm.flat(codec.characters)
+        if skip_search:
+            res = ctc.nbest_skip_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, n, beam, len_bonus,
+                                        input_lengths, lm=flat, lm_panelty=lm_panelty)
+            if codec is not None:
+                res.texts = [codec.labels_to_text(line) for line in res.label_lists()]
+            return res
         res = ctc.nbest_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, n, beam, depth, len_bonus,
                                input_lengths, lm=flat, lm_panelty=lm_panelty)
         if codec is not None:

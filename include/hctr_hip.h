@@ -524,6 +524,76 @@ int hctr_nbest_lm(hctr_ctx* ctx, const hctr_lm* lm, const void* img, int img_dty
                   const int32_t* input_lengths, int32_t* labels, int32_t* lengths, double* logp, double* score,
                   int32_t* count, double* lm_score);
 
+/* ---- N-best texts by the reference's SKIP search, on the device -------------------------------------------------
+ * __cbs_skip__ of utils/ctc_codec.py:124-181 (test.py -ss; what hctr_beam_search does with skip_search != 0 and
+ * builtin_lm == 3 or 1): the search of hctr_nbest_lm*, except that a column in which ONE class alone has probability above
+ * 0.001 updates the kept hypotheses in place - no extension fan-out, no LM call, no sort. lm == NULL is the zero LM (the
+ * reference's skip_zero setting); lm_panelty is then unused. Line numbers below refer to utils/ctc_codec.py.
+ *   Greedy line, end step, suffix: exactly those of hctr_nbest_lm*, from the top-1 class of each row, computed on the
+ *     device. An empty greedy text gives count[b] = 0 (status 1).
+ *   Candidate set: at step t < end_b the row's candidate list, the m classes whose float32 log-prob exceeds ln(0.001), in
+ *     class-ascending order (np.where, :144) - not the top-k list.
+ *   In-place step (m == 1, :147-171). If the class c is >= C-1, nothing changes. Otherwise every hypothesis is updated on
+ *     its own, in list order, with l the class's log-prob, l0 the row's blank log-prob and tot = logaddexp(pb, pnb):
+ *       c == 0:                       pb = tot + l (pnb stays);
+ *       c != tail:                    append c, pnb = tot + l, pb = -inf;
+ *       c == tail and pb != -inf:     append c, pnb = pb + l, pb = -inf;
+ *       c == tail and pb == -inf:     pb = tot + l0, pnb = pnb + l - pb first, from the old pnb; the blank is read though
+ *                                     it is no candidate (:170).
+ *     No merge, no LM ranking, no sort, no cut: the list keeps its order and may afterwards hold equal texts. An appended
+ *     label advances the hypothesis' fingerprint, length, last label, running n-gram score (one term) and context.
+ *   Ranked step (m != 1): steps 1-5 of hctr_nbest* with the ranking of hctr_nbest_lm* and the m candidates in list order
+ *     (first-touch keys and the tie rule follow that order). Hypotheses with equal texts are FOLDED before the step: the
+ *     first keeps its place and its LM state and takes pb = logaddexp over their pb in list order, pnb likewise; the
+ *     later ones leave and the rest close up. This is the sum the reference's dict forms in that step - equal texts see
+ *     the same candidates - with another order of additions: results agree with the reference's order of operations to
+ *     rounding, not to the bit. m == 0 empties the list, as the reference's empty dict does: count[b] = 0 (status 2),
+ *     where the reference raises IndexError at :179.
+ *   Cap: a ranked step holds at most 32 candidates. A line with a row of m > 32 inside its end step is not searched:
+ *     count[b] = 0, status 3; the other lines are unaffected and the call returns HCTR_OK. (Probabilities above 0.001
+ *     allow m up to 999; searching such rows in chunks of 32 is the follow-up)
+ *   Result: the first nbest hypotheses of the final list AS THE LIST STANDS. After a trailing run of in-place steps it
+ *     is not sorted by score and may hold a text twice; the reference returns kept_beams[0] of exactly that list.
+ * Outputs as hctr_nbest_lm*: logp = logaddexp(pb, pnb); lm_score = the running n-gram score of the text, 0 in used
+ * slots for lm == NULL (-inf in unused ones); score = logp + lm_score * lm_panelty + len * len_bonus, each product rounded
+ * on its own, computed at the end (logp + len * len_bonus for lm == NULL); and per line
+ *   status int32 [B]: 0 ok, 1 empty greedy text, 2 list emptied by a row without usable candidates, 3 overflow;
+ *   ranked int32 [B]: how many of the line's end_b steps have m != 1 (ranked steps); the others are in-place.
+ * Any output may be NULL (labels needs lengths). Limits and errors as hctr_nbest_lm* (1 <= nbest <= beam <= 32, a NaN
+ * len_bonus, with an lm a NaN lm_panelty and an lm built for another C); HCTR_ERR_NOMEM leaves the context usable. No
+ * atomics: repeated calls are bit-identical. The context's device copy of the lm is the one hctr_nbest_lm* use.
+ * hctr_nbest_skip_lists takes the caller's lists on the host, as hctr_beam_frontend(want_candidates = 1) and
+ *   hctr_beam_fetch_candidates return them: top1_idx int32 [W][B] (the greedy line needs no more of the top-k),
+ *   blank_logp float32 [W][B], cand_off int64 [W*B + 1] / cand_idx / cand_logp (row r = t*B + b). The search alone; needs
+ *   no weights. HCTR_ERR_ARG for offsets that decrease, a class outside [0, C), classes of a row not strictly ascending.
+ * hctr_nbest_skip_logits takes logits (or log-probs) in WBC layout, host or device pointer, runs the stored-logits
+ *   front end and the search on its lists; needs no weights.
+ * hctr_nbest_skip runs the forward of img (arguments as hctr_nbest_lm, without k: only the top-1 class is read) in
+ *   internal passes; inside a pass the candidate counts stay on the device - the lists go to a padded layout, 32
+ *   entries per row beside the row's count - so nothing visits the host between front end and search. Mode 2 runs
+ *   every line in f16x3 and leaves the guard figures alone, as hctr_nbest* do.
+ * Launches after the front end's own: skip_candidates (not for _lists), beam_lm_prepass, prefix_beam_skip,
+ * prefix_backtrace.
+ * Device scratch (the CTC scratch; n = B, for hctr_nbest_skip the lines of one pass): 4 * B (steps) + 8 * n*W*beam
+ * (history: one {place, label} per step and place, in-place steps included) + 4 * n*nbest*W (labels) + 28 * n*nbest +
+ * 16 * n*W (suffixes) + 16 * n (count, end step, status, ranked), each array rounded up to 256 bytes; besides, for
+ * hctr_nbest_skip_lists 268 * W*B bytes for the uploaded lists (count, top-1, blank and 32 padded candidates per row),
+ * for the other two 256 * n*W bytes of padded candidates beside the front end's own outputs, and for
+ * hctr_nbest_skip_logits the rows as hctr_nbest_logits holds them. */
+int hctr_nbest_skip_lists(hctr_ctx* ctx, const hctr_lm* lm, const int32_t* top1_idx, const float* blank_logp,
+                          const int64_t* cand_off, const int32_t* cand_idx, const float* cand_logp, int W, int B, int C,
+                          int beam, int nbest, double lm_panelty, double len_bonus, const int32_t* input_lengths,
+                          int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count, double* lm_score,
+                          int32_t* status, int32_t* ranked);
+int hctr_nbest_skip_logits(hctr_ctx* ctx, const hctr_lm* lm, const float* logits_wbc, int on_device, int W, int B, int C,
+                           int beam, int nbest, double lm_panelty, double len_bonus, const int32_t* input_lengths,
+                           int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count, double* lm_score,
+                           int32_t* status, int32_t* ranked);
+int hctr_nbest_skip(hctr_ctx* ctx, const hctr_lm* lm, const void* img, int img_dtype, int img_on_device,
+                    const int32_t* widths, int B, int W, int beam, int nbest, double lm_panelty, double len_bonus,
+                    const int32_t* input_lengths, int32_t* labels, int32_t* lengths, double* logp, double* score,
+                    int32_t* count, double* lm_score, int32_t* status, int32_t* ranked);
+
 /* ---- line preprocessing on the device: replaces read_resize_image / pil_loader -----------------
  * test.py:207-216 (cv2.cvtColor BGR2GRAY + cv2.resize(src, (tw, 128), interpolation=cv2.INTER_AREA)) and
  * utils/dataset.py:47-60 (the same resize inside ImageDataset.pil_loader). Image files are decoded by

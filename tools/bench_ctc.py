@@ -58,7 +58,16 @@ hctr_beam_search(builtin_lm = 3) on 16 threads on the same lists, at beam 10 / d
 model is an ARPA file the tool writes itself: order 5 over the synthetic vocabulary, deterministic, about 330 000
 n-grams (a 32 MB table, so the probes miss L2). Calls alternate after warm-up calls of each, medians; the device time of
 the search's launches (pre-pass, search, backtrace) and of the zero-LM prefix_beam over the same end steps come from
-profiled calls of the same run; the lines whose 1-best differs from the host search's are counted."""
+profiled calls of the same run; the lines whose 1-best differs from the host search's are counted.
+
+    python tools/bench_ctc.py --nbest-skip ...
+
+times the device skip search (hctr_nbest_skip*) on the trained-like checkpoint's glyph-font lines (the random head is no
+use here: its rows have no class above 0.001 and every line empties) with the same order-5 model at beam 10: the skip
+search on the front end's lists (hctr_nbest_skip_lists) against the device full search (hctr_nbest_lm_topk) and the host
+skip search (hctr_beam_search(skip_search = 1, builtin_lm = 3), 16 threads) on the same lists in the same process; calls
+alternate after warm-up calls of each, medians. Reports the share of in-place steps, the largest row, the line statuses
+and the device time of each search's launches from profiled calls."""
 import argparse
 import json
 import os
@@ -85,12 +94,16 @@ def main():
     ap.add_argument("--evaluate", action="store_true")
     ap.add_argument("--nbest", action="store_true")
     ap.add_argument("--nbest-lm", action="store_true")
+    ap.add_argument("--nbest-skip", action="store_true")
     ap.add_argument("--host-lines", type=int, default=4)
     args = ap.parse_args()
     import torch
     import hctr_amd
     s = hctr_amd.synth
     C = s.DEFAULT_VOCAB + 2
+    if args.nbest_skip:
+        print(json.dumps(nbest_skip(args, hctr_amd)))
+        return
     m = hctr_amd.hctr_model(C, precision=args.precision).cuda(0)
     m.load_state_dict(s.make_state_dict(C, seed=0))
     imgs = torch.from_numpy(s.make_line_images(args.lines, args.width, seed=2)).cuda(0)
@@ -511,6 +524,109 @@ def nbest_lm(args, hctr_amd, m, imgs):
             "images_entry_equals_topk_entry": bool(same_entries),
             "mean_text_length": float(np.mean([len(t) for t in one_best])),
             "mean_lm_score": float(np.mean(out["nbest_lm_topk"].lm_scores[:, 0]))}
+
+
+def nbest_skip(args, hctr_amd):
+    import tempfile
+    import torch
+    from hctr_amd import package
+    ctc = sys.modules[package.__name__ + ".ctc"]
+    s = hctr_amd.synth
+    C, k, beam, n, pen, bonus = s.DEFAULT_VOCAB + 2, 10, 10, 5, 2.0, 5.8
+    m = hctr_amd.hctr_model(C, precision=args.precision).cuda(0)
+    m.load_state_dict(s.make_state_dict(C, seed=0, head="trained"))
+    imgs = torch.from_numpy(s.make_font_lines(args.lines, args.width, seed=2)).cuda(0)
+    B, W = int(imgs.shape[0]), int(imgs.shape[-1])
+    chars = s.characters()
+    codec = hctr_amd.ctc_codec(chars).attach(m)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "bench5.arpa")
+        ngrams = write_bench_arpa(path, chars)
+        codec.set_beam_search(ngram_path=path, use_tfm_pred=False, lm_panelty=pen, len_bonus=bonus, beam_size=beam,
+                              search_depth=k, skip_search=True)
+    lm = codec.ngram
+    codec.num_threads = 16
+    flat = lm.flat(codec.characters)
+    fe = m.beam_frontend(imgs, k, want_candidates=True)
+    top1 = np.ascontiguousarray(fe["topk_idx"][:, :, 0])
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    def skip_lists():
+        return ctc.nbest_skip_lists(m._ctx, top1, fe["blank_logp"], fe["cand_off"], fe["cand_idx"], fe["cand_logp"], C, n,
+                                    beam, bonus, None, lm=flat, lm_panelty=pen)
+
+    def full_topk():
+        return ctc.nbest_topk(m._ctx, fe["topk_idx"], fe["topk_logp"], C, n, beam, bonus, None, lm=flat, lm_panelty=pen)
+
+    def host_skip():
+        try:
+            return codec.decode_frontend(fe)
+        except IndexError:                                         # a line emptied: the reference's IndexError
+            return None
+
+    calls = {"nbest_skip_lists": skip_lists, "nbest_lm_topk": full_topk, "host_skip_search": host_skip,
+             "nbest_skip_images": lambda: m.nbest(imgs, n=n, beam=beam, len_bonus=bonus, lm=lm, lm_panelty=pen, codec=codec,
+                                                  skip_search=True)}
+    for _ in range(args.warmup):
+        for f in calls.values():
+            f()
+    ms = {name: [] for name in calls}
+    out = {}
+    for _ in range(args.steps):
+        for name, f in calls.items():
+            dt, out[name] = timed(f)
+            ms[name].append(1e3 * dt)
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    m.set_profiling(True)
+    skip_lists()
+    prof_skip = dict(m.last_profile())
+    full_topk()
+    prof_full = dict(m.last_profile())
+    m.set_profiling(False)
+    res = out["nbest_skip_lists"]
+    rows = np.diff(fe["cand_off"]).reshape(W, B)
+    # the steps the skip search ran: the reference's end steps, from the front end's top-1 classes
+    ends = np.zeros(B, np.int64)
+    for b in range(B):
+        t = top1[:, b]
+        keep = (t != 0) & (t != C - 1)
+        keep[1:] &= t[1:] != t[:-1]
+        ends[b] = min(int(np.flatnonzero(keep)[-1]) + 4, W) if keep.any() else 0
+    steps = int(ends.sum())
+    one_best = codec.labels_to_text([line[0] if line else [] for line in res.label_lists()])
+    host = out["host_skip_search"]
+    full_best = codec.labels_to_text([line[0] if line else [] for line in out["nbest_lm_topk"].label_lists()])
+    same_entries = all(getattr(res, f).tobytes() == getattr(out["nbest_skip_images"], f).tobytes()
+                       for f in ("labels", "lengths", "logps", "scores", "counts", "lm_scores", "status", "ranked"))
+    skip_names = ("beam_lm_prepass", "prefix_beam_skip", "prefix_backtrace")
+    full_names = ("beam_lm_prepass", "prefix_beam_lm", "prefix_backtrace")
+    return {"mode": "nbest-skip", "lines": B, "width": W, "classes": C, "precision": args.precision, "beam": beam,
+            "nbest": n, "lm_order": lm.order, "lm_ngrams": ngrams, "lm_panelty": pen, "len_bonus": bonus,
+            "host_threads": 16, "mean_steps": float(ends.mean()),
+            "ranked_steps": int(res.ranked.sum()), "steps": steps,
+            "in_place_share": round(1.0 - float(res.ranked.sum()) / max(steps, 1), 4),
+            "largest_row": int(max(int(rows[:int(ends[b]), b].max()) if ends[b] else 0 for b in range(B))),
+            "status_counts": {str(v): int((res.status == v).sum()) for v in range(4)},
+            "skip_search_device_ms": round(sum(prof_skip.get(key, 0.0) for key in skip_names), 3),
+            "skip_search_launches_ms": {key: round(prof_skip.get(key, 0.0), 4) for key in skip_names},
+            "full_search_device_ms": round(sum(prof_full.get(key, 0.0) for key in full_names), 3),
+            "full_search_launches_ms": {key: round(prof_full.get(key, 0.0), 4) for key in full_names},
+            "nbest_skip_lists_call_ms_median": round(med["nbest_skip_lists"], 3),
+            "nbest_lm_topk_call_ms_median": round(med["nbest_lm_topk"], 3),
+            "host_skip_search_ms_median": round(med["host_skip_search"], 3),
+            "nbest_skip_images_call_ms_median": round(med["nbest_skip_images"], 3),
+            "ms": {name: [round(v, 3) for v in vals] for name, vals in ms.items()},
+            "one_best_lines_differing_from_host_skip_search":
+                None if host is None else int(sum(a != b for a, b in zip(one_best, host))),
+            "one_best_lines_differing_from_full_search": int(sum(a != b for a, b in zip(one_best, full_best))),
+            "images_entry_equals_lists_entry": bool(same_entries),
+            "mean_text_length": float(np.mean([len(t) for t in one_best]))}
 
 
 def evaluate(args, hctr_amd, m, imgs, labels):
