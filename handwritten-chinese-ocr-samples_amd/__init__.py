@@ -16,12 +16,14 @@ Public surface = the reference's surface for this path:
                confidences and runners-up                          (engine-backed; no counterpart)
   NBest        result of hctr_model.nbest / ctc_codec.nbest: the N best texts of a line with their log-probabilities,
                by the device prefix beam search without a language model (engine-backed)
+  LMSweep      result of hctr_model.lm_sweep / ctc_codec.lm_sweep: edit distances of the LM-scored 1-best under a grid of
+               (lm_panelty, len_bonus) pairs; LMSweepTotals adds batches up and answers the reference's test.py -gs
 plus ``synth`` (deterministic synthetic checkpoints / line images) and ``build`` / ``load_library``.
 """
 from . import preprocess, synth  # noqa: F401
 from ._lib import build, load as load_library  # noqa: F401
 from .codec import ArpaLM, ToyBigramLM, ZeroLM, ctc_codec  # noqa: F401
-from .ctc import CTCAligner, CTCAlignment, CTCLoss, Evaluation, NBest, Recognition  # noqa: F401
+from .ctc import CTCAligner, CTCAlignment, CTCLoss, Evaluation, LMSweep, LMSweepTotals, NBest, Recognition  # noqa: F401
 from .model import hctr_model  # noqa: F401
 
 _EDIT_BOUND = None
@@ -38,4 +40,4 @@ def edit_distance(hyps, refs, device=0):
         _EDIT_BOUND = ctc._EngineBound().cuda(device)
     return ctc.edit_distance_sequences(_EDIT_BOUND._context(), list(hyps), list(refs), maps=False).edits
 
-__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "Recognition", "Evaluation", "NBest", "edit_distance", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]
+__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "Recognition", "Evaluation", "NBest", "LMSweep", "LMSweepTotals", "edit_distance", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]

@@ -187,6 +187,14 @@ SIGNATURES = [
                                   _VP, _VP, _VP, _VP, _VP]),
     ("hctr_nbest_lm", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double, _VP, _VP, _VP,
                            _VP, _VP, _VP, _VP]),
+    # ..., k, beam, lm_panelty[G], len_bonus[G], G, chunk, input_lengths, targets, target_lengths, 7 outputs
+    ("hctr_lm_sweep_chunk", _I, [_I, _I, _I, _I]),
+    ("hctr_lm_sweep_topk", _I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                _VP, _VP, _VP]),
+    ("hctr_lm_sweep_logits", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                  _VP, _VP, _VP]),
+    ("hctr_lm_sweep", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _I, _I, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                           _VP, _VP, _VP]),
     # ctx, lm, top1, blank, cand_off, cand_idx, cand_logp, W, B, C, beam, nbest, lm_panelty, len_bonus, input_lengths, 8 outputs
     ("hctr_nbest_skip_lists", _I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, ctypes.c_double, ctypes.c_double,
                                    _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -252,6 +252,30 @@ class ctc_codec(object):
         res.texts = [self.labels_to_text(line) for line in res.label_lists()]
         return res
 
+    def lm_sweep(self, preds, truths, lm, alphas=None, betas=None, beam=10, depth=10, pairs=None, input_lengths=None,
+                 chunk=0, texts=False):
+        """The reference's grid search over ``lm_panelty`` x ``len_bonus`` (test.py -gs) on one batch, in one call: for
+        every pair of ``alphas`` x ``betas`` (alpha-major, as the reference's loops run; or a flat ``pairs`` list) the
+        1-best of ``nbest(lm=, n=1)`` of every line of ``preds`` and its edit distance to ``encode(truths)``, searched
+        and scored on the device on one set of lists (include/hctr_hip.h ``hctr_lm_sweep_logits``). Returns a
+        ``ctc.LMSweep``; with ``texts=True`` it carries the per-pair labels and scores and ``.texts[g][b]``.
+        ``ctc.LMSweepTotals`` adds the batches up and gives the reference's ``min params`` answer."""
+        from . import ctc
+        logits, on_dev = self._as_logits(preds)
+        W, B, C = (int(v) for v in logits.shape)
+        if C != len(self.characters):
+            raise ValueError("logits have %d classes, codec has %d" % (C, len(self.characters)))
+        if W == 0:
+            raise ValueError("preds have no steps (W = 0)")
+        if lm is None:
+            raise ValueError("lm_sweep needs lm= (an ArpaLM)")
+        tg, tl = self.encode(list(truths))
+        res = ctc.lm_sweep_logits(self._context(), logits, on_dev, tg, tl, lm.flat(self.characters), alphas, betas, pairs,
+                                  beam, min(int(depth), C), chunk, input_lengths, texts)
+        if texts:
+            res.texts = [self.labels_to_text(line) for line in res.label_lists()]
+        return res
+
     def evaluate(self, preds, truths, maps=True):
         """Score decoded text against the truth strings on the device: returns ``(texts, ctc.Evaluation)``.
         ``preds`` is what ``decode`` takes - then the greedy decode is scored in label space against ``encode(truths)``

@@ -1869,6 +1869,146 @@ int skip_launch(hctr_ctx* c, const NbestCall& n, const int32_t* d_top1, int ks, 
     return HCTR_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// the LM weight sweep (hctr_lm_sweep*): the 1-best of the LM-scored search under G pairs of weights and its edit distance
+// to the line's transcription, on one pre-pass and one set of lists per pass
+// ---------------------------------------------------------------------------------------------
+struct SweepArgs {           // what hctr_lm_sweep* take beyond hctr_nbest_lm*; the outputs are host pointers, any may be null
+    const double *lm_panelty, *len_bonus;
+    int G, chunk;
+    const int32_t *targets, *target_lengths;
+    int32_t *edits, *hyp_lengths;
+    uint8_t* empty;
+    int32_t* labels;
+    double *logp, *score, *lm_score;
+};
+
+// pairs per launch when the caller leaves the choice to the engine (hctr_hip.h states the formula)
+constexpr int64_t kSweepFillGroups = 8192;               // four times the ~2048 workgroups of the 10/10 rung the chip holds
+constexpr int64_t kSweepChunkBytes = (int64_t)2 << 30;
+int64_t sweep_pair_bytes(int lines, int W, int beam) { return (int64_t)lines * (8 * (int64_t)W * beam + 4 * (int64_t)W + 36); }
+int sweep_chunk(int lines, int W, int beam, int G) {
+    const int64_t l = std::max(lines, 1);
+    const int64_t fill = std::max<int64_t>(1, kSweepFillGroups / l),
+                  fit = std::max<int64_t>(1, kSweepChunkBytes / sweep_pair_bytes((int)l, std::max(W, 1), std::max(beam, 1)));
+    return (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)G, fill, fit}));
+}
+
+struct SweepCall {
+    bool on = false;
+    SweepArgs a{};
+    EditCall e;                   // the references (tab), their checks and max_len
+    std::vector<double2> grid;    // [G] {lm_panelty, len_bonus}
+    std::vector<int32_t> end;     // [B] the end steps, fetched for `empty`
+    int Gc = 0;                   // pairs per launch
+    const int32_t* d_tab = nullptr;
+    double2* d_grid = nullptr;
+    int32_t* d_edits = nullptr;
+};
+
+int sweep_prepare(hctr_ctx* c, const NbestCall& n, const SweepArgs& a, SweepCall* s) {
+    if (a.G < 1) return fail(c, HCTR_ERR_ARG, "need G >= 1, got G=%d", a.G);
+    if (!a.lm_panelty || !a.len_bonus) return fail(c, HCTR_ERR_ARG, "lm_panelty/len_bonus is NULL");
+    for (int g = 0; g < a.G; ++g)
+        if (a.lm_panelty[g] != a.lm_panelty[g] || a.len_bonus[g] != a.len_bonus[g])
+            return fail(c, HCTR_ERR_ARG, "pair %d: %s is NaN", g, a.lm_panelty[g] != a.lm_panelty[g] ? "lm_panelty" : "len_bonus");
+    if (a.chunk < 0 || a.chunk > a.G) return fail(c, HCTR_ERR_ARG, "chunk=%d outside [0,%d]", a.chunk, a.G);
+    if ((int64_t)a.G * std::max(n.B, 1) > INT32_MAX) return fail(c, HCTR_ERR_ARG, "G*B=%lld too large", (long long)a.G * n.B);
+    s->on = true; s->a = a;
+    if (n.B == 0) return HCTR_OK;
+    TRY(edit_prepare(c, n.B, n.W, a.targets, a.target_lengths, nullptr, false, &s->e));
+    for (size_t j = 0; j < s->e.total; ++j)              // hctr_evaluate_logits' check of the ids
+        if (a.targets[j] < 1 || a.targets[j] > n.C - 1)
+            return fail(c, HCTR_ERR_ARG, "target id %d (position %zu) outside [1,%d]", a.targets[j], j, n.C - 1);
+    s->grid.resize((size_t)a.G);
+    for (int g = 0; g < a.G; ++g) s->grid[(size_t)g] = make_double2(a.lm_panelty[g], a.len_bonus[g]);
+    s->end.assign((size_t)n.B, 0);
+    return HCTR_OK;
+}
+
+// scratch for passes of at most `lines` lines, in the context's CTC block:
+// T[B] | tab | grid[G] | suffix | wid | end (one pass's) | history | labels | len | cnt | edits | logp | score | lm (one chunk's);
+// uploads T, the references and the pairs
+int sweep_scratch(hctr_ctx* c, NbestCall* n, SweepCall* s, int lines) {
+    s->Gc = s->a.chunk ? s->a.chunk : sweep_chunk(lines, n->W, n->beam, s->a.G);
+    const size_t gl = (size_t)s->Gc * lines;
+    const size_t T_b = align256((size_t)n->B * 4), tab_b = align256(s->e.tab.size() * 4),
+                 grid_b = align256((size_t)s->a.G * sizeof(double2)),
+                 suf_b = align256((size_t)lines * n->W * sizeof(int4)), wid_b = align256((size_t)lines * n->W * n->k * 4),
+                 end_b = align256((size_t)lines * 4), hist_b = align256(gl * n->W * n->beam * sizeof(int2)),
+                 lab_b = align256(gl * n->W * 4), i32_b = align256(gl * 4), f64_b = align256(gl * 8);
+    TRY(ctc_reserve(c, T_b + tab_b + grid_b + suf_b + wid_b + end_b + hist_b + lab_b + 3 * i32_b + 3 * f64_b));
+    TRY(lm_on_device(c, n->lm));
+    char* q = c->ctc_buf;
+    auto take = [&](size_t bytes) { char* r = q; q += bytes; return r; };
+    n->d_T = (int32_t*)take(T_b);
+    s->d_tab = (const int32_t*)take(tab_b);
+    s->d_grid = (double2*)take(grid_b);
+    n->d_suf = (int4*)take(suf_b);
+    n->d_wid = (int32_t*)take(wid_b);
+    n->d_end = (int32_t*)take(end_b);
+    n->d_hist = (int2*)take(hist_b);
+    n->d_lab = (int32_t*)take(lab_b);
+    n->d_len = (int32_t*)take(i32_b);
+    n->d_cnt = (int32_t*)take(i32_b);
+    s->d_edits = (int32_t*)take(i32_b);
+    n->d_logp = (double*)take(f64_b);
+    n->d_score = (double*)take(f64_b);
+    n->d_lm = (double*)take(f64_b);
+    HIP_TRY(c, hipMemcpyAsync(n->d_T, n->T.data(), (size_t)n->B * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync((void*)s->d_tab, s->e.tab.data(), s->e.tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(s->d_grid, s->grid.data(), s->grid.size() * sizeof(double2), hipMemcpyHostToDevice, c->stream));
+    return HCTR_OK;
+}
+
+// the sweep of the pass's lines [b0, b0 + nb) on their lists (rows r = t*nb + b): the pre-pass once, then per chunk of
+// pairs the grid search, the backtrace and the distances of its gc * nb grid lines, queued to rows [g][b0 ..] of the outputs
+int sweep_launch(hctr_ctx* c, const NbestCall& n, SweepCall& s, const int32_t* d_idx, const float* d_lp, int b0, int nb) {
+    Prof pf(c);
+    const SweepArgs& a = s.a;
+    const size_t B = (size_t)n.B;
+    PROF_TRY(pf, "beam_lm_prepass", launch_beam_lm_prepass(d_idx, nb, n.W, n.k, n.C, n.d_T + b0, c->lm_words, n.d_wid, n.d_suf,
+                                                           n.d_end, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(s.end.data() + b0, n.d_end, (size_t)nb * 4, hipMemcpyDeviceToHost, c->stream));
+    BeamLm lm;
+    lm.table = LmView{c->lm_slots, (uint32_t)n.lm->slots.size() - 1u, n.lm->order, n.lm->unk};
+    lm.wid = n.d_wid; lm.suffix = n.d_suf; lm.bos = n.lm->bos; lm.o_lm = n.d_lm;
+    // grid line g * nb + b is measured against the reference of batch line b0 + b
+    EditLines m{s.d_tab + b0, s.d_tab + B + b0, s.d_tab + 2 * B, nb};
+    // rows [g0 .. g0 + gc) of a host array [G][B][per], columns of lines [b0, b0 + nb): one strided copy
+    auto fetch = [&](void* dst, const void* src, int g0, int gc, size_t per, size_t elem) {
+        if (!dst) return hipSuccess;
+        return hipMemcpy2DAsync((char*)dst + ((size_t)g0 * B + b0) * per * elem, B * per * elem, src, (size_t)nb * per * elem,
+                                (size_t)nb * per * elem, (size_t)gc, hipMemcpyDeviceToHost, c->stream);
+    };
+    for (int g0 = 0; g0 < a.G; g0 += s.Gc) {
+        const int gc = std::min(s.Gc, a.G - g0), gl = gc * nb;
+        HIP_TRY(c, hipMemsetAsync(n.d_lab, 0, (size_t)gl * n.W * 4, c->stream));
+        lm.grid = s.d_grid + g0;
+        PROF_TRY(pf, "prefix_beam_lm_grid", launch_prefix_beam_lm_grid(d_idx, d_lp, nb, n.W, n.k, n.C, n.beam, gc, n.d_end, lm,
+                                                                       n.d_hist, n.d_len, n.d_logp, n.d_score, n.d_cnt,
+                                                                       c->stream));
+        PROF_TRY(pf, "prefix_backtrace", launch_prefix_backtrace(n.d_hist, n.d_end, gl, n.W, n.beam, 1, n.d_len, n.d_cnt,
+                                                                 n.d_lab, c->stream, nb));
+        PROF_TRY(pf, "edit_distance", launch_edit_distance(m, 0, nullptr, gl, n.d_lab, n.d_len, n.W, s.e.max_len, nullptr,
+                                                           nullptr, s.d_edits, c->stream));
+        HIP_TRY(c, fetch(a.edits, s.d_edits, g0, gc, 1, 4));
+        HIP_TRY(c, fetch(a.hyp_lengths, n.d_len, g0, gc, 1, 4));
+        HIP_TRY(c, fetch(a.labels, n.d_lab, g0, gc, (size_t)n.W, 4));
+        HIP_TRY(c, fetch(a.logp, n.d_logp, g0, gc, 1, 8));
+        HIP_TRY(c, fetch(a.score, n.d_score, g0, gc, 1, 8));
+        HIP_TRY(c, fetch(a.lm_score, n.d_lm, g0, gc, 1, 8));
+    }
+    return HCTR_OK;
+}
+
+// after the stream has drained: the empty-greedy flags from the end steps
+int sweep_finish(int rc, const SweepCall& s) {
+    if (rc == HCTR_OK && s.on && s.a.empty)
+        for (size_t b = 0; b < s.end.size(); ++b) s.a.empty[b] = s.end[b] == 0;
+    return rc;
+}
+
 // the skip search on the lists of one front-end pass (made with k = 1 and candidates wanted): the candidates go to the
 // padded layout where the counts already lie - no count visits the host - and the search follows in stream order
 int skip_on_lists(hctr_ctx* c, const NbestCall& n, const BeamLists& L, int b0, int nb) {
@@ -2364,11 +2504,13 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
 }
 
 // The three N-best entry points, each with and without an n-gram model: `lm` (null or the three extra arguments of
-// hctr_nbest_lm*) is all that tells the two apart.
+// hctr_nbest_lm*) is all that tells the two apart. With lm->sweep they are the entry points of hctr_lm_sweep*: the same
+// checks, lists and passes, the sweep's scratch and launches in place of the single search's.
 struct NbestLmArgs {
     const hctr_lm* lm;
     double lm_panelty;
     double* lm_score;
+    const SweepArgs* sweep = nullptr;
 };
 
 static int nbest_topk_impl(hctr_ctx* c, const NbestLmArgs* lm, const int32_t* topk_idx, const float* topk_logp, int W, int B,
@@ -2379,6 +2521,8 @@ static int nbest_topk_impl(hctr_ctx* c, const NbestLmArgs* lm, const int32_t* to
         NbestCall n;
         TRY(nbest_prepare(c, B, W, C, k, beam, nbest, len_bonus, input_lengths, o, &n));
         if (lm) TRY(nbest_lm_prepare(c, &n, lm->lm, lm->lm_panelty, lm->lm_score));
+        SweepCall sw;
+        if (lm && lm->sweep) TRY(sweep_prepare(c, n, *lm->sweep, &sw));
         if (B == 0) return HCTR_OK;
         // the lists are the caller's: classes in [0, C) and distinct within a row, as the front end produces them
         const size_t rows = (size_t)W * B;
@@ -2396,16 +2540,16 @@ static int nbest_topk_impl(hctr_ctx* c, const NbestLmArgs* lm, const int32_t* to
         prof_reset(c);
         std::vector<void*> tmp;
         PoolGuard tmp_guard{tmp};
-        return synced(c, [&]() -> int {
+        return sweep_finish(synced(c, [&]() -> int {
             int32_t* d_idx = nullptr;
             float* d_lp = nullptr;
-            TRY(nbest_scratch(c, &n, B));
+            TRY(sw.on ? sweep_scratch(c, &n, &sw, B) : nbest_scratch(c, &n, B));
             TRY(dev_alloc(c, tmp, &d_idx, rows * k, false));
             TRY(dev_alloc(c, tmp, &d_lp, rows * k, false));
             HIP_TRY(c, hipMemcpyAsync(d_idx, topk_idx, rows * k * 4, hipMemcpyHostToDevice, c->stream));
             HIP_TRY(c, hipMemcpyAsync(d_lp, topk_logp, rows * k * 4, hipMemcpyHostToDevice, c->stream));
-            return nbest_launch(c, n, d_idx, d_lp, 0, B);
-        }());
+            return sw.on ? sweep_launch(c, n, sw, d_idx, d_lp, 0, B) : nbest_launch(c, n, d_idx, d_lp, 0, B);
+        }()), sw);
     });
 }
 
@@ -2417,19 +2561,21 @@ static int nbest_logits_impl(hctr_ctx* c, const NbestLmArgs* lm, const float* lo
         NbestCall n;
         TRY(nbest_prepare(c, B, W, C, k, beam, nbest, len_bonus, input_lengths, o, &n));
         if (lm) TRY(nbest_lm_prepare(c, &n, lm->lm, lm->lm_panelty, lm->lm_score));
+        SweepCall sw;
+        if (lm && lm->sweep) TRY(sweep_prepare(c, n, *lm->sweep, &sw));
         if (B == 0) return HCTR_OK;
         HIP_TRY(c, hipSetDevice(c->device));
         prof_reset(c);
         const std::vector<int> all = line_indices(B);
         const int rc = synced(c, [&]() -> int {
             BeamLists L;
-            TRY(nbest_scratch(c, &n, B));
+            TRY(sw.on ? sweep_scratch(c, &n, &sw, B) : nbest_scratch(c, &n, B));
             TRY(beam_lists_pass(c, nullptr, Pass{all.data(), B, 0, B, false, nullptr}, logits_wbc, on_device, W, C, k, false,
                                 std::log(0.001), &L));
-            return nbest_launch(c, n, L.idx, L.lp, 0, B);
+            return sw.on ? sweep_launch(c, n, sw, L.idx, L.lp, 0, B) : nbest_launch(c, n, L.idx, L.lp, 0, B);
         }());
         free_pool(c->beam_allocs);
-        return rc;
+        return sweep_finish(rc, sw);
     });
 }
 
@@ -2441,18 +2587,20 @@ static int nbest_images_impl(hctr_ctx* c, const NbestLmArgs* lm, const void* img
         NbestCall n;
         TRY(nbest_prepare(c, B, W, c->num_classes, k, beam, nbest, len_bonus, input_lengths, o, &n));
         if (lm) TRY(nbest_lm_prepare(c, &n, lm->lm, lm->lm_panelty, lm->lm_score));
+        SweepCall sw;
+        if (lm && lm->sweep) TRY(sweep_prepare(c, n, *lm->sweep, &sw));
         if (B == 0) return HCTR_OK;
         HIP_TRY(c, hipSetDevice(c->device));
         const Batch in{img, img_dtype, img_on_device, widths, B, W};
         // inside each pass the search runs on the front end's lists where they lie; only its results go to the host
         const int rc = synced(c, run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
-            if (p.first == 0) TRY(nbest_scratch(c, &n, p.nb));      // no later pass is larger
+            if (p.first == 0) TRY(sw.on ? sweep_scratch(c, &n, &sw, p.nb) : nbest_scratch(c, &n, p.nb));      // no later pass is larger
             BeamLists L;
             TRY(beam_lists_pass(c, &in, p, nullptr, 0, W, n.C, k, false, std::log(0.001), &L));
-            return nbest_launch(c, n, L.idx, L.lp, p.first, p.nb);
+            return sw.on ? sweep_launch(c, n, sw, L.idx, L.lp, p.first, p.nb) : nbest_launch(c, n, L.idx, L.lp, p.first, p.nb);
         }));
         free_pool(c->beam_allocs);
-        return rc;
+        return sweep_finish(rc, sw);
     });
 }
 
@@ -2502,6 +2650,38 @@ int hctr_nbest_lm(hctr_ctx* c, const hctr_lm* lm, const void* img, int img_dtype
     return nbest_images_impl(c, &a, img, img_dtype, img_on_device, widths, B, W, k, beam, nbest, len_bonus, input_lengths,
                              NbestOut{labels, lengths, logp, score, count});
 }
+
+#define SWEEP_TAIL_PARAMS                                                                                             \
+    const double *lm_panelty, const double *len_bonus, int G, int chunk, const int32_t *input_lengths,               \
+        const int32_t *targets, const int32_t *target_lengths, int32_t *edits, int32_t *hyp_lengths, uint8_t *empty, \
+        int32_t *labels, double *logp, double *score, double *lm_score
+#define SWEEP_TAIL_ARGS \
+    SweepArgs { lm_panelty, len_bonus, G, chunk, targets, target_lengths, edits, hyp_lengths, empty, labels, logp, score, lm_score }
+
+int hctr_lm_sweep_chunk(int lines, int W, int beam, int G) { return G < 1 ? 0 : sweep_chunk(lines, W, beam, G); }
+
+int hctr_lm_sweep_topk(hctr_ctx* c, const hctr_lm* lm, const int32_t* topk_idx, const float* topk_logp, int W, int B, int C,
+                       int k, int beam, SWEEP_TAIL_PARAMS) {
+    const SweepArgs s = SWEEP_TAIL_ARGS;
+    const NbestLmArgs a{lm, 0.0, nullptr, &s};
+    return nbest_topk_impl(c, &a, topk_idx, topk_logp, W, B, C, k, beam, 1, 0.0, input_lengths, NbestOut{});
+}
+
+int hctr_lm_sweep_logits(hctr_ctx* c, const hctr_lm* lm, const float* logits_wbc, int on_device, int W, int B, int C, int k,
+                         int beam, SWEEP_TAIL_PARAMS) {
+    const SweepArgs s = SWEEP_TAIL_ARGS;
+    const NbestLmArgs a{lm, 0.0, nullptr, &s};
+    return nbest_logits_impl(c, &a, logits_wbc, on_device, W, B, C, k, beam, 1, 0.0, input_lengths, NbestOut{});
+}
+
+int hctr_lm_sweep(hctr_ctx* c, const hctr_lm* lm, const void* img, int img_dtype, int img_on_device, const int32_t* widths,
+                  int B, int W, int k, int beam, SWEEP_TAIL_PARAMS) {
+    const SweepArgs s = SWEEP_TAIL_ARGS;
+    const NbestLmArgs a{lm, 0.0, nullptr, &s};
+    return nbest_images_impl(c, &a, img, img_dtype, img_on_device, widths, B, W, k, beam, 1, 0.0, input_lengths, NbestOut{});
+}
+#undef SWEEP_TAIL_PARAMS
+#undef SWEEP_TAIL_ARGS
 
 int hctr_nbest_skip_lists(hctr_ctx* c, const hctr_lm* lm, const int32_t* top1_idx, const float* blank_logp,
                           const int64_t* cand_off, const int32_t* cand_idx, const float* cand_logp, int W, int B, int C,

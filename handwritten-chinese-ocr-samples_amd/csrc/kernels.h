@@ -273,6 +273,8 @@ struct EditLines {
     const int32_t* L;       // [B] reference length
     const int32_t* off;     // [B] offset of the line's reference in ref
     const int32_t* ref;     // [sum L] reference symbols, any int32 values
+    int32_t wrap = 0;       // > 0 (launch_edit_distance without bp only): line gb is measured against reference
+                            // gb mod wrap - the G * wrap grid lines of hctr_lm_sweep* over wrap references
 };
 // launch_edit_distance: edits[gb] = D[L][H]; max_len = the longest reference of the launch's lines. bp (else null: the
 //   distance-only instance, same arithmetic) keeps the 2-bit backpointers (0 diagonal, 1 deletion, 2 insertion; row i of
@@ -298,7 +300,7 @@ hipError_t launch_prefix_beam(const int32_t* idx, const float* lp, int nb, int W
                               double len_bonus, const int32_t* T, int2* hist, int32_t* len, double* logp, double* score,
                               int32_t* cnt, hipStream_t s);
 hipError_t launch_prefix_backtrace(const int2* hist, const int32_t* T, int nb, int W, int beam, int nbest,
-                                   const int32_t* len, const int32_t* cnt, int32_t* labels, hipStream_t s);
+                                   const int32_t* len, const int32_t* cnt, int32_t* labels, hipStream_t s, int wrap = 0);
 
 // ---- the same search scored by an n-gram model (hctr_nbest_lm*; lm_flat.h has the table and the lookup) ----
 // launch_beam_lm_prepass: from the lists and T[b] (the columns of line b that count) the word ids of every list entry
@@ -314,12 +316,20 @@ struct BeamLm {
     double lm_panelty = 0.0;
     int32_t bos = -1;
     double* o_lm = nullptr;
+    const double2* grid = nullptr;      // launch_prefix_beam_lm_grid: [G] {lm_panelty, len_bonus} on the device
 };
 hipError_t launch_beam_lm_prepass(const int32_t* idx, int nb, int W, int k, int C, const int32_t* T, const int32_t* words,
                                   int32_t* wid, int4* suffix, int32_t* end, hipStream_t s);
 hipError_t launch_prefix_beam_lm(const int32_t* idx, const float* lp, int nb, int W, int k, int C, int beam, int nbest,
                                  double len_bonus, const int32_t* end, const BeamLm& lm, int2* hist, int32_t* len,
                                  double* logp, double* score, int32_t* cnt, hipStream_t s);
+// launch_prefix_beam_lm_grid (hctr_lm_sweep*): the 1-best of launch_prefix_beam_lm for every line b = 0..nb-1 under
+//   every pair g = 0..G-1 of lm.grid, in one launch of G * nb workgroups, b fastest. Grid line g * nb + b reads line b's
+//   lists, lm.wid, lm.suffix and end[b] and owns hist[(g * nb + b) * W * beam ..] and place g * nb + b of len, logp,
+//   score, cnt, lm.o_lm; lm.lm_panelty is unread. launch_prefix_backtrace then takes G * nb lines, end and wrap = nb.
+hipError_t launch_prefix_beam_lm_grid(const int32_t* idx, const float* lp, int nb, int W, int k, int C, int beam, int G,
+                                      const int32_t* end, const BeamLm& lm, int2* hist, int32_t* len, double* logp,
+                                      double* score, int32_t* cnt, hipStream_t s);
 
 // ---- the skip search (hctr_nbest_skip*): __cbs_skip__ on the thresholded candidate lists in the padded layout - row
 // r = t*nb + b has cnt[r] candidates, the first min(cnt[r], kBeamMaxK) of them in ascending class order at

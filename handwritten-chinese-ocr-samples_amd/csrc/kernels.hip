@@ -3889,7 +3889,8 @@ __global__ __launch_bounds__(64 * NW) void edit_distance_kernel(const EditLines 
                                                                  uint8_t* __restrict__ bp, int32_t* __restrict__ edits) {
     static_assert(NS <= 4, "one byte holds the backpointers of a lane");
     __shared__ int xb[2][NW];
-    const int b = blockIdx.x, gb = line_of ? line_of[b] : b0 + b, tid = threadIdx.x;
+    // ob = the line's place in edits; its reference is line ob's, or with m.wrap line (ob mod wrap)'s (the LM sweep)
+    const int b = blockIdx.x, ob = line_of ? line_of[b] : b0 + b, gb = m.wrap > 0 ? ob % m.wrap : ob, tid = threadIdx.x;
     const int L = m.L[gb], H = hlen[b];
     const int32_t* __restrict__ r = m.ref + m.off[gb];
     const int32_t* __restrict__ h = hyp + (int64_t)b * stride;
@@ -3946,11 +3947,11 @@ __global__ __launch_bounds__(64 * NW) void edit_distance_kernel(const EditLines 
         }
     }
     if (L == 0) {
-        if (tid == 0) edits[gb] = H;
+        if (tid == 0) edits[ob] = H;
     } else if (tid == (L - 1) / NS) {
 #pragma unroll
         for (int i = 0; i < NS; ++i)
-            if (i == (L - 1) % NS) edits[gb] = left[i];
+            if (i == (L - 1) % NS) edits[ob] = left[i];
     }
 }
 
@@ -4160,7 +4161,11 @@ struct alignas(16) BeamSortKey {
 // form of lm_word_logp, an extension adds one term to its parent's, and every valid entry is ranked by its log-prob +
 // (score of prefix + the step's suffix) * lm_panelty + len * len_bonus. Tl holds the end steps of the pre-pass, 0 for a
 // line without a greedy text, which returns nothing. With LM = false none of it is compiled.
-template <int BEAM, int K, int NW, bool LM>
+// GRID (with LM) is the search of hctr_lm_sweep* (DESIGN.md 4i): workgroup ob = g * nb + b searches line b under the
+// weights lm.grid[g] = {lm_panelty, len_bonus}. The lists, word ids, suffixes and end steps are line b's, shared by the
+// pairs; history and outputs are grid line ob's. Nothing else differs, so pair g computes what the single-pair
+// instance computes with its two weights.
+template <int BEAM, int K, int NW, bool LM, bool GRID = false>
 __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __restrict__ idx, const float* __restrict__ lp,
                                                               int nb, int W, int k, int unk, int beam, int nbest,
                                                               double len_bonus, const int32_t* __restrict__ Tl,
@@ -4182,9 +4187,15 @@ __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __r
     __shared__ double r_lp[2][K];
     __shared__ int r_meta[2][2];                   // {the row's first usable class j0, the place of the blank}, -1 = none
     __shared__ int s_n[2], s_valid[NW];
-    const int b = blockIdx.x, tid = threadIdx.x, k1 = k + 1;
+    static_assert(LM || !GRID, "the grid is a grid of LM weights");
+    const int ob = blockIdx.x, b = GRID ? ob % nb : ob, tid = threadIdx.x, k1 = k + 1;
     const int T = Tl[b];
-    int2* __restrict__ hb = hist + (int64_t)b * W * beam;
+    int2* __restrict__ hb = hist + (int64_t)ob * W * beam;
+    double lm_w = lm.lm_panelty, len_w = len_bonus;
+    if constexpr (GRID) {
+        const double2 w = lm.grid[ob / nb];
+        lm_w = w.x; len_w = w.y;
+    }
 
     // a row's classes into LDS (wave 0; every lane of it takes part in the ballots)
     auto put_row = [&](int buf, bool have, int c, float l, int w) {
@@ -4308,7 +4319,7 @@ __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __r
                         lm_roll(cx, rest.x);
                         rest = make_int4(rest.y, rest.z, rest.w, -2);
                     }
-                    total = beam_total_lm(tot, sc, leni + (jj ? 1 : 0), lm.lm_panelty, len_bonus);
+                    total = beam_total_lm(tot, sc, leni + (jj ? 1 : 0), lm_w, len_w);
                 }
             } else {
                 total = beam_total(tot, leni + (jj ? 1 : 0), len_bonus);
@@ -4363,25 +4374,26 @@ __global__ __launch_bounds__(64 * NW) void prefix_beam_kernel(const int32_t* __r
         const bool have = tid < n;
         const int len = have ? h_len[cur][tid] : 0;
         const double logp = have ? h_tot[cur][tid] : NINF;
-        const int64_t o = (int64_t)b * nbest + tid;
+        const int64_t o = (int64_t)ob * nbest + tid;
         o_len[o] = len;
         o_logp[o] = logp;
         if constexpr (LM) {
             const double sc = have ? h_lm[cur][tid] : NINF;
-            o_score[o] = have ? beam_total_lm(logp, sc, len, lm.lm_panelty, len_bonus) : NINF;
+            o_score[o] = have ? beam_total_lm(logp, sc, len, lm_w, len_w) : NINF;
             lm.o_lm[o] = sc;
         } else {
             o_score[o] = have ? beam_total(logp, len, len_bonus) : NINF;
         }
     }
-    if (tid == 0) o_cnt[b] = min(n, nbest);
+    if (tid == 0) o_cnt[ob] = min(n, nbest);
 }
 
 // labels of the returned hypotheses, one lane each: from the last step back, place to parent place, the appended labels
 // filling the text from its end. The labels array is zero on entry. Places and positions are clamped, so a history
-// left unspecified by a NaN row is walked without leaving the line's arrays.
+// left unspecified by a NaN row is walked without leaving the line's arrays. With wrap > 0 the steps of line b are
+// Tl[b mod wrap]: the grid lines of hctr_lm_sweep*, which share the end steps of their lines.
 __global__ __launch_bounds__(64) void prefix_backtrace_kernel(const int2* __restrict__ hist, const int32_t* __restrict__ Tl,
-                                                              int W, int beam, int nbest,
+                                                              int wrap, int W, int beam, int nbest,
                                                               const int32_t* __restrict__ o_len,
                                                               const int32_t* __restrict__ o_cnt,
                                                               int32_t* __restrict__ labels) {
@@ -4390,7 +4402,7 @@ __global__ __launch_bounds__(64) void prefix_backtrace_kernel(const int2* __rest
     const int2* __restrict__ hb = hist + (int64_t)b * W * beam;
     int32_t* __restrict__ out = labels + ((int64_t)b * nbest + s) * W;
     int pos = min(max(o_len[(int64_t)b * nbest + s], 0), W), place = s;
-    for (int t = min(Tl[b], W) - 1; t >= 0 && pos > 0; --t) {
+    for (int t = min(Tl[wrap > 0 ? b % wrap : b], W) - 1; t >= 0 && pos > 0; --t) {
         const int2 h = hb[(int64_t)t * beam + place];
         if (h.y >= 0) out[--pos] = h.y;
         place = (int)min((unsigned)h.x, (unsigned)(beam - 1));
@@ -4497,11 +4509,30 @@ hipError_t launch_prefix_beam_lm(const int32_t* idx, const float* lp, int nb, in
     return hipErrorInvalidValue;
 }
 
+hipError_t launch_prefix_beam_lm_grid(const int32_t* idx, const float* lp, int nb, int W, int k, int C, int beam, int G,
+                                      const int32_t* end, const BeamLm& lm, int2* hist, int32_t* len, double* logp,
+                                      double* score, int32_t* cnt, hipStream_t s) {
+    if (nb <= 0 || G <= 0) return hipSuccess;
+    if (k < 1 || beam < 1 || C < 2 || W < 1 || (int64_t)G * nb > INT32_MAX) return hipErrorInvalidValue;
+    if (!lm.table.slots || lm.table.order < 1 || lm.table.order > kLmMaxOrder || !lm.wid || !lm.suffix || !lm.o_lm ||
+        !lm.grid)
+        return hipErrorInvalidValue;
+#define BEAM_RUNG(BEAM, K, NW)                                                                                       \
+    if (beam <= BEAM && k <= K) {                                                                                    \
+        hipLaunchKernelGGL((prefix_beam_kernel<BEAM, K, NW, true, true>), dim3((unsigned)(G * nb)), dim3(64 * NW), 0, s, \
+                           idx, lp, nb, W, k, C - 1, beam, 1, 0.0, end, hist, len, logp, score, cnt, lm);            \
+        return hipGetLastError();                                                                                    \
+    }
+    HCTR_BEAM_LADDER(BEAM_RUNG)
+#undef BEAM_RUNG
+    return hipErrorInvalidValue;
+}
+
 hipError_t launch_prefix_backtrace(const int2* hist, const int32_t* T, int nb, int W, int beam, int nbest,
-                                   const int32_t* len, const int32_t* cnt, int32_t* labels, hipStream_t s) {
+                                   const int32_t* len, const int32_t* cnt, int32_t* labels, hipStream_t s, int wrap) {
     if (nb <= 0) return hipSuccess;
-    if (beam < 1 || nbest < 1 || nbest > 64) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(prefix_backtrace_kernel, dim3((unsigned)nb), dim3(64), 0, s, hist, T, W, beam, nbest, len, cnt,
+    if (beam < 1 || nbest < 1 || nbest > 64 || wrap < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(prefix_backtrace_kernel, dim3((unsigned)nb), dim3(64), 0, s, hist, T, wrap, W, beam, nbest, len, cnt,
                        labels);
     return hipGetLastError();
 }

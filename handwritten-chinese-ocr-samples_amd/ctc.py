@@ -638,6 +638,176 @@ def nbest_skip_images(ctx, x, dt, on_dev, widths, B, W, n=5, beam=10, len_bonus=
     return _skip_result(out)
 
 
+def sweep_pairs(alphas=None, betas=None, pairs=None):
+    """(lm_panelty [G], len_bonus [G]) float64 of a weight grid: ``alphas`` x ``betas`` expanded alpha-major, the order
+    in which the reference's loops run (``for a in alphas: for b in betas``, test.py:352-353), or a flat ``pairs`` list
+    of (lm_panelty, len_bonus)."""
+    if pairs is not None:
+        if alphas is not None or betas is not None:
+            raise ValueError("give alphas and betas, or pairs, not both")
+        pr = np.asarray(list(pairs), np.float64).reshape(-1, 2)
+    else:
+        if alphas is None or betas is None:
+            raise ValueError("a sweep needs alphas and betas, or pairs")
+        al, be = np.asarray(alphas, np.float64).reshape(-1), np.asarray(betas, np.float64).reshape(-1)
+        pr = np.stack([np.repeat(al, be.size), np.tile(be, al.size)], axis=1)
+    if pr.shape[0] < 1:
+        raise ValueError("a sweep needs at least one (lm_panelty, len_bonus) pair")
+    return np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+
+
+class LMSweep(object):
+    """Result of the LM weight sweep over B lines and G pairs (numpy arrays, on the host; include/hctr_hip.h
+    ``hctr_lm_sweep*``): ``lm_panelty`` / ``len_bonus`` float64 [G], the pairs; ``edits`` int32 [G, B], the edit distance
+    of line b's 1-best text under pair g to its transcription; ``hyp_lengths`` int32 [G, B]; ``empty`` uint8 [B], 1 for
+    a line whose greedy text is empty (it contributes the empty text under every pair; the reference raises
+    IndexError there); ``ref_lengths`` int32 [B]. With ``texts=True`` also ``labels`` int32 [G, B, W], ``logps``,
+    ``scores``, ``lm_scores`` float64 [G, B], the 1-best's values as ``nbest(lm=, n=1)`` returns them; otherwise None."""
+
+    def __init__(self, lm_panelty, len_bonus, edits, hyp_lengths, empty, ref_lengths, labels=None, logps=None, scores=None,
+                 lm_scores=None):
+        self.lm_panelty, self.len_bonus = np.asarray(lm_panelty, np.float64), np.asarray(len_bonus, np.float64)
+        self.edits, self.hyp_lengths, self.empty = edits, hyp_lengths, empty
+        self.ref_lengths = np.asarray(ref_lengths, np.int32)
+        self.labels, self.logps, self.scores, self.lm_scores = labels, logps, scores, lm_scores
+
+    def __len__(self):
+        return len(self.lm_panelty)
+
+    @property
+    def pairs(self):
+        return [(float(a), float(b)) for a, b in zip(self.lm_panelty, self.len_bonus)]
+
+    @property
+    def total_edits(self):
+        """int64 [G]"""
+        return np.asarray(self.edits, np.int64).reshape(len(self), -1).sum(axis=1)
+
+    @property
+    def nchars(self):
+        return int(self.ref_lengths.astype(np.int64).sum())
+
+    @property
+    def cer(self):
+        """float64 [G]: total_edits / nchars, the reference's CER (test.py:285); NaN without a reference character"""
+        n = self.nchars
+        return self.total_edits / n if n else np.full((len(self),), np.nan)
+
+    def label_lists(self):
+        """per pair, per line the 1-best's label array (``texts=True`` only)"""
+        if self.labels is None:
+            raise ValueError("the sweep was run without texts=True")
+        return [[self.labels[g, b, :int(self.hyp_lengths[g, b])].copy() for b in range(self.labels.shape[1])]
+                for g in range(len(self))]
+
+
+class LMSweepTotals(object):
+    """Sweeps of successive batches over one grid, added up: ``update(sweep)`` per batch, then ``cer`` [G], ``best()``
+    and ``report()``, which are what the reference's grid search (test.py:347-382) computes and prints."""
+
+    def __init__(self):
+        self.lm_panelty = self.len_bonus = self.total_edits = None
+        self.nchars = 0
+        self.nlines = 0
+
+    def update(self, sweep):
+        if self.total_edits is None:
+            self.lm_panelty, self.len_bonus = sweep.lm_panelty.copy(), sweep.len_bonus.copy()
+            self.total_edits = np.zeros((len(sweep),), np.int64)
+        elif not (np.array_equal(self.lm_panelty, sweep.lm_panelty) and np.array_equal(self.len_bonus, sweep.len_bonus)):
+            raise ValueError("the sweep was run over another grid of pairs")
+        self.total_edits += sweep.total_edits
+        self.nchars += sweep.nchars
+        self.nlines += int(sweep.ref_lengths.size)
+        return self
+
+    @property
+    def pairs(self):
+        return [] if self.total_edits is None else [(float(a), float(b)) for a, b in zip(self.lm_panelty, self.len_bonus)]
+
+    @property
+    def cer(self):
+        if self.total_edits is None:
+            return np.zeros((0,), np.float64)
+        return self.total_edits / self.nchars if self.nchars else np.full(self.total_edits.shape, np.nan)
+
+    def _walk(self):
+        """per pair (pair, cer, running minimum before it), then the final minimum: the reference's rule - start from
+        min_cer = 1.0, min_params = (0, 0), replace only on strictly smaller"""
+        min_cer, min_params, steps = 1.0, (0, 0), []
+        for pair, cer in zip(self.pairs, self.cer.tolist()):
+            steps.append((pair, cer, min_params, min_cer))
+            if cer < min_cer:
+                min_cer, min_params = cer, pair
+        return steps, min_params, min_cer
+
+    def best(self):
+        """((lm_panelty, len_bonus), cer) of the first pair with the lowest CER below 1.0; ((0, 0), 1.0) when none is"""
+        _, params, cer = self._walk()
+        return params, cer
+
+    def report(self):
+        """the lines the reference's loop prints (test.py:354-355, 382), the running minimum as it stood before each pair"""
+        steps, params, cer = self._walk()
+        out = ["searching with a:{}, b:{}, min params:{}, min cer:{}".format(a, b, mp, mc) for (a, b), _, mp, mc in steps]
+        out.append("min params:{}, min cer: {}".format(params, cer))
+        return out
+
+
+def _sweep_args(B, W, targets, target_lengths, lm, alphas, betas, pairs, chunk, input_lengths, texts):
+    if lm is None:
+        raise ValueError("the sweep needs an n-gram model (lm=)")
+    tg, tl = normalize_targets(targets, target_lengths, B)
+    al, be = sweep_pairs(alphas, betas, pairs)
+    G = int(al.size)
+    il = normalize_input_lengths(input_lengths, B)
+    out = [np.zeros((G, B), np.int32), np.zeros((G, B), np.int32), np.zeros((B,), np.uint8), None, None, None, None]
+    if texts:
+        out[3:] = [np.zeros((G, B, W), np.int32)] + [np.full((G, B), -np.inf, np.float64) for _ in range(3)]
+    tail = [_lib.ptr(al), _lib.ptr(be), G, int(chunk), _lib.ptr(il), _lib.ptr(tg), _lib.ptr(tl)] + [_lib.ptr(a) for a in out]
+    keep = (al, be, il, tg, tl)
+    return tail, keep, lambda: LMSweep(al, be, out[0], out[1], out[2], tl, *out[3:])
+
+
+def lm_sweep_chunk(lines, W, beam, G):
+    """pairs per launch the engine chooses for ``chunk=0`` (hctr_lm_sweep_chunk)"""
+    return int(_lib.load().hctr_lm_sweep_chunk(int(lines), int(W), int(beam), int(G)))
+
+
+def lm_sweep_topk(ctx, topk_idx, topk_logp, C, targets, target_lengths, lm, alphas=None, betas=None, pairs=None, beam=10,
+                  chunk=0, input_lengths=None, texts=False):
+    """LMSweep of front-end lists ``topk_idx`` int32 / ``topk_logp`` float32 [W, B, k] over ``C`` classes
+    (hctr_lm_sweep_topk): per pair what ``nbest_topk(lm=, n=1)`` + ``edit_distance_labels`` return, in one call."""
+    idx = np.ascontiguousarray(topk_idx, dtype=np.int32)
+    lp = np.ascontiguousarray(topk_logp, dtype=np.float32)
+    if idx.ndim != 3 or idx.shape != lp.shape:
+        raise ValueError("topk_idx and topk_logp must both be [W,B,k]")
+    W, B, k = (int(v) for v in idx.shape)
+    tail, keep, result = _sweep_args(B, W, targets, target_lengths, lm, alphas, betas, pairs, chunk, input_lengths, texts)
+    _lib.check(_lib.load().hctr_lm_sweep_topk(ctx, lm, _lib.ptr(idx), _lib.ptr(lp), W, B, int(C), k, int(beam), *tail), ctx)
+    return result()
+
+
+def lm_sweep_logits(ctx, logits, on_dev, targets, target_lengths, lm, alphas=None, betas=None, pairs=None, beam=10, depth=10,
+                    chunk=0, input_lengths=None, texts=False):
+    """LMSweep of caller logits / log-probs in WBC layout (hctr_lm_sweep_logits)"""
+    if len(logits.shape) != 3:
+        raise ValueError("logits must be [W,B,C]")
+    W, B, C = (int(v) for v in logits.shape)
+    tail, keep, result = _sweep_args(B, W, targets, target_lengths, lm, alphas, betas, pairs, chunk, input_lengths, texts)
+    _lib.check(_lib.load().hctr_lm_sweep_logits(ctx, lm, _lib.ptr(logits), on_dev, W, B, C, int(depth), int(beam), *tail), ctx)
+    return result()
+
+
+def lm_sweep_images(ctx, x, dt, on_dev, widths, B, W, targets, target_lengths, lm, alphas=None, betas=None, pairs=None,
+                    beam=10, depth=10, chunk=0, input_lengths=None, texts=False):
+    """LMSweep of line images (hctr_lm_sweep); x, dt, on_dev, widths as in ``nbest_images``"""
+    tail, keep, result = _sweep_args(B, W, targets, target_lengths, lm, alphas, betas, pairs, chunk, input_lengths, texts)
+    _lib.check(_lib.load().hctr_lm_sweep(ctx, lm, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, int(depth), int(beam),
+                                         *tail), ctx)
+    return result()
+
+
 _FN = None
 
 

@@ -332,6 +332,30 @@ class hctr_model(object):
             res.texts = [codec.labels_to_text(line) for line in res.label_lists()]
         return res
 
+    def lm_sweep(self, input, truths_or_targets, target_lengths=None, lm=None, codec=None, alphas=None, betas=None, beam=10,
+                 depth=10, pairs=None, widths=None, input_lengths=None, chunk=0, texts=False):
+        """Forward once, then the reference's grid search over ``lm_panelty`` x ``len_bonus`` (test.py -gs) on this
+        batch: under every pair the 1-best of ``nbest(lm=, n=1)`` of every line and its edit distance to the line's
+        transcription, all pairs searched on the same lists on the device (include/hctr_hip.h ``hctr_lm_sweep``).
+        ``truths_or_targets`` is a list of strings (encoded with ``codec``) or targets with ``target_lengths`` as
+        ``evaluate`` takes them; ``lm`` (a ``codec.ArpaLM``) and ``codec`` are required; ``alphas`` x ``betas`` expand
+        alpha-major, or give ``pairs``. Returns a ``ctc.LMSweep`` (``texts=True``: with per-pair labels, scores and
+        ``.texts``); ``ctc.LMSweepTotals`` accumulates batches. In "auto" precision every line runs in f16x3."""
+        from . import ctc
+        ctx = self._require_ctx()
+        x, dt, on_dev, B, W = self._img_args(input)
+        if lm is None or codec is None:
+            raise ValueError("lm_sweep needs lm= (an ArpaLM) and codec= (the ctc_codec of this model's classes)")
+        if target_lengths is None:
+            targets, target_lengths = codec.encode(list(truths_or_targets))
+        else:
+            targets = truths_or_targets
+        res = ctc.lm_sweep_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, targets, target_lengths,
+                                  lm.flat(codec.characters), alphas, betas, pairs, beam, depth, chunk, input_lengths, texts)
+        if texts:
+            res.texts = [codec.labels_to_text(line) for line in res.label_lists()]
+        return res
+
     # -- precision mode ---------------------------------------------------------------------------
     def set_precision(self, precision):
         """Switch the mode of a loaded model among those whose weight set is resident (all three for a model built

@@ -524,6 +524,62 @@ int hctr_nbest_lm(hctr_ctx* ctx, const hctr_lm* lm, const void* img, int img_dty
                   const int32_t* input_lengths, int32_t* labels, int32_t* lengths, double* logp, double* score,
                   int32_t* count, double* lm_score);
 
+/* ---- LM weight sweep: the LM-scored search under a grid of (lm_panelty, len_bonus) pairs, with CER, on the device ---
+ * What test.py -gs (test.py:347-382) computes with one complete evaluation run per pair: for every pair g = 0..G-1,
+ * (lm_panelty[g], len_bonus[g]), the 1-best text of every line by the search of hctr_nbest_lm* and its edit distance
+ * to the line's transcription. Nothing before the ranking depends on the weights, so a call runs the forward, the front
+ * end and the pre-pass (word ids, greedy line, suffixes, end steps) once per pass, searches `chunk` pairs per launch on
+ * the shared lists - one workgroup per (pair, line), grid line g * n + b - and takes the distances of the grid lines
+ * against the references, which are uploaded once, with the distance-only instance of hctr_edit_distance.
+ * CONTRACT: for every g, every output equals, bit for bit, what the matching hctr_nbest_lm* entry called with nbest = 1,
+ * lm_panelty[g], len_bonus[g] returns, followed by hctr_edit_distance on its labels. Results do not depend on chunk;
+ * there are no atomics, and repeated calls are bit-identical.
+ * Arguments up to beam as the matching hctr_nbest_lm* entry; input_lengths likewise. targets / target_lengths: the
+ * transcriptions back to back, as for hctr_evaluate* (codec.encode's layout); ids in [1, C-1], lengths in [0, 2047].
+ * Outputs, host pointers, any may be NULL:
+ *   edits       int32 [G][B]: editdistance.eval(1-best text of line b under pair g, transcription of line b);
+ *   hyp_lengths int32 [G][B]: the length of that text;
+ *   empty       uint8 [B]: 1 when the line's greedy text is empty. The greedy text does not depend on the pair. Such a
+ *               line contributes the empty text under every pair (hyp_lengths = 0, edits = L_b, logp = score = lm_score
+ *               = -inf, as hctr_nbest_lm* return count = 0 for it) and the call still returns HCTR_OK. The reference
+ *               raises IndexError for such a line, and hctr_beam_search reports HCTR_ERR_EMPTY_LINE;
+ *   labels      int32 [G][B][W], zero padded; logp, score, lm_score float64 [G][B]: the 1-best's values exactly as
+ *               hctr_nbest_lm* with nbest = 1 returns them. They are large and exist so that the sweep can be checked;
+ *               callers normally pass NULL.
+ * chunk: pairs per launch. 0 = the engine's choice, hctr_lm_sweep_chunk(n, W, beam, G) =
+ *   max(1, min(G, 8192 / n, 2^31 / (n * (8 * W*beam + 4 * W + 36)))), n = B, for hctr_lm_sweep the lines of its first
+ *   (largest) pass: enough (pair, line) workgroups to fill the chip about four times over (about 2048 single-wave
+ *   workgroups of the beam 10 / k 10 instance are resident at once), capped by G and by 2 GiB of per-chunk scratch.
+ *   Any other value in [1, G] is used as given.
+ * Errors: HCTR_ERR_ARG with a message for everything the matching hctr_nbest_lm* entry and hctr_evaluate_logits reject
+ * (shapes, k, beam, input_lengths, lists, a NULL lm, an lm built for another C, NULL target_lengths, a target id outside
+ * [1, C-1], a transcription longer than 2047), for G < 1, a NULL weight array, a NaN among the weights (the message
+ * names the pair) and chunk outside [0, G]. B == 0 is a no-op. HCTR_ERR_NOMEM leaves the context usable.
+ * hctr_lm_sweep runs the forward and the front end once, in internal passes as hctr_nbest_lm does; mode 2 runs every
+ * line in f16x3 and hctr_last_guard is left as it was; no list goes to the host.
+ * Launches after the front end's own: beam_lm_prepass (once per pass), then per chunk prefix_beam_lm_grid,
+ * prefix_backtrace and edit_distance (hctr_last_profile adds up entries of one name).
+ * Device scratch (the context's grow-only CTC scratch; n as above, c = the chunk): 4 * B (steps) + 4 * (2 * B + sum L)
+ * (references) + 16 * G (pairs) + 16 * n*W (suffixes) + 4 * n*W*k (word ids) + 4 * n (end steps), held once per pass,
+ * plus per chunk 8 * c*n*W*beam (history) + 4 * c*n*W (labels) + 36 * c*n (length, count, distance, logp, score,
+ * lm_score), each array rounded up to 256 bytes; the lists and the table as hctr_nbest_lm* hold them. */
+int hctr_lm_sweep_chunk(int lines, int W, int beam, int G);
+int hctr_lm_sweep_topk(hctr_ctx* ctx, const hctr_lm* lm, const int32_t* topk_idx, const float* topk_logp, int W, int B,
+                       int C, int k, int beam, const double* lm_panelty, const double* len_bonus, int G, int chunk,
+                       const int32_t* input_lengths, const int32_t* targets, const int32_t* target_lengths,
+                       int32_t* edits, int32_t* hyp_lengths, uint8_t* empty, int32_t* labels, double* logp, double* score,
+                       double* lm_score);
+int hctr_lm_sweep_logits(hctr_ctx* ctx, const hctr_lm* lm, const float* logits_wbc, int on_device, int W, int B, int C,
+                         int k, int beam, const double* lm_panelty, const double* len_bonus, int G, int chunk,
+                         const int32_t* input_lengths, const int32_t* targets, const int32_t* target_lengths,
+                         int32_t* edits, int32_t* hyp_lengths, uint8_t* empty, int32_t* labels, double* logp,
+                         double* score, double* lm_score);
+int hctr_lm_sweep(hctr_ctx* ctx, const hctr_lm* lm, const void* img, int img_dtype, int img_on_device,
+                  const int32_t* widths, int B, int W, int k, int beam, const double* lm_panelty, const double* len_bonus,
+                  int G, int chunk, const int32_t* input_lengths, const int32_t* targets, const int32_t* target_lengths,
+                  int32_t* edits, int32_t* hyp_lengths, uint8_t* empty, int32_t* labels, double* logp, double* score,
+                  double* lm_score);
+
 /* ---- N-best texts by the reference's SKIP search, on the device -------------------------------------------------
  * __cbs_skip__ of utils/ctc_codec.py:124-181 (test.py -ss; what hctr_beam_search does with skip_search != 0 and
  * builtin_lm == 3 or 1): the search of hctr_nbest_lm*, except that a column in which ONE class alone has probability above

@@ -17,7 +17,10 @@ Differences from the reference, by design:
     (the reference's DataLoader workers, test.py:240-245); ``-jw 0`` decodes inline;
   * ``-f synthetic[:seed]`` loads the package's deterministic synthetic checkpoint (no checkpoint files
     are bundled with the reference), and then the vocabulary defaults to the synthetic one;
-  * ``-kp zero|toy`` selects a built-in language model for beam search when kenlm is not installed.
+  * ``-kp zero|toy`` selects a built-in language model for beam search when kenlm is not installed;
+  * ``-gs --device-sweep`` answers the grid search with one pass over the dataset: one model, one forward per batch,
+    every (lm_panelty, len_bonus) pair searched and scored on the device (``hctr_model.lm_sweep``), then the
+    reference's lines. Without the flag ``-gs`` runs the reference's loop of complete evaluation runs.
 """
 import argparse
 import os
@@ -65,6 +68,8 @@ def build_argparser():
     a.add_argument("-bl", "--beta-lower", type=float, default=4.2)
     a.add_argument("-bu", "--beta-upper", type=float, default=6.6)
     a.add_argument("-bc", "--beta-count", type=int, default=25)
+    # engine option (not a reference flag): the grid search in one pass over the dataset, all pairs on the device
+    a.add_argument("--device-sweep", dest="device_sweep", action="store_true")
     # engine option (not a reference flag): f16 (default), f16x3, or auto = f16 with uncertain lines re-run in f16x3
     a.add_argument("--precision", type=str, default=os.environ.get("HCTR_PRECISION", "f16"), choices=["f16", "f16x3", "auto"])
     return p
@@ -126,6 +131,29 @@ def edit_distance(a, b):
             cur.append(min(prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + (ca != cb)))
         prev = cur
     return prev[-1]
+
+
+def check_device_sweep(args):
+    """--device-sweep is the grid search of the n-gram-scored full search only: -gs -bm -dm beam-search -kp <file.arpa>,
+    without -ss and without the transformer options. Raises ValueError naming the option in the way."""
+    def no(why):
+        raise ValueError("--device-sweep " + why)
+    if not args.grid_search:
+        no("needs -gs (--grid-search): it is the grid search's device path")
+    if not args.benchmark_mode:
+        no("needs -bm (--benchmark-mode): the grid search scores against test_img_id_gt.txt")
+    if args.decode_method != "beam-search":
+        no("needs -dm beam-search, got -dm %s" % args.decode_method)
+    if args.skip_search:
+        no("does not take -ss (--skip-search): the skip search is not swept on the device")
+    for on, flag in ((args.use_tfm_pred, "-utp (--use-tfm-pred)"), (args.use_tfm_score, "-uts (--use-tfm-score)"),
+                     (bool(args.tfm_path), "-tp (--transformer-path)"), (args.use_openvino, "-uov (--use-openvino)")):
+        if on:
+            no("does not take %s: transformer language models are not swept on the device" % flag)
+    if not args.kenlm_path or args.kenlm_path in ("zero", "toy"):
+        no("needs -kp <file.arpa>: an n-gram model, got -kp %r" % args.kenlm_path)
+    if not os.path.isfile(args.kenlm_path):
+        no("needs -kp <file.arpa>: no file at %s" % args.kenlm_path)
 
 
 def build(args):
@@ -190,9 +218,10 @@ def test(args):
     return None
 
 
-def benchmark(model, codec, args):
-    """CER over ``<input>/test_img_id_gt.txt`` ('<image name>,<text>' per line, images under
-    ``<input>/test/``; utils/dataset.py:31-37)."""
+def benchmark_batches(model, args):
+    """The batches of ``-bm`` over ``<input>/test_img_id_gt.txt`` ('<image name>,<text>' per line, images under
+    ``<input>/test/``; utils/dataset.py:31-37): yields (batch index, number of batches, [(name, truth)], device images,
+    widths), the truths cut as AlignCollate cuts them."""
     if not os.path.isdir(args.input):
         raise AssertionError("Input should be a folder under benchmark mode.")
     import hctr_amd
@@ -210,16 +239,22 @@ def benchmark(model, codec, args):
                     items.append((hit[0], parts[1]))
                     break
     items = items[:args.batch_size * (len(items) // args.batch_size)]      # ImageDataset.__len__
-    total = nchars = 0
-    cer = 0.0
-    t_all = time.time()
     chunks = [items[i:i + args.batch_size] for i in range(0, len(items), args.batch_size)]
     for bi, (names, arrs) in enumerate(prefetched([[n for n, _ in ch] for ch in chunks], args.workers)):
-        i = bi * args.batch_size
         chunk = chunks[bi]
         full = [pp.target_width(a.shape[0], a.shape[1], model.img_height, "dataset") for a in arrs]
         imgs, widths = pp.resize_lines(model, arrs, model.img_height, "dataset", "rgb", ALIGN_MAX_WIDTH, device_out=True)
         chunk = [(n, pp.truncate_label(tru, fw, int(imgs.shape[2]))) for (n, tru), fw in zip(chunk, full)]
+        yield bi, len(chunks), chunk, imgs, widths
+
+
+def benchmark(model, codec, args):
+    """CER of ``-bm`` (test.py:230-306) over the batches of ``benchmark_batches``."""
+    total = nchars = 0
+    cer = 0.0
+    t_all = time.time()
+    for bi, nbatches, chunk, imgs, widths in benchmark_batches(model, args):
+        i = bi * args.batch_size
         t0 = time.time()
         result = recognise(model, codec, imgs, widths)
         # editdistance.eval(pre, tru) of every line (test.py:275) in one call on the device, whatever decoded them
@@ -235,14 +270,46 @@ def benchmark(model, codec, args):
             raise ValueError("Number of label characters should not be 0.")
         cer = total * 1.0 / nchars
         if (i // args.batch_size) % args.print_freq == 0:
-            print("TEST: [{0}/{1}]\tTime {2:.3f}\tErr {3:.4f}".format(i // args.batch_size,
-                  (len(items) + args.batch_size - 1) // args.batch_size, time.time() - t0, cer))
+            print("TEST: [{0}/{1}]\tTime {2:.3f}\tErr {3:.4f}".format(i // args.batch_size, nbatches, time.time() - t0, cer))
     print("Total Test CER: {} ({:.1f}s)".format(cer, time.time() - t_all))
     return cer
 
 
+def device_sweep(args):
+    """``-gs --device-sweep``: the model is built once and the dataset walked once; every batch is searched under all
+    alpha x beta pairs on the device and scored there (``hctr_model.lm_sweep``). Prints the reference loop's lines."""
+    import hctr_amd
+    check_device_sweep(args)
+    alphas = np.linspace(args.alpha_lower, args.alpha_upper, args.alpha_count)
+    betas = np.linspace(args.beta_lower, args.beta_upper, args.beta_count)
+    args.kenlm_path, arpa = "", args.kenlm_path          # the codec's own host search is not used
+    model, codec = build(args)
+    lm = hctr_amd.ArpaLM(arpa)
+    totals = hctr_amd.LMSweepTotals()
+    empty = 0
+    t_all = time.time()
+    for bi, nbatches, chunk, imgs, widths in benchmark_batches(model, args):
+        sweep = model.lm_sweep(imgs, [tru for _, tru in chunk], lm=lm, codec=codec, alphas=alphas, betas=betas,
+                               beam=args.beam_size, depth=min(args.search_depth, model.noutput), widths=widths)
+        totals.update(sweep)
+        empty += int(sweep.empty.sum())
+        if bi % args.print_freq == 0:
+            print("SWEEP: [{0}/{1}]\tTime {2:.1f}s\tbest so far {3}".format(bi, nbatches, time.time() - t_all, totals.best()))
+    if totals.nchars == 0:
+        raise ValueError("Number of label characters should not be 0.")
+    if empty:
+        print("{} lines had an empty greedy text (the reference's search raises IndexError there); they count as empty "
+              "predictions under every pair".format(empty))
+    for line in totals.report():
+        print(line)
+    return totals
+
+
 def main():
     args = build_argparser().parse_args()
+    if args.device_sweep:
+        device_sweep(args)
+        return
     if not args.grid_search:
         test(args)
         return

@@ -67,7 +67,17 @@ use here: its rows have no class above 0.001 and every line empties) with the sa
 search on the front end's lists (hctr_nbest_skip_lists) against the device full search (hctr_nbest_lm_topk) and the host
 skip search (hctr_beam_search(skip_search = 1, builtin_lm = 3), 16 threads) on the same lists in the same process; calls
 alternate after warm-up calls of each, medians. Reports the share of in-place steps, the largest row, the line statuses
-and the device time of each search's launches from profiled calls."""
+and the device time of each search's launches from profiled calls.
+
+    python tools/bench_ctc.py --lm-sweep --pairs 250 ...
+
+times the LM weight sweep (hctr_lm_sweep_topk: G pairs of (lm_panelty, len_bonus) searched on one set of lists, the edit
+distances taken on the device) on the batch, lists and order-5 model of --nbest-lm, against G successive calls of
+hctr_nbest_lm_topk(nbest = 1) + hctr_edit_distance on the same lists in the same process - the way to the same numbers
+without the sweep. The pairs are the first G of the reference's default grid (10 x 25, alpha-major); the transcriptions
+are the lines' greedy texts. The two alternate after warm-up calls of each, medians of the wall time per call; the device
+time of each one's launches comes from one profiled call of each in the same run. Every ``edits`` value of the two is
+compared before anything is reported."""
 import argparse
 import json
 import os
@@ -95,6 +105,8 @@ def main():
     ap.add_argument("--nbest", action="store_true")
     ap.add_argument("--nbest-lm", action="store_true")
     ap.add_argument("--nbest-skip", action="store_true")
+    ap.add_argument("--lm-sweep", action="store_true")
+    ap.add_argument("--pairs", type=int, default=250)
     ap.add_argument("--host-lines", type=int, default=4)
     args = ap.parse_args()
     import torch
@@ -127,6 +139,9 @@ def main():
         return
     if args.nbest_lm:
         print(json.dumps(nbest_lm(args, hctr_amd, m, imgs)))
+        return
+    if args.lm_sweep:
+        print(json.dumps(lm_sweep(args, hctr_amd, m, imgs, targets, tl)))
         return
 
     def t_greedy():
@@ -524,6 +539,88 @@ def nbest_lm(args, hctr_amd, m, imgs):
             "images_entry_equals_topk_entry": bool(same_entries),
             "mean_text_length": float(np.mean([len(t) for t in one_best])),
             "mean_lm_score": float(np.mean(out["nbest_lm_topk"].lm_scores[:, 0]))}
+
+
+def lm_sweep(args, hctr_amd, m, imgs, targets, tl):
+    import tempfile
+    import torch
+    from hctr_amd import package
+    ctc = sys.modules[package.__name__ + ".ctc"]
+    B, W = int(imgs.shape[0]), int(imgs.shape[-1])
+    C, k, beam, G = int(m.noutput), 10, 10, int(args.pairs)
+    chars = hctr_amd.synth.characters()
+    codec = hctr_amd.ctc_codec(chars)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, "bench5.arpa")
+        ngrams = write_bench_arpa(path, chars)
+        lm = hctr_amd.ArpaLM(path)
+    flat = lm.flat(codec.characters)
+    fe = m.beam_frontend(imgs, k)
+    idx, lp = fe["topk_idx"], fe["topk_logp"]
+    al, be = ctc.sweep_pairs(np.linspace(0.7, 1.1, 10), np.linspace(4.2, 6.6, 25))      # the reference's default grid
+    reps = -(-G // al.size)
+    grid = list(zip(np.tile(al, reps)[:G].tolist(), np.tile(be, reps)[:G].tolist()))
+
+    def timed(f):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = f()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, out
+
+    def sweep():
+        return ctc.lm_sweep_topk(m._ctx, idx, lp, C, targets, tl, flat, pairs=grid, beam=beam).edits
+
+    def successive():
+        out = np.zeros((G, B), np.int32)
+        for g, (a, b) in enumerate(grid):
+            nb = ctc.nbest_topk(m._ctx, idx, lp, C, 1, beam, b, None, lm=flat, lm_panelty=a)
+            out[g] = ctc.edit_distance_labels(m._ctx, nb.labels[:, 0], nb.lengths[:, 0], targets, tl, maps=False).edits
+        return out
+
+    calls = {"lm_sweep": sweep, "successive": successive}
+    for _ in range(args.warmup):
+        for f in calls.values():
+            f()
+    ms = {name: [] for name in calls}
+    out = {}
+    for step in range(args.steps):
+        for name, f in calls.items():
+            dt, out[name] = timed(f)
+            ms[name].append(1e3 * dt)
+            print("step %d %s: %.1f ms" % (step, name, 1e3 * dt), file=sys.stderr, flush=True)      # (a step takes a while)
+    if not np.array_equal(out["lm_sweep"], out["successive"]):
+        raise SystemExit("the sweep and the successive calls disagree on %d of %d edits values"
+                         % (int((out["lm_sweep"] != out["successive"]).sum()), out["lm_sweep"].size))
+    med = {name: float(np.median(v)) for name, v in ms.items()}
+    m.set_profiling(True)
+    sweep()
+    prof = dict(m.last_profile())
+    names = ("beam_lm_prepass", "prefix_beam_lm", "prefix_backtrace", "edit_distance")
+    single = {key: 0.0 for key in names}
+    for a, b in grid:
+        nb = ctc.nbest_topk(m._ctx, idx, lp, C, 1, beam, b, None, lm=flat, lm_panelty=a)
+        for key, v in dict(m.last_profile()).items():
+            if key in single:
+                single[key] += v
+        ctc.edit_distance_labels(m._ctx, nb.labels[:, 0], nb.lengths[:, 0], targets, tl, maps=False)
+        single["edit_distance"] += dict(m.last_profile()).get("edit_distance", 0.0)
+    m.set_profiling(False)
+    sweep_names = ("beam_lm_prepass", "prefix_beam_lm_grid", "prefix_backtrace", "edit_distance")
+    chunk = ctc.lm_sweep_chunk(B, W, beam, G)
+    cer = out["lm_sweep"].astype(np.int64).sum(axis=1) / float(max(int(np.sum(tl)), 1))
+    return {"mode": "lm-sweep", "lines": B, "width": W, "classes": C, "precision": args.precision, "beam": beam, "depth": k,
+            "pairs": G, "chunk": chunk, "launches": -(-G // chunk), "lm_order": lm.order, "lm_ngrams": ngrams,
+            "edits_equal": True, "distinct_cer_values": int(np.unique(cer).size),
+            "sweep_device_ms": round(sum(prof.get(key, 0.0) for key in sweep_names), 3),
+            "sweep_device_launches_ms": {key: round(prof.get(key, 0.0), 4) for key in sweep_names},
+            "successive_device_ms": round(sum(single.values()), 3),
+            "successive_device_launches_ms": {key: round(v, 4) for key, v in single.items()},
+            "sweep_call_ms_median": round(med["lm_sweep"], 3),
+            "successive_calls_ms_median": round(med["successive"], 3),
+            "successive_over_sweep_wall": round(med["successive"] / med["lm_sweep"], 3),
+            "successive_over_sweep_device": round(sum(single.values()) / max(sum(prof.get(key, 0.0) for key in sweep_names), 1e-9), 3),
+            "ms": {name: [round(v, 3) for v in vals] for name, vals in ms.items()}}
 
 
 def nbest_skip(args, hctr_amd):
