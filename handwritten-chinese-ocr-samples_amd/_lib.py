@@ -221,6 +221,7 @@ SIGNATURES = [
     ("hctr_last_profile", _I, [_VP, ctypes.c_char_p, _I, c_f32p, _I]),
     ("hctr_debug_stamps", _I64, [_VP, ctypes.c_char_p, _VP, _I64]),
     ("hctr_debug_activation", _I64, [_VP, ctypes.c_char_p, _VP, _I64, ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    ("hctr_debug_se", _I, [_VP, ctypes.c_char_p, _VP, _VP, _I64]),
 ]
 
 

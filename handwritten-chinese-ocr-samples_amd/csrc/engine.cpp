@@ -24,6 +24,7 @@ constexpr int kFeat = 2048;                      // 512 channels x 4 rows, :168-
 constexpr double kBnEps = 1e-5;                  // nn.BatchNorm2d default
 constexpr int kStagePlanes[4] = {128, 256, 512, 512};
 constexpr int kStageBlocks[4] = {2, 4, 5, 1};    // ResNet(1, 512, BasicBlock, [2,4,5,1]), :166
+constexpr int kSeBlocks = 2 + 4 + 5 + 1;         // SE layers = blocks of the trunk (one statistics slot each)
 constexpr int kStageH[5] = {128, 64, 32, 16, 8}; // rows entering stage s (stage 0 = stem)
 constexpr int64_t kDefaultMaxCols = 131072;      // pixel columns (B*W) per internal pass
 
@@ -63,9 +64,9 @@ struct Workspace {
     half_t* headin = nullptr;       // [B*W][2048], k = h*512 + c
     float* logits = nullptr;        // [B*W][Cpad]
     float* se_part = nullptr;
-    float* se_scale = nullptr;
+    float* se_scale = nullptr;      // [kSeBlocks][B][512]: one slot per block, so that hctr_debug_se can read them back
     float* se_border = nullptr;     // [B][4][8 segments][512]
-    float* se_mean = nullptr;       // [B][512]
+    float* se_mean = nullptr;       // [kSeBlocks][B][512]
     int32_t* se_counter = nullptr;  // [B] last-block-done tickets of se_premean (zero between launches)
     int32_t* colidx = nullptr;      // [B*W]
     float* amax_val = nullptr;      // [P][B*W] fused head argmax partials, P <= Cpad/64
@@ -526,9 +527,9 @@ int ensure_workspace(hctr_ctx* c, int B, int W, int features = 0) {
             for (int i = 0; i < 4; ++i) A(&pool4[i], pool_elems);
         A(&ws.headin, cols * kFeat * m);
         A(&ws.se_part, se_max);
-        A(&ws.se_scale, (size_t)B * 512);
+        A(&ws.se_scale, (size_t)kSeBlocks * B * 512);
         A(&ws.se_border, (size_t)B * 5 * 8 * 512);
-        A(&ws.se_mean, (size_t)B * 512);
+        A(&ws.se_mean, (size_t)kSeBlocks * B * 512);
         A(&ws.se_counter, (size_t)B);
         A(&ws.colidx, cols);
         const size_t P = (size_t)head_parts_max(c);           // class parts per row of the fused head epilogues
@@ -746,9 +747,11 @@ int run_conv(hctr_ctx* c, Prof& pf, const char* name, const ConvW& cw, ActDesc i
 // epilogue applies relu(acc * scale + residual) itself. HCTR_FUSE_SE=0 selects the unfused form
 // (conv2 -> o, SE on sums of o, separate se_apply pass) for A/B runs.
 int run_block(hctr_ctx* c, Prof& pf, const std::string& name, const BlockW& bw, ActDesc in, half_t* t,
-              half_t* o, half_t* r, int planes) {
+              half_t* o, half_t* r, int planes, int se_slot) {
     const Workspace& ws = c->ws;
     const int H = in.H;
+    float* const se_mean = ws.se_mean + (size_t)se_slot * ws.B * 512;       // this block's slot (hctr_debug_se)
+    float* const se_scale = ws.se_scale + (size_t)se_slot * ws.B * 512;
     auto tiles_of = [&](const ConvW& cw) {
         const ConvTile t = pick_tile(c, cw, H);
         return (H / conv_tile_rows(t)) * ((ws.W + conv_tile_cols(t) - 1) / conv_tile_cols(t));
@@ -773,14 +776,14 @@ int run_block(hctr_ctx* c, Prof& pf, const std::string& name, const BlockW& bw, 
                                                                     ws.se_part, tiles1, ws.se_border, c->stream));
         PROF_TRY(pf, (name + ".se_scale").c_str(), launch_se_premean(ws.se_border, t, bw.conv2.w, bw.conv2.bias, ws.B,
                                                                      H, ws.W, ws.Wa, planes, bw.conv2.coutPad, c->split,
-                                                                     ws.se_mean, bw.se.w1, bw.se.w2, ws.se_scale,
+                                                                     se_mean, bw.se.w1, bw.se.w2, se_scale,
                                                                      ws.se_counter, c->stream));
         if (fuse_ds)
             TRY(run_conv(c, pf, (name + ".conv2+se+ds").c_str(), bw.conv2, ActDesc{t, H, planes}, o, H, true, false,
-                         nullptr, false, ws.se_scale, nullptr, &bw.ds, in.p));
+                         nullptr, false, se_scale, nullptr, &bw.ds, in.p));
         else
             TRY(run_conv(c, pf, (name + ".conv2+se").c_str(), bw.conv2, ActDesc{t, H, planes}, o, H, true, false,
-                         nullptr, false, ws.se_scale, res));
+                         nullptr, false, se_scale, res));
         return HCTR_OK;
     }
     c->out_class = 2;
@@ -789,9 +792,9 @@ int run_block(hctr_ctx* c, Prof& pf, const std::string& name, const BlockW& bw, 
     TRY(run_conv(c, pf, (name + ".conv2").c_str(), bw.conv2, ActDesc{t, H, planes}, o, H, false, false,
                  ws.se_part, false));
     const int tiles = tiles_of(bw.conv2);
-    PROF_TRY(pf, (name + ".se_fc").c_str(), launch_se_fc(ws.se_part, tiles, bw.se.w1, bw.se.w2, ws.se_scale, ws.B,
+    PROF_TRY(pf, (name + ".se_fc").c_str(), launch_se_fc(ws.se_part, tiles, bw.se.w1, bw.se.w2, se_scale, ws.B,
                                                          planes, inv_hw, c->stream));
-    PROF_TRY(pf, (name + ".se_apply").c_str(), launch_se_apply(o, res, ws.se_scale, (int64_t)(H + 2) * ws.Wa * planes,
+    PROF_TRY(pf, (name + ".se_apply").c_str(), launch_se_apply(o, res, se_scale, (int64_t)(H + 2) * ws.Wa * planes,
                                                                ws.B, planes, c->stream));
     return HCTR_OK;
 }
@@ -863,7 +866,7 @@ int run_forward(hctr_ctx* c, int img_f32, bool have_widths, HeadMode mode = HEAD
                                                  c->split ? ((c->x3_mask & 8) ? 1 : 2) : 0, c->stream));
         TRY(run_conv(c, pf, "conv0_2+pool", wt.conv0_2, ActDesc{ws.s0, 128, 64}, ws.x[1], 64, true, true, nullptr, false));
     }
-    int cin = 64;
+    int cin = 64, se_slot = 0;
     for (int s = 1; s <= 4; ++s) {
         const int H = kStageH[s], planes = kStagePlanes[s - 1];
         ActDesc cur{ws.x[s], H, cin};
@@ -876,7 +879,9 @@ int run_forward(hctr_ctx* c, int img_f32, bool have_widths, HeadMode mode = HEAD
             // 1x1-downsample residual (first block of stages 1-3 only) uses the third.
             const int ti = ci < 0 ? 0 : (ci + 1) % 3, oi = ci < 0 ? 1 : (ci + 2) % 3;
             if (bw.has_ds && ci >= 0) return fail(c, HCTR_ERR_STATE, "downsample only expected on a stage's first block");
-            TRY(run_block(c, pf, nm, bw, cur, ws.p[s][ti], ws.p[s][oi], bw.has_ds ? ws.p[s][2] : nullptr, planes));
+            if (se_slot >= kSeBlocks) return fail(c, HCTR_ERR_STATE, "more blocks than SE slots");
+            TRY(run_block(c, pf, nm, bw, cur, ws.p[s][ti], ws.p[s][oi], bw.has_ds ? ws.p[s][2] : nullptr, planes,
+                          se_slot++));
             cur = ActDesc{ws.p[s][oi], H, planes};
             ci = oi;
         }
@@ -3275,6 +3280,36 @@ int64_t hctr_debug_activation(hctr_ctx* c, const char* name, float* out, int64_t
                         out[(((int64_t)b * C + ch) * H + h) * ws.W + w] = v;
                     }
         return total;
+    });
+}
+
+int hctr_debug_se(hctr_ctx* c, const char* name, float* mean_out, float* scale_out, int64_t cap) {
+    return guard<int>(c, [&]() -> int {
+        if (!c || !name) return HCTR_ERR_ARG;
+        const Workspace& ws = c->ws;
+        if (ws.B == 0) return fail(c, HCTR_ERR_STATE, "no forward has run");
+        int st = 0, bi = 0, slot = 0;
+        char tail = 0;
+        if (sscanf(name, "block%d.%d%c", &st, &bi, &tail) != 2 || st < 1 || st > 4 || bi < 0 ||
+            bi >= (int)c->wts().blocks[st - 1].size())
+            return fail(c, HCTR_ERR_ARG, "unknown block '%s'", name);
+        for (int s = 1; s < st; ++s) slot += (int)c->wts().blocks[s - 1].size();
+        slot += bi;
+        if (slot >= kSeBlocks) return fail(c, HCTR_ERR_STATE, "more blocks than SE slots");
+        // (f16x3 passes always take the fused form, see run_block)
+        if (!c->fuse_se && !ws.split)
+            return fail(c, HCTR_ERR_STATE, "the unfused SE path (HCTR_FUSE_SE=0) computes no channel means ahead of conv2");
+        const int C = kStagePlanes[st - 1];
+        const int64_t total = (int64_t)ws.B * C;
+        if (cap < total || (!mean_out && !scale_out))
+            return fail(c, HCTR_ERR_ARG, "hctr_debug_se(%s): room for %lld values needed", name, (long long)total);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        const size_t off = (size_t)slot * ws.B * 512;
+        if (mean_out)
+            HIP_TRY(c, hipMemcpy(mean_out, ws.se_mean + off, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+        if (scale_out)
+            HIP_TRY(c, hipMemcpy(scale_out, ws.se_scale + off, (size_t)total * sizeof(float), hipMemcpyDeviceToHost));
+        return HCTR_OK;
     });
 }
 

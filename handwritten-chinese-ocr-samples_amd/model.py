@@ -434,6 +434,19 @@ class hctr_model(object):
             _lib.check(int(n2), ctx)
         return out.reshape(batch, C.value, H.value, -1)
 
+    def debug_se(self, name, batch):
+        """(means, scales), float32 [batch, C] each, of SE block ``name`` ("block<s>.<i>") in the last forward: the
+        channel means of bn2(conv2(t)) the engine derived ahead of conv2 and the scales it applied. ``batch`` is the
+        batch size of that forward. Raises RuntimeError on the unfused SE path (HCTR_FUSE_SE=0)."""
+        ctx = self._require_ctx()
+        planes = {"1": 128, "2": 256, "3": 512, "4": 512}.get(name[5:6])
+        if not name.startswith("block") or planes is None:
+            raise ValueError("unknown block %r" % (name,))
+        mean = np.empty((batch, planes), dtype=np.float32)
+        scale = np.empty((batch, planes), dtype=np.float32)
+        _lib.check(_lib.load().hctr_debug_se(ctx, name.encode(), _lib.ptr(mean), _lib.ptr(scale), mean.size), ctx)
+        return mean, scale
+
 
 def beam_frontend_call(ctx, x, dt, on_dev, widths, logits, logits_on_dev, B, W, C, k, want_candidates):
     lib = _lib.load()

@@ -712,6 +712,12 @@ int64_t hctr_debug_stamps(hctr_ctx* ctx, const char* layer, uint64_t* out, int64
  * as float32 NCHW [B][C][H][W]. name: "stage0".."stage4", "conv0_1". Returns element count or <0. */
 int64_t hctr_debug_activation(hctr_ctx* ctx, const char* name, float* out, int64_t cap,
                               int* C, int* H);
+/* SE statistics of block "block<s>.<i>" in the last forward (fused SE form, the default): the channel means of
+ * bn2(conv2(t)) that se_premean derived from conv1's sums, and the channel scales it computed from them, each as
+ * float32 [B][C] (C = the block's planes; either pointer may be NULL; cap = room in each, in floats). Every block
+ * keeps its own slot in the workspace, so all twelve are readable after one forward. HCTR_ERR_STATE on the unfused
+ * path (HCTR_FUSE_SE=0 in f16 mode), which computes no means ahead of conv2. */
+int hctr_debug_se(hctr_ctx* ctx, const char* name, float* mean_out, float* scale_out, int64_t cap);
 
 #ifdef __cplusplus
 }

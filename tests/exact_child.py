@@ -1,0 +1,43 @@
+"""Child process of test_gpu_exact.py::test_kernel_families: the engine, under whatever HCTR_* kernel-selection
+variables its environment sets (they are read once per process), against the oracle on the exact-arithmetic checkpoint
+(tests/exact_ckpt.py) at three widths. Logits, every readable activation and the greedy labels must equal the oracle's
+bit for bit; with HCTR_WS_ALIAS=1 the stages share their buffers, so only logits and labels are compared. With
+HCTR_FUSE_SE=0 the SE statistics reader has nothing to read and must fail with its own message.
+Prints every difference (first differing element of each array) and exits with 1 if there is one."""
+import importlib
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+
+
+def main():
+    import exact_ckpt as ex
+    pkg = importlib.import_module("handwritten-chinese-ocr-samples_amd")
+    with_taps = os.environ.get("HCTR_WS_ALIAS", "") != "1"
+    failed = False
+    for seed, nc, B, W in ex.child_cases():
+        x, logits, taps = ex.oracle_case(seed, nc, B, W)
+        model = pkg.hctr_model(nc).cuda(0)
+        model.load_state_dict(ex.cached_state_dict(nc, seed))
+        diffs = ex.engine_differences(model, x, logits, taps, with_taps=with_taps)
+        if os.environ.get("HCTR_FUSE_SE", "") == "0":         # the unfused SE form has no means to read back: an error
+            try:
+                model.debug_se("block1.0", B)
+                diffs.append("debug_se did not fail on the unfused SE path")
+            except RuntimeError as exc:
+                if "unfused" not in str(exc):
+                    diffs.append("debug_se failed with another message: %s" % exc)
+        del model
+        print("seed %d, %d classes, %d lines x %d columns: %s" % (seed, nc, B, W, "equal" if not diffs else "DIFFERENT"),
+              flush=True)
+        for d in diffs:
+            print("  " + d, flush=True)
+        failed = failed or bool(diffs)
+    return 1 if failed else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

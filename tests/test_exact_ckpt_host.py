@@ -1,0 +1,178 @@
+"""CPU proof that the oracle alone is exact on the exact-arithmetic checkpoint (tests/exact_ckpt.py).
+
+These are the conditions that make the equalities of tests/test_gpu_exact.py legitimate: for every (seed, class count,
+B, W) the GPU tests use, every value of the forward is an integer that fp16 and fp32 hold exactly, whatever the order
+of summation and wherever a value is rounded - so the three formulations of the oracle and a float64 run agree bit for
+bit, and an engine that adds up the right terms has to agree with them too."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import exact_ckpt as ex
+from oracle import hctr_ref
+
+synth = ex.synth
+F16_EXACT = 2048.0            # every integer of magnitude <= 2^11 is an fp16 value
+F32_EXACT = float(1 << 24)    # every integer of magnitude <= 2^24 is an fp32 value
+BLOCKS = [(s, i) for s, nb in enumerate(hctr_ref.STAGE_BLOCKS, start=1) for i in range(nb)]
+
+
+def _is_int(t):
+    return bool((t == t.round()).all())
+
+
+@pytest.mark.parametrize("seed", ex.SEEDS)
+def test_fold_returns_the_intended_integers(seed):
+    """BN folds to scale exactly 1: the folded weights are the integer conv weights, the folded biases the integer BN
+    biases, with and without the fp16 rounding of the weights - and the low part that the f16x3 mode would carry for
+    a folded weight (the float64 product minus its fp16 value, rounded to fp16) is 0."""
+    sd = ex.cached_state_dict(ex.CLASS_COUNTS[0], seed)
+    for ck, bk, cin, cout, ks, has_bias in synth.conv_specs():
+        for half in (False, True):
+            w, b = hctr_ref._fold(sd, ck, bk, half)
+            assert np.array_equal(w.numpy(), sd[ck + ".weight"]), (ck, half)
+            assert np.array_equal(b.numpy(), sd[bk + ".bias"]), (ck, half)
+        sc = 1.0 / np.sqrt(sd[bk + ".running_var"].astype(np.float64) + hctr_ref.BN_EPS)
+        v = sd[ck + ".weight"].astype(np.float64) * sc[:, None, None, None]
+        hi = v.astype(np.float32).astype(np.float16)
+        assert not (v - hi.astype(np.float64)).astype(np.float32).astype(np.float16).any(), ck
+        assert _is_int(w) and float(w.abs().sum(dim=(1, 2, 3)).max()) <= 2.0, ck
+    head = sd["linear.weight"]
+    assert np.array_equal(head.astype(np.float16).astype(np.float32), head)
+    assert float(np.abs(head).sum(axis=1).max()) <= 3.0
+
+
+def test_weights_cover_every_tap_group_and_channel():
+    """Across the seeds used, every layer has a nonzero weight in each of its taps, in each 32-channel group of its
+    input, and for every output channel (each seed on its own does, too)."""
+    for seed in ex.SEEDS:
+        sd = ex.cached_state_dict(ex.CLASS_COUNTS[0], seed)
+        for ck, bk, cin, cout, ks, has_bias in synth.conv_specs():
+            nz = sd[ck + ".weight"] != 0
+            assert nz.any(axis=(1, 2, 3)).all(), (ck, "an output channel without a weight")
+            assert nz.any(axis=(0, 1)).all(), (ck, "a tap without a weight")
+            per_ci = nz.any(axis=(0, 2, 3))
+            for g in range((cin + 31) // 32):
+                assert per_ci[g * 32:(g + 1) * 32].any(), (ck, "input group %d without a weight" % g)
+        for sk, c in synth.se_specs():
+            p = ex.se_pattern(seed, sk, c)
+            assert p.any() and not p.all()
+            assert np.array_equal(sd[sk + ".fc.2.weight"][:, 0] != 0, p)
+        for nc in ex.CLASS_COUNTS:
+            head = ex.cached_state_dict(nc, seed)["linear.weight"]
+            assert (head != 0).any(axis=1).all()
+            f = (head != 0).any(axis=0).reshape(512, 4)           # feature d = c*4 + h
+            assert f.any(axis=0).all() and f.reshape(16, 32, 4).any(axis=(1, 2)).all()
+
+
+def _forward_f64(sd, x, rec):
+    """The folded forward in float64 (input and folded weights cast to double, no rounding anywhere). ``rec`` receives
+    what the exactness conditions are stated on: every conv's pre-rounding output range, the per-image channel sums of
+    every block's t and |conv2 output|, the SE pre-sigmoid values, and the taps."""
+    def conv(x, ck, bk, relu, pad, pool=False):
+        w, b = hctr_ref._fold(sd, ck, bk, True)
+        y = F.conv2d(x, w.double(), b.double(), stride=1, padding=pad)
+        rec["pre"][ck] = float(y.abs().max())
+        z = F.relu(y) if relu else y
+        return y, (hctr_ref._pool(z) if pool else z)
+
+    taps = rec["taps"]
+    x = torch.from_numpy(x).double()
+    _, x = conv(x, "cnn.conv0_1", "cnn.bn0_1", True, 1)
+    taps["conv0_1"] = x
+    _, x = conv(x, "cnn.conv0_2", "cnn.bn0_2", True, 1, pool=True)
+    taps["stage0"] = x
+    for s, nb in enumerate(hctr_ref.STAGE_BLOCKS, start=1):
+        for i in range(nb):
+            p, nm = "cnn.block%d.%d" % (s, i), "block%d.%d" % (s, i)
+            _, t = conv(x, p + ".conv1", p + ".bn1", True, 1)
+            y, _ = conv(t, p + ".conv2", p + ".bn2", False, 1)
+            rec["tsum"][nm] = float(t.abs().sum(dim=(2, 3)).max())
+            rec["ysum"][nm] = float(y.abs().sum(dim=(2, 3)).max())
+            m = y.mean(dim=(2, 3))
+            w0 = hctr_ref._t(sd, p + ".se.fc.0.weight")
+            w2 = hctr_ref._t(sd, p + ".se.fc.2.weight")
+            rec["presig"][nm] = F.linear(F.relu(F.linear(m, w0.double())), w2.double())
+            # the same value as the three fp32 runs compute it (they see this y, which fp32 holds exactly)
+            rec["presig32"][nm] = F.linear(F.relu(F.linear(y.float().mean(dim=(2, 3)), w0)), w2)
+            rec["mean"][nm] = m
+            sc = torch.sigmoid(rec["presig"][nm])
+            r = x
+            if (p + ".downsample.0.weight") in sd:
+                _, r = conv(x, p + ".downsample.0", p + ".downsample.1", False, 0)
+            x = F.relu(y * sc[:, :, None, None] + r)
+            taps[nm + ".conv1"], taps[nm + ".conv2"], taps[nm + ".res"], taps[nm] = t, y, r, x
+            taps[nm + ".scale"] = sc
+        _, x = conv(x, "cnn.conv%d" % s, "cnn.bn%d" % s, True, 1, pool=True)
+        taps["stage%d" % s] = x
+    f = x.flatten(1, 2).permute(0, 2, 1)
+    lg = F.linear(f, hctr_ref._t(sd, "linear.weight").double(), hctr_ref._t(sd, "linear.bias").double())
+    return lg.permute(1, 0, 2).contiguous()
+
+
+@pytest.mark.parametrize("seed,nc,B,W", ex.all_cases())
+def test_oracle_is_exact(seed, nc, B, W):
+    sd = ex.cached_state_dict(nc, seed)
+    x, widths = ex.case_input(seed, B, W)
+    assert x.shape == (B, 1, 128, W) and _is_int(torch.from_numpy(x)) and x.min() >= -1 and x.max() <= 2
+    if widths is not None:
+        for b, wi in enumerate(widths):
+            assert (x[b, 0, :, wi:] == x[b, 0, :, wi - 1:wi]).all()
+    t_fused, t_unfused, t_plain = {}, {}, {}
+    lg = hctr_ref.forward_f16(sd, x, t_fused, fused_se=True)
+    lg_u = hctr_ref.forward_f16(sd, x, t_unfused, fused_se=False)
+    lg_p = hctr_ref.forward(sd, x, t_plain)
+    rec = {k: {} for k in ("pre", "tsum", "ysum", "presig", "presig32", "mean", "taps")}
+    lg_d = _forward_f64(sd, x, rec)
+    # ---- the three formulations and the float64 run agree bit for bit, logits and every common tap
+    assert torch.equal(lg, lg_u) and torch.equal(lg, lg_p) and torch.equal(lg.double(), lg_d)
+    for k, v in t_fused.items():
+        assert torch.equal(v, t_unfused[k]), k
+        assert torch.equal(v.double(), rec["taps"][k]), k
+        if k in t_plain:
+            assert torch.equal(v, t_plain[k]), k
+    assert set(t_plain) <= set(t_fused)
+    # ---- every stored value is an integer that fp16 holds; every scale is exactly 0.5 or 1.0, in the planted pattern
+    biggest = 0.0
+    for k, v in t_fused.items():
+        if k.endswith(".scale"):
+            want = np.where(ex.se_pattern(seed, "cnn." + k[:-6] + ".se", v.shape[1]), 1.0, 0.5).astype(np.float32)
+            assert np.array_equal(v.numpy(), np.broadcast_to(want, v.shape)), k
+            continue
+        assert _is_int(v), k
+        biggest = max(biggest, float(v.abs().max()))
+        assert float(v.abs().max()) <= F16_EXACT, (k, float(v.abs().max()))
+    # ---- every sum is exact in fp32 in any order: a conv channel has at most two weights of total magnitude 2 (the head
+    #      three of magnitude 1, test_fold_returns_the_intended_integers), so every partial sum of a conv is bounded by
+    #      2 * 2048 + |bias|; the SE statistics add up to H*W values of t or of conv2's output per image and channel, and
+    #      se_premean doubles them (conv2's weight) before it divides
+    assert max(rec["pre"].values()) < F32_EXACT
+    assert 2 * F16_EXACT + 3 < F32_EXACT and 3 * F16_EXACT + 3 < F32_EXACT
+    assert 2 * max(rec["tsum"].values()) < F32_EXACT, max(rec["tsum"].values())
+    assert max(rec["ysum"].values()) < F32_EXACT
+    assert float(lg.abs().max()) < F32_EXACT
+    # ---- SE: the pre-sigmoid value is exactly 0 or at least 40, in float64 and as the three fp32 runs compute it (an
+    #      engine's differs from those by the rounding of the means and of their sum, a relative 1e-5 at most)
+    for s, i in BLOCKS:
+        nm = "block%d.%d" % (s, i)
+        for v in (rec["presig"][nm], rec["presig32"][nm]):
+            assert bool(((v == 0) | (v >= 40.0)).all()), (nm, float(v[v != 0].min()))
+        # the engine's mean (bias + fp32(total) / fp32(H*W), total an exact integer) is within 2 fp32 ulp of the float64
+        # mean: the reasoning behind the bound that test_gpu_exact.py::test_se_means_exact asserts, checked here
+        H = rec["taps"][nm + ".conv2"].shape[2]
+        bias = torch.from_numpy(sd["cnn." + nm + ".bn2.bias"])
+        tot = (rec["taps"][nm + ".conv2"] - bias.double()[None, :, None, None]).sum(dim=(2, 3))
+        assert float(tot.abs().max()) < F32_EXACT
+        emu = bias[None, :] + tot.float() / (torch.tensor(float(H)) * torch.tensor(float(W)))
+        ref = rec["mean"][nm]
+        ulp = np.spacing(np.abs(ref.numpy()).astype(np.float32)).astype(np.float64)
+        assert (np.abs(emu.double().numpy() - ref.numpy()) <= 2 * ulp).all(), nm
+    # ---- the head input is busy, the logits are varied, and the row maximum is tied exactly in some columns
+    srt = np.sort(lg.numpy(), axis=2)
+    tied = srt[:, :, -1] == srt[:, :, -2]
+    print("case seed %d C %d B %d W %d: largest stored |v| %d, head input nonzero %.2f, distinct logits %d, "
+          "columns with a tied maximum %.2f" % (seed, nc, B, W, biggest, float((t_fused["stage4"] != 0).float().mean()),
+                                                len(np.unique(lg.numpy())), float(tied.mean())))
+    assert tied.any()
+    assert float((t_fused["stage4"] != 0).float().mean()) >= 0.3
