@@ -1,8 +1,12 @@
 """Child process of test_gpu_exact.py::test_kernel_families: the engine, under whatever HCTR_* kernel-selection
 variables its environment sets (they are read once per process), against the oracle on the exact-arithmetic checkpoint
-(tests/exact_ckpt.py) at three widths. Logits, every readable activation and the greedy labels must equal the oracle's
-bit for bit; with HCTR_WS_ALIAS=1 the stages share their buffers, so only logits and labels are compared. With
-HCTR_FUSE_SE=0 the SE statistics reader has nothing to read and must fail with its own message.
+(tests/exact_ckpt.py) at three widths, and on one keyed case (three contrasting lines whose SE scale patterns differ
+from line to line: a scale from another line shows). Logits, every readable activation and the greedy labels must equal
+the oracle's bit for bit, in the keyed case the SE scales too; with HCTR_WS_ALIAS=1 the stages share their buffers, so
+only logits, scales and labels are compared. With HCTR_FUSE_SE=0 the SE statistics reader has nothing to read and must
+fail with its own message.
+With the argument "passes" (test_keyed_lines_in_several_passes): the five-line keyed case in contexts whose passes hold
+fewer than five lines, in f16 and in f16x3.
 Prints every difference (first differing element of each array) and exits with 1 if there is one."""
 import importlib
 import os
@@ -36,8 +40,40 @@ def main():
         for d in diffs:
             print("  " + d, flush=True)
         failed = failed or bool(diffs)
+    seed, nc, B, W = ex.KEYED_CHILD_CASE
+    x, widths, logits, taps = ex.keyed_oracle_case(seed, nc, B, W)
+    model = pkg.hctr_model(nc).cuda(0)
+    model.load_state_dict(ex.keyed_state_dict(nc, seed, B, W))
+    diffs = ex.engine_differences(model, x, logits, taps, with_taps=with_taps,
+                                  with_scales=os.environ.get("HCTR_FUSE_SE", "") != "0")
+    print("keyed, seed %d, %d classes, %d lines x %d columns: %s" % (seed, nc, B, W, "equal" if not diffs else "DIFFERENT"),
+          flush=True)
+    for d in diffs:
+        print("  " + d, flush=True)
+    return 1 if failed or diffs else 0
+
+
+def several_passes():
+    """HCTR_MAX_COLS (read when a context is created) of three lines' columns: the five lines run as 3 + 2"""
+    import exact_ckpt as ex
+    pkg = importlib.import_module("handwritten-chinese-ocr-samples_amd")
+    seed, nc, B, W = ex.KEYED_PASSES_CASE
+    x, widths, logits, taps = ex.keyed_oracle_case(seed, nc, B, W)
+    failed = False
+    for precision, cols in (("f16", 3 * W), ("f16x3", 9 * W)):
+        os.environ["HCTR_MAX_COLS"] = str(cols)
+        model = pkg.hctr_model(nc, precision=precision).cuda(0)
+        model.load_state_dict(ex.keyed_state_dict(nc, seed, B, W))
+        n = model.lines_per_pass(B, W)
+        assert 0 < n < B and B % n != 0, (precision, cols, n)
+        diffs = ex.engine_differences(model, x, logits, taps, last=B - (B - 1) // n * n, with_scales=True)
+        del model
+        print("keyed, %s, passes of %d of %d lines: %s" % (precision, n, B, "equal" if not diffs else "DIFFERENT"), flush=True)
+        for d in diffs:
+            print("  " + d, flush=True)
+        failed = failed or bool(diffs)
     return 1 if failed else 0
 
 
 if __name__ == "__main__":
-    sys.exit(main())
+    sys.exit(several_passes() if sys.argv[1:] == ["passes"] else main())

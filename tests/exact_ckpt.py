@@ -25,6 +25,17 @@ The construction (keys and shapes: the reference checkpoint schema, from synth.c
                 hash-chosen half of the channels: the pre-sigmoid value there is 64 * sum_k |s_k| (sigmoid == 1.0f in
                 fp32 from about 17 up) and exactly 0 elsewhere (sigmoid == 0.5): a per-block, non-periodic 0.5 / 1.0
                 pattern, so that a scale taken from the wrong channel or block shows
+  SE, keyed     (keyed_state_dict: a variant per case (seed, B, W); only fc.0 / fc.2 differ) the pattern above is the
+                same for every line of a batch, so a scale taken from another LINE would equal the right one. Here
+                units 0 / 1 stay +-sum of the means of the channels c % 4 == 0 (gain 64), and units 2+2j / 3+2j are
+                relu(+d_j) / relu(-d_j) of three sums d_j = u * |mean_p| - v * |mean_q| (1 <= u, v <= 3; no bias, so
+                the sign comes from the line). fc.2 puts each channel into one of eight sets - always 1.0, always 0.5,
+                1.0 iff d_j > 0, 1.0 iff d_j < 0 - four channels of each in every 32-channel group, hashed per block.
+                The images are contrasting lines (KEYED_VALUES), and keyed_se searches p, q, u, v block by block in
+                forward order on the oracle, so that the signs of d_0..d_2 tell every line of the batch from every
+                other one in every block, |d_j| is at least 1000 worst-case fp32 summation errors on every line and
+                gain_j * |d_j| >= 80 (gain_j a power of two): every scale is still exactly 0.5 or 1.0, now in a pattern
+                of the line's own, and a scale, mean or tile of another line is a mismatch of at least 0.5
   head          rows with three +-1 entries and integer biases; the rows of the lower half of the classes are repeated,
                 bias included, half the class count above: the row maximum of every column is then tied exactly,
                 between classes that lie in different parts of the head's class tiling (a very narrow image leaves
@@ -141,7 +152,11 @@ def make_exact_images(B, W, seed, widths=None):
     """float32 [B,1,128,W] with integer pixels in [-1, 2]. With ``widths`` the columns from a line's width onwards
     replicate its last valid column (NormalizePAD's rule, utils/dataset.py:83-93)."""
     x = (_ints(seed, "images/%d/%d" % (B, W), B * synth.IMG_H * W, 4) - 1).astype(np.float32)
-    x = x.reshape(B, 1, synth.IMG_H, W)
+    return _replicate_pad(x.reshape(B, 1, synth.IMG_H, W), widths)
+
+
+def _replicate_pad(x, widths):
+    W = x.shape[3]
     if widths is not None:
         for i, wi in enumerate(widths):
             wi = int(wi)
@@ -211,6 +226,219 @@ def cached_state_dict(num_classes, seed):
     return _SD_CACHE[(num_classes, seed)]
 
 
+# ---- the keyed variant: SE scales that depend on the LINE (module docstring, "SE, keyed") ----
+KEYED_VALUES = ((-1, 0, 1, 2), (0, 1), (-1, 0), (1, 2), (-1, 2))    # pixel values of line b % 5: contrasting lines
+KEYED_UNITS = 3                # sign-keyed sums d_0..d_2, in hidden units 2+2j (relu(+d_j)) and 3+2j (relu(-d_j))
+KEYED_POOL = 64                # channels the search draws the two channels of a d_j from
+KEYED_MAXW = 3                 # |a_c| <= 3
+KEYED_MARGIN = 1000.0          # |d| >= KEYED_MARGIN * C * 2^-24 * sum|a_c||mean_c|
+PRESIG_FLOOR = 40.0            # a scale of 1.0 has a pre-sigmoid value of at least this
+SET_ALWAYS, SET_NEVER = 0, 1   # channel sets: 0 always 1.0, 1 always 0.5, 2+2j: 1.0 iff d_j > 0, 3+2j: 1.0 iff d_j < 0
+
+
+def make_keyed_images(B, W, seed, widths=None):
+    """float32 [B,1,128,W] of integer pixels within [-1, 2]; line b draws from KEYED_VALUES[b % 5] only, so that the
+    lines' channel means differ by much more than noise. ``widths`` as make_exact_images."""
+    x = np.empty((B, 1, synth.IMG_H, W), np.float32)
+    for b in range(B):
+        vals = np.asarray(KEYED_VALUES[b % len(KEYED_VALUES)], np.float32)
+        x[b, 0] = vals[_ints(seed, "keyed/%d/%d/%d" % (B, W, b), synth.IMG_H * W, len(vals))].reshape(synth.IMG_H, W)
+    return _replicate_pad(x, widths)
+
+
+def keyed_sets(seed, sk, c):
+    """int [c]: the channel set (SET_ALWAYS, SET_NEVER, 2+2j, 3+2j) of every channel of SE layer ``sk``. Every 32-channel
+    group holds four channels of each of the eight sets, in a hash-chosen order."""
+    out = np.empty((c,), np.int64)
+    for g in range(c // 32):
+        order = np.argsort(_ints(seed, "%s/keyed/%d" % (sk, g), 32, 1 << 30), kind="stable")
+        out[g * 32 + order] = np.repeat(np.arange(2 + 2 * KEYED_UNITS), 32 // (2 + 2 * KEYED_UNITS))
+    return out
+
+
+def keyed_se_weights(seed, sk, mean):
+    """(fc.0 weight, fc.2 weight, info) of SE layer ``sk`` for the float64 channel means ``mean`` [B, C] that the lines
+    of the case have there. Each d_j = u * |mean_p| - v * |mean_q| (a channel's mean has the sign of its conv2 weight
+    on every line) takes two channels p, q of a hash-chosen pool and 1 <= u, v <= KEYED_MAXW, picked so that the signs
+    of d_0..d_2 tell every line of the batch from every other one, each d_j changes sign within the batch, and |d_j|
+    keeps the summation-error margin on every line; among those, the widest relative margin. info: "sets" [C],
+    "a" [3, C], "gain" [3], "d" [B, 3] (float64), "pattern" [B, C] bool (the scales that are 1.0)."""
+    B, C = mean.shape
+    r = C // 16
+    pool = np.argsort(_ints(seed, sk + "/keyed/pool", C, 1 << 30), kind="stable")
+    pool = pool[np.abs(mean[:, pool]).min(axis=0) > 0][:KEYED_POOL]
+    sgn = np.sign(mean[:, pool]).max(axis=0) + np.sign(mean[:, pool]).min(axis=0)        # +-2: one sign on every line
+    pool, sgn = pool[sgn != 0], np.sign(sgn[sgn != 0])
+    A = np.abs(mean[:, pool])                                                           # [B, P]
+    uv = np.arange(1, KEYED_MAXW + 1, dtype=np.float64)
+    d = uv[None, None, None, :, None] * A[:, :, None, None, None] - uv[None, None, None, None, :] * A[:, None, :, None, None]
+    mag = uv[None, None, None, :, None] * A[:, :, None, None, None] + uv[None, None, None, None, :] * A[:, None, :, None, None]
+    shape = d.shape[1:]
+    d, mag = d.reshape(B, -1), mag.reshape(B, -1)
+    rel = (np.abs(d) / mag).min(axis=0)
+    # (twice the margin the host test asks for: that test states it on the fp32 means, these are the float64 ones)
+    ok = (rel >= 2 * KEYED_MARGIN * C * 2.0 ** -24) & (np.abs(d).min(axis=0) >= 2.0 ** -10)
+    bits = d > 0
+    pairs = [(i, j) for i in range(B) for j in range(i + 1, B)]
+    apart, taken = {pq: False for pq in pairs}, []
+    w0 = np.zeros((r, C), np.float32)
+    w0[0, 0::4], w0[1, 0::4] = 1.0, -1.0
+    sets = keyed_sets(seed, sk, C)
+    w2 = np.zeros((C, r), np.float32)
+    w2[sets == SET_ALWAYS, :2] = SE_GAIN
+    info = {"sets": sets, "a": np.zeros((KEYED_UNITS, C)), "gain": np.zeros((KEYED_UNITS,)), "d": np.zeros((B, KEYED_UNITS))}
+    for j in range(KEYED_UNITS):
+        new, every = np.zeros(d.shape[1]), np.zeros(d.shape[1])        # pairs of lines a candidate newly separates / separates
+        for p, q in pairs:
+            every += bits[p] != bits[q]
+            if not apart[(p, q)]:
+                new += bits[p] != bits[q]
+        for t in taken:                                # no split (or its mirror image) twice
+            same = (bits == bits[:, t:t + 1]).all(axis=0) | (bits != bits[:, t:t + 1]).all(axis=0)
+            every[same] = 0
+        score = np.where(ok & (every > 0), new * 1000.0 + rel, -1.0)
+        k = int(score.argmax())
+        if score[k] < 0:
+            raise RuntimeError("%s: no channel pair gives d_%d a sign change with the required margin" % (sk, j))
+        taken.append(k)
+        p, q, iu, iv = np.unravel_index(k, shape)
+        info["a"][j, pool[p]] += uv[iu] * sgn[p]
+        info["a"][j, pool[q]] -= uv[iv] * sgn[q]
+        info["d"][:, j] = d[:, k]
+        gain = max(SE_GAIN, 2.0 ** np.ceil(np.log2(2 * PRESIG_FLOOR / np.abs(d[:, k]).min())))
+        info["gain"][j] = gain
+        w0[2 + 2 * j], w0[3 + 2 * j] = info["a"][j], -info["a"][j]
+        w2[sets == 2 + 2 * j, 2 + 2 * j] = gain
+        w2[sets == 3 + 2 * j, 3 + 2 * j] = gain
+        for pq in pairs:
+            apart[pq] = apart[pq] or bool(bits[pq[0], k] != bits[pq[1], k])
+    if not all(apart.values()):
+        raise RuntimeError("%s: the signs of d_0..d_%d do not tell every pair of lines apart" % (sk, KEYED_UNITS - 1))
+    pat = np.zeros((B, C), bool)
+    pat[:, sets == SET_ALWAYS] = True
+    for j in range(KEYED_UNITS):
+        pat[:, sets == 2 + 2 * j] = (info["d"][:, j] > 0)[:, None]
+        pat[:, sets == 3 + 2 * j] = (info["d"][:, j] < 0)[:, None]
+    info["pattern"] = pat
+    return w0, w2, info
+
+
+def keyed_cases():
+    """(seed, num_classes, B, W) of the keyed cases: three contrasting ragged lines at three widths, five at one"""
+    shapes = ((3, 17), (3, 33), (3, 65), (5, 33))
+    return [(SEEDS[i % 3], CLASS_COUNTS[i % 2], B, W) for i, (B, W) in enumerate(shapes)]
+
+
+KEYED_CHILD_CASE = keyed_cases()[1]            # B = 3, W = 33: what every kernel family runs
+KEYED_PASSES_CASE = keyed_cases()[3]           # B = 5, W = 33: what runs in several passes
+
+
+def keyed_input(seed, B, W):
+    """(images, widths) of a keyed case (always ragged)"""
+    widths = ragged_widths(B, W)
+    return make_keyed_images(B, W, seed, widths), widths
+
+
+_KEYED_CACHE = {}
+
+
+_FOLD_CACHE = {}
+
+
+def _conv_folded(sd, x, ck, bk, relu, pad, pool=False, half_weights=True):
+    """hctr_ref._conv_f16 with the folded weights kept (the fold of a 512-channel layer costs more than its conv here)"""
+    import torch.nn.functional as F
+    from oracle import hctr_ref as R
+    key = (id(sd[ck + ".weight"]), id(sd[bk + ".bias"]), half_weights)
+    if key not in _FOLD_CACHE:
+        _FOLD_CACHE[key] = R._fold(sd, ck, bk, half_weights) + (sd[ck + ".weight"], sd[bk + ".bias"])   # (ids stay taken)
+    w, b = _FOLD_CACHE[key][:2]
+    y = F.conv2d(x, w, b, stride=1, padding=pad)
+    z = F.relu(y) if relu else y
+    return y, R._r16(R._pool(z) if pool else z)
+
+
+def oracle_from(sd, x, first=None, se=None, entries=None):
+    """The f16 oracle (oracle/hctr_ref.py forward_f16, fused-SE form, out of its own pieces) from block number ``first``
+    of BLOCK_NAMES on. ``x``: that block's input (a torch tensor), or the images with first None. ``se(n, name, y32)``
+    may return the scales [B, C] that block n applies instead of those of ``sd``'s SE weights; ``entries`` (a list)
+    receives every block's input. Returns the logits [W, B, C]. tests/test_exact_ckpt_host.py checks that, left
+    alone, it gives forward_f16's bits."""
+    import torch
+    import torch.nn.functional as F
+    from oracle import hctr_ref as R
+    with torch.no_grad():
+        if first is None:
+            _, x = _conv_folded(sd, x, "cnn.conv0_1", "cnn.bn0_1", True, 1, half_weights=False)
+            _, x = _conv_folded(sd, x, "cnn.conv0_2", "cnn.bn0_2", True, 1, pool=True)
+            first = 0
+        n = -1
+        for s, nb in enumerate(R.STAGE_BLOCKS, start=1):
+            for i in range(nb):
+                n += 1
+                if n < first:
+                    continue
+                if entries is not None:
+                    entries.append(x)
+                p = "cnn.block%d.%d" % (s, i)
+                _, t = _conv_folded(sd, x, p + ".conv1", p + ".bn1", True, 1)
+                y32, _ = _conv_folded(sd, t, p + ".conv2", p + ".bn2", False, 1)
+                sc = se(n, p[4:], y32) if se is not None else None
+                if sc is None:
+                    sc = F.relu(F.linear(y32.mean(dim=(2, 3)), R._t(sd, p + ".se.fc.0.weight")))
+                    sc = torch.sigmoid(F.linear(sc, R._t(sd, p + ".se.fc.2.weight")))
+                r = x
+                if (p + ".downsample.0.weight") in sd:
+                    _, r = _conv_folded(sd, x, p + ".downsample.0", p + ".downsample.1", False, 0)
+                x = R._r16(F.relu(y32 * sc[:, :, None, None] + r))
+            if n >= first:
+                _, x = _conv_folded(sd, x, "cnn.conv%d" % s, "cnn.bn%d" % s, True, 1, pool=True)
+        x = F.linear(x.flatten(1, 2).permute(0, 2, 1), R._r16(R._t(sd, "linear.weight")), R._t(sd, "linear.bias"))
+        return x.permute(1, 0, 2).contiguous()
+
+
+def keyed_se(seed, B, W):
+    """({SE key: array} of the keyed case's fc.0 / fc.2 weights, {block name: info of keyed_se_weights}). Found block by
+    block in forward order on the f16 oracle: the means of a block depend on the scales of the blocks before it only."""
+    if (seed, B, W) in _KEYED_CACHE:
+        return _KEYED_CACHE[(seed, B, W)]
+    import torch
+    import torch.nn.functional as F
+    se, infos = {}, {}
+
+    def search(n, name, y32):
+        w0, w2, infos[name] = keyed_se_weights(seed, "cnn." + name + ".se", y32.double().mean(dim=(2, 3)).numpy())
+        se["cnn." + name + ".se.fc.0.weight"], se["cnn." + name + ".se.fc.2.weight"] = w0, w2
+        hid = F.relu(F.linear(y32.mean(dim=(2, 3)), torch.from_numpy(w0)))
+        return torch.sigmoid(F.linear(hid, torch.from_numpy(w2)))
+
+    oracle_from(cached_state_dict(2, seed), torch.from_numpy(keyed_input(seed, B, W)[0]), se=search)
+    _KEYED_CACHE[(seed, B, W)] = (se, infos)
+    return se, infos
+
+
+def keyed_state_dict(num_classes, seed, B, W):
+    """cached_state_dict with the SE weights of the keyed case (seed, B, W); every other entry is the same array"""
+    key = ("keyed", num_classes, seed, B, W)
+    if key not in _SD_CACHE:
+        sd = dict(cached_state_dict(num_classes, seed))
+        sd.update(keyed_se(seed, B, W)[0])
+        _SD_CACHE[key] = sd
+    return _SD_CACHE[key]
+
+
+def keyed_oracle_case(seed, nc, B, W):
+    """oracle_case for a keyed case: (images, widths, logits [W,B,C], taps as numpy arrays)"""
+    from oracle import hctr_ref
+    key = ("oracle", seed, nc, B, W)
+    if key not in _KEYED_CACHE:
+        x, widths = keyed_input(seed, B, W)
+        taps = {}
+        logits = hctr_ref.forward_f16(keyed_state_dict(nc, seed, B, W), x, taps).numpy()
+        _KEYED_CACHE[key] = (x, widths, logits, {k: v.numpy() for k, v in taps.items()})
+    return _KEYED_CACHE[key]
+
+
 # ---- comparing an engine with the oracle (tests/test_gpu_exact.py, tests/exact_child.py) ----
 # What every readable buffer holds after a full forward (three rotating block buffers per stage, two in stage 4:
 # csrc/engine.cpp run_forward), and so which launch it pins:
@@ -255,23 +483,34 @@ def greedy_labels(logits):
     return ctc_ref.CtcCodecRef(synth.characters(logits.shape[2] - 2)).greedy_indices(logits)
 
 
-def engine_differences(model, x, logits, taps, with_taps=True, with_greedy=True):
+def engine_differences(model, x, logits, taps, with_taps=True, with_greedy=True, widths=None, last=None,
+                       with_scales=False):
     """Every way in which ``model`` (an hctr_model on a GPU, any precision mode) differs from the oracle's results for
-    the images ``x``: logits, every readable activation after that forward, the greedy labels. [] = bit for bit."""
+    the images ``x``: logits, every readable activation after that forward, the greedy labels. [] = bit for bit.
+    ``widths``: passed on to the engine. ``last``: the number of lines in the last internal pass of the call, when it
+    ran in several (the buffers hold that pass: the last ``last`` lines). ``with_scales``: also the SE scales of every
+    block (debug_se) against the oracle's, per line."""
     out = []
     B = x.shape[0]
-    d = first_difference("logits", model(x), logits, ("column", "line", "class"))
+    n = B if last is None else last
+    d = first_difference("logits", model(x, widths=widths), logits, ("column", "line", "class"))
     if d:
         out.append(d)
     if with_taps:
         for buf, tap in READABLE:
-            d = first_difference("%s (buffer %s)" % (tap, buf), model.debug_activation(buf, B), taps[tap],
+            d = first_difference("%s (buffer %s)" % (tap, buf), model.debug_activation(buf, n), taps[tap][B - n:],
                                  ("line", "channel", "row", "column"))
             if d:
                 out.append(d)
+    if with_scales:
+        for nm in BLOCK_NAMES:
+            d = first_difference(nm + " scales", model.debug_se(nm, n)[1], taps[nm + ".scale"][B - n:], ("line", "channel"))
+            if d:
+                out.append(d)
     if with_greedy:
-        got, want = model.greedy(x), greedy_labels(logits)
+        got, want = model.greedy(x, widths=widths), greedy_labels(logits)
         for b in range(B):
             if not np.array_equal(got[b], want[b]):
-                out.append("greedy labels of line %d: engine %s, oracle %s" % (b, list(got[b]), list(want[b])))
+                out.append("greedy labels of line %d: engine %s, oracle %s" % (b, [int(v) for v in got[b]],
+                                                                               [int(v) for v in want[b]]))
     return out

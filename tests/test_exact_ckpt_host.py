@@ -113,8 +113,19 @@ def _forward_f64(sd, x, rec):
 
 @pytest.mark.parametrize("seed,nc,B,W", ex.all_cases())
 def test_oracle_is_exact(seed, nc, B, W):
-    sd = ex.cached_state_dict(nc, seed)
     x, widths = ex.case_input(seed, B, W)
+
+    def planted(nm, shape):
+        want = np.where(ex.se_pattern(seed, "cnn." + nm + ".se", shape[1]), 1.0, 0.5).astype(np.float32)
+        return np.broadcast_to(want, shape)
+
+    _check_exact(ex.cached_state_dict(nc, seed), x, widths, planted, "case seed %d C %d B %d W %d" % (seed, nc, B, W))
+
+
+def _check_exact(sd, x, widths, planted, label):
+    """The exactness conditions of checkpoint ``sd`` on the images ``x``; ``planted(block, shape)`` is the scale pattern
+    the checkpoint was built to give. Returns (logits, the fused run's taps, the float64 run's records)."""
+    B, W = x.shape[0], x.shape[3]
     assert x.shape == (B, 1, 128, W) and _is_int(torch.from_numpy(x)) and x.min() >= -1 and x.max() <= 2
     if widths is not None:
         for b, wi in enumerate(widths):
@@ -137,8 +148,7 @@ def test_oracle_is_exact(seed, nc, B, W):
     biggest = 0.0
     for k, v in t_fused.items():
         if k.endswith(".scale"):
-            want = np.where(ex.se_pattern(seed, "cnn." + k[:-6] + ".se", v.shape[1]), 1.0, 0.5).astype(np.float32)
-            assert np.array_equal(v.numpy(), np.broadcast_to(want, v.shape)), k
+            assert np.array_equal(v.numpy(), planted(k[:-6], v.shape)), k
             continue
         assert _is_int(v), k
         biggest = max(biggest, float(v.abs().max()))
@@ -171,8 +181,117 @@ def test_oracle_is_exact(seed, nc, B, W):
     # ---- the head input is busy, the logits are varied, and the row maximum is tied exactly in some columns
     srt = np.sort(lg.numpy(), axis=2)
     tied = srt[:, :, -1] == srt[:, :, -2]
-    print("case seed %d C %d B %d W %d: largest stored |v| %d, head input nonzero %.2f, distinct logits %d, "
-          "columns with a tied maximum %.2f" % (seed, nc, B, W, biggest, float((t_fused["stage4"] != 0).float().mean()),
+    print("%s: largest stored |v| %d, head input nonzero %.2f, distinct logits %d, "
+          "columns with a tied maximum %.2f" % (label, biggest, float((t_fused["stage4"] != 0).float().mean()),
                                                 len(np.unique(lg.numpy())), float(tied.mean())))
     assert tied.any()
     assert float((t_fused["stage4"] != 0).float().mean()) >= 0.3
+    return lg, t_fused, rec
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the keyed variant (tests/exact_ckpt.py, "SE, keyed"): scales that depend on the line
+# ------------------------------------------------------------------------------------------------------------------
+def test_keyed_checkpoint_changes_the_se_weights_only():
+    """Every entry of a keyed checkpoint but the SE weights IS the unkeyed checkpoint's array; every 32-channel group
+    of every SE layer holds channels of all eight sets; |a_c| <= 3 on two channels per keyed sum."""
+    seed, nc, B, W = ex.KEYED_CHILD_CASE
+    base, keyed = ex.cached_state_dict(nc, seed), ex.keyed_state_dict(nc, seed, B, W)
+    assert set(base) == set(keyed)
+    for k in base:
+        if ".se.fc." in k:
+            assert keyed[k].shape == base[k].shape and keyed[k].dtype == base[k].dtype, k
+            assert not np.array_equal(keyed[k], base[k]), k
+        else:
+            assert keyed[k] is base[k], k
+    for sk, c in synth.se_specs():
+        sets = ex.keyed_sets(seed, sk, c)
+        for g in range(c // 32):
+            assert np.array_equal(np.bincount(sets[g * 32:(g + 1) * 32], minlength=8), np.full(8, 4)), (sk, g)
+        w0 = keyed[sk + ".fc.0.weight"]
+        assert np.array_equal(w0[2:8:2], -w0[3:8:2]) and not w0[8:].any()
+        assert (np.abs(w0[2:8]) <= ex.KEYED_MAXW).all() and ((w0[2:8] != 0).sum(axis=1) == 2).all(), sk
+        w2 = keyed[sk + ".fc.2.weight"]
+        for u in range(2, 8):                               # unit u gains the channels of set u alone
+            assert np.array_equal(w2[:, u] != 0, sets == u), (sk, u)
+        assert np.array_equal(w2[:, 0] != 0, sets == ex.SET_ALWAYS) and np.array_equal(w2[:, 0], w2[:, 1])
+
+
+@pytest.fixture(scope="module")
+def keyed_runs():
+    """per keyed case, made once: what _check_exact returns for it"""
+    cache = {}
+
+    def get(case):
+        if case not in cache:
+            seed, nc, B, W = case
+            x, widths = ex.keyed_input(seed, B, W)
+            infos = ex.keyed_se(seed, B, W)[1]
+            assert len({tuple(np.unique(x[b])) for b in range(B)}) == B          # contrasting lines
+            cache[case] = _check_exact(ex.keyed_state_dict(nc, seed, B, W), x, widths,
+                                       lambda nm, shape: np.where(infos[nm]["pattern"], np.float32(1.0), np.float32(0.5)),
+                                       "keyed case seed %d C %d B %d W %d" % case)
+        return cache[case]
+
+    yield get
+    cache.clear()
+
+
+@pytest.mark.parametrize("case", ex.keyed_cases(), ids=lambda c: "seed%d-C%d-B%d-W%d" % c)
+def test_keyed_oracle_is_exact_and_keeps_its_margins(keyed_runs, case):
+    """A keyed case meets every exactness condition of the unkeyed ones (formulations, magnitudes, scales exactly the
+    planted 0.5 / 1.0 - here a pattern per line), and for every block, line and keyed sum d: |d| is at least 1000
+    times the worst-case fp32 summation error C * 2^-24 * sum|a_c||mean_c|, and gain * |d| at least 40 - on the float64
+    means and on the fp32 means of the oracle. The engine's differently ordered sum of differently rounded means
+    (within 2 ulp each, test_oracle_is_exact) then cannot flip a sign or leave the saturated region."""
+    seed, nc, B, W = case
+    lg, taps, rec = keyed_runs(case)
+    sd = ex.keyed_state_dict(nc, seed, B, W)
+    infos = ex.keyed_se(seed, B, W)[1]
+    assert torch.equal(lg, torch.from_numpy(ex.keyed_oracle_case(*case)[2]))
+    worst_rel, worst_pre = np.inf, np.inf
+    for nm in ex.BLOCK_NAMES:
+        w0 = sd["cnn." + nm + ".se.fc.0.weight"].astype(np.float64)
+        w2 = sd["cnn." + nm + ".se.fc.2.weight"].astype(np.float64)
+        C = w0.shape[1]
+        for mean in (rec["mean"][nm].numpy(), taps[nm + ".conv2"].mean(dim=(2, 3)).double().numpy()):
+            for j in range(ex.KEYED_UNITS):
+                a, gain = w0[2 + 2 * j], w2[:, 2 + 2 * j].max()
+                d = mean @ a
+                err = C * 2.0 ** -24 * (np.abs(mean) @ np.abs(a))
+                assert (np.abs(d) >= ex.KEYED_MARGIN * err).all(), (nm, j, d.tolist(), err.tolist())
+                assert (gain * np.abs(d) >= ex.PRESIG_FLOOR).all(), (nm, j, gain, d.tolist())
+                assert (d > 0).any() and (d < 0).any(), (nm, j, "no sign change within the batch")
+                worst_rel = min(worst_rel, float((np.abs(d) / err).min()))
+                worst_pre = min(worst_pre, float(gain * np.abs(d).min()))
+    print("smallest |d| / summation error %.0f, smallest keyed pre-sigmoid value %.0f" % (worst_rel, worst_pre))
+
+
+@pytest.mark.parametrize("case", ex.keyed_cases(), ids=lambda c: "seed%d-C%d-B%d-W%d" % c)
+def test_keyed_lines_differ_and_a_wrong_line_shows(keyed_runs, case):
+    """Every pair of lines: in EVERY block the oracle's scale vectors differ in at least 8 channels, at least one of
+    them in each 32-channel group. And with line b's scales replaced by those of line (b + r) % B in ONE block, for every
+    block and every r = 1..B-1 (all ordered pairs of lines), the logits of every line b change: no (block, pair of
+    lines) is left for which a scale taken from the other line would go unseen."""
+    seed, nc, B, W = case
+    lg, taps, _ = keyed_runs(case)
+    for nm in ex.BLOCK_NAMES:
+        sc = taps[nm + ".scale"].numpy()
+        for b in range(B):
+            for b2 in range(b + 1, B):
+                diff = sc[b] != sc[b2]
+                assert diff.sum() >= 8, (nm, b, b2, int(diff.sum()))
+                assert diff.reshape(-1, 32).any(axis=1).all(), (nm, b, b2)
+    sd = ex.keyed_state_dict(nc, seed, B, W)
+    entries = []
+    again = ex.oracle_from(sd, torch.from_numpy(ex.keyed_input(seed, B, W)[0]), entries=entries)
+    assert torch.equal(again, lg) and len(entries) == len(ex.BLOCK_NAMES)        # the harness is the oracle
+    unseen = []
+    for n, nm in enumerate(ex.BLOCK_NAMES):
+        # one run of B - 1 copies of the batch: in copy r - 1, line b gets line (b + r) % B's scales
+        wrong = torch.cat([torch.roll(taps[nm + ".scale"], -r, 0) for r in range(1, B)])
+        got = ex.oracle_from(sd, entries[n].repeat(B - 1, 1, 1, 1), first=n,
+                             se=lambda k, name, y32: wrong if k == n else None)
+        unseen += [(nm, b, (b + r) % B) for r in range(1, B) for b in range(B)
+                   if torch.equal(got[:, (r - 1) * B + b], lg[:, b])]
+    assert not unseen, unseen

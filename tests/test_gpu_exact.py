@@ -6,7 +6,7 @@ oracle's three formulations and a float64 run then agree bit for bit. The result
 on a rounding point or on the f16x3 split, so the engine has to EQUAL the oracle: on the logits, on every activation
 buffer that can be read back, on the greedy labels, in every precision mode and kernel family. A wrong halo column,
 channel group, tap, pad column, pooled row, residual or scale channel is a mismatch of at least 0.5, however small its
-share of the logits. No assertion here has a tolerance, except the three derived bounds on the SE statistics of the
+share of the logits; in the keyed cases, whose scale patterns differ from line to line, so is a wrong LINE. No assertion here has a tolerance, except the three derived bounds on the SE statistics of the
 synthetic (inexact) checkpoint at the end.
 """
 import os
@@ -93,6 +93,42 @@ def test_kernel_families(env):
     e = dict(os.environ)
     e.update(env)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "exact_child.py")], env=e, capture_output=True,
+                       text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The keyed checkpoints (tests/exact_ckpt.py, "SE, keyed"): every line of a batch has its own 0.5 / 1.0 scale pattern
+# in every block, so a scale, mean or tile taken from another LINE is a mismatch of at least 0.5 as well
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("precision", ["f16", "f16x3", "auto"])
+@pytest.mark.parametrize("case", ex.keyed_cases(), ids=_ids)
+def test_keyed_lines(pkg, case, precision):
+    """Logits, all sixteen readable buffers, the SE scales of every block (per line) and the greedy labels equal the
+    oracle's on contrasting ragged lines whose scale patterns differ from line to line; and the same batch with garbage
+    in the padding and widths= given (the engine's own replicate padding) gives the same logits. Default kernel family:
+    this pins the line index of the fused conv2+SE epilogue (every block buffer) and of the fused downsample path
+    (p1.1, and through the stage outputs the first blocks of stages 2 and 3)."""
+    seed, nc, B, W = case
+    x, widths, logits, taps = ex.keyed_oracle_case(*case)
+    model = pkg.hctr_model(nc, precision=precision).cuda(0)
+    model.load_state_dict(ex.keyed_state_dict(nc, seed, B, W))
+    diffs = ex.engine_differences(model.eval(), x, logits, taps, with_scales=True)
+    assert not diffs, "\n".join(diffs)
+    if precision == "auto":
+        assert model.last_guard()["flagged"] == B
+    y = x.copy()
+    for b, wi in enumerate(widths):
+        y[b, 0, :, wi:] = 7.0
+    d = ex.first_difference("logits with widths=", model(y, widths=widths), logits, ("column", "line", "class"))
+    assert d is None, d
+
+
+def test_keyed_lines_in_several_passes():
+    """The five-line keyed case in a context whose passes hold fewer lines (tests/exact_child.py passes): the lines of a
+    later pass, at b0 + b of the caller's batch, against the ORACLE - not against another run of the engine."""
+    from conftest import ROOT
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "exact_child.py"), "passes"], capture_output=True,
                        text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
 
