@@ -169,6 +169,11 @@ SIGNATURES = [
     ("hctr_ctc_loss_logits_grad", _I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _I]),
     ("hctr_ctc_align", _I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_ctc_align_logits", _I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    # ..., queries, query_lengths, Q, input_lengths, contain_logp, seg_logp, seg_start, seg_end
+    ("hctr_spot", _I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_spot_logits", _I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_spot_automaton", _I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
+    ("hctr_spot_chunk_classes", _I, [_I, _I]),
     ("hctr_recognize", _I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_recognize_logits", _I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_edit_distance", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP]),

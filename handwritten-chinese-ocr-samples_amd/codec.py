@@ -220,6 +220,33 @@ class ctc_codec(object):
         rec = ctc.recognize_logits(self._context(), logits, on_dev)
         return self.labels_to_text(rec.label_lists()), rec
 
+    def encode_queries(self, queries):
+        """(concatenated int32 labels, int32 lengths) of keyword strings, as ``encode`` gives them - but a query must be
+        spelt in the vocabulary: a character outside it (``encode`` would make it <unknown>) or an empty query is a
+        ValueError."""
+        queries = list(queries)
+        for s in queries:
+            if not s:
+                raise ValueError("empty query")
+            for ch in s:
+                if ch not in self.dict or len(ch) != 1:
+                    raise ValueError("query %r: character %r is not in the vocabulary" % (s, ch))
+        return self.encode(queries)
+
+    def spot(self, preds, queries, input_lengths=None):
+        """Keyword spotting in ``preds`` (what ``decode`` takes; a CUDA tensor is read in place): ``queries`` are strings
+        of 1..32 characters of the vocabulary. Returns a ``ctc.Spotting``: per (line, query) the posterior probability
+        that the line's text contains the query and the best segment that reads it (include/hctr_hip.h
+        ``hctr_spot_logits``)."""
+        from . import ctc
+        logits, on_dev = self._as_logits(preds)
+        C = int(logits.shape[2])
+        if C != len(self.characters):
+            raise ValueError("logits have %d classes, codec has %d" % (C, len(self.characters)))
+        flat, ql = self.encode_queries(queries)
+        split = np.split(flat, np.cumsum(ql)[:-1])
+        return ctc.spot_logits(self._context(), logits, on_dev, split, input_lengths)
+
     def nbest(self, preds, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None, lm=None, lm_panelty=2.0,
               skip_search=False):
         """The ``n`` best texts of every line of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) with

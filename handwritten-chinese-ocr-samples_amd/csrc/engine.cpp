@@ -1331,6 +1331,240 @@ int ctc_image_call(hctr_ctx* c, const Batch& in, const CtcHost& h, size_t extra_
 }
 
 // ---------------------------------------------------------------------------------------------
+// keyword spotting (hctr_spot*): the queries' automata, the chunks of queries that share one emission pass, scratch
+// ---------------------------------------------------------------------------------------------
+// The KMP automaton of one query lifted to CTC (include/hctr_hip.h): states Z = 0, N_j = j, B_j = L - 1 + j, A = 2L - 1;
+// local slots 0 = blank, 1..nq = the distinct classes ascending, nq + 1 = rest, nq + 2 = the constant 1.
+struct SpotAuto {
+    int L = 0, nq = 0, maxdeg = 0;
+    std::vector<int32_t> cls, qslot, delta;       // [nq], [L], [L][nq]: delta(j, cls[i]) for j = 0..L-1
+    std::vector<int32_t> ptr, src, slot;          // in-edge CSR over the 2L states, a state's edges by (src, slot)
+    std::vector<uint64_t> mask;                   // [2L] the local slots a state sends to Z
+};
+
+void spot_automaton(const int32_t* q, int L, SpotAuto* a) {
+    a->L = L;
+    a->cls.assign(q, q + L);
+    std::sort(a->cls.begin(), a->cls.end());
+    a->cls.erase(std::unique(a->cls.begin(), a->cls.end()), a->cls.end());
+    const int nq = a->nq = (int)a->cls.size(), S = 2 * L, A = S - 1;
+    a->qslot.resize((size_t)L);
+    for (int j = 0; j < L; ++j)
+        a->qslot[(size_t)j] = 1 + (int32_t)(std::lower_bound(a->cls.begin(), a->cls.end(), q[j]) - a->cls.begin());
+    std::vector<int> border((size_t)L + 1, 0);    // border[k] = the longest proper border of q_1..q_k
+    for (int k = 2; k <= L; ++k) {
+        int m = border[(size_t)k - 1];
+        while (m > 0 && q[m] != q[k - 1]) m = border[(size_t)m];
+        border[(size_t)k] = q[m] == q[k - 1] ? m + 1 : 0;
+    }
+    a->delta.assign((size_t)L * nq, 0);
+    for (int j = 0; j < L; ++j)
+        for (int i = 0; i < nq; ++i) {
+            int m = j;
+            while (m > 0 && q[m] != a->cls[(size_t)i]) m = border[(size_t)m];
+            a->delta[(size_t)j * nq + i] = q[m] == a->cls[(size_t)i] ? m + 1 : 0;
+        }
+    std::vector<std::vector<std::pair<int, int>>> in((size_t)S);
+    a->mask.assign((size_t)S, 0);
+    const uint64_t rest = (uint64_t)1 << (nq + 1);
+    auto tgt = [&](int k) { return k == 0 ? 0 : k == L ? A : k; };
+    // out of a state with j characters matched on class slot i: to tgt(delta), or back to Z
+    auto on_class = [&](int s, int j, int i) {
+        const int d = a->delta[(size_t)j * nq + (i - 1)];
+        if (d) in[(size_t)tgt(d)].push_back({s, i});
+        else a->mask[(size_t)s] |= (uint64_t)1 << i;
+    };
+    a->mask[0] = rest | 1;                        // Z: the blank, rest and every class but q_1 stay
+    for (int i = 1; i <= nq; ++i) on_class(0, 0, i);
+    for (int j = 1; j < L; ++j) {                 // N_j: q_j repeats the character, the blank moves to B_j
+        const int own = a->qslot[(size_t)j - 1];
+        in[(size_t)j].push_back({j, own});
+        in[(size_t)L - 1 + j].push_back({j, 0});
+        a->mask[(size_t)j] = rest;
+        for (int i = 1; i <= nq; ++i)
+            if (i != own) on_class(j, j, i);
+    }
+    for (int j = 1; j < L; ++j) {                 // B_j: after a blank q_j is a new character too
+        const int s = L - 1 + j;
+        in[(size_t)s].push_back({s, 0});
+        a->mask[(size_t)s] = rest;
+        for (int i = 1; i <= nq; ++i) on_class(s, j, i);
+    }
+    in[(size_t)A].push_back({A, nq + 2});
+    a->ptr.assign((size_t)S + 1, 0);
+    a->src.clear(); a->slot.clear();
+    a->maxdeg = 0;
+    for (int s = 0; s < S; ++s) {
+        std::sort(in[(size_t)s].begin(), in[(size_t)s].end());
+        for (const auto& e : in[(size_t)s]) {
+            a->src.push_back(e.first);
+            a->slot.push_back(e.second);
+        }
+        a->ptr[(size_t)s + 1] = (int32_t)a->src.size();
+        a->maxdeg = std::max(a->maxdeg, (int)in[(size_t)s].size());
+    }
+}
+
+// classes (blank included) one chunk of queries may hold: HCTR_SPOT_CLASSES, else what keeps the emissions of `lines`
+// lines of W columns within 256 MB, held to [64, 1024]. A single query that exceeds it gets a chunk of its own.
+int spot_class_cap(int lines, int W) {
+    if (const char* e = getenv("HCTR_SPOT_CLASSES")) {
+        const int v = atoi(e);
+        if (v >= 2) return v;
+    }
+    const int64_t rows = std::max<int64_t>(1, (int64_t)std::max(lines, 1) * std::max(W, 1));
+    return (int)std::min<int64_t>(1024, std::max<int64_t>(64, ((int64_t)256 << 20) / (4 * rows)));
+}
+
+struct SpotChunk {
+    int q0, n, D;                                 // queries [q0, q0 + n), D emission slots (blank first)
+    size_t pair_off, gslot_off, nd_off, cls_off;  // words into SpotHost::up
+};
+
+struct SpotHost {
+    int B = 0, Q = 0, Dmax = 1;
+    std::vector<SpotAuto> autos;
+    std::vector<SpotChunk> chunks;
+    // the call's one upload: T[B] | zero[B] | qoff[Q] | blob | per chunk pair_q[n] | gslot[n][kSpotSlots] | nd[B] | cls[B][D]
+    std::vector<int32_t> up;
+    size_t qoff_off = 0, blob_off = 0;
+    // the tables that make launch_ctc_lse write a chunk's classes for every line, over a copy of `up` at d
+    CtcLines lines(const int32_t* d, const SpotChunk& ch) const {
+        return CtcLines{d, d + B, d + B, d + ch.nd_off, d + ch.cls_off, d + B, ch.D};
+    }
+};
+
+int spot_prepare(hctr_ctx* c, int B, int W, int C, const int32_t* queries, const int32_t* query_lengths, int Q,
+                 const int32_t* input_lengths, int lines_per_launch, SpotHost* h) {
+    if (Q < 1) return fail(c, HCTR_ERR_ARG, "need Q >= 1 queries, got Q=%d", Q);
+    if (!queries || !query_lengths) return fail(c, HCTR_ERR_ARG, "queries/query_lengths is NULL");
+    if ((int64_t)std::max(B, 1) * Q > INT32_MAX) return fail(c, HCTR_ERR_ARG, "B*Q=%lld too large", (long long)B * Q);
+    int64_t o = 0;
+    for (int k = 0; k < Q; ++k) {
+        const int L = query_lengths[k];
+        if (L < 1 || L > kSpotMaxLen) return fail(c, HCTR_ERR_ARG, "query_lengths[%d]=%d outside [1,%d]", k, L, kSpotMaxLen);
+        for (int j = 0; j < L; ++j)
+            if (queries[o + j] < 1 || queries[o + j] > C - 1)
+                return fail(c, HCTR_ERR_ARG, "query id %d (query %d, position %d) outside [1,%d]", queries[o + j], k, j, C - 1);
+        o += L;
+    }
+    for (int b = 0; b < B && input_lengths; ++b)
+        if (input_lengths[b] < 0 || input_lengths[b] > W)
+            return fail(c, HCTR_ERR_ARG, "input_lengths[%d]=%d outside [0,%d]", b, input_lengths[b], W);
+    h->B = B; h->Q = Q;
+    h->autos.resize((size_t)Q);
+    std::vector<int32_t>& up = h->up;
+    up.assign((size_t)2 * B, 0);
+    for (int b = 0; b < B; ++b) up[(size_t)b] = input_lengths ? input_lengths[b] : W;
+    h->qoff_off = up.size();
+    up.resize(up.size() + (size_t)Q);
+    h->blob_off = up.size();
+    o = 0;
+    for (int k = 0; k < Q; ++k) {
+        SpotAuto& a = h->autos[(size_t)k];
+        spot_automaton(queries + o, query_lengths[k], &a);
+        o += a.L;
+        up[h->qoff_off + k] = (int32_t)(up.size() - h->blob_off);
+        const int32_t head[4] = {a.L, a.nq, a.maxdeg, (int32_t)a.src.size()};
+        up.insert(up.end(), head, head + 4);
+        up.insert(up.end(), a.qslot.begin(), a.qslot.end());
+        up.insert(up.end(), a.ptr.begin(), a.ptr.end());
+        for (uint64_t m : a.mask) up.push_back((int32_t)(uint32_t)m);
+        for (uint64_t m : a.mask) up.push_back((int32_t)(uint32_t)(m >> 32));
+        for (size_t e = 0; e < a.src.size(); ++e) up.push_back(a.src[e] | (a.slot[e] << 8));
+    }
+    // chunks of consecutive queries whose classes, with the blank, stay within the cap
+    const int cap = spot_class_cap(lines_per_launch, W);
+    h->Dmax = 1;
+    for (int q0 = 0; q0 < Q;) {
+        std::vector<int32_t> uni;
+        int n = 0;
+        while (q0 + n < Q) {
+            const SpotAuto& a = h->autos[(size_t)q0 + n];
+            std::vector<int32_t> merged;
+            std::set_union(uni.begin(), uni.end(), a.cls.begin(), a.cls.end(), std::back_inserter(merged));
+            if (n > 0 && (int)merged.size() + 1 > cap) break;
+            uni.swap(merged);
+            ++n;
+        }
+        SpotChunk ch;
+        ch.q0 = q0; ch.n = n; ch.D = 1 + (int)uni.size();
+        ch.pair_off = up.size();
+        for (int i = 0; i < n; ++i) up.push_back(q0 + i);
+        ch.gslot_off = up.size();
+        for (int i = 0; i < n; ++i) {
+            const SpotAuto& a = h->autos[(size_t)q0 + i];
+            int32_t row[kSpotSlots] = {0};
+            for (int j = 0; j < a.nq; ++j)
+                row[1 + j] = 1 + (int32_t)(std::lower_bound(uni.begin(), uni.end(), a.cls[(size_t)j]) - uni.begin());
+            up.insert(up.end(), row, row + kSpotSlots);
+        }
+        ch.nd_off = up.size();
+        up.insert(up.end(), (size_t)B, ch.D);
+        ch.cls_off = up.size();
+        for (int b = 0; b < B; ++b) {
+            up.push_back(0);
+            up.insert(up.end(), uni.begin(), uni.end());
+        }
+        h->chunks.push_back(ch);
+        h->Dmax = std::max(h->Dmax, ch.D);
+        q0 += n;
+    }
+    return HCTR_OK;
+}
+
+struct SpotOut {             // the caller's host outputs, [B][Q]; any may be null
+    float *contain, *seg;
+    int32_t *seg_start, *seg_end;
+};
+
+struct SpotDev {
+    const int32_t* up = nullptr;
+    float *contain = nullptr, *seg = nullptr, *emis = nullptr;
+    int32_t *seg_start = nullptr, *seg_end = nullptr;
+};
+
+// scratch of a spot call that launches n lines at a time: the upload, the four [B][Q] results, n*W*Dmax emissions
+int spot_scratch(hctr_ctx* c, const SpotHost& h, int n, int W, SpotDev* d) {
+    const size_t up_b = align256(h.up.size() * 4), out_b = align256((size_t)h.B * h.Q * 4);
+    TRY(ctc_reserve(c, up_b + 4 * out_b + (size_t)n * W * h.Dmax * 4));
+    char* p = c->ctc_buf;
+    d->up = (const int32_t*)p;
+    d->contain = (float*)(p + up_b);
+    d->seg = (float*)(p + up_b + out_b);
+    d->seg_start = (int32_t*)(p + up_b + 2 * out_b);
+    d->seg_end = (int32_t*)(p + up_b + 3 * out_b);
+    d->emis = (float*)(p + up_b + 4 * out_b);
+    HIP_TRY(c, hipMemcpyAsync(p, h.up.data(), h.up.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return HCTR_OK;
+}
+
+// the lines [b0, b0 + nb) whose logit rows lie at x + (b*sb + t*st) * ld: per chunk the emissions, then the recursions
+int spot_launch(hctr_ctx* c, const SpotHost& h, const SpotDev& d, const float* x, int64_t ld, int64_t sb, int64_t st,
+                int C, int b0, int nb, int W) {
+    Prof pf(c);
+    for (const SpotChunk& ch : h.chunks) {
+        PROF_TRY(pf, "ctc_lse", launch_ctc_lse(x, ld, sb, st, C, h.lines(d.up, ch), b0, nb, W, d.emis, nullptr, c->stream));
+        const SpotArgs a{d.emis, d.up, b0, nb, W, ch.D, d.up + h.blob_off, d.up + h.qoff_off, d.up + ch.pair_off,
+                         d.up + ch.gslot_off, ch.n, h.Q, d.contain, d.seg, d.seg_start, d.seg_end};
+        PROF_TRY(pf, "spot", launch_spot(a, c->stream));
+    }
+    return HCTR_OK;
+}
+
+int spot_fetch(hctr_ctx* c, const SpotHost& h, const SpotDev& d, const SpotOut& o) {
+    const size_t bytes = (size_t)h.B * h.Q * 4;
+    auto fetch = [&](void* dst, const void* src) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    HIP_TRY(c, fetch(o.contain, d.contain));
+    HIP_TRY(c, fetch(o.seg, d.seg));
+    HIP_TRY(c, fetch(o.seg_start, d.seg_start));
+    HIP_TRY(c, fetch(o.seg_end, d.seg_end));
+    return HCTR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // greedy recognition (hctr_recognize*)
 // ---------------------------------------------------------------------------------------------
 struct RecOut {              // the caller's host outputs, [B][W] / [B]; any may be null
@@ -2975,6 +3209,81 @@ int hctr_ctc_align_logits(hctr_ctx* c, const float* logits_wbc, int on_device, i
             PROF_TRY(pf, "ctc_lse", launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, nullptr, c->stream));
             TRY(align_launch(c, pf, emis, m, h, a, 0, B, W, d_score));
             return align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
+        }());
+    });
+}
+
+int hctr_spot_chunk_classes(int lines, int W) { return spot_class_cap(lines, W); }
+
+int hctr_spot_automaton(const int32_t* query, int L, int32_t* classes, int32_t* num_classes, int32_t* delta,
+                        int32_t* num_states, int32_t* in_ptr, int32_t* in_src, int32_t* in_slot, int edge_cap,
+                        int32_t* num_edges, uint64_t* fall_mask) {
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!query) return fail(nullptr, HCTR_ERR_ARG, "query is NULL");
+        if (L < 1 || L > kSpotMaxLen) return fail(nullptr, HCTR_ERR_ARG, "query length %d outside [1,%d]", L, kSpotMaxLen);
+        for (int j = 0; j < L; ++j)
+            if (query[j] < 1) return fail(nullptr, HCTR_ERR_ARG, "query id %d (position %d) is not a label (>= 1)", query[j], j);
+        SpotAuto a;
+        spot_automaton(query, L, &a);
+        const int ne = (int)a.src.size();
+        if ((in_src || in_slot) && edge_cap < ne)
+            return fail(nullptr, HCTR_ERR_ARG, "edge_cap=%d is less than the automaton's %d edges", edge_cap, ne);
+        if (classes) std::copy(a.cls.begin(), a.cls.end(), classes);
+        if (num_classes) *num_classes = a.nq;
+        if (delta) std::copy(a.delta.begin(), a.delta.end(), delta);
+        if (num_states) *num_states = 2 * L;
+        if (in_ptr) std::copy(a.ptr.begin(), a.ptr.end(), in_ptr);
+        if (in_src) std::copy(a.src.begin(), a.src.end(), in_src);
+        if (in_slot) std::copy(a.slot.begin(), a.slot.end(), in_slot);
+        if (num_edges) *num_edges = ne;
+        if (fall_mask) std::copy(a.mask.begin(), a.mask.end(), fall_mask);
+        return HCTR_OK;
+    });
+}
+
+int hctr_spot(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
+              const int32_t* queries, const int32_t* query_lengths, int Q, const int32_t* input_lengths,
+              float* contain_logp, float* seg_logp, int32_t* seg_start, int32_t* seg_end) {
+    return guard(c, [&]() -> int {
+        TRY(check_forward_args(c, img, img_dtype, B, W));
+        SpotHost h;
+        TRY(spot_prepare(c, B, W, c->num_classes, queries, query_lengths, Q, input_lengths, B, &h));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        const Batch in{img, img_dtype, img_on_device, widths, B, W};
+        SpotDev d;
+        // the pageable upload queued below was staged before hipMemcpyAsync returned. PASS_EXACT as hctr_ctc_loss: mode
+        // 2's guard certifies argmaxes, not probabilities
+        return synced(c, [&]() -> int {
+            TRY(run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
+                if (p.first == 0) TRY(spot_scratch(c, h, p.nb, W, &d));      // no later pass is larger
+                TRY(forward_pass(c, in, p, HEAD_LOGITS));
+                return spot_launch(c, h, d, c->ws.logits, c->cpad, W, 1, c->num_classes, p.first, p.nb, W);
+            }));
+            return spot_fetch(c, h, d, SpotOut{contain_logp, seg_logp, seg_start, seg_end});
+        }());
+    });
+}
+
+int hctr_spot_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W, int B, int C, const int32_t* queries,
+                     const int32_t* query_lengths, int Q, const int32_t* input_lengths, float* contain_logp,
+                     float* seg_logp, int32_t* seg_start, int32_t* seg_end) {
+    return guard(c, [&]() -> int {
+        TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
+        SpotHost h;
+        TRY(spot_prepare(c, B, W, C, queries, query_lengths, Q, input_lengths, B, &h));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
+        std::vector<void*> tmp;
+        PoolGuard tmp_guard{tmp};
+        return synced(c, [&]() -> int {
+            SpotDev d;
+            const float* dev = nullptr;
+            TRY(spot_scratch(c, h, B, W, &d));
+            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
+            TRY(spot_launch(c, h, d, dev, C, 1, B, C, 0, B, W));      // rows of the WBC tensor are r = t*B + b
+            return spot_fetch(c, h, d, SpotOut{contain_logp, seg_logp, seg_start, seg_end});
         }());
     });
 }

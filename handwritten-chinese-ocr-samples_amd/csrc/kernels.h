@@ -346,6 +346,31 @@ hipError_t launch_prefix_beam_skip(const int32_t* cnt, const int32_t* ci, const 
                                    const BeamLm& lm, int2* hist, int32_t* len, double* logp, double* score,
                                    int32_t* o_cnt, int32_t* status, int32_t* ranked, hipStream_t s);
 
+// ---- keyword spotting (hctr_spot*): one wave64 per (line, query) pair over the emissions of launch_ctc_lse, whose
+// tables give every line the chunk's class list (slot 0 = blank). Local slots of a query: 0 = blank, 1..nq = its distinct
+// classes in ascending order, nq + 1 = `rest` (formed per column), nq + 2 = the constant 1 (the accepting state's loop).
+// A query's automaton in `blob`, at word qoff[k]:
+//   L, nq, maxdeg, nedges | qslot[L] (local slot of q_j) | ptr[2L + 1] (in-edge CSR over the states Z, N_1..N_{L-1},
+//   B_1..B_{L-1}, A) | mask_lo[2L], mask_hi[2L] (the local slots a state sends to Z) | edge[nedges] = src | slot << 8
+constexpr int kSpotMaxLen = 32;                       // HCTR_SPOT_MAX_LEN: 2L states fill one wave
+constexpr int kSpotSlots = kSpotMaxLen + 3;
+constexpr int kSpotMaxEdges = (2 * kSpotMaxLen - 1) * (kSpotMaxLen + 1) + 1;      // one edge per (state, class) + A's loop
+struct SpotArgs {
+    const float* emis;        // [nb][W][D]
+    const int32_t* T;         // [B] columns that count, indexed by b0 + b
+    int b0, nb, W, D;
+    const int32_t* blob;
+    const int32_t* qoff;      // [Q]
+    const int32_t* pair_q;    // [npairs] query of each of the launch's pairs
+    const int32_t* gslot;     // [npairs][kSpotSlots] emission slot (of D) of the pair's local slots 0..nq
+    int npairs, Q;
+    float* contain;           // [B][Q] each, or null
+    float* seg;
+    int32_t* seg_start;
+    int32_t* seg_end;
+};
+hipError_t launch_spot(const SpotArgs& a, hipStream_t s);
+
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {
     int64_t src_off;          // byte offset of the image inside the packed source buffer

@@ -4930,4 +4930,146 @@ hipError_t launch_prefix_beam_skip(const int32_t* cnt, const int32_t* ci, const 
     return hipErrorInvalidValue;
 }
 
+// -------------------------------------------------------------------------------------------
+// Keyword spotting (hctr_spot*): for a (line, query) pair the probability that the line's text contains the query (the
+// forward recursion over the query's KMP automaton lifted to CTC, 2L states) and the best tight segment that reads the
+// query (max-plus over its 2L - 1 extended states, each carrying its start column). See SpotArgs in kernels.h and
+// DESIGN.md 4j. One wave64 per pair, one lane per state; the four waves of a workgroup take four queries of one line and
+// walk its columns in step (they share T), so plain barriers order each wave's LDS rows.
+// The containment masses are float64 and linear: the transition matrix is stochastic, the total mass stays 1 and the
+// accepting mass only grows, so nothing needs rescaling while log P stays above float64's floor (about -700).
+// Every sum has a fixed order that depends on the query alone (its local slots, its edge list), never on where the
+// chunk put its classes: a pair's result is the same bits in any chunk and any launch.
+// -------------------------------------------------------------------------------------------
+__device__ __forceinline__ double spot_wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);      // a + b == b + a: every lane ends with the same bits
+    return v;
+}
+
+// the better of two (score, start) candidates: the strictly greater score, the larger start on equal scores
+__device__ __forceinline__ void spot_take(float& m, int& ms, float c, int cs) {
+    if (c > m || (c == m && cs > ms)) {
+        m = c;
+        ms = cs;
+    }
+}
+
+constexpr int kSpotPF = 4, kSpotWaves = 4;
+
+__global__ __launch_bounds__(64 * kSpotWaves) void spot_kernel(const SpotArgs a) {
+    __shared__ double s_st[kSpotWaves][64];              // the states' masses of the previous column
+    __shared__ double s_p[kSpotWaves][kSpotSlots + 1];   // the column's probabilities by local slot, rest and 1
+    __shared__ float s_lp[kSpotWaves][kSpotSlots + 1];   // and their logs (slots 0..nq)
+    __shared__ uint16_t s_edge[kSpotWaves][kSpotMaxEdges];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int b = blockIdx.y, gb = a.b0 + b;
+    const int T = a.T[gb], D = a.D;
+    const int own = (int)blockIdx.x * kSpotWaves + wv;
+    const bool valid = own < a.npairs;
+    const int pi = valid ? own : (int)blockIdx.x * kSpotWaves;      // a wave without a pair shadows the block's first: it
+    const int k = __builtin_amdgcn_readfirstlane(a.pair_q[pi]);     // keeps the barriers' count and writes nothing
+    const int32_t* au = a.blob + a.qoff[k];
+    const int L = __builtin_amdgcn_readfirstlane(au[0]), nq = __builtin_amdgcn_readfirstlane(au[1]);
+    const int maxdeg = __builtin_amdgcn_readfirstlane(au[2]);
+    const int ne = min(__builtin_amdgcn_readfirstlane(au[3]), kSpotMaxEdges);
+    const int S = 2 * L, SS = 2 * L - 1;
+    const int32_t *qslot = au + 4, *ptr = qslot + L, *mlo = ptr + S + 1, *mhi = mlo + S, *ed = mhi + S;
+    for (int e = lane; e < ne; e += 64) s_edge[wv][e] = (uint16_t)ed[e];
+    const int e0 = lane < S ? ptr[lane] : 0, e1 = lane < S ? ptr[lane + 1] : 0;
+    const uint64_t mask = lane < S ? ((uint64_t)(uint32_t)mlo[lane] | ((uint64_t)(uint32_t)mhi[lane] << 32)) : 0;
+    const int gs = lane <= nq ? a.gslot[(int64_t)pi * kSpotSlots + lane] : 0;      // the lane's emission column
+    // the segment's extended states q_1, blank, q_2, ..., q_L: lane s, characters on the even ones
+    const bool seg_on = lane < SS, is_chr = seg_on && !(lane & 1);
+    const int myslot = is_chr ? qslot[lane >> 1] : 0;
+    const bool skip = is_chr && lane >= 2 && qslot[lane >> 1] != qslot[(lane >> 1) - 1];
+    double st = lane == 0 ? 1.0 : 0.0;
+    float sc = -INFINITY, best = -INFINITY;
+    int sst = -1, bs = -1, be = -1;
+    if (lane == nq + 2) s_p[wv][lane] = 1.0;
+    const float* base = a.emis + (int64_t)b * a.W * D;
+    float e[kSpotPF];
+#pragma unroll
+    for (int i = 0; i < kSpotPF; ++i) e[i] = T > 0 ? base[(int64_t)min(i, T - 1) * D + gs] : 0.f;
+    __syncthreads();
+    for (int t0 = 0; t0 < T; t0 += kSpotPF) {
+#pragma unroll
+        for (int i = 0; i < kSpotPF; ++i) {
+            const int t = t0 + i;
+            if (t < T) {                                   // (block-uniform)
+                const float le = e[i];
+                const double p = lane <= nq ? exp((double)le) : 0.0;
+                const double seen = spot_wave_sum(p);      // p(0) + the query's classes, in local slot order
+                if (lane <= nq) {
+                    s_p[wv][lane] = p;
+                    s_lp[wv][lane] = le;
+                }
+                if (lane == 0) s_p[wv][nq + 1] = fmax(0.0, 1.0 - seen);
+                s_st[wv][lane] = st;
+                __syncthreads();
+                // Z: what every state sends back to it; the others: their in-edges, in the host's order
+                double fall = 0.0;
+                for (int j = 0; j <= nq + 1; ++j)
+                    if ((mask >> j) & 1) fall += s_p[wv][j];
+                const double z = spot_wave_sum(st * fall);
+                double acc = 0.0;
+                for (int j = 0; j < maxdeg; ++j) {
+                    if (e0 + j < e1) {
+                        const unsigned w = s_edge[wv][e0 + j];
+                        acc += s_st[wv][w & 63] * s_p[wv][w >> 8];
+                    }
+                }
+                st = lane == 0 ? z : acc;
+                // the segment: a fresh start (score 0, start t) is offered to the first state at every column
+                const float lp = s_lp[wv][myslot];
+                float c1 = __shfl_up(sc, 1), c2 = __shfl_up(sc, 2);
+                int s1 = __shfl_up(sst, 1), s2 = __shfl_up(sst, 2);
+                if (lane == 0) {
+                    c1 = 0.f;
+                    s1 = t;
+                }
+                if (!skip) {
+                    c2 = -INFINITY;
+                    s2 = -1;
+                }
+                float m = sc;
+                int ms = sst;
+                spot_take(m, ms, c1, s1);
+                spot_take(m, ms, c2, s2);
+                sc = seg_on ? m + lp : -INFINITY;
+                sst = sc == -INFINITY ? -1 : ms;           // a state nothing has reached has no start
+                if (lane == SS - 1 && sc > best) {         // strictly greater: the earliest end wins
+                    best = sc;
+                    bs = sst;
+                    be = t + 1;
+                }
+                __syncthreads();                           // the rows are rewritten by the next column
+                e[i] = base[(int64_t)min(t + kSpotPF, T - 1) * D + gs];      // refill the slot just used
+            }
+        }
+    }
+    if (!valid) return;
+    const int64_t o = (int64_t)gb * a.Q + k;
+    if (lane == S - 1 && a.contain) a.contain[o] = (float)log(st);      // log 0 = -inf: T = 0, or no path holds the query
+    if (lane == SS - 1) {
+        if (a.seg) a.seg[o] = best;
+        if (a.seg_start) a.seg_start[o] = bs;
+        if (a.seg_end) a.seg_end[o] = be;
+    }
+}
+
+hipError_t launch_spot(const SpotArgs& a, hipStream_t s) {
+    if (a.nb <= 0 || a.npairs <= 0) return hipSuccess;
+    if (a.D < 1 || a.W < 1 || a.Q < 1) return hipErrorInvalidValue;
+    for (int l0 = 0; l0 < a.nb; l0 += 65535) {             // (grid.y's limit)
+        SpotArgs c = a;
+        c.b0 = a.b0 + l0;
+        c.nb = std::min(65535, a.nb - l0);
+        c.emis = a.emis + (int64_t)l0 * a.W * a.D;
+        const dim3 grid((unsigned)((a.npairs + kSpotWaves - 1) / kSpotWaves), (unsigned)c.nb);
+        hipLaunchKernelGGL(spot_kernel, grid, dim3(64 * kSpotWaves), 0, s, c);
+    }
+    return hipGetLastError();
+}
+
 }  // namespace hctr

@@ -9,6 +9,9 @@ host-side helpers below, with the semantics of ``torch.nn.CTCLoss``.
 
 ``CTCAligner`` and ``hctr_model.align`` are the third member: the best path of a known transcription
 (``hctr_ctc_align*``), which says where in the line each character lies and how confident the engine is of it.
+
+``KeywordSpotter`` and ``hctr_model.spot`` answer the word-spotting question (``hctr_spot*``): for every (line, query)
+pair the posterior probability that the line's text contains the query, and the best segment that reads it.
 """
 import ctypes
 
@@ -231,6 +234,91 @@ def align_images(ctx, x, dt, on_dev, widths, B, W, targets, target_lengths, inpu
                                               _lib.ptr(tl), _lib.ptr(il), _lib.ptr(path), _lib.ptr(st), _lib.ptr(en),
                                               _lib.ptr(lp), _lib.ptr(score)), ctx)
     return CTCAlignment(path, score, st, en, lp, tg, tl)
+
+
+SPOT_MAX_LEN = 32      # HCTR_SPOT_MAX_LEN
+
+
+def normalize_queries(queries):
+    """(concatenated int32 labels, int32 query_lengths [Q]) from a sequence of label sequences (lists, arrays); every
+    query has 1..32 labels. Label ranges are checked by the engine, which knows C."""
+    qs = [np.asarray(_host_int32(q, "queries")).reshape(-1) for q in queries]
+    if not qs:
+        raise ValueError("need at least one query")
+    ql = np.array([q.size for q in qs], dtype=np.int32)
+    if (ql < 1).any() or (ql > SPOT_MAX_LEN).any():
+        raise ValueError("every query must have 1..%d labels, got lengths %s" % (SPOT_MAX_LEN, ql.tolist()))
+    flat = np.concatenate(qs)
+    if flat.min() < np.iinfo(np.int32).min or flat.max() > np.iinfo(np.int32).max:
+        raise ValueError("query id out of the int32 range")
+    return np.ascontiguousarray(flat, dtype=np.int32), ql
+
+
+class Spotting(object):
+    """Result of keyword spotting of Q queries in B lines (numpy arrays, on the host; include/hctr_hip.h ``hctr_spot``):
+    ``logp`` float32 [B, Q], the log of the probability that the line's text contains the query (an exact sum over all
+    CTC paths; -inf where it cannot); ``seg_logp`` float32 [B, Q], ``starts`` / ``ends`` int32 [B, Q]: the best tight
+    segment that reads the query, its log-probability and pixel-column span [start, end) (-inf, -1, -1 where none fits).
+    The span runs from inside the first character's run to inside the last one's; ``align`` / ``recognize`` give full
+    character extents."""
+
+    def __init__(self, logp, seg_logp, starts, ends):
+        self.logp, self.seg_logp, self.starts, self.ends = logp, seg_logp, starts, ends
+
+    def __len__(self):
+        return int(self.logp.shape[0])
+
+    def probs(self):
+        """float64 [B, Q]: the probability that line b contains query k"""
+        return np.exp(self.logp.astype(np.float64))
+
+    def hits(self, threshold=0.5):
+        """the (line, query, prob, start, end) of every pair whose containment probability is >= threshold, by line
+        then query"""
+        p = self.probs()
+        return [(int(b), int(k), float(p[b, k]), int(self.starts[b, k]), int(self.ends[b, k]))
+                for b, k in zip(*np.nonzero(p >= threshold))]
+
+    def lines(self):
+        """yields per line the list of (query, prob, start, end), one per query"""
+        p = self.probs()
+        for b in range(len(self)):
+            yield [(k, float(p[b, k]), int(self.starts[b, k]), int(self.ends[b, k])) for k in range(p.shape[1])]
+
+
+def _spot_outputs(B, Q):
+    return (np.full((B, Q), -np.inf, np.float32), np.full((B, Q), -np.inf, np.float32), np.full((B, Q), -1, np.int32),
+            np.full((B, Q), -1, np.int32))
+
+
+def spot_logits(ctx, logits, on_dev, queries, input_lengths=None):
+    """Spotting of caller logits / log-probs in WBC layout (hctr_spot_logits); ``queries``: label sequences."""
+    W, B, C = (int(v) for v in logits.shape)
+    qf, ql = normalize_queries(queries)
+    il = normalize_input_lengths(input_lengths, B)
+    logp, seg, st, en = _spot_outputs(B, int(ql.size))
+    if B and W:
+        _lib.check(_lib.load().hctr_spot_logits(ctx, _lib.ptr(logits), on_dev, W, B, C, _lib.ptr(qf), _lib.ptr(ql),
+                                                int(ql.size), _lib.ptr(il), _lib.ptr(logp), _lib.ptr(seg), _lib.ptr(st),
+                                                _lib.ptr(en)), ctx)
+    return Spotting(logp, seg, st, en)
+
+
+def spot_images(ctx, x, dt, on_dev, widths, B, W, queries, input_lengths=None):
+    """Spotting of line images (hctr_spot); x, dt, on_dev, widths as hctr_model._img_args / _widths give them."""
+    qf, ql = normalize_queries(queries)
+    il = normalize_input_lengths(input_lengths, B)
+    logp, seg, st, en = _spot_outputs(B, int(ql.size))
+    if B:
+        _lib.check(_lib.load().hctr_spot(ctx, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, _lib.ptr(qf), _lib.ptr(ql),
+                                         int(ql.size), _lib.ptr(il), _lib.ptr(logp), _lib.ptr(seg), _lib.ptr(st),
+                                         _lib.ptr(en)), ctx)
+    return Spotting(logp, seg, st, en)
+
+
+def spot_chunk_classes(lines, W):
+    """classes (blank included) one chunk of queries may hold for `lines` lines of W columns (hctr_spot_chunk_classes)"""
+    return int(_lib.load().hctr_spot_chunk_classes(int(lines), int(W)))
 
 
 class Recognition(object):
@@ -922,6 +1010,28 @@ class CTCAligner(_EngineBound):
             log_probs = log_probs.detach()
         logits, on_dev = ctc_codec._as_logits(log_probs)
         return align_logits(self._context(), logits, on_dev, targets, target_lengths, input_lengths)
+
+    __call__ = forward
+
+
+class KeywordSpotter(_EngineBound):
+    """Keyword spotting on the engine: ``KeywordSpotter().cuda(0)(log_probs_or_logits, queries, input_lengths=None)``
+    with ``[T, B, C]`` input (numpy array or torch tensor, a CUDA tensor is read in place) and ``queries`` a sequence of
+    label sequences (1..32 labels each) returns the ``Spotting`` of every (line, query) pair: the posterior probability
+    that the line's text contains the query, and the best segment that reads it. Only blank=0 is supported."""
+
+    def __init__(self, blank=0):
+        if blank != 0:
+            raise NotImplementedError("the engine's CTC kernels use blank = 0 (the reference's codec)")
+        _EngineBound.__init__(self)
+        self.blank = blank
+
+    def forward(self, log_probs, queries, input_lengths=None):
+        from .codec import ctc_codec
+        if _is_torch(log_probs):
+            log_probs = log_probs.detach()
+        logits, on_dev = ctc_codec._as_logits(log_probs)
+        return spot_logits(self._context(), logits, on_dev, queries, input_lengths)
 
     __call__ = forward
 

@@ -272,6 +272,22 @@ class hctr_model(object):
         x, dt, on_dev, B, W = self._img_args(input)
         return ctc.align_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, targets, target_lengths, input_lengths)
 
+    def spot(self, input, queries, widths=None, input_lengths=None, codec=None):
+        """Keyword spotting in line images, the logits never leaving the device: for every (line, query) pair the
+        posterior probability that the line's text contains the query - an exact sum over all CTC paths, not a match on
+        the 1-best text - and the best segment that reads it, as pixel columns of ``input``. ``queries``: label
+        sequences of 1..32 labels, or strings when a ``codec`` is given to encode them (a character outside its
+        vocabulary is a ValueError). ``input_lengths`` None = W for every line. Returns a ``ctc.Spotting`` (numpy arrays):
+        ``logp`` / ``seg_logp`` / ``starts`` / ``ends`` [B, Q], ``probs()``, ``hits(threshold)``, ``lines()``. In "auto"
+        precision every line is scored in f16x3 (include/hctr_hip.h ``hctr_spot``)."""
+        from . import ctc
+        ctx = self._require_ctx()
+        x, dt, on_dev, B, W = self._img_args(input)
+        if codec is not None:
+            flat, ql = codec.encode_queries(queries)
+            queries = np.split(flat, np.cumsum(ql)[:-1])
+        return ctc.spot_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, queries, input_lengths)
+
     def recognize(self, input, widths=None):
         """Forward + greedy decode with what an OCR interface reports beside the text, the logits never leaving the
         device: per character its pixel-column span, confidence and likeliest substitution, per line the greedy path's

@@ -228,6 +228,70 @@ int hctr_ctc_align_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device,
                           const int32_t* targets, const int32_t* target_lengths, const int32_t* input_lengths,
                           int32_t* path, int32_t* span_start, int32_t* span_end, float* span_logp, float* score);
 
+/* ---- keyword spotting on the device: which lines contain a query, how surely, and where ---------------------------
+ * The word-spotting question of handwriting recognition, answered from the CTC posterior and not from the 1-best text.
+ * The reference has no counterpart. A line has T = input_lengths[b] columns that count (NULL = W; 0 <= T <= W),
+ * p_t(c) = softmax(z_t)[c] with lp_t(c) its log in float32 (the loss's emissions, bit for bit), blank = class 0, and
+ * B(pi) is the CTC collapse of a path pi in {0..C-1}^T. A query is q = (q_1 .. q_L), 1 <= L <= HCTR_SPOT_MAX_LEN, labels
+ * in [1, C-1]. Two results per (line b, query k), all outputs [B][Q] on the host, any of them NULL:
+ *
+ * 1. contain_logp = log sum over the paths pi with q a contiguous substring of B(pi) of prod_t p_t(pi_t): the
+ *    probability that the line's text contains the query - an exact sum over all paths. It is the forward recursion over
+ *    the Knuth-Morris-Pratt automaton of q lifted to CTC. delta(j, c) = the longest k with q_1..q_k a suffix of
+ *    q_1..q_j c (0 for every c not in q). The 2L states: Z (nothing matched), N_j (j = 1..L-1: j characters matched, the
+ *    last column emitted q_j), B_j (j matched, the last column was blank), A (accepting, absorbing). Mass 1 starts in Z.
+ *    With tgt(k) = Z for k = 0, A for k = L, else N_k, and rest = the probability of the classes that are neither blank
+ *    nor in q, one column moves
+ *      Z   -> Z: p(0) + rest + sum of p(c) over c in q, c != q_1;            Z -> tgt(1): p(q_1)
+ *      N_j -> N_j: p(q_j);   N_j -> B_j: p(0);   N_j -> tgt(delta(j,c)): p(c), c in q, c != q_j;   N_j -> Z: rest
+ *      B_j -> B_j: p(0);     B_j -> tgt(delta(j,c)): p(c), c in q, q_j included;                   B_j -> Z: rest
+ *      A   -> A: 1
+ *    and contain_logp is the log of A's mass after T columns (-inf for T = 0 and wherever no path holds q; for L = 1 it
+ *    is log(1 - prod_t (1 - p_t(q_1)))). The masses are float64 and linear (the matrix is stochastic, so the total stays 1);
+ *    rest is formed per column as max(0, 1 - p(0) - sum of p(c) over the classes of q) from the float32 emissions. A
+ *    result below float64's floor (about -700) comes back as -inf.
+ * 2. seg_logp, seg_start, seg_end = the maximum over 0 <= t0 < t1 <= T and segment paths s on columns [t0, t1) with
+ *    s_t0 = q_1, s_(t1-1) = q_L and B(s) = q of sum_t lp_t(s_t), and its (t0, t1); -inf, -1, -1 where none fits. The
+ *    max-plus CTC recursion over the 2L - 1 extended states q_1, 0, q_2, .., q_L in float32: a fresh start (score 0, start
+ *    t) is offered to the first state at every column, each state carries the start column of its best path, and the
+ *    answer is the best value the last state ever holds. Ties are part of the contract: between predecessors the
+ *    strictly greater score wins and equal scores prefer the larger start column; the running best is replaced only by a
+ *    strictly greater score, so the earliest end wins. Because lp <= 0 the segment is tight - it runs from inside the
+ *    first character's run to inside the last one's; hctr_ctc_align / hctr_recognize give full character extents.
+ * contain_logp >= seg_logp, and contain_logp >= -nll of hctr_ctc_loss with q as the line's target.
+ *   queries:       int32, the queries back to back, sum(query_lengths) entries, host.   query_lengths: int32 [Q], host.
+ * L outside [1, 32], a label outside [1, C-1], Q < 1, an input length outside [0, W] -> HCTR_ERR_ARG; B == 0 is a no-op.
+ * A pair's results depend on its own line and query only, bit for bit: not on the other queries, their order, the chunk
+ * it lands in, host or device pointers.
+ * Queries are processed in chunks whose classes, blank included, number at most hctr_spot_chunk_classes(lines, W) (the
+ * environment variable HCTR_SPOT_CLASSES overrides it; a single query with more classes gets a chunk of its own); one
+ * pass over the logits per chunk writes the emissions every query of the chunk reads.
+ * Device scratch (the context's grow-only CTC scratch; HCTR_ERR_NOMEM leaves the context usable): 4 * n*W*D emissions
+ * (n = B, or the lines of one pass for images; D = the largest chunk's classes) + 16 * B*Q results + the automata and
+ * per-chunk tables (4 * B*D each); plus W*B*C floats for logits passed as a host pointer.
+ * hctr_spot runs the forward of img in internal passes on the stored-logits head exactly as hctr_ctc_loss does: mode 0
+ * f16, mode 1 f16x3, mode 2 EVERY line in f16x3, hctr_last_guard's figures left as they were. hctr_spot_logits takes
+ * caller logits or log-probs in WBC layout, host or device pointer, and needs no weights.
+ * hctr_spot_automaton (host only, no context; errors are read with hctr_last_error(NULL)) exports the tables the kernel
+ * is given for one query, so that they can be checked without a GPU. States are numbered Z = 0, N_j = j, B_j = L-1+j,
+ * A = 2L-1; slots 0 = blank, 1..nq = the query's distinct classes in ascending order, nq+1 = rest, nq+2 = the constant 1.
+ *   classes [nq], num_classes = nq;  delta [L][nq]: delta(j, classes[i]) for j = 0..L-1;  num_states = 2L;
+ *   in_ptr [2L+1], in_src / in_slot [num_edges <= HCTR_SPOT_MAX_EDGES]: the in-edges of every state but Z in CSR form,
+ *   a state's edges ordered by (source, slot) - the order the kernel adds them in; edge_cap = the room in in_src / in_slot;
+ *   fall_mask [2L]: bit s set = the state sends slot s to Z (Z's inflow is the sum of those flows). Any output may be NULL. */
+#define HCTR_SPOT_MAX_LEN 32
+#define HCTR_SPOT_MAX_EDGES 2080
+int hctr_spot(hctr_ctx* ctx, const void* img, int img_dtype, int img_on_device, const int32_t* widths, int B, int W,
+              const int32_t* queries, const int32_t* query_lengths, int Q, const int32_t* input_lengths,
+              float* contain_logp, float* seg_logp, int32_t* seg_start, int32_t* seg_end);
+int hctr_spot_logits(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C,
+                     const int32_t* queries, const int32_t* query_lengths, int Q, const int32_t* input_lengths,
+                     float* contain_logp, float* seg_logp, int32_t* seg_start, int32_t* seg_end);
+int hctr_spot_automaton(const int32_t* query, int L, int32_t* classes, int32_t* num_classes, int32_t* delta,
+                        int32_t* num_states, int32_t* in_ptr, int32_t* in_src, int32_t* in_slot, int edge_cap,
+                        int32_t* num_edges, uint64_t* fall_mask);
+int hctr_spot_chunk_classes(int lines, int W);
+
 /* ---- greedy recognition: the decoded text with per-character spans, confidences and runners-up -------------------
  * What hctr_greedy / hctr_decode_greedy_logits decode, plus the figures the CTC family above gives only for a
  * transcription the caller already knows - in one pass over the logits, without a Viterbi recursion: the greedy path is

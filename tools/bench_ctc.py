@@ -77,7 +77,15 @@ hctr_nbest_lm_topk(nbest = 1) + hctr_edit_distance on the same lists in the same
 without the sweep. The pairs are the first G of the reference's default grid (10 x 25, alpha-major); the transcriptions
 are the lines' greedy texts. The two alternate after warm-up calls of each, medians of the wall time per call; the device
 time of each one's launches comes from one profiled call of each in the same run. Every ``edits`` value of the two is
-compared before anything is reported."""
+compared before anything is reported.
+
+    python tools/bench_ctc.py --spot [--queries 16] [--layers] ...
+
+times keyword spotting on the same caller logits (hctr_spot_logits, every output fetched) for --queries queries of
+length 2-4, half of them drawn from the lines' greedy texts and half absent from every line, and in the same run the
+loss (hctr_ctc_loss_logits, each line's greedy text as its target), alternately after warm-up calls of each, medians.
+--layers adds the device time of the call's launches, which the engine sums per name over the chunks of queries
+(ctc_lse: one pass over the logits per chunk; spot: the recursions)."""
 import argparse
 import json
 import os
@@ -106,6 +114,8 @@ def main():
     ap.add_argument("--nbest-lm", action="store_true")
     ap.add_argument("--nbest-skip", action="store_true")
     ap.add_argument("--lm-sweep", action="store_true")
+    ap.add_argument("--spot", action="store_true")
+    ap.add_argument("--queries", type=int, default=16)
     ap.add_argument("--pairs", type=int, default=250)
     ap.add_argument("--host-lines", type=int, default=4)
     args = ap.parse_args()
@@ -130,6 +140,9 @@ def main():
         return
     if args.recognize:
         print(json.dumps(recognize(args, hctr_amd, m, imgs)))
+        return
+    if args.spot:
+        print(json.dumps(spot(args, hctr_amd, m, imgs, labels, targets, tl)))
         return
     if args.evaluate:
         print(json.dumps(evaluate(args, hctr_amd, m, imgs, labels)))
@@ -298,6 +311,83 @@ def align(args, hctr_amd, m, imgs, targets, tl):
         m.set_profiling(False)
         rec["loss_only_layers_ms"] = {k: round(v, 4) for k, v in fprof.items()}
         rec["align_layers_ms"] = {k: round(v, 4) for k, v in aprof.items()}
+    return rec
+
+
+def spot_queries(labels, C, Q, seed=3):
+    """Q queries of length 2-4: the even ones cut from the lines' texts (line k mod B), the odd ones of classes no line
+    decodes to (so they are absent from every 1-best text)"""
+    rng = np.random.RandomState(seed)
+    used = np.zeros(C, bool)
+    for v in labels:
+        used[np.asarray(v, np.int64)] = True
+    free = np.flatnonzero(~used[1:C - 1]) + 1
+    assert free.size >= 4, "every class is decoded somewhere: no absent query can be drawn"
+    out = []
+    for k in range(Q):
+        n = int(rng.randint(2, 5))
+        text = labels[k % len(labels)]
+        if k % 2 == 0 and len(text) >= n:
+            at = int(rng.randint(0, len(text) - n + 1))
+            out.append([int(c) for c in text[at:at + n]])
+        else:
+            out.append([int(c) for c in rng.choice(free, size=n)])
+    return out
+
+
+def spot(args, hctr_amd, m, imgs, labels, targets, tl):
+    import torch
+    sp = hctr_amd.KeywordSpotter().attach(m)
+    mod = sys.modules[type(sp).__module__]
+    ctx = sp._context()
+    logits = m(imgs)                                             # device tensor [W, lines, C]
+    W, B, C = (int(v) for v in logits.shape)
+    qs = spot_queries(labels, C, args.queries)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def loss_only():
+        assert np.isfinite(mod.loss_logits(ctx, logits, 1, targets, tl, None)).all()
+
+    last = {}
+
+    def spot_all():
+        last["r"] = mod.spot_logits(ctx, logits, 1, qs, None)
+        assert not np.isnan(last["r"].logp).any()
+
+    fns = (("loss_only", loss_only), ("spot", spot_all))
+    for _ in range(args.warmup):
+        for _, fn in fns:
+            fn()
+    ms = {k: [] for k, _ in fns}
+    for _ in range(args.steps):
+        for k, fn in fns:
+            ms[k].append(1e3 * timed(fn))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    r = last["r"]
+    drawn = np.arange(len(qs)) % 2 == 0
+    rec = {"mode": "spot", "lines": B, "width": W, "classes": C, "precision": args.precision, "queries": len(qs),
+           "chunk_classes": mod.spot_chunk_classes(B, W),
+           "mean_prob_of_own_text_queries": round(float(np.mean([r.probs()[k % B, k] for k in np.flatnonzero(drawn)])), 4),
+           "max_prob_of_absent_queries": float(r.probs()[:, ~drawn].max()) if (~drawn).any() else None}
+    for k, v in ms.items():
+        rec[k + "_ms"] = [round(x, 3) for x in v]
+        rec[k + "_ms_median"] = round(med[k], 3)
+    rec["spot_over_loss_only"] = round(med["spot"] / med["loss_only"], 4)
+    if args.layers:
+        m.set_profiling(True)
+        loss_only()
+        fprof = dict(m.last_profile())
+        spot_all()
+        sprof = dict(m.last_profile())
+        m.set_profiling(False)
+        rec["loss_only_layers_ms"] = {k: round(v, 4) for k, v in fprof.items()}
+        rec["spot_layers_ms"] = {k: round(v, 4) for k, v in sprof.items()}
     return rec
 
 
