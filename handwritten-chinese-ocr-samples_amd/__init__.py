@@ -19,6 +19,10 @@ Public surface = the reference's surface for this path:
   KeywordSpotter  keyword spotting on logits: per (line, query) the posterior probability that the line's text contains
                the query, and the best segment that reads it; Spotting is its result and that of hctr_model.spot /
                ctc_codec.spot                                       (engine-backed; no counterpart)
+  LexiconRecognizer  lexicon recognition on logits: which entry of a closed list (a Lexicon) each line is - the exact
+               log p(entry | line) of every entry by one CTC forward over the lexicon's trie, the n best with ranks and
+               posteriors; LexiconResult is its result and that of hctr_model.lexicon / ctc_codec.lexicon
+                                                                    (engine-backed; no counterpart)
   LMSweep      result of hctr_model.lm_sweep / ctc_codec.lm_sweep: edit distances of the LM-scored 1-best under a grid of
                (lm_panelty, len_bonus) pairs; LMSweepTotals adds batches up and answers the reference's test.py -gs
 plus ``synth`` (deterministic synthetic checkpoints / line images) and ``build`` / ``load_library``.
@@ -27,7 +31,7 @@ from . import preprocess, synth  # noqa: F401
 from ._lib import build, load as load_library  # noqa: F401
 from .codec import ArpaLM, ToyBigramLM, ZeroLM, ctc_codec  # noqa: F401
 from .ctc import (CTCAligner, CTCAlignment, CTCLoss, Evaluation, KeywordSpotter, LMSweep, LMSweepTotals, NBest,  # noqa: F401
-                  Recognition, Spotting)
+                  Lexicon, LexiconRecognizer, LexiconResult, Recognition, Spotting)
 from .model import hctr_model  # noqa: F401
 
 _EDIT_BOUND = None
@@ -44,4 +48,4 @@ def edit_distance(hyps, refs, device=0):
         _EDIT_BOUND = ctc._EngineBound().cuda(device)
     return ctc.edit_distance_sequences(_EDIT_BOUND._context(), list(hyps), list(refs), maps=False).edits
 
-__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "Recognition", "Evaluation", "NBest", "LMSweep", "LMSweepTotals", "KeywordSpotter", "Spotting", "edit_distance", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]
+__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "Recognition", "Evaluation", "NBest", "LMSweep", "LMSweepTotals", "KeywordSpotter", "Spotting", "Lexicon", "LexiconRecognizer", "LexiconResult", "edit_distance", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]

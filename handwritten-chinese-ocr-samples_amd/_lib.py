@@ -26,7 +26,8 @@ U8, F32, I64 = 0, 1, 2
 
 
 def _headers():
-    return [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "ngram_lm.h"), os.path.join(CSRC, "lm_flat.h"), HEADER]
+    return [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "ngram_lm.h"), os.path.join(CSRC, "lm_flat.h"),
+            os.path.join(CSRC, "lex_flat.h"), HEADER]
 
 
 def _deps():
@@ -174,6 +175,15 @@ SIGNATURES = [
     ("hctr_spot_logits", _I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_spot_automaton", _I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _VP, _VP]),
     ("hctr_spot_chunk_classes", _I, [_I, _I]),
+    # lexicon recognition: entries, entry_lengths, N, C, log_prior, unit_nodes, out
+    ("hctr_lex_build", _I, [_VP, _VP, _I, _I, _VP, _I, ctypes.POINTER(_VP)]),
+    ("hctr_lex_free", None, [_VP]),
+    ("hctr_lex_info", _I, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_lex_tables", _I, [_VP] * 15),
+    # ctx, lex, ..., input_lengths, n, top_entry, top_logp, top_rank, log_total, count, scores
+    ("hctr_lexicon", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_lexicon_logits", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("hctr_lexicon_chunk_classes", _I, [_I, _I]),
     ("hctr_recognize", _I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_recognize_logits", _I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_edit_distance", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP]),

@@ -247,6 +247,20 @@ class ctc_codec(object):
         split = np.split(flat, np.cumsum(ql)[:-1])
         return ctc.spot_logits(self._context(), logits, on_dev, split, input_lengths)
 
+    def lexicon(self, preds, lex, n=5, input_lengths=None, scores=False):
+        """Lexicon recognition of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) against ``lex``, a
+        ``ctc.Lexicon`` (built with ``codec=self`` from strings, or from label sequences). Returns ``(best_texts,
+        result)``: per line the best entry as text ('' where no entry fits) and the ``ctc.LexiconResult`` with the ``n``
+        best entries, their exact log-probabilities, ranks and posteriors (include/hctr_hip.h ``hctr_lexicon_logits``)."""
+        from . import ctc
+        logits, on_dev = self._as_logits(preds)
+        C = int(logits.shape[2])
+        if C != len(self.characters):
+            raise ValueError("logits have %d classes, codec has %d" % (C, len(self.characters)))
+        res = ctc.lexicon_logits(self._context(), logits, on_dev, lex, n, input_lengths, scores)
+        best = [[] if e < 0 else lex.labels[int(e)].tolist() for e in res.entries[:, 0]]
+        return self.labels_to_text(best), res
+
     def nbest(self, preds, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None, lm=None, lm_panelty=2.0,
               skip_search=False):
         """The ``n`` best texts of every line of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) with

@@ -5,12 +5,15 @@
 #include "kernels.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cfloat>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <iterator>
 #include <map>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -200,6 +203,9 @@ struct hctr_ctx {
     LmSlot* lm_slots = nullptr;
     int32_t* lm_words = nullptr;
     uint64_t lm_serial = 0;
+    // device copy of the most recently used hctr_lex (hctr_lexicon*): its unit tables in one block, likewise
+    int32_t* lex_dev = nullptr;
+    uint64_t lex_serial = 0;
 };
 
 namespace {
@@ -1565,6 +1571,196 @@ int spot_fetch(hctr_ctx* c, const SpotHost& h, const SpotDev& d, const SpotOut& 
 }
 
 // ---------------------------------------------------------------------------------------------
+// lexicon recognition (hctr_lexicon*): the device copy of the lexicon, the chunks of units that share one emission
+// pass, scratch
+// ---------------------------------------------------------------------------------------------
+// classes (blank included) one chunk of units may hold: HCTR_LEX_CLASSES, else what keeps the emissions of `lines`
+// lines of W columns within 4 GiB, at least 64. A single unit that exceeds it gets a chunk of its own. The spot
+// function's 256 MB (what the last-level cache holds) is the wrong budget here, by measurement: every
+// chunk costs one read of all logits and launches its units alone, and a class-rich lexicon's units hold thousands of
+// classes each, so the flagship shape ran one chunk per unit: 324 ms at 100 000 entries against 56 ms in one chunk.
+// 4 GiB holds every class of the flagship shape (64 x 2000 x 7358): the emissions then never exceed the logits' size.
+int lex_class_cap(int lines, int W) {
+    if (const char* e = getenv("HCTR_LEX_CLASSES")) {
+        const int v = atoi(e);
+        if (v >= 2) return v;
+    }
+    const int64_t rows = std::max<int64_t>(1, (int64_t)std::max(lines, 1) * std::max(W, 1));
+    return (int)std::min<int64_t>(1 << 20, std::max<int64_t>(64, ((int64_t)4 << 30) / (4 * rows)));
+}
+
+// the words of the device block: uoff | coff | node | kidx | eptr | elist | prior (float bits)
+struct LexLayout {
+    size_t uoff, coff, node, kidx, eptr, elist, prior, words;
+    explicit LexLayout(const hctr_lex& x) {
+        size_t o = 0;
+        auto take = [&](size_t n) { const size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
+        uoff = take(x.uoff.size()); coff = take(x.coff.size()); node = take(x.node.size()); kidx = take(x.kidx.size());
+        eptr = take(x.eptr.size()); elist = take(x.elist.size()); prior = take(x.prior.size());
+        words = o;
+    }
+};
+
+// the context's device copy of the call's lexicon: uploaded when the context holds another one (or none)
+int lex_on_device(hctr_ctx* c, const hctr_lex* x) {
+    if (c->lex_serial == x->serial) return HCTR_OK;
+    c->lex_serial = 0;
+    if (c->lex_dev) (void)hipFree(c->lex_dev);
+    c->lex_dev = nullptr;
+    const LexLayout lay(*x);
+    std::vector<int32_t> img(lay.words, 0);
+    std::copy(x->uoff.begin(), x->uoff.end(), img.begin() + lay.uoff);
+    std::copy(x->coff.begin(), x->coff.end(), img.begin() + lay.coff);
+    std::copy(x->node.begin(), x->node.end(), img.begin() + lay.node);
+    std::copy(x->kidx.begin(), x->kidx.end(), img.begin() + lay.kidx);
+    std::copy(x->eptr.begin(), x->eptr.end(), img.begin() + lay.eptr);
+    std::copy(x->elist.begin(), x->elist.end(), img.begin() + lay.elist);
+    memcpy(img.data() + lay.prior, x->prior.data(), x->prior.size() * 4);
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, lay.words * 4);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, HCTR_ERR_NOMEM, "no device memory for the lexicon tables (%zu bytes): %s", lay.words * 4,
+                    hipGetErrorString(e));
+    }
+    c->lex_dev = (int32_t*)p;
+    HIP_TRY(c, hipMemcpyAsync(p, img.data(), lay.words * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the image is this call's, the lexicon the caller's)
+    c->lex_serial = x->serial;
+    return HCTR_OK;
+}
+
+struct LexChunk {
+    int u0, nu, D;            // units [u0, u0 + nu), D emission slots (blank first)
+    size_t cls_off;           // words into LexHost::up: the chunk's class list [D]
+};
+
+struct LexHost {
+    const hctr_lex* lex = nullptr;
+    int B = 0, n = 0, Dmax = 1;
+    std::vector<LexChunk> chunks;
+    std::vector<int32_t> up;  // the call's one upload: T[B] | zero[B] | umap[coff[units]] | per chunk cls[D]
+    size_t umap_off = 0;
+};
+
+struct LexOut {               // the caller's host outputs; any may be null
+    int32_t* top_entry;
+    float* top_logp;
+    double* top_rank;
+    double* log_total;
+    int32_t* count;
+    float* scores;
+};
+
+int lex_prepare(hctr_ctx* c, const hctr_lex* lex, int B, int W, int C, const int32_t* input_lengths, int n,
+                int lines_per_launch, LexHost* h) {
+    if (!lex) return fail(c, HCTR_ERR_ARG, "lex is NULL");
+    if (lex->C != C) return fail(c, HCTR_ERR_ARG, "the lexicon was built for %d classes, the call has %d", lex->C, C);
+    if (n < 1 || n > kLexMaxTop) return fail(c, HCTR_ERR_ARG, "n=%d outside [1,%d]", n, kLexMaxTop);
+    if ((int64_t)std::max(B, 1) * lex->N > INT32_MAX) return fail(c, HCTR_ERR_ARG, "B*N=%lld too large", (long long)B * lex->N);
+    for (int b = 0; b < B && input_lengths; ++b)
+        if (input_lengths[b] < 1 || input_lengths[b] > W)
+            return fail(c, HCTR_ERR_ARG, "input_lengths[%d]=%d outside [1,%d]", b, input_lengths[b], W);
+    h->lex = lex; h->B = B; h->n = n;
+    std::vector<int32_t>& up = h->up;
+    up.assign((size_t)2 * B, 0);
+    for (int b = 0; b < B; ++b) up[(size_t)b] = input_lengths ? input_lengths[b] : W;
+    h->umap_off = up.size();
+    up.resize(up.size() + lex->ucls.size(), 0);
+    // chunks of consecutive units whose classes, with the blank, stay within the cap
+    const int cap = lex_class_cap(lines_per_launch, W), U = lex->units();
+    for (int u0 = 0; u0 < U;) {
+        std::vector<int32_t> uni{0};
+        int nu = 0;
+        while (u0 + nu < U) {
+            const int32_t *f = lex->ucls.data() + lex->coff[(size_t)u0 + nu], *l = lex->ucls.data() + lex->coff[(size_t)u0 + nu + 1];
+            std::vector<int32_t> merged;
+            std::set_union(uni.begin(), uni.end(), f, l, std::back_inserter(merged));
+            if (nu > 0 && (int)merged.size() > cap) break;
+            uni.swap(merged);
+            ++nu;
+        }
+        for (int u = u0; u < u0 + nu; ++u)
+            for (int32_t k = lex->coff[(size_t)u]; k < lex->coff[(size_t)u + 1]; ++k)
+                up[h->umap_off + (size_t)k] =
+                    (int32_t)(std::lower_bound(uni.begin(), uni.end(), lex->ucls[(size_t)k]) - uni.begin());
+        LexChunk ch{u0, nu, (int)uni.size(), up.size()};
+        up.insert(up.end(), uni.begin(), uni.end());
+        h->chunks.push_back(ch);
+        h->Dmax = std::max(h->Dmax, ch.D);
+        u0 += nu;
+    }
+    return HCTR_OK;
+}
+
+struct LexDev {
+    const int32_t* up = nullptr;
+    float *score = nullptr, *top_logp = nullptr, *emis = nullptr;
+    int32_t *top_entry = nullptr, *count = nullptr, *cls = nullptr, *nd = nullptr;
+    double *top_rank = nullptr, *log_total = nullptr;
+};
+
+// scratch of a lexicon call that launches nl lines at a time: the upload, the [B][N] scores, the ranking's results, the
+// per-line class tables of one chunk, nl*W*Dmax emissions
+int lex_scratch(hctr_ctx* c, const LexHost& h, int nl, int W, LexDev* d) {
+    const size_t B = (size_t)h.B, n = (size_t)h.n;
+    const size_t up_b = align256(h.up.size() * 4), sc_b = align256(B * h.lex->N * 4), top8 = align256(B * n * 8),
+                 top4 = align256(B * n * 4), b8 = align256(B * 8), b4 = align256(B * 4), cls_b = align256(B * h.Dmax * 4);
+    TRY(ctc_reserve(c, up_b + sc_b + top8 + 2 * top4 + b8 + 2 * b4 + cls_b + (size_t)nl * W * h.Dmax * 4));
+    char* p = c->ctc_buf;
+    d->up = (const int32_t*)p; p += up_b;
+    d->score = (float*)p; p += sc_b;
+    d->top_rank = (double*)p; p += top8;
+    d->top_entry = (int32_t*)p; p += top4;
+    d->top_logp = (float*)p; p += top4;
+    d->log_total = (double*)p; p += b8;
+    d->count = (int32_t*)p; p += b4;
+    d->nd = (int32_t*)p; p += b4;
+    d->cls = (int32_t*)p; p += cls_b;
+    d->emis = (float*)p;
+    HIP_TRY(c, hipMemcpyAsync(c->ctc_buf, h.up.data(), h.up.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return HCTR_OK;
+}
+
+// the lines [b0, b0 + nb) whose logit rows lie at x + (b*sb + t*st) * ld: per chunk the emissions, then the trie
+int lex_launch(hctr_ctx* c, const LexHost& h, const LexDev& d, const float* x, int64_t ld, int64_t sb, int64_t st, int C,
+               int b0, int nb, int W) {
+    Prof pf(c);
+    const hctr_lex& lx = *h.lex;
+    const LexLayout lay(lx);
+    const int32_t* t = c->lex_dev;
+    for (const LexChunk& ch : h.chunks) {
+        PROF_TRY(pf, "lexicon_classes", launch_lexicon_classes(d.up + ch.cls_off, ch.D, h.B, d.cls, d.nd, c->stream));
+        const CtcLines m{d.up, d.up + h.B, d.up + h.B, d.nd, d.cls, d.up + h.B, ch.D};
+        PROF_TRY(pf, "ctc_lse", launch_ctc_lse(x, ld, sb, st, C, m, b0, nb, W, d.emis, nullptr, c->stream));
+        const LexArgs a{d.emis, d.up, b0, nb, W, ch.D, t + lay.uoff, t + lay.coff, t + lay.node, t + lay.kidx, t + lay.eptr,
+                        t + lay.elist, d.up + h.umap_off, ch.u0, ch.nu, lx.max_unit, lx.N, d.score};
+        PROF_TRY(pf, "lexicon_trie", launch_lexicon_trie(a, c->stream));
+    }
+    return HCTR_OK;
+}
+
+// the ranking of every line once all scores are there, and the results to the host
+int lex_finish(hctr_ctx* c, const LexHost& h, const LexDev& d, const LexOut& o) {
+    Prof pf(c);
+    const hctr_lex& lx = *h.lex;
+    const float* prior = lx.has_prior ? (const float*)(c->lex_dev + LexLayout(lx).prior) : nullptr;
+    PROF_TRY(pf, "lexicon_rank", launch_lexicon_rank(d.score, prior, h.B, lx.N, h.n, d.top_entry, d.top_logp, d.top_rank,
+                                                     d.log_total, d.count, c->stream));
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    const size_t B = (size_t)h.B, n = (size_t)h.n;
+    HIP_TRY(c, fetch(o.top_entry, d.top_entry, B * n * 4));
+    HIP_TRY(c, fetch(o.top_logp, d.top_logp, B * n * 4));
+    HIP_TRY(c, fetch(o.top_rank, d.top_rank, B * n * 8));
+    HIP_TRY(c, fetch(o.log_total, d.log_total, B * 8));
+    HIP_TRY(c, fetch(o.count, d.count, B * 4));
+    HIP_TRY(c, fetch(o.scores, d.score, B * lx.N * 4));
+    return HCTR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // greedy recognition (hctr_recognize*)
 // ---------------------------------------------------------------------------------------------
 struct RecOut {              // the caller's host outputs, [B][W] / [B]; any may be null
@@ -2345,6 +2541,7 @@ void hctr_destroy(hctr_ctx* c) {
     if (c->ctc_buf) (void)hipFree(c->ctc_buf);
     if (c->lm_slots) (void)hipFree(c->lm_slots);
     if (c->lm_words) (void)hipFree(c->lm_words);
+    if (c->lex_dev) (void)hipFree(c->lex_dev);
     if (c->stamp_buf) (void)hipFree(c->stamp_buf);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -3284,6 +3481,103 @@ int hctr_spot_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W,
             TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
             TRY(spot_launch(c, h, d, dev, C, 1, B, C, 0, B, W));      // rows of the WBC tensor are r = t*B + b
             return spot_fetch(c, h, d, SpotOut{contain_logp, seg_logp, seg_start, seg_end});
+        }());
+    });
+}
+
+int hctr_lexicon_chunk_classes(int lines, int W) { return lex_class_cap(lines, W); }
+
+int hctr_lex_build(const int32_t* entries, const int32_t* entry_lengths, int N, int C, const float* log_prior,
+                   int unit_nodes, hctr_lex** out) {
+    if (out) *out = nullptr;
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!out) return fail(nullptr, HCTR_ERR_ARG, "hctr_lex_build: out is NULL");
+        static std::atomic<uint64_t> serial{0};
+        std::unique_ptr<hctr_lex> x(new hctr_lex());
+        std::string msg;
+        if (!lex_build(entries, entry_lengths, N, C, log_prior, unit_nodes, x.get(), &msg))
+            return fail(nullptr, HCTR_ERR_ARG, "%s", msg.c_str());
+        x->serial = ++serial;
+        *out = x.release();
+        return HCTR_OK;
+    });
+}
+
+void hctr_lex_free(hctr_lex* lex) { delete lex; }
+
+int hctr_lex_info(const hctr_lex* lex, int32_t* num_entries, int32_t* num_nodes, int32_t* num_units, int32_t* num_classes,
+                  int32_t* max_len) {
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!lex) return fail(nullptr, HCTR_ERR_ARG, "lex is NULL");
+        if (num_entries) *num_entries = lex->N;
+        if (num_nodes) *num_nodes = lex->nodes();
+        if (num_units) *num_units = lex->units();
+        if (num_classes) *num_classes = (int32_t)lex->classes.size();
+        if (max_len) *max_len = lex->max_len;
+        return HCTR_OK;
+    });
+}
+
+int hctr_lex_tables(const hctr_lex* lex, int32_t* parent, int32_t* label, int32_t* entry_node, int32_t* unit_off,
+                    int32_t* class_off, int64_t* unit_total, int64_t* class_total, int32_t* unit_node, int32_t* unit_word,
+                    uint8_t* unit_owned, int32_t* unit_kidx, int32_t* unit_class, int32_t* entry_ptr, int32_t* entry_list) {
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!lex) return fail(nullptr, HCTR_ERR_ARG, "lex is NULL");
+        auto put = [](auto* dst, const auto& v) { if (dst) std::copy(v.begin(), v.end(), dst); };
+        put(parent, lex->parent); put(label, lex->label); put(entry_node, lex->entry_node);
+        put(unit_off, lex->uoff); put(class_off, lex->coff);
+        if (unit_total) *unit_total = (int64_t)lex->gnode.size();
+        if (class_total) *class_total = (int64_t)lex->ucls.size();
+        put(unit_node, lex->gnode); put(unit_word, lex->node); put(unit_owned, lex->owned); put(unit_kidx, lex->kidx);
+        put(unit_class, lex->ucls); put(entry_ptr, lex->eptr); put(entry_list, lex->elist);
+        return HCTR_OK;
+    });
+}
+
+int hctr_lexicon(hctr_ctx* c, const hctr_lex* lex, const void* img, int img_dtype, int img_on_device,
+                 const int32_t* widths, int B, int W, const int32_t* input_lengths, int n, int32_t* top_entry,
+                 float* top_logp, double* top_rank, double* log_total, int32_t* count, float* scores) {
+    return guard(c, [&]() -> int {
+        TRY(check_forward_args(c, img, img_dtype, B, W));
+        LexHost h;
+        TRY(lex_prepare(c, lex, B, W, c->num_classes, input_lengths, n, B, &h));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        TRY(lex_on_device(c, lex));
+        const Batch in{img, img_dtype, img_on_device, widths, B, W};
+        LexDev d;
+        // PASS_EXACT as hctr_ctc_loss: mode 2's guard certifies argmaxes, not probabilities
+        return synced(c, [&]() -> int {
+            TRY(run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
+                if (p.first == 0) TRY(lex_scratch(c, h, p.nb, W, &d));       // no later pass is larger
+                TRY(forward_pass(c, in, p, HEAD_LOGITS));
+                return lex_launch(c, h, d, c->ws.logits, c->cpad, W, 1, c->num_classes, p.first, p.nb, W);
+            }));
+            return lex_finish(c, h, d, LexOut{top_entry, top_logp, top_rank, log_total, count, scores});
+        }());
+    });
+}
+
+int hctr_lexicon_logits(hctr_ctx* c, const hctr_lex* lex, const float* logits_wbc, int on_device, int W, int B, int C,
+                        const int32_t* input_lengths, int n, int32_t* top_entry, float* top_logp, double* top_rank,
+                        double* log_total, int32_t* count, float* scores) {
+    return guard(c, [&]() -> int {
+        TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
+        LexHost h;
+        TRY(lex_prepare(c, lex, B, W, C, input_lengths, n, B, &h));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
+        TRY(lex_on_device(c, lex));
+        std::vector<void*> tmp;
+        PoolGuard tmp_guard{tmp};
+        return synced(c, [&]() -> int {
+            LexDev d;
+            const float* dev = nullptr;
+            TRY(lex_scratch(c, h, B, W, &d));
+            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
+            TRY(lex_launch(c, h, d, dev, C, 1, B, C, 0, B, W));       // rows of the WBC tensor are r = t*B + b
+            return lex_finish(c, h, d, LexOut{top_entry, top_logp, top_rank, log_total, count, scores});
         }());
     });
 }

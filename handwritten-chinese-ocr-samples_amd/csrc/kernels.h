@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "lm_flat.h"
+#include "lex_flat.h"
 
 namespace hctr {
 
@@ -370,6 +371,33 @@ struct SpotArgs {
     int32_t* seg_end;
 };
 hipError_t launch_spot(const SpotArgs& a, hipStream_t s);
+
+// ---- lexicon recognition (hctr_lexicon*): the CTC forward over the trie of a lexicon, one workgroup per (line, unit)
+// over the emissions of launch_ctc_lse. The tables are those of lex_flat.h, flat over the units: unit u's local nodes are
+// [uoff[u], uoff[u + 1]) (local node 0 = the root), its classes [coff[u], coff[u + 1]). ----
+struct LexArgs {
+    const float* emis;        // [nb][W][D]
+    const int32_t* T;         // [B] columns that count, indexed by b0 + b
+    int b0, nb, W, D;
+    const int32_t* uoff;      // [units + 1]
+    const int32_t* coff;      // [units + 1]
+    const int32_t* node;      // [total] local parent | kLexSkip | kLexFirst
+    const int32_t* kidx;      // [total] place of the node's label in its unit's class list (0 = the blank)
+    const int32_t* eptr;      // [total + 1] the entries that end on an owned local node: elist[eptr[i] .. eptr[i + 1])
+    const int32_t* elist;
+    const int32_t* umap;      // [coff[units]] per call: the emission slot (of D) of every unit class in its chunk
+    int u0, nu, max_unit;     // the launch's units [u0, u0 + nu); the largest unit of the lexicon
+    int N;
+    float* score;             // [B][N]
+};
+hipError_t launch_lexicon_trie(const LexArgs& a, hipStream_t s);
+// cls[b][j] = list[j], nd[b] = D for b < B: the per-line tables launch_ctc_lse reads, for a chunk's class list
+hipError_t launch_lexicon_classes(const int32_t* list, int D, int B, int32_t* cls, int32_t* nd, hipStream_t s);
+// per line of score [B][N] (prior [N] or null): rank = (double)score + (double)prior; log_total; the n <= kLexMaxTop best
+// entries by (rank descending, index ascending) without those at -inf, unused places -1 / -inf; count
+constexpr int kLexMaxTop = 32;
+hipError_t launch_lexicon_rank(const float* score, const float* prior, int B, int N, int n, int32_t* top_entry,
+                               float* top_logp, double* top_rank, double* log_total, int32_t* count, hipStream_t s);
 
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {

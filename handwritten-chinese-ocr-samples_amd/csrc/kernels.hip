@@ -5,6 +5,7 @@
 #include "kernels.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstdlib>
 
 namespace hctr {
@@ -5069,6 +5070,223 @@ hipError_t launch_spot(const SpotArgs& a, hipStream_t s) {
         const dim3 grid((unsigned)((a.npairs + kSpotWaves - 1) / kSpotWaves), (unsigned)c.nb);
         hipLaunchKernelGGL(spot_kernel, grid, dim3(64 * kSpotWaves), 0, s, c);
     }
+    return hipGetLastError();
+}
+
+// -------------------------------------------------------------------------------------------
+// Lexicon recognition (hctr_lexicon*): the exact log p(entry | line) of every entry of a closed list at once, by one CTC
+// forward pass over the trie of the lexicon. The forward variable of an extended-target state depends only on the
+// labels up to it, so entries that share a prefix share that part of the recursion. Every trie node v has two states,
+// n_v (the last column emitted c_v) and b_v (the last column was a blank after the prefix):
+//   a'(n_v) = logsum3(a(n_v), a(b_p), [p != root and c_p != c_v] a(n_p)) + lp_t(c_v)
+//   a'(b_v) = logsum3(a(b_v), a(n_v), -inf) + lp_t(0)
+// which is the loss's recursion with the loss's ctc_logsum3 in the loss's argument order: a score has the bits of -nll
+// of ctc_alpha_kernel with the entry as the line's target. Within a step a node needs its own and its parent's previous
+// states only, so the step is parallel across the unit's nodes (the loss's recursion leaves the chip almost empty).
+// One workgroup per (line, unit of the partition, lex_flat.h); a thread keeps its NPT nodes' states in registers and
+// publishes them in LDS for its children, double-buffered: one barrier per step, 16 bytes of LDS per node. The emissions
+// of the next PF steps are in flight while a step is computed, as in ctc_forward_line. After step T - 1 every owned
+// node writes logadd(b_v, n_v) once per entry that ends on it: no atomics, and copies of ancestors write nothing.
+// -------------------------------------------------------------------------------------------
+constexpr int kLexPF = 4, kLexThreads = 1024;
+
+template <int NPT>
+__global__ __launch_bounds__(kLexThreads) void lexicon_trie_kernel(const LexArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float2* st = (float2*)smem;                           // [2][nn]: (n_v, b_v) of the previous and the current step
+    const int u = a.u0 + (int)blockIdx.x, b = blockIdx.y, gb = a.b0 + b;
+    const int T = max(a.T[gb], 1), D = a.D, tid = threadIdx.x, nt = blockDim.x;      // (the host admits T >= 1 only)
+    const int n0 = a.uoff[u], nn = min(a.uoff[u + 1] - n0, a.max_unit), c0 = a.coff[u];
+    const float* base = a.emis + (int64_t)b * a.W * D;
+    int par[NPT], slot[NPT];
+    bool skip[NPT], live[NPT];
+    float an[NPT], ab[NPT];
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+        const int v = tid + i * nt;
+        live[i] = v < nn;
+        const int w = live[i] ? a.node[n0 + v] : 0;
+        par[i] = min(w & kLexParMask, nn - 1);
+        skip[i] = (w & kLexSkip) != 0;
+        slot[i] = live[i] ? a.umap[c0 + a.kidx[n0 + v]] : 0;
+        an[i] = (w & kLexFirst) ? base[slot[i]] : -INFINITY;
+        ab[i] = v == 0 ? base[0] : -INFINITY;
+        if (live[i]) st[v] = make_float2(an[i], ab[i]);
+    }
+    float e[kLexPF][NPT], eb[kLexPF];
+#pragma unroll
+    for (int k = 0; k < kLexPF; ++k) {
+        const float* r = base + (int64_t)min(1 + k, T - 1) * D;
+        ctc_ring_load(r, slot, e[k]);
+        eb[k] = r[0];
+    }
+    __syncthreads();
+    for (int t0 = 1; t0 < T; t0 += kLexPF) {
+#pragma unroll
+        for (int k = 0; k < kLexPF; ++k) {
+            const int t = t0 + k;
+            if (t < T) {                                   // (block-uniform)
+                const float2* prev = st + ((t - 1) & 1) * nn;
+                float2* cur = st + (t & 1) * nn;
+#pragma unroll
+                for (int i = 0; i < NPT; ++i) {
+                    if (live[i]) {
+                        const int v = tid + i * nt;
+                        const float2 p = prev[par[i]];
+                        const float n1 = ctc_logsum3(an[i], p.y, skip[i] ? p.x : -INFINITY) + e[k][i];
+                        const float b1 = ctc_logsum3(ab[i], an[i], -INFINITY) + eb[k];
+                        an[i] = v == 0 ? -INFINITY : n1;   // the root has the blank state only
+                        ab[i] = b1;
+                        cur[v] = make_float2(an[i], ab[i]);
+                    }
+                }
+                __syncthreads();
+            }
+            const float* r = base + (int64_t)min(t + kLexPF, T - 1) * D;      // refill the slot just used
+            ctc_ring_load(r, slot, e[k]);
+            eb[k] = r[0];
+        }
+    }
+    float* out = a.score + (int64_t)gb * a.N;
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+        if (live[i]) {
+            const int v = n0 + tid + i * nt;
+            const int e0 = a.eptr[v], e1 = a.eptr[v + 1];
+            if (e0 < e1) {
+                const float sc = ctc_logadd(ab[i], an[i]);
+                for (int j = e0; j < e1; ++j) out[a.elist[j]] = sc;
+            }
+        }
+    }
+}
+
+template <int NPT>
+static hipError_t launch_lexicon_trie_t(const LexArgs& a, int threads, hipStream_t s) {
+    static bool raised[64] = {};
+    const int lds = 2 * a.max_unit * (int)sizeof(float2);
+    hipError_t e = raise_lds_limit((const void*)lexicon_trie_kernel<NPT>, 2 * kLexMaxUnit * (int)sizeof(float2), raised);
+    if (e != hipSuccess) return e;
+    for (int l0 = 0; l0 < a.nb; l0 += 65535) {            // (grid.y's limit)
+        LexArgs c = a;
+        c.b0 = a.b0 + l0;
+        c.nb = std::min(65535, a.nb - l0);
+        c.emis = a.emis + (int64_t)l0 * a.W * a.D;
+        hipLaunchKernelGGL(lexicon_trie_kernel<NPT>, dim3((unsigned)a.nu, (unsigned)c.nb), dim3(threads), lds, s, c);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_lexicon_trie(const LexArgs& a, hipStream_t s) {
+    if (a.nb <= 0 || a.nu <= 0) return hipSuccess;
+    if (a.D < 1 || a.W < 1 || a.N < 1 || a.max_unit < 2 || a.max_unit > kLexMaxUnit) return hipErrorInvalidValue;
+    if (a.max_unit <= kLexThreads) return launch_lexicon_trie_t<1>(a, (a.max_unit + 63) / 64 * 64, s);
+    if (a.max_unit <= 2 * kLexThreads) return launch_lexicon_trie_t<2>(a, kLexThreads, s);
+    return launch_lexicon_trie_t<4>(a, kLexThreads, s);
+}
+
+__global__ __launch_bounds__(256) void lexicon_classes_kernel(const int32_t* __restrict__ list, int D, int B,
+                                                              int32_t* __restrict__ cls, int32_t* __restrict__ nd) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < (int64_t)B * D) cls[i] = list[i % D];
+    if (i < B) nd[i] = D;
+}
+
+hipError_t launch_lexicon_classes(const int32_t* list, int D, int B, int32_t* cls, int32_t* nd, hipStream_t s) {
+    if (B <= 0 || D <= 0) return hipSuccess;
+    const int64_t n = (int64_t)B * D;
+    hipLaunchKernelGGL(lexicon_classes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, list, D, B, cls, nd);
+    return hipGetLastError();
+}
+
+// One workgroup per line. rank[e] = (double)score[e] + (double)prior[e]. log_total = max + log(sum of exp(rank - max)):
+// thread i of 256 adds its entries i, i + 256, .. in ascending order, the 256 partial sums are combined by block_sum_d
+// (a butterfly within each wave, then (w0 + w1) + (w2 + w3)): the order is a function of N alone. The n best are taken
+// one per round: every thread offers the best of its entries that come after the previous winner in the order (rank
+// descending, index ascending), and the block takes the best offer. No atomics.
+__global__ __launch_bounds__(256) void lexicon_rank_kernel(const float* __restrict__ score, const float* __restrict__ prior,
+                                                           int N, int n, int32_t* __restrict__ top_entry,
+                                                           float* __restrict__ top_logp, double* __restrict__ top_rank,
+                                                           double* __restrict__ log_total, int32_t* __restrict__ count) {
+    __shared__ double rd[4];
+    __shared__ double wr[4];
+    __shared__ int wi[4];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const float* sc = score + (int64_t)b * N;
+    auto rank = [&](int e) { return (double)sc[e] + (prior ? (double)prior[e] : 0.0); };
+    auto better = [](double r, int i, double r2, int i2) { return r > r2 || (r == r2 && i < i2); };
+    // every thread ends with the block's best (rank, index) offer
+    auto block_best = [&](double r, int i) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const double r2 = __shfl_xor(r, off);
+            const int i2 = __shfl_xor(i, off);
+            if (better(r2, i2, r, i)) {
+                r = r2;
+                i = i2;
+            }
+        }
+        __syncthreads();
+        if (lane == 0) {
+            wr[wv] = r;
+            wi[wv] = i;
+        }
+        __syncthreads();
+        r = wr[0];
+        i = wi[0];
+#pragma unroll
+        for (int w = 1; w < 4; ++w)
+            if (better(wr[w], wi[w], r, i)) {
+                r = wr[w];
+                i = wi[w];
+            }
+        return make_double2(r, (double)i);
+    };
+    double mx = -INFINITY;
+    for (int e = tid; e < N; e += 256) mx = fmax(mx, rank(e));
+    mx = block_best(mx, INT_MAX).x;
+    double sum = 0.0;
+    if (mx != -INFINITY)
+        for (int e = tid; e < N; e += 256) sum += exp(rank(e) - mx);
+    sum = block_sum_d(sum, rd);
+    if (tid == 0) log_total[b] = mx == -INFINITY ? -INFINITY : mx + log(sum);
+    double pr = INFINITY;
+    int pi = -1, got = 0;
+    for (int k = 0; k < n; ++k) {
+        double br = -INFINITY;
+        int bi = INT_MAX;
+        for (int e = tid; e < N; e += 256) {
+            const double r = rank(e);
+            if (r != -INFINITY && (r < pr || (r == pr && e > pi)) && better(r, e, br, bi)) {
+                br = r;
+                bi = e;
+            }
+        }
+        const double2 w = block_best(br, bi);
+        pr = w.x;
+        pi = (int)w.y;
+        const bool have = pi != INT_MAX;
+        if (tid == 0) {
+            top_entry[(int64_t)b * n + k] = have ? pi : -1;
+            top_logp[(int64_t)b * n + k] = have ? sc[pi] : -INFINITY;
+            top_rank[(int64_t)b * n + k] = have ? pr : -INFINITY;
+        }
+        if (!have) {                                       // (block-uniform) nothing is left: the later places are empty too
+            pr = -INFINITY;
+            pi = INT_MAX;
+        } else {
+            ++got;
+        }
+    }
+    if (tid == 0) count[b] = got;
+}
+
+hipError_t launch_lexicon_rank(const float* score, const float* prior, int B, int N, int n, int32_t* top_entry,
+                               float* top_logp, double* top_rank, double* log_total, int32_t* count, hipStream_t s) {
+    if (B <= 0) return hipSuccess;
+    if (N < 1 || n < 1 || n > kLexMaxTop) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(lexicon_rank_kernel, dim3((unsigned)B), dim3(256), 0, s, score, prior, N, n, top_entry, top_logp,
+                       top_rank, log_total, count);
     return hipGetLastError();
 }
 

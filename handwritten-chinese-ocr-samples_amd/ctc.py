@@ -321,6 +321,173 @@ def spot_chunk_classes(lines, W):
     return int(_lib.load().hctr_spot_chunk_classes(int(lines), int(W)))
 
 
+LEX_MAX_LEN = 64       # HCTR_LEX_MAX_LEN
+LEX_MAX_TOP = 32       # HCTR_LEX_MAX_TOP
+LEX_SKIP, LEX_FIRST, LEX_PARENT_MASK = 1 << 30, 1 << 29, 0xFFFF
+
+
+class Lexicon(object):
+    """A closed list of admissible texts for lexicon recognition (include/hctr_hip.h ``hctr_lex_build``): the trie of the
+    entries and its partition into units, built on the host (no GPU needed). ``entries``: strings when a ``codec`` is
+    given to encode them (a character outside its vocabulary is a ValueError), else label sequences of 1..64 labels in
+    [1, C-1], with ``num_classes`` = C (with a codec, its character count). ``priors``: one finite log prior per entry,
+    or None. ``unit_nodes``: trie nodes one workgroup holds (0 = the default; else 128..4096). Duplicates are separate
+    entries. The object is immutable and serves any number of contexts."""
+
+    def __init__(self, entries, codec=None, priors=None, unit_nodes=0, num_classes=None):
+        entries = list(entries)
+        self.texts = None
+        if codec is not None:
+            if any(not isinstance(s, str) for s in entries):
+                raise ValueError("with a codec the entries are strings")
+            flat, ln = codec.encode_queries(entries)
+            labels = np.split(np.asarray(flat, dtype=np.int32), np.cumsum(ln)[:-1]) if len(entries) else []
+            self.texts = entries
+            if num_classes is None:
+                num_classes = len(codec.characters)
+        else:
+            labels = [np.asarray(_host_int32(e, "entries")).reshape(-1) for e in entries]
+        if num_classes is None:
+            raise ValueError("num_classes is needed when the entries are label sequences")
+        if not labels:
+            raise ValueError("need at least one entry")
+        ln = np.array([e.size for e in labels], dtype=np.int32)
+        flat = np.concatenate(labels) if ln.sum() else np.zeros(0, np.int64)
+        if flat.size and (flat.min() < np.iinfo(np.int32).min or flat.max() > np.iinfo(np.int32).max):
+            raise ValueError("label out of the int32 range")
+        flat = np.ascontiguousarray(flat, dtype=np.int32)
+        pr = None
+        if priors is not None:
+            pr = np.ascontiguousarray(np.asarray(priors, dtype=np.float64).reshape(-1), dtype=np.float32)
+            if pr.shape != (len(labels),):
+                raise ValueError("priors must have one value per entry")
+        self.labels = [np.asarray(e, dtype=np.int32) for e in labels]
+        self.priors = pr
+        self.num_classes = int(num_classes)
+        lib = _lib.load()
+        h = ctypes.c_void_p()
+        rc = lib.hctr_lex_build(_lib.ptr(flat), _lib.ptr(ln), len(labels), self.num_classes, _lib.ptr(pr), int(unit_nodes),
+                                ctypes.byref(h))
+        self._h = h if rc == 0 else None
+        _lib.check(rc, None)
+
+    def __len__(self):
+        return len(self.labels)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _lib.load().hctr_lex_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def entry(self, e):
+        """entry e as the caller gave it: its string (built with a codec) or its labels as a list"""
+        return self.texts[e] if self.texts is not None else self.labels[e].tolist()
+
+    def info(self):
+        """dict: entries, nodes (the trie's, root included), units, classes (distinct), max_len"""
+        v = [ctypes.c_int32() for _ in range(5)]
+        _lib.check(_lib.load().hctr_lex_info(self._h, *[ctypes.byref(x) for x in v]), None)
+        return dict(zip(("entries", "nodes", "units", "classes", "max_len"), (int(x.value) for x in v)))
+
+    def tables(self):
+        """dict of numpy arrays: what ``hctr_lex_tables`` exports - the global trie (parent, label, entry_node) and the
+        unit tables the kernel is given (unit_off, class_off, unit_node, unit_word, unit_owned, unit_kidx, unit_class,
+        entry_ptr, entry_list)."""
+        lib, i = _lib.load(), self.info()
+        ut, ct = ctypes.c_int64(), ctypes.c_int64()
+        none = [None] * 7
+        _lib.check(lib.hctr_lex_tables(self._h, None, None, None, None, None, ctypes.byref(ut), ctypes.byref(ct), *none), None)
+        ut, ct = int(ut.value), int(ct.value)
+        t = {"parent": np.zeros(i["nodes"], np.int32), "label": np.zeros(i["nodes"], np.int32),
+             "entry_node": np.zeros(i["entries"], np.int32), "unit_off": np.zeros(i["units"] + 1, np.int32),
+             "class_off": np.zeros(i["units"] + 1, np.int32), "unit_node": np.zeros(ut, np.int32),
+             "unit_word": np.zeros(ut, np.int32), "unit_owned": np.zeros(ut, np.uint8), "unit_kidx": np.zeros(ut, np.int32),
+             "unit_class": np.zeros(ct, np.int32), "entry_ptr": np.zeros(ut + 1, np.int32),
+             "entry_list": np.zeros(i["entries"], np.int32)}
+        _lib.check(lib.hctr_lex_tables(self._h, _lib.ptr(t["parent"]), _lib.ptr(t["label"]), _lib.ptr(t["entry_node"]),
+                                       _lib.ptr(t["unit_off"]), _lib.ptr(t["class_off"]), None, None,
+                                       _lib.ptr(t["unit_node"]), _lib.ptr(t["unit_word"]), _lib.ptr(t["unit_owned"]),
+                                       _lib.ptr(t["unit_kidx"]), _lib.ptr(t["unit_class"]), _lib.ptr(t["entry_ptr"]),
+                                       _lib.ptr(t["entry_list"])), None)
+        return t
+
+
+class LexiconResult(object):
+    """Result of lexicon recognition of B lines against N entries (numpy arrays, on the host; include/hctr_hip.h
+    ``hctr_lexicon``): ``entries`` int32 [B, n], the best entries of each line in descending rank (ties to the lower
+    index; -1 in unused places); ``logp`` float32 [B, n], their exact log p(entry | line); ``rank`` float64 [B, n] =
+    logp + log prior; ``log_total`` float64 [B], the log of the lexicon's total mass on the line; ``count`` int32 [B];
+    ``scores`` float32 [B, N], every entry's logp, or None."""
+
+    def __init__(self, lex, entries, logp, rank, log_total, count, scores=None):
+        self.lex = lex
+        self.entries, self.logp, self.rank, self.log_total, self.count, self.scores = (entries, logp, rank, log_total,
+                                                                                       count, scores)
+
+    def __len__(self):
+        return int(self.entries.shape[0])
+
+    def posteriors(self):
+        """float64 [B, n]: exp(rank - log_total), the probability of each returned entry within the lexicon (0 in unused
+        places)"""
+        with np.errstate(invalid="ignore"):
+            p = np.exp(self.rank - self.log_total[:, None])
+        return np.where(self.entries >= 0, p, 0.0)
+
+    def best(self):
+        """per line the best entry as the lexicon was given it (a string or a label list), None where no entry fits"""
+        return [self.lex.entry(int(e)) if e >= 0 else None for e in self.entries[:, 0]]
+
+    def lines(self):
+        """yields per line the list of (entry_index, text_or_labels, logp, posterior) of its returned entries"""
+        post = self.posteriors()
+        for b in range(len(self)):
+            yield [(int(self.entries[b, k]), self.lex.entry(int(self.entries[b, k])), float(self.logp[b, k]),
+                    float(post[b, k])) for k in range(int(self.count[b]))]
+
+
+def _lexicon_outputs(lex, B, n, scores):
+    if not isinstance(lex, Lexicon):
+        raise ValueError("lex must be a ctc.Lexicon")
+    n = int(n)
+    if n < 1 or n > LEX_MAX_TOP:
+        raise ValueError("n must be in 1..%d, got %d" % (LEX_MAX_TOP, n))
+    return (np.full((B, n), -1, np.int32), np.full((B, n), -np.inf, np.float32), np.full((B, n), -np.inf, np.float64),
+            np.full(B, -np.inf, np.float64), np.zeros(B, np.int32),
+            np.full((B, len(lex)), -np.inf, np.float32) if scores else None)
+
+
+def lexicon_logits(ctx, logits, on_dev, lex, n=5, input_lengths=None, scores=False):
+    """LexiconResult of caller logits / log-probs in WBC layout (hctr_lexicon_logits)"""
+    W, B, C = (int(v) for v in logits.shape)
+    il = normalize_input_lengths(input_lengths, B)
+    ent, lp, rk, tot, cnt, sc = _lexicon_outputs(lex, B, n, scores)
+    if B and W:
+        _lib.check(_lib.load().hctr_lexicon_logits(ctx, lex._h, _lib.ptr(logits), on_dev, W, B, C, _lib.ptr(il), int(n),
+                                                   _lib.ptr(ent), _lib.ptr(lp), _lib.ptr(rk), _lib.ptr(tot), _lib.ptr(cnt),
+                                                   _lib.ptr(sc)), ctx)
+    return LexiconResult(lex, ent, lp, rk, tot, cnt, sc)
+
+
+def lexicon_images(ctx, x, dt, on_dev, widths, B, W, lex, n=5, input_lengths=None, scores=False):
+    """LexiconResult of line images (hctr_lexicon); x, dt, on_dev, widths as hctr_model._img_args / _widths give them."""
+    il = normalize_input_lengths(input_lengths, B)
+    ent, lp, rk, tot, cnt, sc = _lexicon_outputs(lex, B, n, scores)
+    if B:
+        _lib.check(_lib.load().hctr_lexicon(ctx, lex._h, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, _lib.ptr(il),
+                                            int(n), _lib.ptr(ent), _lib.ptr(lp), _lib.ptr(rk), _lib.ptr(tot), _lib.ptr(cnt),
+                                            _lib.ptr(sc)), ctx)
+    return LexiconResult(lex, ent, lp, rk, tot, cnt, sc)
+
+
+def lexicon_chunk_classes(lines, W):
+    """classes (blank included) one chunk of units may hold for `lines` lines of W columns (hctr_lexicon_chunk_classes)"""
+    return int(_lib.load().hctr_lexicon_chunk_classes(int(lines), int(W)))
+
+
 class Recognition(object):
     """Result of a greedy recognition of B lines of W steps (numpy arrays, on the host; include/hctr_hip.h
     ``hctr_recognize``): ``labels`` int32 [B, W] and ``lengths`` int32 [B], the decoded text as the greedy decode gives it
@@ -1032,6 +1199,28 @@ class KeywordSpotter(_EngineBound):
             log_probs = log_probs.detach()
         logits, on_dev = ctc_codec._as_logits(log_probs)
         return spot_logits(self._context(), logits, on_dev, queries, input_lengths)
+
+    __call__ = forward
+
+
+class LexiconRecognizer(_EngineBound):
+    """Lexicon recognition on the engine: ``LexiconRecognizer().cuda(0)(log_probs_or_logits, lex, n=5,
+    input_lengths=None, scores=False)`` with ``[T, B, C]`` input (numpy array or torch tensor, a CUDA tensor is read in
+    place) and ``lex`` a ``Lexicon`` returns the ``LexiconResult``: per line the ``n`` best entries with their exact
+    log p(entry | line), ranks and the lexicon's total mass. Only blank=0 is supported."""
+
+    def __init__(self, blank=0):
+        if blank != 0:
+            raise NotImplementedError("the engine's CTC kernels use blank = 0 (the reference's codec)")
+        _EngineBound.__init__(self)
+        self.blank = blank
+
+    def forward(self, log_probs, lex, n=5, input_lengths=None, scores=False):
+        from .codec import ctc_codec
+        if _is_torch(log_probs):
+            log_probs = log_probs.detach()
+        logits, on_dev = ctc_codec._as_logits(log_probs)
+        return lexicon_logits(self._context(), logits, on_dev, lex, n, input_lengths, scores)
 
     __call__ = forward
 

@@ -288,6 +288,18 @@ class hctr_model(object):
             queries = np.split(flat, np.cumsum(ql)[:-1])
         return ctc.spot_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, queries, input_lengths)
 
+    def lexicon(self, input, lex, n=5, widths=None, input_lengths=None, scores=False):
+        """Lexicon recognition of line images, the logits never leaving the device: which entry of the closed list
+        ``lex`` (a ``ctc.Lexicon``) each line is. Returns a ``ctc.LexiconResult`` (numpy arrays): the ``n`` best
+        ``entries`` [B, n] with their exact ``logp`` = log p(entry | line) - a sum over all CTC paths, unpruned -,
+        ``rank`` = logp + log prior, ``log_total`` and ``count`` [B], ``scores`` [B, N] when asked for; ``posteriors()``,
+        ``best()``, ``lines()``. ``input_lengths`` None = W for every line. In "auto" precision every line is scored in
+        f16x3 (include/hctr_hip.h ``hctr_lexicon``)."""
+        from . import ctc
+        ctx = self._require_ctx()
+        x, dt, on_dev, B, W = self._img_args(input)
+        return ctc.lexicon_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, lex, n, input_lengths, scores)
+
     def recognize(self, input, widths=None):
         """Forward + greedy decode with what an OCR interface reports beside the text, the logits never leaving the
         device: per character its pixel-column span, confidence and likeliest substitution, per line the greedy path's

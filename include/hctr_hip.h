@@ -292,6 +292,94 @@ int hctr_spot_automaton(const int32_t* query, int L, int32_t* classes, int32_t* 
                         int32_t* num_edges, uint64_t* fall_mask);
 int hctr_spot_chunk_classes(int lines, int W);
 
+/* ---- lexicon recognition on the device: which entry of a closed list a line is, how surely, and the runners-up ------
+ * Reading a field whose value comes from a list (place names, surnames, amounts, form options): the exact
+ * log p(entry | line) of EVERY entry at once, by one CTC forward pass over the trie of the lexicon. The reference has
+ * no counterpart. The free-text searches are pruned to each column's top-k classes and hctr_spot answers containment;
+ * this answers "the whole line is this text", unpruned.
+ * Lexicon: N >= 1 entries; entry e is a sequence of 1..HCTR_LEX_MAX_LEN labels in [1, C-1]; log_prior[e] float32,
+ *   finite (NULL = 0). Duplicates are allowed and are separate entries.
+ * Trie: node 0 is the root, plus one node per distinct non-empty prefix, numbered in the order in which inserting entry
+ *   0, 1, .. first reaches them (a parent has a lower number than its children). Node v has label c_v and parent p_v.
+ * States: every non-root node has n_v (the last column emitted c_v) and b_v (the last column was a blank after the
+ *   prefix); the root has b_0 only.
+ * Emissions: lp_t(c) = float32((double)z_t[c] - lse_t), the loss's, bit for bit. T = input_lengths[b] in [1, W], NULL = W.
+ *   t = 0:  a(b_0) = lp_0(0);  a(n_v) = lp_0(c_v) for the children of the root;  -inf elsewhere
+ *   t >= 1: a'(n_v) = logsum3(a(n_v), a(b_p), [p != root and c_p != c_v] a(n_p)) + lp_t(c_v)
+ *           a'(b_v) = logsum3(a(b_v), a(n_v), -inf) + lp_t(0)             (the root: a(b_0), -inf, -inf)
+ *   score[b][e] = logadd(a_{T-1}(b_v), a_{T-1}(n_v)) for v = the node where e ends
+ * in float32 with the loss's log-sum of three sorted arguments and its argument order. Hence
+ * - score[b][e] equals, bit for bit, -nll of hctr_ctc_loss_logits for line b with entry e as its target, and is -inf
+ *   exactly where the loss reports +inf (L + adjacent equal labels > T);
+ * - a pair's score bits depend on the line and the entry's own labels only: not on the other entries or their order, the
+ *   partition into units, the chunking of classes, host or device pointers, repetition. There are no atomics.
+ * Ranking: rank[b][e] = (double)score[b][e] + (double)log_prior[e]. The first n (1 <= n <= 32) entries in descending
+ *   rank, ties to the lower entry index, entries with rank -inf left out: top_entry int32 [B][n], top_logp float32 [B][n]
+ *   (their scores), top_rank float64 [B][n]; count[b] = how many were returned, the unused places hold -1 and -inf.
+ *   log_total[b] = log sum_e exp(rank[b][e]) in float64 as max + log(sum of exp(rank - max)): 256 partial sums, the i-th
+ *   over the entries i, i + 256, .. in ascending order, added up by a butterfly within each group of 64 (distances 32, 16,
+ *   .., 1) and then (g0 + g1) + (g2 + g3) - an order that is a function of N alone; -inf if no entry fits. The posterior
+ *   of an entry within the lexicon is exp(rank - log_total). scores: float32 [B][N], every score. All outputs are host
+ *   pointers and any may be NULL.
+ * hctr_lex_build (host only, no GPU, no context; errors are read with hctr_last_error(NULL)) builds the lexicon object:
+ *   entries int32, back to back, sum(entry_lengths) labels; entry_lengths int32 [N]; unit_nodes = 0 for the default
+ *   (4096), else in [128, 4096]. HCTR_ERR_ARG with a message for a label outside [1, C-1], a length outside [1, 64],
+ *   N < 1, a non-finite prior, unit_nodes outside its range; HCTR_ERR_NOMEM; no exception crosses the ABI. The object
+ *   is immutable and may serve any number of contexts; a context uploads its tables on first use, keeps the device copy
+ *   of the lexicon it used last (recognised by a serial number, not by address) and frees it with the context.
+ * Units: a unit is what one workgroup computes for one line: at most unit_nodes local nodes, local node 0 being the
+ *   root, stored parents before children. It consists of whole subtrees plus a private copy of each subtree root's
+ *   ancestor chain. Copies compute the same bits as the originals and only owned nodes report scores. The root's
+ *   children are walked in label order: a subtree that fits an empty unit together with its chain goes into the open
+ *   unit, or into a new one when the open one lacks the room; a larger subtree places its root alone and is split among
+ *   its children, in label order, by the same rule.
+ * hctr_lex_info: N, the trie's nodes (root included), units, distinct classes, the longest entry.
+ * hctr_lex_tables exports what the kernel is given (any pointer may be NULL; call once for the totals):
+ *   parent, label [nodes] (parent[0] = -1, label[0] = 0); entry_node [N];
+ *   unit_off, class_off [units + 1]: unit u's local nodes are [unit_off[u], unit_off[u+1]), its classes
+ *   [class_off[u], class_off[u+1]); unit_total = unit_off[units], class_total = class_off[units];
+ *   unit_node [unit_total]: the trie node of a local node; unit_word [unit_total]: the index of its parent within the
+ *   unit | HCTR_LEX_SKIP (n_p feeds n_v) | HCTR_LEX_FIRST (the parent is the root); unit_owned [unit_total]: 1 = owned,
+ *   0 = a copy; unit_kidx [unit_total]: the place of the node's label in the unit's class list; unit_class
+ *   [class_total]: per unit 0 (the blank), then its labels ascending; entry_ptr [unit_total + 1], entry_list [N]: the
+ *   entries that end on an owned local node i are entry_list[entry_ptr[i] .. entry_ptr[i+1]), ascending.
+ * Units are processed in chunks of consecutive units whose classes, blank included, number at most
+ * hctr_lexicon_chunk_classes(lines, W) (what keeps the emissions within 4 GiB, at least 64 - every class of 64 lines x
+ * 2000 columns x 7358 classes, so the emissions never exceed the logits' own size there; the environment variable
+ * HCTR_LEX_CLASSES overrides it at every call; a single unit with more classes gets a chunk of its own); one pass over
+ * the logits per chunk writes the emissions its units read, and a chunk's units run in one launch.
+ * Errors of hctr_lexicon*: HCTR_ERR_ARG with a message for a NULL lex, a lexicon built for another C, n outside [1, 32],
+ * an input length outside [1, W]; B == 0 is a no-op.
+ * Device scratch (the context's grow-only CTC scratch; HCTR_ERR_NOMEM leaves the context usable): 4 * n*W*D emissions
+ * (n = B, or the lines of one pass for images; D = the largest chunk's classes) + 4 * B*N scores + 4 * B*D class tables
+ * + the ranking's results + 4 bytes per unit class; plus W*B*C floats for logits passed as a host pointer. The lexicon's
+ * device copy (about 16 bytes per local node + 8 per entry) is separate.
+ * Launches (hctr_last_profile): per chunk lexicon_classes, ctc_lse, lexicon_trie; then one lexicon_rank.
+ * hctr_lexicon runs the forward of img in internal passes on the stored-logits head exactly as hctr_ctc_loss does: mode 0
+ * f16, mode 1 f16x3, mode 2 EVERY line in f16x3, hctr_last_guard's figures left as they were. hctr_lexicon_logits takes
+ * caller logits or log-probs in WBC layout, host or device pointer, and needs no weights. */
+#define HCTR_LEX_MAX_LEN 64
+#define HCTR_LEX_MAX_TOP 32
+#define HCTR_LEX_SKIP (1 << 30)
+#define HCTR_LEX_FIRST (1 << 29)
+#define HCTR_LEX_PARENT_MASK 0xFFFF
+typedef struct hctr_lex hctr_lex;
+int hctr_lex_build(const int32_t* entries, const int32_t* entry_lengths, int N, int C, const float* log_prior,
+                   int unit_nodes, hctr_lex** out);
+void hctr_lex_free(hctr_lex* lex);
+int hctr_lex_info(const hctr_lex* lex, int32_t* num_entries, int32_t* num_nodes, int32_t* num_units, int32_t* num_classes,
+                  int32_t* max_len);
+int hctr_lex_tables(const hctr_lex* lex, int32_t* parent, int32_t* label, int32_t* entry_node, int32_t* unit_off,
+                    int32_t* class_off, int64_t* unit_total, int64_t* class_total, int32_t* unit_node, int32_t* unit_word,
+                    uint8_t* unit_owned, int32_t* unit_kidx, int32_t* unit_class, int32_t* entry_ptr, int32_t* entry_list);
+int hctr_lexicon(hctr_ctx* ctx, const hctr_lex* lex, const void* img, int img_dtype, int img_on_device,
+                 const int32_t* widths, int B, int W, const int32_t* input_lengths, int n, int32_t* top_entry,
+                 float* top_logp, double* top_rank, double* log_total, int32_t* count, float* scores);
+int hctr_lexicon_logits(hctr_ctx* ctx, const hctr_lex* lex, const float* logits_wbc, int on_device, int W, int B, int C,
+                        const int32_t* input_lengths, int n, int32_t* top_entry, float* top_logp, double* top_rank,
+                        double* log_total, int32_t* count, float* scores);
+int hctr_lexicon_chunk_classes(int lines, int W);
+
 /* ---- greedy recognition: the decoded text with per-character spans, confidences and runners-up -------------------
  * What hctr_greedy / hctr_decode_greedy_logits decode, plus the figures the CTC family above gives only for a
  * transcription the caller already knows - in one pass over the logits, without a Viterbi recursion: the greedy path is

@@ -47,7 +47,9 @@ def build_argparser():
     a.add_argument("--gpu", type=int, default=0)
     a.add_argument("-bm", "--benchmark-mode", dest="benchmark_mode", action="store_true")
     a.add_argument("-dm", "--decode-method", dest="decode_method", type=str, default="beam-search",
-                   choices=["greedy-search", "beam-search"])
+                   choices=["greedy-search", "beam-search", "lexicon"])
+    a.add_argument("--lexicon", dest="lexicon", type=str, default="",
+                   help="-dm lexicon: a text file with one admissible text per line")
     a.add_argument("-ss", "--skip-search", dest="skip_search", action="store_true")
     a.add_argument("-kp", "--kenlm-path", dest="kenlm_path", type=str, default="")
     a.add_argument("-utp", "--use-tfm-pred", dest="use_tfm_pred", action="store_true")
@@ -189,7 +191,20 @@ def build(args):
     return model, codec
 
 
-def recognise(model, codec, imgs, widths):
+def load_lexicon(path, codec):
+    """-dm lexicon --lexicon FILE: the closed list of admissible texts, one per line (empty lines are skipped)"""
+    import hctr_amd
+    if not path or not os.path.isfile(path):
+        raise FileNotFoundError("-dm lexicon needs --lexicon FILE with one entry per line")
+    with open(path, "r", encoding="utf-8") as f:
+        entries = [line.rstrip("\r\n") for line in f]
+    return hctr_amd.Lexicon([e for e in entries if e], codec=codec)
+
+
+def recognise(model, codec, imgs, widths, lexicon=None):
+    if lexicon is not None:                                     # the best entry of the list per image
+        res = model.lexicon(imgs, lexicon, n=1, widths=widths)
+        return [t if t is not None else "" for t in res.best()]
     if codec.use_beam_search and not codec.use_tfm_pred:
         fe = model.beam_frontend(imgs, k=min(codec.search_depth, model.noutput), widths=widths,
                                  want_candidates=codec.skip_search)
@@ -205,13 +220,14 @@ def test(args):
         return benchmark(model, codec, args)
     import hctr_amd
     pp = hctr_amd.preprocess
+    lexicon = load_lexicon(args.lexicon, codec) if args.decode_method == "lexicon" else None
     paths = list_inputs(args.input)
     batches = [paths[i * args.batch_size:(i + 1) * args.batch_size] for i in range(len(paths) // args.batch_size)]
     for i, (_, arrs) in enumerate(prefetched(batches, args.workers)):
         print("batch {} is being processed...".format(i))
         imgs, widths = pp.resize_lines(model, arrs, model.img_height, "test", "rgb", None, device_out=True)
         t0 = time.time()
-        result = recognise(model, codec, imgs, widths)
+        result = recognise(model, codec, imgs, widths, lexicon)
         dt = time.time() - t0
         print("max_width: {}, throughput: {} ms/img".format(int(widths.max()), dt / args.batch_size * 1000))
         print("predicted results: {}".format(result))

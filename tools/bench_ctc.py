@@ -85,7 +85,15 @@ times keyword spotting on the same caller logits (hctr_spot_logits, every output
 length 2-4, half of them drawn from the lines' greedy texts and half absent from every line, and in the same run the
 loss (hctr_ctc_loss_logits, each line's greedy text as its target), alternately after warm-up calls of each, medians.
 --layers adds the device time of the call's launches, which the engine sums per name over the chunks of queries
-(ctc_lse: one pass over the logits per chunk; spot: the recursions)."""
+(ctc_lse: one pass over the logits per chunk; spot: the recursions).
+
+    python tools/bench_ctc.py --lexicon [--entries 10000] [--unit-nodes 0] [--layers] ...
+
+times lexicon recognition on the same caller logits (hctr_lexicon_logits, the 5 best of every line fetched) against
+--entries synthetic entries of 2-6 labels, half of them cut from the lines' greedy texts, and in the same run the loss
+(hctr_ctc_loss_logits, each line's greedy text as its target), alternately after warm-up calls of each, medians with
+range, and the cost per (line, entry) next to the loss's per (line, target). --layers adds the device time of the call's
+launches, summed per name over the chunks of units (lexicon_classes, ctc_lse, lexicon_trie; lexicon_rank)."""
 import argparse
 import json
 import os
@@ -116,6 +124,9 @@ def main():
     ap.add_argument("--lm-sweep", action="store_true")
     ap.add_argument("--spot", action="store_true")
     ap.add_argument("--queries", type=int, default=16)
+    ap.add_argument("--lexicon", action="store_true")
+    ap.add_argument("--entries", type=int, default=10000)
+    ap.add_argument("--unit-nodes", type=int, default=0, help="--lexicon: trie nodes per workgroup (0 = the default)")
     ap.add_argument("--pairs", type=int, default=250)
     ap.add_argument("--host-lines", type=int, default=4)
     args = ap.parse_args()
@@ -143,6 +154,9 @@ def main():
         return
     if args.spot:
         print(json.dumps(spot(args, hctr_amd, m, imgs, labels, targets, tl)))
+        return
+    if args.lexicon:
+        print(json.dumps(lexicon(args, hctr_amd, m, imgs, labels, targets, tl)))
         return
     if args.evaluate:
         print(json.dumps(evaluate(args, hctr_amd, m, imgs, labels)))
@@ -388,6 +402,77 @@ def spot(args, hctr_amd, m, imgs, labels, targets, tl):
         m.set_profiling(False)
         rec["loss_only_layers_ms"] = {k: round(v, 4) for k, v in fprof.items()}
         rec["spot_layers_ms"] = {k: round(v, 4) for k, v in sprof.items()}
+    return rec
+
+
+def lexicon_entries(labels, C, N, seed=4):
+    """N entries of 2-6 labels: the even ones cut from the lines' texts (line k mod B), the odd ones random"""
+    rng = np.random.RandomState(seed)
+    out = []
+    for k in range(N):
+        n = int(rng.randint(2, 7))
+        text = labels[k % len(labels)]
+        if k % 2 == 0 and len(text) >= n:
+            at = int(rng.randint(0, len(text) - n + 1))
+            out.append([int(c) for c in text[at:at + n]])
+        else:
+            out.append([int(c) for c in rng.randint(1, C - 1, size=n)])
+    return out
+
+
+def lexicon(args, hctr_amd, m, imgs, labels, targets, tl):
+    import torch
+    rc = hctr_amd.LexiconRecognizer().attach(m)
+    mod = sys.modules[type(rc).__module__]
+    ctx = rc._context()
+    logits = m(imgs)                                             # device tensor [W, lines, C]
+    W, B, C = (int(v) for v in logits.shape)
+    t0 = time.perf_counter()
+    lex = mod.Lexicon(lexicon_entries(labels, C, args.entries), num_classes=C, unit_nodes=args.unit_nodes)
+    build_ms = 1e3 * (time.perf_counter() - t0)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def loss_only():
+        assert np.isfinite(mod.loss_logits(ctx, logits, 1, targets, tl, None)).all()
+
+    last = {}
+
+    def lexicon_all():
+        last["r"] = mod.lexicon_logits(ctx, logits, 1, lex, 5, None, False)
+        assert (last["r"].count > 0).all()
+
+    fns = (("loss_only", loss_only), ("lexicon", lexicon_all))
+    for _ in range(args.warmup):
+        for _, fn in fns:
+            fn()
+    ms = {k: [] for k, _ in fns}
+    for _ in range(args.steps):
+        for k, fn in fns:
+            ms[k].append(1e3 * timed(fn))
+    med = {k: float(np.median(v)) for k, v in ms.items()}
+    rec = {"mode": "lexicon", "lines": B, "width": W, "classes": C, "precision": args.precision, "build_ms": round(build_ms, 1),
+           "chunk_classes": mod.lexicon_chunk_classes(B, W), "unit_nodes": args.unit_nodes}
+    rec.update(lex.info())
+    for k, v in ms.items():
+        rec[k + "_ms"] = [round(x, 3) for x in v]
+        rec[k + "_ms_median"] = round(med[k], 3)
+    rec["lexicon_us_per_line_entry"] = round(1e3 * med["lexicon"] / (B * len(lex)), 5)
+    rec["loss_us_per_line_target"] = round(1e3 * med["loss_only"] / B, 3)
+    if args.layers:
+        m.set_profiling(True)
+        loss_only()
+        fprof = dict(m.last_profile())
+        lexicon_all()
+        lprof = dict(m.last_profile())
+        m.set_profiling(False)
+        rec["loss_only_layers_ms"] = {k: round(v, 4) for k, v in fprof.items()}
+        rec["lexicon_layers_ms"] = {k: round(v, 4) for k, v in lprof.items()}
     return rec
 
 
