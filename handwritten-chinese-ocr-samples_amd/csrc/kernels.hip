@@ -812,6 +812,7 @@ constexpr int kHaloBytes = kHaloRows * kHaloCols * 128;  // 46080
 constexpr int kHaloPieces = kHaloRows * kHaloCols / 8;   // 45 one-KiB DMA pieces
 constexpr int kHaloLds = 2 * 32768 + 2 * kHaloBytes;     // 157696
 
+template <bool SPLIT>
 __global__ __launch_bounds__(512) void conv3x3_halo_kernel(const ConvArgs a) {
     constexpr int WN = 2, WM = 4, JT = 8, BN = 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -981,7 +982,8 @@ __global__ __launch_bounds__(512) void conv3x3_halo_kernel(const ConvArgs a) {
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the last (redundant) DMA has landed
-    conv_epilogue<WN, WM, JT, false, false>(a, acc, smem, tid, lane, wn, wm, n0, mt, img, th, tw, th * 16 + wm * 4,
+    // (f16x3: the K loop above only sees Cin' = 3 * Cin; the epilogue has to write all three planes of the output)
+    conv_epilogue<WN, WM, JT, false, SPLIT>(a, acc, smem, tid, lane, wn, wm, n0, mt, img, th, tw, th * 16 + wm * 4,
                                             tw * 16);
 }
 
@@ -1753,15 +1755,19 @@ static hipError_t launch_conv_halo4(const ConvArgs& a0, hipStream_t s) {
     return a.split ? launch_conv_halo4_t<GEOM, true>(a, s) : launch_conv_halo4_t<GEOM, false>(a, s);
 }
 
-static hipError_t launch_conv_halo(const ConvArgs& a, hipStream_t s) {
+template <bool SPLIT>
+static hipError_t launch_conv_halo_t(const ConvArgs& a, hipStream_t s) {
     static bool done[64] = {};
-    hipError_t e0 = raise_lds_limit((const void*)conv3x3_halo_kernel, kHaloLds, done);
+    hipError_t e0 = raise_lds_limit((const void*)conv3x3_halo_kernel<SPLIT>, kHaloLds, done);
     if (e0 != hipSuccess) return e0;
     static const int dbg = env_dbg();
     ConvArgs b = a;
     b.dbg |= dbg;
-    hipLaunchKernelGGL(conv3x3_halo_kernel, dim3(a.mtiles * a.ntiles), dim3(512), kHaloLds, s, b);
+    hipLaunchKernelGGL(conv3x3_halo_kernel<SPLIT>, dim3(a.mtiles * a.ntiles), dim3(512), kHaloLds, s, b);
     return hipGetLastError();
+}
+static hipError_t launch_conv_halo(const ConvArgs& a, hipStream_t s) {
+    return a.split ? launch_conv_halo_t<true>(a, s) : launch_conv_halo_t<false>(a, s);
 }
 
 size_t conv_lds_bytes(ConvTile tile) {

@@ -7,6 +7,9 @@ only logits, scales and labels are compared. With HCTR_FUSE_SE=0 the SE statisti
 fail with its own message.
 With the argument "passes" (test_keyed_lines_in_several_passes): the five-line keyed case in contexts whose passes hold
 fewer than five lines, in f16 and in f16x3.
+With the argument "split" (test_split_kernel_families): f16x3 against the split oracle on the split-exact variants,
+whose activation lo planes and w_lo rows are not zero - fractional images at three widths and four weight-lo layers;
+the same rules for HCTR_WS_ALIAS=1 (no buffers) and HCTR_FUSE_SE=0 (no scales).
 Prints every difference (first differing element of each array) and exits with 1 if there is one."""
 import importlib
 import os
@@ -75,5 +78,29 @@ def several_passes():
     return 1 if failed else 0
 
 
+def split():
+    """f16x3 against the split oracle (exact_ckpt.forward_split) under the environment's kernel family: the fractional
+    images of split_child_cases() (activation lo planes), then the four weight-lo variants of split_child_layer_cases()"""
+    import exact_ckpt as ex
+    pkg = importlib.import_module("handwritten-chinese-ocr-samples_amd")
+    with_taps = os.environ.get("HCTR_WS_ALIAS", "") != "1"
+    with_scales = os.environ.get("HCTR_FUSE_SE", "") != "0"
+    runs = [("fractional images, seed %d, %d classes, %d lines x %d columns" % c, c[1], ex.cached_state_dict(c[1], c[0]),
+             ex.split_oracle_case(*c)) for c in ex.split_child_cases()]
+    runs += [("w_lo in %s, seed %d, %d classes" % (layer, seed, nc), nc, ex.split_layer_state_dict(nc, seed, layer),
+              ex.split_layer_oracle_case(seed, nc, layer)) for seed, nc, layer in ex.split_child_layer_cases()]
+    failed = False
+    for label, nc, sd, (x, logits, taps) in runs:
+        model = pkg.hctr_model(nc, precision="f16x3").cuda(0)
+        model.load_state_dict(sd)
+        diffs = ex.engine_differences(model, x, logits, taps, with_taps=with_taps, with_scales=with_scales)
+        del model
+        print("%s: %s" % (label, "equal" if not diffs else "DIFFERENT"), flush=True)
+        for d in diffs:
+            print("  " + d, flush=True)
+        failed = failed or bool(diffs)
+    return 1 if failed else 0
+
+
 if __name__ == "__main__":
-    sys.exit(several_passes() if sys.argv[1:] == ["passes"] else main())
+    sys.exit(several_passes() if sys.argv[1:] == ["passes"] else split() if sys.argv[1:] == ["split"] else main())

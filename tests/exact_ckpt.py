@@ -40,6 +40,29 @@ The construction (keys and shapes: the reference checkpoint schema, from synth.c
                 bias included, half the class count above: the row maximum of every column is then tied exactly,
                 between classes that lie in different parts of the head's class tiling (a very narrow image leaves
                 most of the trunk at its biases, so nothing less makes sure of a tie there)
+
+Split-exact: the f16x3 lo planes. On the checkpoint above every activation lo plane and every w_lo row of the f16x3
+mode (products w_hi*x_hi + w_hi*x_lo + w_lo*x_hi over [x_hi | x_lo | x_hi] planes and [w_hi | w_hi | w_lo] rows) holds
+zeros, so two of the three products are never looked at. Two variants fill them and stay exact. The bit budget: the
+integer forward stays below about 620 in magnitude (10 bits), fp32 sums hold 24 bits, so 12 bits are free below the
+binary point (2^-12 >= fp16's smallest normal 2^-14: no subnormals); a value with 12 fraction bits and a magnitude
+under 2048 is hi + lo of two fp16 values exactly, so r_split(v) = f16(v) + f16(v - f16(v)) is the identity where f16(v)
+is not, and an engine that forms the right three products EQUALS forward_split here, while one that gets a lo term
+wrong cannot (forward_f16, which has no lo, differs in most logits).
+  A, activations  (make_split_images) pixel = integer + j * 2^-12, j hashed in [0, 4096); the weights stay integers, so
+                w_lo = 0 and the dropped lo*lo term is exactly 0. Every activation from the stem on is a multiple of
+                2^-12: conv1 has +-1 weights, conv2 +-2 and the SE scales are 0.5 or 1.0, so the quantum survives every
+                block, and about half of the nonzero values of every tap have lo != 0.
+  B, weights    (split_layer_state_dict) integer images, and ONE layer's BatchNorm weight 1 + 2^-12 on the channels
+                0 mod 4, 1 - 2^-12 on the channels 1 mod 4, 1 elsewhere: its folded weights have hi = +-1 / +-2 and
+                lo = +-2^-12 / +-2^-11 on half of the output channels. Its input holds integers (x_lo = 0, lo*lo = 0
+                again), every layer after it sees nonzero activation lo planes under integer weights as in A. The head
+                ("linear"): linear.weight times 1 +- 2^-12 per input FEATURE (even +, odd -), which keeps the repeated
+                rows that tie every column's maximum. One layer per checkpoint: a fractional layer costs 12 of the 14
+                free bits (2^24 / 620 leaves 14), and hi has to stay +-1 or +-2. SPLIT_LAYERS: every BatchNorm and the
+                head, 34 variants; f = 12 holds for every one of them (tests/test_exact_ckpt_host.py), f = 13 is not used.
+What is NOT exact in these variants: the image-wide sums behind the SE means (the scales still saturate to exactly
+0.5 / 1.0: the pre-sigmoid value is 0 or at least PRESIG_FLOOR) and f16 mode, whose roundings depend on the order.
 """
 import importlib
 
@@ -437,6 +460,219 @@ def keyed_oracle_case(seed, nc, B, W):
         logits = hctr_ref.forward_f16(keyed_state_dict(nc, seed, B, W), x, taps).numpy()
         _KEYED_CACHE[key] = (x, widths, logits, {k: v.numpy() for k, v in taps.items()})
     return _KEYED_CACHE[key]
+
+
+# ---- the split-exact variants: nonzero f16x3 lo planes (module docstring, "Split-exact") ----
+SPLIT_F = 12                   # the fraction's bits: images j * 2^-12, BatchNorm weights 1 +- 2^-12
+SPLIT_QUANTUM = 2.0 ** -SPLIT_F
+SPLIT_LAYERS = tuple(bk for _, bk, _, _, _, _ in synth.conv_specs()) + ("linear",)
+SPLIT_LAYER_SHAPE = (2, 33)    # B, W of the weight-lo cases (ragged)
+SPLIT_CHILD_LAYERS = ("cnn.block2.1.bn1", "cnn.block3.2.bn2", "cnn.block3.0.downsample.1", "linear")
+# the taps in forward order, and for every BatchNorm key the first tap that carries its fraction
+TAP_ORDER = ("conv0_1", "stage0") + tuple(
+    t for s, nb in enumerate(synth.STAGE_BLOCKS, start=1)
+    for t in [n for i in range(nb) for n in ("block%d.%d.conv1" % (s, i), "block%d.%d" % (s, i))] + ["stage%d" % s])
+
+
+def first_fractional_tap(layer):
+    """the first tap of TAP_ORDER that holds fractions when BatchNorm ``layer`` carries 1 +- 2^-f (None: the head)"""
+    if layer == "linear":
+        return None
+    k = layer[4:]                                                    # without "cnn."
+    if k.startswith("bn0_"):
+        return "conv0_1" if k == "bn0_1" else "stage0"
+    if k.startswith("bn"):
+        return "stage" + k[2:]
+    blk, what = k.rsplit(".", 1) if not k.endswith(".downsample.1") else (k[:-len(".downsample.1")], "ds")
+    return blk + ".conv1" if what == "bn1" else blk
+
+
+def make_split_images(B, W, seed, widths=None):
+    """make_exact_images plus a hashed 12-bit fraction: float32 [B,1,128,W], pixel = integer in [-1, 2] + j * 2^-12
+    with j in [0, 4096). Replicate padding after the fraction is added."""
+    x = (_ints(seed, "images/%d/%d" % (B, W), B * synth.IMG_H * W, 4) - 1).astype(np.float32)
+    x += _ints(seed, "split/%d/%d" % (B, W), B * synth.IMG_H * W, 1 << SPLIT_F).astype(np.float32) * np.float32(SPLIT_QUANTUM)
+    return _replicate_pad(x.reshape(B, 1, synth.IMG_H, W), widths)
+
+
+def split_layer_state_dict(num_classes, seed, layer, f=SPLIT_F):
+    """cached_state_dict with ONE layer's folded weights given a low part; every other entry is the same array.
+    ``layer`` a BatchNorm key of synth.conv_specs(): its weight becomes 1 + 2^-f on the channels 0 mod 4, 1 - 2^-f on
+    the channels 1 mod 4 and stays 1 elsewhere. "linear": linear.weight times 1 + 2^-f on the even input features and
+    1 - 2^-f on the odd ones (per feature, so the repeated rows still tie every column's maximum)."""
+    key = ("split", num_classes, seed, layer, f)
+    if key not in _SD_CACHE:
+        if layer not in SPLIT_LAYERS:
+            raise ValueError(layer)
+        sd = dict(cached_state_dict(num_classes, seed))
+        e = np.float32(2.0 ** -f)
+        if layer == "linear":
+            g = np.where(np.arange(synth.FEAT) % 2 == 0, 1 + e, 1 - e).astype(np.float32)
+            sd["linear.weight"] = sd["linear.weight"] * g[None, :]
+        else:
+            g = sd[layer + ".weight"].copy()
+            g[0::4], g[1::4] = 1 + e, 1 - e
+            sd[layer + ".weight"] = g
+        _SD_CACHE[key] = sd
+    return _SD_CACHE[key]
+
+
+def split16(v):
+    """(hi, lo) of the f16x3 storage of a float32 tensor: hi = f16(v), lo = f16(v - hi)"""
+    hi = v.half().float()
+    return hi, (v - hi).half().float()
+
+
+def r_split(v):
+    """what the two planes of the f16x3 storage add up to: f16(v) + f16(v - f16(v))"""
+    hi, lo = split16(v)
+    return hi + lo
+
+
+_SPLIT_FOLD_CACHE = {}
+
+
+def folded_split(sd, ck, bk):
+    """(w_hi, w_lo, bias) of a folded conv as the f16x3 weight rows hold it: the fold in float64, hi its fp16 value,
+    lo the fp16 value of the rest (csrc/engine.cpp build_conv); the bias fp32. "linear": the fp32 weight split."""
+    import torch
+    from oracle import hctr_ref as R
+    key = (id(sd[ck + ".weight"]), id(sd[bk + ".weight"]), id(sd[bk + ".bias"]))
+    if key not in _SPLIT_FOLD_CACHE:
+        if ck == "linear":
+            w = R._t(sd, "linear.weight").double()
+            b = R._t(sd, "linear.bias")
+        else:
+            sc = R._t(sd, bk + ".weight").double() / torch.sqrt(R._t(sd, bk + ".running_var").double() + R.BN_EPS)
+            w = R._t(sd, ck + ".weight").double() * sc.view(-1, 1, 1, 1)
+            b = R._fold(sd, ck, bk, False)[1]
+        hi = w.float().half().double()
+        lo = (w - hi).float().half().float()
+        _SPLIT_FOLD_CACHE[key] = (hi.float(), lo, b, sd[ck + ".weight"], sd[bk + ".weight"], sd[bk + ".bias"])  # (ids stay taken)
+    return _SPLIT_FOLD_CACHE[key][:3]
+
+
+def forward_split(sd, x, taps=None, drop_lo_after_stem=False, fault=None):
+    """The f16x3 oracle: oracle/hctr_ref.py forward_f16 (fused-SE form, the same taps) with the engine's documented
+    f16x3 rounding points (DESIGN.md "Precision"). Every stored activation is r_split(v) where forward_f16 stores
+    f16(v); every folded weight is w_hi + w_lo; a product is w_hi*x_hi + w_hi*x_lo + w_lo*x_hi, the lo*lo term left
+    out, summed in fp32. conv0_1 is fp32 arithmetic on the fp32 image with fp32 weights, as in forward_f16.
+    ``drop_lo_after_stem``: every activation after stage0 is stored as f16(v) alone (what an engine without activation
+    lo planes would hold). ``fault(ck, x_hi, x_lo, w_hi, w_lo, bias, pad)`` may return the fp32 output of conv ``ck``
+    ("linear": [B, W, C]) in place of the right one: tests plant wrong terms with it."""
+    import torch
+    import torch.nn.functional as F
+    from oracle import hctr_ref as R
+
+    def store(v, stem=False):
+        return R._r16(v) if drop_lo_after_stem and not stem else r_split(v)
+
+    def conv(x, ck, bk, relu, pad, pool=False, stem=False):
+        w_hi, w_lo, b = folded_split(sd, ck, bk)
+        x_hi, x_lo = split16(x)
+        y = fault(ck, x_hi, x_lo, w_hi, w_lo, b, pad) if fault is not None else None
+        if y is None:
+            y = F.conv2d(x_hi + x_lo, w_hi, b, stride=1, padding=pad)
+            if bool(w_lo.any()):
+                y = y + F.conv2d(x_hi, w_lo, None, stride=1, padding=pad)
+        z = F.relu(y) if relu else y
+        return y, store(R._pool(z) if pool else z, stem)
+
+    with torch.no_grad():
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(np.ascontiguousarray(x))
+        w, b = R._fold(sd, "cnn.conv0_1", "cnn.bn0_1", False)
+        x = store(F.relu(F.conv2d(x.float(), w, b, stride=1, padding=1)), True)
+        if taps is not None:
+            taps["conv0_1"] = x
+        _, x = conv(x, "cnn.conv0_2", "cnn.bn0_2", True, 1, pool=True, stem=True)
+        if taps is not None:
+            taps["stage0"] = x
+        for s, nb in enumerate(R.STAGE_BLOCKS, start=1):
+            for i in range(nb):
+                p, nm = "cnn.block%d.%d" % (s, i), "block%d.%d" % (s, i)
+                _, t = conv(x, p + ".conv1", p + ".bn1", True, 1)
+                y32, o = conv(t, p + ".conv2", p + ".bn2", False, 1)
+                sc = F.relu(F.linear(y32.mean(dim=(2, 3)), R._t(sd, p + ".se.fc.0.weight")))
+                sc = torch.sigmoid(F.linear(sc, R._t(sd, p + ".se.fc.2.weight")))
+                r = x
+                if (p + ".downsample.0.weight") in sd:
+                    _, r = conv(x, p + ".downsample.0", p + ".downsample.1", False, 0)
+                x = store(F.relu(y32 * sc[:, :, None, None] + r))
+                if taps is not None:
+                    taps[nm + ".conv1"], taps[nm + ".conv2"], taps[nm] = t, o, x
+                    taps[nm + ".scale"], taps[nm + ".res"] = sc, r
+            _, x = conv(x, "cnn.conv%d" % s, "cnn.bn%d" % s, True, 1, pool=True)
+            if taps is not None:
+                taps["stage%d" % s] = x
+        x = x.flatten(1, 2).permute(0, 2, 1)
+        w_hi, w_lo, b = folded_split(sd, "linear", "linear")
+        x_hi, x_lo = split16(x)
+        y = fault("linear", x_hi, x_lo, w_hi, w_lo, b, 0) if fault is not None else None
+        if y is None:
+            y = F.linear(x_hi + x_lo, w_hi, b)
+            if bool(w_lo.any()):
+                y = y + F.linear(x_hi, w_lo)
+        return y.permute(1, 0, 2).contiguous()
+
+
+SPLIT_W1_SEED = 9
+
+
+def split_edge_cases():
+    """(seed, num_classes, B, W) of the activation-lo width sweep: edge_cases(), but for the seed of the two cases at
+    W = 1. A one-column image leaves two thirds of every 3x3 kernel on the zero padding, most of the deep trunk sits at
+    its integer biases, and with each of SEEDS some readable tap of stages 3 / 4 holds NO element with lo != 0 (seeds
+    0..39 tried: 9, 36 and 38 keep the host test's floor of 8 per (line, column) in every readable tap; 9 gives 10 for
+    one line and 9 for the ragged three)."""
+    return [(SPLIT_W1_SEED if W == 1 else seed, nc, B, W) for seed, nc, B, W in edge_cases()]
+
+
+def split_child_cases():
+    return child_cases()
+
+
+def split_layer_cases():
+    """(seed, num_classes, layer) of the weight-lo cases, every one at SPLIT_LAYER_SHAPE, ragged"""
+    return [(SEEDS[i % 3], CLASS_COUNTS[i % 2], layer) for i, layer in enumerate(SPLIT_LAYERS)]
+
+
+def split_child_layer_cases():
+    """the weight-lo cases every kernel family runs: a block conv1, a block conv2, a downsample and the head"""
+    return [c for c in split_layer_cases() if c[2] in SPLIT_CHILD_LAYERS]
+
+
+def split_input(seed, B, W):
+    """(images, widths or None) of an activation-lo case: case_input's shapes, make_split_images' pixels"""
+    widths = ragged_widths(B, W) if B > 1 else None
+    return make_split_images(B, W, seed, widths), widths
+
+
+_SPLIT_CACHE = {}
+_SPLIT_CACHE_MAX = 8           # (the taps of a case are some hundred kB per line and column)
+
+
+def _split_oracle(key, sd, x):
+    if key not in _SPLIT_CACHE:
+        taps = {}
+        logits = forward_split(sd, x, taps).numpy()
+        keep = {t for _, t in READABLE}
+        while len(_SPLIT_CACHE) >= _SPLIT_CACHE_MAX:
+            del _SPLIT_CACHE[next(iter(_SPLIT_CACHE))]
+        _SPLIT_CACHE[key] = (x, logits, {k: v.numpy() for k, v in taps.items() if k in keep or k.endswith(".scale")})
+    return _SPLIT_CACHE[key]
+
+
+def split_oracle_case(seed, nc, B, W):
+    """oracle_case for an activation-lo case: (images, logits [W,B,C], the taps engine_differences reads as numpy
+    arrays), the last few cases kept"""
+    return _split_oracle(("A", seed, nc, B, W), cached_state_dict(nc, seed), split_input(seed, B, W)[0])
+
+
+def split_layer_oracle_case(seed, nc, layer):
+    """oracle_case for a weight-lo case (integer images, SPLIT_LAYER_SHAPE, ragged)"""
+    B, W = SPLIT_LAYER_SHAPE
+    return _split_oracle(("B", seed, nc, layer), split_layer_state_dict(nc, seed, layer), case_input(seed, B, W)[0])
 
 
 # ---- comparing an engine with the oracle (tests/test_gpu_exact.py, tests/exact_child.py) ----

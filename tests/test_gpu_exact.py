@@ -8,6 +8,9 @@ buffer that can be read back, on the greedy labels, in every precision mode and 
 channel group, tap, pad column, pooled row, residual or scale channel is a mismatch of at least 0.5, however small its
 share of the logits; in the keyed cases, whose scale patterns differ from line to line, so is a wrong LINE. No assertion here has a tolerance, except the three derived bounds on the SE statistics of the
 synthetic (inexact) checkpoint at the end.
+On all of those every f16x3 lo plane and w_lo row holds zeros; the split-exact variants (images with a 12-bit
+fraction, one layer's folded weights with a low part) fill them and are still exact, so f16x3 must equal
+exact_ckpt.forward_split there, and a wrong lo term is a mismatch of at least 2^-12.
 """
 import os
 import subprocess
@@ -130,6 +133,85 @@ def test_keyed_lines_in_several_passes():
     from conftest import ROOT
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "exact_child.py"), "passes"], capture_output=True,
                        text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# The split-exact variants (tests/exact_ckpt.py, "Split-exact"): on the checkpoints above every activation lo plane and
+# every w_lo row of f16x3 holds zeros. Here they do not, and the forward is still exact: the oracle is
+# exact_ckpt.forward_split, and tests/test_exact_ckpt_host.py proves for every case that it equals forward() and a
+# float64 run bit for bit, and that the case cannot be passed without the lo terms. No tolerance anywhere. The SE means
+# are not asserted (their image-wide sums are not exact with a 2^-12 quantum; the scales saturate and are), nor is f16
+# mode (its roundings depend on the order of the sums here).
+# ------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ex.split_edge_cases(), ids=_ids)
+def test_split_widths_at_the_tile_edges(engines, case):
+    """f16x3 on images with a 12-bit fraction (activation lo planes in use from the stem on): logits, all sixteen
+    readable buffers (hi + lo) and the greedy labels equal the split oracle's at every tile-edge width, for one line
+    and a ragged batch of three; and the ragged batch again through the engine's own replicate padding."""
+    seed, nc, B, W = case
+    x, logits, taps = ex.split_oracle_case(*case)
+    model = engines(nc, seed, "f16x3")
+    diffs = ex.engine_differences(model, x, logits, taps)
+    assert not diffs, "\n".join(diffs)
+    if B > 1:
+        widths = ex.ragged_widths(B, W)
+        y = x.copy()
+        for b, wi in enumerate(widths):
+            y[b, 0, :, wi:] = 7.0
+        d = ex.first_difference("logits with widths=", model(y, widths=widths), logits, ("column", "line", "class"))
+        assert d is None, d
+
+
+@pytest.mark.parametrize("case", ex.split_child_cases(), ids=_ids)
+def test_split_auto_mode(engines, case):
+    """auto on the fractional images: the head's exact ties send every line to the f16x3 re-run, so what comes back is
+    the f16x3 result, equal to the split oracle's (the buffers hold the re-run)."""
+    seed, nc, B, W = case
+    x, logits, taps = ex.split_oracle_case(*case)
+    model = engines(nc, seed, "auto")
+    diffs = ex.engine_differences(model, x, logits, taps)
+    assert not diffs, "\n".join(diffs)
+    assert model.last_guard()["flagged"] == B
+
+
+@pytest.fixture(scope="module")
+def layer_engines(pkg):
+    """one f16x3 engine per class count for the weight-lo variants, given each variant's weights by load_state_dict"""
+    cache = {}
+
+    def get(nc):
+        if nc not in cache:
+            cache[nc] = pkg.hctr_model(nc, precision="f16x3").cuda(0)
+        return cache[nc]
+
+    yield get
+    cache.clear()
+
+
+@pytest.mark.parametrize("case", ex.split_layer_cases(), ids=lambda c: "seed%d-C%d-%s" % (c[0], c[1], c[2].replace("cnn.", "")))
+def test_split_weight_layer(layer_engines, case):
+    """f16x3 with ONE layer's folded weights carrying lo = +-2^-12 / +-2^-11 on half of its output channels (every
+    BatchNorm in turn, and the head), integer images, two ragged lines of 33 columns: logits, all sixteen buffers, the
+    SE scales of every block and the greedy labels equal the split oracle's. Pins the packer's w_lo row of that layer
+    and its pairing with the x_hi plane; every later layer runs on nonzero activation lo planes."""
+    seed, nc, layer = case
+    x, logits, taps = ex.split_layer_oracle_case(*case)
+    model = layer_engines(nc)
+    model.load_state_dict(ex.split_layer_state_dict(nc, seed, layer))
+    diffs = ex.engine_differences(model.eval(), x, logits, taps, with_scales=True)
+    assert not diffs, "\n".join(diffs)
+
+
+@pytest.mark.parametrize("env", VARIANTS, ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
+def test_split_kernel_families(env):
+    """Every alternative kernel family in f16x3 against the split oracle (tests/exact_child.py split): the fractional
+    images at three widths, and four weight-lo variants (a block conv1, a block conv2, a downsample, the head)."""
+    from conftest import ROOT
+    e = dict(os.environ)
+    e.update(env)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "exact_child.py"), "split"], env=e,
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
 
 
