@@ -27,7 +27,7 @@ U8, F32, I64 = 0, 1, 2
 
 def _headers():
     return [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "ngram_lm.h"), os.path.join(CSRC, "lm_flat.h"),
-            os.path.join(CSRC, "lex_flat.h"), HEADER]
+            os.path.join(CSRC, "lex_flat.h"), os.path.join(CSRC, "pat_flat.h"), HEADER]
 
 
 def _deps():
@@ -184,6 +184,15 @@ SIGNATURES = [
     ("hctr_lexicon", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_lexicon_logits", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_lexicon_chunk_classes", _I, [_I, _I]),
+    # pattern recognition: arcs_src, arcs_label, arcs_dst, num_arcs, finals, num_finals, num_states, C, out
+    ("hctr_pat_build", _I, [_VP, _VP, _VP, _I, _VP, _I, _I, _I, ctypes.POINTER(_VP)]),
+    ("hctr_pat_free", None, [_VP]),
+    ("hctr_pat_info", _I, [_VP] * 6),
+    ("hctr_pat_tables", _I, [_VP] * 10),
+    # ctx, pat, ..., input_lengths, logp, best_logp, path, labels, lengths, span_start, span_end, char_logp, text_nll
+    ("hctr_pattern", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _VP] + [_VP] * 9),
+    ("hctr_pattern_logits", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP] + [_VP] * 9),
+    ("hctr_pattern_group_lines", _I, [_I, _I, _I]),
     ("hctr_recognize", _I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_recognize_logits", _I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_edit_distance", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP]),

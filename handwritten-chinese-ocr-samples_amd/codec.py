@@ -261,6 +261,20 @@ class ctc_codec(object):
         best = [[] if e < 0 else lex.labels[int(e)].tolist() for e in res.entries[:, 0]]
         return self.labels_to_text(best), res
 
+    def pattern(self, preds, pat, input_lengths=None, full=True):
+        """Pattern-constrained recognition of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) against
+        ``pat``, a ``ctc.Pattern`` (``Pattern.compile(expr, self)`` or a DFA). Returns ``(texts, result)``: per line the
+        best reading that matches the pattern ('' where none does, and None for ``full=False``) and the
+        ``ctc.PatternResult`` with the probability that the line matches, spans and confidences (include/hctr_hip.h
+        ``hctr_pattern_logits``)."""
+        from . import ctc
+        logits, on_dev = self._as_logits(preds)
+        C = int(logits.shape[2])
+        if C != len(self.characters):
+            raise ValueError("logits have %d classes, codec has %d" % (C, len(self.characters)))
+        res = ctc.pattern_logits(self._context(), logits, on_dev, pat, input_lengths, full)
+        return (res.texts(self) if full else None), res
+
     def nbest(self, preds, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None, lm=None, lm_panelty=2.0,
               skip_search=False):
         """The ``n`` best texts of every line of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) with

@@ -206,6 +206,9 @@ struct hctr_ctx {
     // device copy of the most recently used hctr_lex (hctr_lexicon*): its unit tables in one block, likewise
     int32_t* lex_dev = nullptr;
     uint64_t lex_serial = 0;
+    // device copy of the most recently used hctr_pat (hctr_pattern*): its tables in one block, likewise
+    int32_t* pat_dev = nullptr;
+    uint64_t pat_serial = 0;
 };
 
 namespace {
@@ -1761,6 +1764,214 @@ int lex_finish(hctr_ctx* c, const LexHost& h, const LexDev& d, const LexOut& o) 
 }
 
 // ---------------------------------------------------------------------------------------------
+// pattern-constrained recognition (hctr_pattern*): the device copy of the pattern, the groups of lines that share one
+// block of emissions and backpointers, scratch
+// ---------------------------------------------------------------------------------------------
+// lines one group holds: HCTR_PAT_LINES, else what keeps a group's emissions (4*W*D bytes a line) and backpointers
+// (2*W*S bytes a line) within 2 GiB, at least 1. Results do not depend on it.
+constexpr int64_t kPatGroupBytes = (int64_t)2 << 30;
+int pat_group_lines(int S, int D, int W) {
+    if (const char* e = getenv("HCTR_PAT_LINES")) {
+        const int v = atoi(e);
+        if (v >= 1) return v;
+    }
+    const int64_t per = (int64_t)std::max(W, 1) * (4 * (int64_t)std::max(D, 1) + 2 * (int64_t)std::max(S, 1));
+    return (int)std::min<int64_t>(1 << 20, std::max<int64_t>(1, kPatGroupBytes / per));
+}
+
+// the words of the device block: slot | label | in_ptr | accept | start | cls (0, then the classes) | in_src (uint16)
+struct PatLayout {
+    size_t slot, label, in_ptr, accept, start, cls, in_src, words;
+    explicit PatLayout(const hctr_pat& x) {
+        size_t o = 0;
+        auto take = [&](size_t n) { const size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
+        slot = take(x.slot.size()); label = take(x.label.size()); in_ptr = take(x.in_ptr.size());
+        accept = take(x.accept.size()); start = take(x.start.size()); cls = take(x.classes.size() + 1);
+        in_src = take((x.in_src.size() + 1) / 2);
+        words = o;
+    }
+};
+
+// the context's device copy of the call's pattern: uploaded when the context holds another one (or none)
+int pat_on_device(hctr_ctx* c, const hctr_pat* x) {
+    if (c->pat_serial == x->serial) return HCTR_OK;
+    c->pat_serial = 0;
+    if (c->pat_dev) (void)hipFree(c->pat_dev);
+    c->pat_dev = nullptr;
+    const PatLayout lay(*x);
+    std::vector<int32_t> img(lay.words, 0);
+    std::copy(x->slot.begin(), x->slot.end(), img.begin() + lay.slot);
+    std::copy(x->label.begin(), x->label.end(), img.begin() + lay.label);
+    std::copy(x->in_ptr.begin(), x->in_ptr.end(), img.begin() + lay.in_ptr);
+    std::copy(x->accept.begin(), x->accept.end(), img.begin() + lay.accept);
+    std::copy(x->start.begin(), x->start.end(), img.begin() + lay.start);
+    std::copy(x->classes.begin(), x->classes.end(), img.begin() + lay.cls + 1);
+    memcpy(img.data() + lay.in_src, x->in_src.data(), x->in_src.size() * 2);
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, lay.words * 4);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, HCTR_ERR_NOMEM, "no device memory for the pattern tables (%zu bytes): %s", lay.words * 4,
+                    hipGetErrorString(e));
+    }
+    c->pat_dev = (int32_t*)p;
+    HIP_TRY(c, hipMemcpyAsync(p, img.data(), lay.words * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the image is this call's, the pattern the caller's)
+    c->pat_serial = x->serial;
+    return HCTR_OK;
+}
+
+struct PatOut {               // the caller's host outputs; any may be null
+    float *logp, *best;
+    int32_t *path, *labels, *lengths, *span_start, *span_end;
+    float *char_logp, *text_nll;
+    bool viterbi() const { return best || path || labels || lengths || span_start || span_end || char_logp || text_nll; }
+};
+
+struct PatHost {
+    const hctr_pat* pat = nullptr;
+    int B = 0, D = 1, group = 1;
+    bool vit = false;
+    std::vector<int32_t> up;      // the call's upload: T[B] | zero[B]
+    std::vector<uint8_t> nll_fix; // [B] text_nll: 0 = the kernel's, 1 = NaN (the text exceeds the loss's labels), 2 = +inf
+};
+
+int pat_prepare(hctr_ctx* c, const hctr_pat* pat, int B, int W, int C, const int32_t* input_lengths, const PatOut& o,
+                PatHost* h) {
+    if (!pat) return fail(c, HCTR_ERR_ARG, "pat is NULL");
+    if (pat->C != C) return fail(c, HCTR_ERR_ARG, "the pattern was built for %d classes, the call has %d", pat->C, C);
+    for (int b = 0; b < B && input_lengths; ++b)
+        if (input_lengths[b] < 1 || input_lengths[b] > W)
+            return fail(c, HCTR_ERR_ARG, "input_lengths[%d]=%d outside [1,%d]", b, input_lengths[b], W);
+    h->pat = pat; h->B = B; h->D = (int)pat->classes.size() + 1; h->vit = o.viterbi();
+    h->group = pat_group_lines(pat->S, h->D, W);
+    h->up.assign((size_t)2 * B, 0);
+    for (int b = 0; b < B; ++b) h->up[(size_t)b] = input_lengths ? input_lengths[b] : W;
+    h->nll_fix.assign((size_t)B, 0);
+    return HCTR_OK;
+}
+
+struct PatDev {
+    const int32_t* up = nullptr;
+    int32_t *cls = nullptr, *nd = nullptr, *endst = nullptr, *lengths = nullptr, *path = nullptr, *labels = nullptr,
+            *st = nullptr, *en = nullptr, *nll_tab = nullptr;
+    float *logp = nullptr, *best = nullptr, *nll = nullptr, *clp = nullptr, *lpv = nullptr, *emis = nullptr;
+    uint16_t* bp = nullptr;
+    int g = 1;                    // lines per group of this call's launches
+};
+
+// scratch of a pattern call that launches nl lines at a time, in groups of g = min(group, nl): the upload, the class
+// tables, the per-line and per-column results of all B lines, and per group the walk's scratch, the tables of the
+// decoded texts' loss, the emissions and the backpointers
+int pat_scratch(hctr_ctx* c, const PatHost& h, int nl, int W, PatDev* d) {
+    const size_t B = (size_t)h.B, g = (size_t)std::max(1, std::min(h.group, nl)), S = (size_t)h.pat->S;
+    const size_t up_b = align256(h.up.size() * 4), cls_b = align256(B * h.D * 4), b4 = align256(B * 4),
+                 col_b = h.vit ? align256(B * W * 4) : 0, lpv_b = h.vit ? align256(g * W * 4) : 0,
+                 tab_b = h.vit ? align256((3 * g + g * W) * 4) : 0, emis_b = align256(g * W * h.D * 4),
+                 bp_b = h.vit ? align256(g * W * S * 2) : 0;
+    TRY(ctc_reserve(c, up_b + cls_b + 6 * b4 + 5 * col_b + lpv_b + tab_b + emis_b + bp_b));
+    char* p = c->ctc_buf;
+    auto take = [&](size_t bytes) { char* r = p; p += bytes; return r; };
+    d->g = (int)g;
+    d->up = (const int32_t*)take(up_b);
+    d->cls = (int32_t*)take(cls_b);
+    d->nd = (int32_t*)take(b4);
+    d->logp = (float*)take(b4); d->best = (float*)take(b4); d->nll = (float*)take(b4);
+    d->endst = (int32_t*)take(b4); d->lengths = (int32_t*)take(b4);
+    d->path = (int32_t*)take(col_b); d->labels = (int32_t*)take(col_b); d->st = (int32_t*)take(col_b);
+    d->en = (int32_t*)take(col_b); d->clp = (float*)take(col_b);
+    d->lpv = (float*)take(lpv_b);
+    d->nll_tab = (int32_t*)take(tab_b);
+    d->emis = (float*)take(emis_b);
+    d->bp = (uint16_t*)take(bp_b);
+    HIP_TRY(c, hipMemcpyAsync(c->ctc_buf, h.up.data(), h.up.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return HCTR_OK;
+}
+
+// the loss of the decoded texts of the group's lines [gb0, gb0 + n), over the group's own emissions: the pattern's
+// classes hold every class a decoded text uses, so the loss's tables point into them and ctc_alpha reads what ctc_lse
+// wrote for the pattern - the loss's emissions, bit for bit. The labels must be on the host: drains the stream.
+int pat_text_nll(hctr_ctx* c, Prof& pf, PatHost& h, const PatDev& d, int gb0, int n, int W) {
+    std::vector<int32_t> lab((size_t)n * W), len((size_t)n), end((size_t)n);
+    HIP_TRY(c, hipMemcpyAsync(lab.data(), d.labels + (size_t)gb0 * W, lab.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(len.data(), d.lengths + gb0, len.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(end.data(), d.endst + gb0, end.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const hctr_pat& x = *h.pat;
+    std::vector<int32_t> tab((size_t)3 * n);
+    int max_states = 1;
+    for (int b = 0; b < n; ++b) {
+        const int L = std::min(std::max(len[(size_t)b], 0), W);
+        const bool none = end[(size_t)b] < 0, fits = 2 * (int64_t)L + 1 <= kCtcMaxStates;
+        h.nll_fix[(size_t)gb0 + b] = none ? 2 : fits ? 0 : 1;
+        const bool run = !none && fits;
+        tab[(size_t)b] = run ? h.up[(size_t)gb0 + b] : 0;             // T = 0: the kernel reads nothing of the line
+        tab[(size_t)n + b] = run ? L : 0;
+        tab[(size_t)2 * n + b] = (int32_t)(tab.size() - 3 * (size_t)n);
+        for (int j = 0; j < L && run; ++j) {
+            const int32_t cl = lab[(size_t)b * W + j];
+            tab.push_back(1 + (int32_t)(std::lower_bound(x.classes.begin(), x.classes.end(), cl) - x.classes.begin()));
+        }
+        if (run) max_states = std::max(max_states, 2 * L + 1);
+    }
+    HIP_TRY(c, hipMemcpyAsync(d.nll_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    const int32_t* t = d.nll_tab;
+    const CtcLines m{t, t + n, t + 2 * n, t, t, t + 3 * n, h.D};
+    PROF_TRY(pf, "ctc_alpha", launch_ctc_alpha(d.emis, m, 0, n, W, max_states, d.nll + gb0, nullptr, nullptr, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));          // (tab is this function's)
+    return HCTR_OK;
+}
+
+// the lines [b0, b0 + nb) whose logit rows lie at x + (b*sb + t*st) * ld, a group at a time: emissions, recursion, walk
+int pat_launch(hctr_ctx* c, PatHost& h, const PatDev& d, bool want_nll, const float* x, int64_t ld, int64_t sb, int64_t st,
+               int C, int b0, int nb, int W) {
+    Prof pf(c);
+    const hctr_pat& px = *h.pat;
+    const PatLayout lay(px);
+    const int32_t* t = c->pat_dev;
+    PROF_TRY(pf, "pattern_classes", launch_lexicon_classes(t + lay.cls, h.D, h.B, d.cls, d.nd, c->stream));
+    const CtcLines m{d.up, d.up + h.B, d.up + h.B, d.nd, d.cls, d.up + h.B, h.D};
+    for (int l0 = 0; l0 < nb; l0 += d.g) {
+        const int n = std::min(d.g, nb - l0), gb0 = b0 + l0;
+        PROF_TRY(pf, "ctc_lse", launch_ctc_lse(x + (int64_t)l0 * sb * ld, ld, sb, st, C, m, gb0, n, W, d.emis, nullptr,
+                                               c->stream));
+        const PatArgs a{d.emis, d.up, gb0, n, W, h.D, px.S, px.edges(), t + lay.slot, t + lay.label, t + lay.in_ptr,
+                        (const uint16_t*)(t + lay.in_src), t + lay.accept, t + lay.start, (int)px.accept.size(),
+                        (int)px.start.size(), d.bp, d.logp, d.best, d.endst};
+        PROF_TRY(pf, "pattern", launch_pattern(a, h.vit, c->stream));
+        if (!h.vit) continue;
+        const PatTraceArgs ta{d.emis, d.up, gb0, n, W, h.D, px.S, t + lay.slot, t + lay.label, d.bp, d.endst, d.lpv,
+                              d.path, d.labels, d.lengths, d.st, d.en, d.clp};
+        PROF_TRY(pf, "pattern_trace", launch_pattern_trace(ta, c->stream));
+        if (want_nll) TRY(pat_text_nll(c, pf, h, d, gb0, n, W));
+    }
+    return HCTR_OK;
+}
+
+int pat_finish(hctr_ctx* c, const PatHost& h, const PatDev& d, const PatOut& o, int W) {
+    auto fetch = [&](void* dst, const void* src, size_t bytes) {
+        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+    };
+    const size_t B = (size_t)h.B, cb = B * W * 4;
+    HIP_TRY(c, fetch(o.logp, d.logp, B * 4));
+    HIP_TRY(c, fetch(o.best, d.best, B * 4));
+    HIP_TRY(c, fetch(o.path, d.path, cb));
+    HIP_TRY(c, fetch(o.labels, d.labels, cb));
+    HIP_TRY(c, fetch(o.lengths, d.lengths, B * 4));
+    HIP_TRY(c, fetch(o.span_start, d.st, cb));
+    HIP_TRY(c, fetch(o.span_end, d.en, cb));
+    HIP_TRY(c, fetch(o.char_logp, d.clp, cb));
+    HIP_TRY(c, fetch(o.text_nll, d.nll, B * 4));
+    if (!o.text_nll) return HCTR_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (size_t b = 0; b < B; ++b) {
+        if (h.nll_fix[b] == 1) o.text_nll[b] = std::numeric_limits<float>::quiet_NaN();
+        if (h.nll_fix[b] == 2) o.text_nll[b] = std::numeric_limits<float>::infinity();
+    }
+    return HCTR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
 // greedy recognition (hctr_recognize*)
 // ---------------------------------------------------------------------------------------------
 struct RecOut {              // the caller's host outputs, [B][W] / [B]; any may be null
@@ -2542,6 +2753,7 @@ void hctr_destroy(hctr_ctx* c) {
     if (c->lm_slots) (void)hipFree(c->lm_slots);
     if (c->lm_words) (void)hipFree(c->lm_words);
     if (c->lex_dev) (void)hipFree(c->lex_dev);
+    if (c->pat_dev) (void)hipFree(c->pat_dev);
     if (c->stamp_buf) (void)hipFree(c->stamp_buf);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -3578,6 +3790,104 @@ int hctr_lexicon_logits(hctr_ctx* c, const hctr_lex* lex, const float* logits_wb
             TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
             TRY(lex_launch(c, h, d, dev, C, 1, B, C, 0, B, W));       // rows of the WBC tensor are r = t*B + b
             return lex_finish(c, h, d, LexOut{top_entry, top_logp, top_rank, log_total, count, scores});
+        }());
+    });
+}
+
+int hctr_pattern_group_lines(int S, int D, int W) { return pat_group_lines(S, D, W); }
+
+int hctr_pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const int32_t* arcs_dst, int num_arcs,
+                   const int32_t* finals, int num_finals, int num_states, int C, hctr_pat** out) {
+    if (out) *out = nullptr;
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!out) return fail(nullptr, HCTR_ERR_ARG, "hctr_pat_build: out is NULL");
+        static std::atomic<uint64_t> serial{0};
+        std::unique_ptr<hctr_pat> x(new hctr_pat());
+        std::string msg;
+        if (!pat_build(arcs_src, arcs_label, arcs_dst, num_arcs, finals, num_finals, num_states, C, x.get(), &msg))
+            return fail(nullptr, HCTR_ERR_ARG, "%s", msg.c_str());
+        x->serial = ++serial;
+        *out = x.release();
+        return HCTR_OK;
+    });
+}
+
+void hctr_pat_free(hctr_pat* pat) { delete pat; }
+
+int hctr_pat_info(const hctr_pat* pat, int32_t* dfa_states, int32_t* ctc_states, int32_t* num_edges, int32_t* num_classes,
+                  int32_t* max_in_degree) {
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!pat) return fail(nullptr, HCTR_ERR_ARG, "pat is NULL");
+        if (dfa_states) *dfa_states = pat->nQ;
+        if (ctc_states) *ctc_states = pat->S;
+        if (num_edges) *num_edges = pat->edges();
+        if (num_classes) *num_classes = (int32_t)pat->classes.size();
+        if (max_in_degree) *max_in_degree = pat->max_deg;
+        return HCTR_OK;
+    });
+}
+
+int hctr_pat_tables(const hctr_pat* pat, int32_t* state_label, int32_t* state_slot, int32_t* in_ptr, uint16_t* in_src,
+                    int32_t* classes, int32_t* num_accept, int32_t* accept, int32_t* num_start, int32_t* start) {
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!pat) return fail(nullptr, HCTR_ERR_ARG, "pat is NULL");
+        auto put = [](auto* dst, const auto& v) { if (dst) std::copy(v.begin(), v.end(), dst); };
+        put(state_label, pat->label); put(state_slot, pat->slot); put(in_ptr, pat->in_ptr); put(in_src, pat->in_src);
+        put(classes, pat->classes); put(accept, pat->accept); put(start, pat->start);
+        if (num_accept) *num_accept = (int32_t)pat->accept.size();
+        if (num_start) *num_start = (int32_t)pat->start.size();
+        return HCTR_OK;
+    });
+}
+
+int hctr_pattern(hctr_ctx* c, const hctr_pat* pat, const void* img, int img_dtype, int img_on_device,
+                 const int32_t* widths, int B, int W, const int32_t* input_lengths, float* logp, float* best_logp,
+                 int32_t* path, int32_t* labels, int32_t* lengths, int32_t* span_start, int32_t* span_end,
+                 float* char_logp, float* text_nll) {
+    return guard(c, [&]() -> int {
+        TRY(check_forward_args(c, img, img_dtype, B, W));
+        const PatOut o{logp, best_logp, path, labels, lengths, span_start, span_end, char_logp, text_nll};
+        PatHost h;
+        TRY(pat_prepare(c, pat, B, W, c->num_classes, input_lengths, o, &h));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        TRY(pat_on_device(c, pat));
+        const Batch in{img, img_dtype, img_on_device, widths, B, W};
+        PatDev d;
+        // PASS_EXACT as hctr_ctc_loss: mode 2's guard certifies argmaxes, not probabilities
+        return synced(c, [&]() -> int {
+            TRY(run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
+                if (p.first == 0) TRY(pat_scratch(c, h, p.nb, W, &d));       // no later pass is larger
+                TRY(forward_pass(c, in, p, HEAD_LOGITS));
+                return pat_launch(c, h, d, text_nll != nullptr, c->ws.logits, c->cpad, W, 1, c->num_classes, p.first,
+                                  p.nb, W);
+            }));
+            return pat_finish(c, h, d, o, W);
+        }());
+    });
+}
+
+int hctr_pattern_logits(hctr_ctx* c, const hctr_pat* pat, const float* logits_wbc, int on_device, int W, int B, int C,
+                        const int32_t* input_lengths, float* logp, float* best_logp, int32_t* path, int32_t* labels,
+                        int32_t* lengths, int32_t* span_start, int32_t* span_end, float* char_logp, float* text_nll) {
+    return guard(c, [&]() -> int {
+        TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
+        const PatOut o{logp, best_logp, path, labels, lengths, span_start, span_end, char_logp, text_nll};
+        PatHost h;
+        TRY(pat_prepare(c, pat, B, W, C, input_lengths, o, &h));
+        if (B == 0) return HCTR_OK;
+        HIP_TRY(c, hipSetDevice(c->device));
+        prof_reset(c);
+        TRY(pat_on_device(c, pat));
+        std::vector<void*> tmp;
+        PoolGuard tmp_guard{tmp};
+        return synced(c, [&]() -> int {
+            PatDev d;
+            const float* dev = nullptr;
+            TRY(pat_scratch(c, h, B, W, &d));
+            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
+            TRY(pat_launch(c, h, d, text_nll != nullptr, dev, C, 1, B, C, 0, B, W));      // rows of WBC: r = t*B + b
+            return pat_finish(c, h, d, o, W);
         }());
     });
 }

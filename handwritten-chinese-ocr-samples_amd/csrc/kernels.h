@@ -6,6 +6,7 @@
 
 #include "lm_flat.h"
 #include "lex_flat.h"
+#include "pat_flat.h"
 
 namespace hctr {
 
@@ -398,6 +399,46 @@ hipError_t launch_lexicon_classes(const int32_t* list, int D, int B, int32_t* cl
 constexpr int kLexMaxTop = 32;
 hipError_t launch_lexicon_rank(const float* score, const float* prior, int B, int N, int n, int32_t* top_entry,
                                float* top_logp, double* top_rank, double* log_total, int32_t* count, hipStream_t s);
+
+// ---- pattern-constrained recognition (hctr_pattern*): the CTC forward (sum) and Viterbi (max) recursions over the CTC
+// lift of a DFA (pat_flat.h), one workgroup per line over the emissions of launch_ctc_lse; then the walk back. ----
+struct PatArgs {
+    const float* emis;        // [nb][W][D]
+    const int32_t* T;         // [B] columns that count, indexed by b0 + b
+    int b0, nb, W, D, S, E;
+    const int32_t* slot;      // [S] emission slot of a state (0 = the blank)
+    const int32_t* label;     // [S] its class
+    const int32_t* in_ptr;    // [S + 1] state s is fed by in_src[in_ptr[s] .. in_ptr[s + 1]), sources ascending
+    const uint16_t* in_src;   // [E]
+    const int32_t* accept;    // [num_accept] ascending
+    const int32_t* start;     // [num_start] ascending
+    int num_accept, num_start;
+    uint16_t* bp;             // [nb][W][S] backpointers of the launch's lines (Viterbi only)
+    float* logp;              // [B], indexed by b0 + b, as are best and endst
+    float* best;
+    int32_t* endst;           // the best accepted path's last state, -1 = there is none
+};
+// viterbi = false: logp alone (no backpointers, best, endst), with the bits of the full launch's logp
+hipError_t launch_pattern(const PatArgs& a, bool viterbi, hipStream_t s);
+// whether launch_pattern stages the edge list of a pattern of S states and E edges in LDS
+bool pattern_edges_in_lds(int S, int E, bool viterbi);
+// the walk back from endst over bp, and what follows from the path, all [B][W] indexed by b0 + b: path = the class per
+// column (-1 for t >= T and for a line without an accepted path); labels / lengths = its collapse; span_start, span_end
+// = each character's first column and the column after its run; char_logp = the float32 sum of its emissions in
+// ascending t; zeros beyond lengths. lpv [nb][W] is scratch.
+struct PatTraceArgs {
+    const float* emis;
+    const int32_t* T;
+    int b0, nb, W, D, S;
+    const int32_t* slot;
+    const int32_t* label;
+    const uint16_t* bp;
+    const int32_t* endst;
+    float* lpv;
+    int32_t *path, *labels, *lengths, *span_start, *span_end;
+    float* char_logp;
+};
+hipError_t launch_pattern_trace(const PatTraceArgs& a, hipStream_t s);
 
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {

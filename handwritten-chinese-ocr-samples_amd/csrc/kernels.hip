@@ -5296,4 +5296,247 @@ hipError_t launch_lexicon_rank(const float* score, const float* prior, int B, in
     return hipGetLastError();
 }
 
+// -------------------------------------------------------------------------------------------
+// Pattern-constrained recognition (hctr_pattern*): the probability that a line's text matches a pattern, and the best
+// reading that does, by the CTC forward (sum) and Viterbi (max) recursions over the CTC lift of a deterministic finite
+// automaton (pat_flat.h). The automaton is deterministic, so every CTC path has one state sequence and both are exact.
+//   a_t(s) = logsum over the in-edges of a_{t-1}(src) + lp_t(label(s))
+//   v_t(s) = max    over the in-edges of v_{t-1}(src) + lp_t(label(s)), backpointer = the first maximal source
+// The n-ary log-sum: m = the float32 maximum of the sources; sum = the float64 sum, in edge order, of
+// (double)__expf(a(src) - m); the result is m + __logf((float)sum) in float32, -inf when m is. A state fed by one live
+// source keeps its value exactly (sum = 1).
+// One workgroup per line; thread i owns the states i, i + nt, .. (NPT of them). The step's states are published in LDS,
+// double-buffered - float2 (a, v) with VIT, float a without: one barrier per step. A state walks its in-edges twice over
+// the previous buffer (max and max-plus, then the sum). The emissions of the next PF steps are in flight while a step is
+// computed, as in ctc_forward_line. ELDS stages the edge list in LDS behind the states; otherwise it is read through L2.
+// With VIT every step writes one uint16 backpointer per state, coalesced; a state at -inf (and every state at t = 0)
+// stores its own index, so every stored backpointer is a valid state whatever the logits hold. No atomics; the final
+// reductions over the accepting states are thread 0's, in ascending state order.
+// -------------------------------------------------------------------------------------------
+constexpr int kPatThreads = 1024, kPatLds = 160 * 1024;
+
+template <bool VIT>
+struct PatState {
+    using type = float;
+    static __device__ __forceinline__ float make(float a, float) { return a; }
+};
+template <>
+struct PatState<true> {
+    using type = float2;
+    static __device__ __forceinline__ float2 make(float a, float v) { return make_float2(a, v); }
+};
+__device__ __forceinline__ float pat_a(float x) { return x; }
+__device__ __forceinline__ float pat_a(float2 x) { return x.x; }
+__device__ __forceinline__ float pat_v(float) { return -INFINITY; }
+__device__ __forceinline__ float pat_v(float2 x) { return x.y; }
+__device__ __forceinline__ float pat_lse(float m, double sum) { return m == -INFINITY ? -INFINITY : m + __logf((float)sum); }
+
+template <int NPT, bool VIT, bool ELDS>
+__global__ __launch_bounds__(kPatThreads) void pattern_kernel(const PatArgs a) {
+    using PS = PatState<VIT>;
+    using St = typename PS::type;
+    constexpr int PF = NPT >= 8 ? 1 : NPT >= 4 ? 2 : 4;      // ring depth: NPT * PF emissions in flight per thread
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    St* st = (St*)smem;                                   // [2][S]: the previous and the current step
+    const int S = a.S, D = a.D, b = blockIdx.x, gb = a.b0 + b, tid = threadIdx.x, nt = blockDim.x;
+    const int T = min(max(a.T[gb], 1), a.W);              // (the host admits 1 <= T <= W only)
+    const uint16_t* es = a.in_src;
+    if (ELDS) {
+        uint16_t* l = (uint16_t*)(smem + 2 * (size_t)S * sizeof(St));
+        for (int j = tid; j < a.E; j += nt) l[j] = a.in_src[j];
+        es = l;
+    }
+    const float* base = a.emis + (int64_t)b * a.W * D;
+    uint16_t* bpl = VIT ? a.bp + (int64_t)b * a.W * S : nullptr;
+    int slot[NPT];
+    unsigned edges[NPT];                                  // first edge (18 bits: E <= 2^18) | in-degree << 18 (<= 2^13)
+#pragma unroll
+    for (int i = 0; i < NPT; ++i) {
+        const int s = tid + i * nt;
+        const bool live = s < S;
+        slot[i] = live ? a.slot[s] : 0;
+        edges[i] = live ? (unsigned)a.in_ptr[s] | (unsigned)(a.in_ptr[s + 1] - a.in_ptr[s]) << 18 : 0u;
+        if (live) {
+            st[s] = PS::make(-INFINITY, -INFINITY);
+            if (VIT) bpl[s] = (uint16_t)s;
+        }
+    }
+    __syncthreads();
+    for (int j = tid; j < a.num_start; j += nt) {
+        const int s = min(max(a.start[j], 0), S - 1);
+        const float lp = base[a.slot[s]];
+        st[s] = PS::make(lp, lp);
+    }
+    float e[PF][NPT];
+#pragma unroll
+    for (int k = 0; k < PF; ++k) ctc_ring_load(base + (int64_t)min(1 + k, T - 1) * D, slot, e[k]);
+    __syncthreads();
+    for (int t0 = 1; t0 < T; t0 += PF) {
+#pragma unroll
+        for (int k = 0; k < PF; ++k) {
+            const int t = t0 + k;
+            if (t < T) {                                   // (block-uniform)
+                const St* prev = st + ((t - 1) & 1) * S;
+                St* cur = st + (t & 1) * S;
+#pragma unroll
+                for (int i = 0; i < NPT; ++i) {
+                    const int s = tid + i * nt;
+                    if (s < S) {
+                        const int e0 = (int)(edges[i] & 0x3FFFFu), e1 = e0 + (int)(edges[i] >> 18);
+                        float m = -INFINITY, vm = -INFINITY;
+                        int arg = s;
+#pragma unroll 2
+                        for (int j = e0; j < e1; ++j) {
+                            const int src = es[j];
+                            const St p = prev[src];
+                            m = fmaxf(m, pat_a(p));
+                            if (VIT && pat_v(p) > vm) {
+                                vm = pat_v(p);
+                                arg = src;
+                            }
+                        }
+                        double sum = 0.0;
+                        if (m != -INFINITY) {
+#pragma unroll 2
+                            for (int j = e0; j < e1; ++j) sum += (double)__expf(pat_a(prev[es[j]]) - m);
+                        }
+                        cur[s] = PS::make(pat_lse(m, sum) + e[k][i], vm + e[k][i]);
+                        if (VIT) bpl[(int64_t)t * S + s] = (uint16_t)arg;
+                    }
+                }
+                __syncthreads();
+            }
+            ctc_ring_load(base + (int64_t)min(t + PF, T - 1) * D, slot, e[k]);      // refill the slot just used
+        }
+    }
+    if (tid == 0) {
+        const St* fin = st + ((T - 1) & 1) * S;
+        float m = -INFINITY, vm = -INFINITY;
+        int arg = -1;
+        for (int j = 0; j < a.num_accept; ++j) {
+            const int s = min(max(a.accept[j], 0), S - 1);
+            const St p = fin[s];
+            m = fmaxf(m, pat_a(p));
+            if (VIT && pat_v(p) > vm) {
+                vm = pat_v(p);
+                arg = s;
+            }
+        }
+        double sum = 0.0;
+        if (m != -INFINITY)
+            for (int j = 0; j < a.num_accept; ++j) sum += (double)__expf(pat_a(fin[min(max(a.accept[j], 0), S - 1)]) - m);
+        a.logp[gb] = pat_lse(m, sum);
+        if (VIT) {
+            a.best[gb] = vm;
+            a.endst[gb] = arg;
+        }
+    }
+}
+
+static int pattern_npt(int S) { return S <= kPatThreads ? 1 : S <= 2 * kPatThreads ? 2 : S <= 4 * kPatThreads ? 4 : 8; }
+
+bool pattern_edges_in_lds(int S, int E, bool viterbi) {
+    return 2 * (int64_t)S * (viterbi ? 8 : 4) + 2 * (int64_t)E <= kPatLds;
+}
+
+template <int NPT, bool VIT, bool ELDS>
+static hipError_t launch_pattern_t(const PatArgs& a, hipStream_t s) {
+    static bool raised[64] = {};
+    const int threads = ((a.S + NPT - 1) / NPT + 63) / 64 * 64;
+    const int lds = 2 * a.S * (VIT ? 8 : 4) + (ELDS ? 2 * a.E : 0);
+    if (threads > kPatThreads || lds > kPatLds) return hipErrorInvalidValue;
+    hipError_t e = raise_lds_limit((const void*)pattern_kernel<NPT, VIT, ELDS>, kPatLds, raised);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((pattern_kernel<NPT, VIT, ELDS>), dim3((unsigned)a.nb), dim3(threads), lds, s, a);
+    return hipGetLastError();
+}
+
+template <int NPT>
+static hipError_t launch_pattern_n(const PatArgs& a, bool vit, hipStream_t s) {
+    const bool elds = pattern_edges_in_lds(a.S, a.E, vit);
+    if (vit) return elds ? launch_pattern_t<NPT, true, true>(a, s) : launch_pattern_t<NPT, true, false>(a, s);
+    return elds ? launch_pattern_t<NPT, false, true>(a, s) : launch_pattern_t<NPT, false, false>(a, s);
+}
+
+hipError_t launch_pattern(const PatArgs& a, bool viterbi, hipStream_t s) {
+    if (a.nb <= 0) return hipSuccess;
+    if (a.S < 1 || a.S > kPatMaxStates || a.E < a.S || a.E > kPatMaxEdges || a.D < 1 || a.W < 1 || a.num_accept < 1 ||
+        a.num_start < 1)
+        return hipErrorInvalidValue;
+    switch (pattern_npt(a.S)) {
+        case 1: return launch_pattern_n<1>(a, viterbi, s);
+        case 2: return launch_pattern_n<2>(a, viterbi, s);
+        case 4: return launch_pattern_n<4>(a, viterbi, s);
+        default: return launch_pattern_n<8>(a, viterbi, s);
+    }
+}
+
+// One workgroup per line. Thread 0 walks the backpointers from the end state down to column 0 and leaves the state of
+// every column in `path`; then all threads turn states into classes and fetch each column's emission; then thread 0
+// collapses the path into characters with their spans and the float32 sums of their emissions, in ascending t. The walk
+// is T dependent loads: serial by nature.
+__global__ __launch_bounds__(256) void pattern_trace_kernel(const PatTraceArgs a) {
+    const int b = blockIdx.x, gb = a.b0 + b, tid = threadIdx.x, W = a.W, S = a.S;
+    const int end = a.endst[gb];
+    const int T = end < 0 ? 0 : min(max(a.T[gb], 1), W);
+    int32_t* path = a.path + (int64_t)gb * W;
+    float* lpv = a.lpv + (int64_t)b * W;
+    if (tid == 0) {
+        const uint16_t* bp = a.bp + (int64_t)b * W * S;
+        int s = min(end, S - 1);
+        for (int t = T - 1; t >= 0; --t) {
+            path[t] = s;
+            s = min((int)bp[(int64_t)t * S + s], S - 1);
+        }
+    }
+    __syncthreads();
+    const float* base = a.emis + (int64_t)b * W * a.D;
+    for (int t = tid; t < W; t += 256) {
+        if (t < T) {
+            const int s = path[t];
+            path[t] = a.label[s];
+            lpv[t] = base[(int64_t)t * a.D + a.slot[s]];
+        } else {
+            path[t] = -1;
+        }
+        a.labels[(int64_t)gb * W + t] = 0;
+        a.span_start[(int64_t)gb * W + t] = 0;
+        a.span_end[(int64_t)gb * W + t] = 0;
+        a.char_logp[(int64_t)gb * W + t] = 0.f;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int n = 0, prev = 0;
+        float acc = 0.f;
+        const int64_t o = (int64_t)gb * W;
+        for (int t = 0; t < T; ++t) {
+            const int c = path[t];
+            if (c != prev && prev != 0) {                  // the run of `prev` ends before column t
+                a.span_end[o + n - 1] = t;
+                a.char_logp[o + n - 1] = acc;
+            }
+            if (c != 0 && c != prev) {
+                a.labels[o + n] = c;
+                a.span_start[o + n] = t;
+                acc = 0.f;
+                ++n;
+            }
+            if (c != 0) acc += lpv[t];
+            prev = c;
+        }
+        if (prev != 0) {
+            a.span_end[o + n - 1] = T;
+            a.char_logp[o + n - 1] = acc;
+        }
+        a.lengths[gb] = n;
+    }
+}
+
+hipError_t launch_pattern_trace(const PatTraceArgs& a, hipStream_t s) {
+    if (a.nb <= 0) return hipSuccess;
+    if (a.S < 1 || a.S > kPatMaxStates || a.D < 1 || a.W < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(pattern_trace_kernel, dim3((unsigned)a.nb), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace hctr

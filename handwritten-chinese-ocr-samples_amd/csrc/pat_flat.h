@@ -1,0 +1,183 @@
+// The pattern object behind the C ABI's hctr_pat (include/hctr_hip.h): a deterministic finite automaton over labels,
+// lifted to CTC, as the flat tables pattern_kernel is given. Host only and header only: engine.cpp builds it
+// (hctr_pat_build), tests read it back (hctr_pat_tables), and a stand-alone program can include it without the GPU
+// runtime.
+//
+// DFA: states 0..nQ-1 (0 = the start), arcs (src, label, dst) with at most one arc per (src, label), final states.
+// States that are not both reachable from state 0 and able to reach a final state are pruned with their arcs; the
+// survivors keep their relative order.
+// CTC states: beta_q = q, one per DFA state (the last column was a blank, or nothing was read, in DFA state q); then one
+// eps_(q,c) per distinct (destination q, label c) among the arcs, in ascending (q, c) (the last column emitted c and
+// the text read so far leads to q). Arcs (p,c,q) and (p',c,q) share eps_(q,c): their futures are the same.
+// In-edges, sorted by source ascending: beta_q <- beta_q, every eps_(q,.);  eps_(q,c) <- itself, beta_p for every arc
+// (p,c,q), and for each such p every eps_(p,c') with c' != c.
+#pragma once
+#include <stdint.h>
+
+#include <algorithm>
+#include <string>
+#include <utility>
+#include <vector>
+
+namespace hctr {
+
+constexpr int kPatMaxStates = 8192;              // HCTR_PAT_MAX_STATES
+constexpr int kPatMaxEdges = 262144;             // HCTR_PAT_MAX_EDGES
+
+}  // namespace hctr
+
+struct hctr_pat {
+    int C = 0, nQ = 0, S = 0, max_deg = 0;
+    uint64_t serial = 0;
+    std::vector<int32_t> classes;                // the distinct labels, ascending
+    std::vector<int32_t> label, slot;            // [S] label (0 = blank); its place in (0, classes..)
+    std::vector<int32_t> in_ptr;                 // [S + 1]
+    std::vector<uint16_t> in_src;                // [E] a state's sources, ascending
+    std::vector<int32_t> accept;                 // the accepting states, ascending
+    std::vector<int32_t> start;                  // beta_0, then the eps states of the arcs that leave state 0, ascending
+    int edges() const { return (int)in_src.size(); }
+};
+
+namespace hctr {
+
+// builds *out from checked arguments; false with a message for the caller's mistakes (std::bad_alloc passes through)
+inline bool pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const int32_t* arcs_dst, int num_arcs,
+                      const int32_t* finals, int num_finals, int num_states, int C, hctr_pat* out, std::string* msg) {
+    auto bad = [&](const std::string& m) { *msg = "hctr_pat_build: " + m; return false; };
+    auto str = [](int64_t v) { return std::to_string(v); };
+    if (num_arcs < 0 || num_finals < 0) return bad("negative count");
+    if (num_arcs > 0 && (!arcs_src || !arcs_label || !arcs_dst)) return bad("arcs_src / arcs_label / arcs_dst is NULL");
+    if (num_finals > 0 && !finals) return bad("finals is NULL");
+    if (C < 2) return bad("need C >= 2 classes, got C=" + str(C));
+    if (num_states < 1) return bad("need num_states >= 1, got " + str(num_states));
+    if (num_states > (1 << 24)) return bad("num_states=" + str(num_states) + " exceeds " + str(1 << 24));
+    const size_t nq0 = (size_t)num_states;
+    struct Arc { int32_t src, label, dst; };
+    std::vector<Arc> arcs((size_t)num_arcs);
+    for (int i = 0; i < num_arcs; ++i) {
+        const Arc a{arcs_src[i], arcs_label[i], arcs_dst[i]};
+        if (a.src < 0 || a.src >= num_states || a.dst < 0 || a.dst >= num_states)
+            return bad("arc " + str(i) + " (" + str(a.src) + " -> " + str(a.dst) + ") names a state outside [0," +
+                       str(num_states - 1) + "]");
+        if (a.label < 1 || a.label > C - 1)
+            return bad("label " + str(a.label) + " (arc " + str(i) + ") outside [1," + str(C - 1) + "]");
+        arcs[(size_t)i] = a;
+    }
+    std::sort(arcs.begin(), arcs.end(), [](const Arc& a, const Arc& b) {
+        return a.src != b.src ? a.src < b.src : a.label != b.label ? a.label < b.label : a.dst < b.dst;
+    });
+    for (size_t i = 1; i < arcs.size(); ++i)
+        if (arcs[i].src == arcs[i - 1].src && arcs[i].label == arcs[i - 1].label)
+            return bad("not deterministic: two arcs leave state " + str(arcs[i].src) + " on label " + str(arcs[i].label));
+    std::vector<uint8_t> fin(nq0, 0);
+    for (int i = 0; i < num_finals; ++i) {
+        if (finals[i] < 0 || finals[i] >= num_states)
+            return bad("finals[" + str(i) + "]=" + str(finals[i]) + " outside [0," + str(num_states - 1) + "]");
+        fin[(size_t)finals[i]] = 1;
+    }
+    // prune: forward from state 0, backward from the final states
+    std::vector<int32_t> optr(nq0 + 1, 0), iptr(nq0 + 1, 0), isrc(arcs.size());
+    for (const Arc& a : arcs) { ++optr[(size_t)a.src + 1]; ++iptr[(size_t)a.dst + 1]; }
+    for (size_t q = 0; q < nq0; ++q) { optr[q + 1] += optr[q]; iptr[q + 1] += iptr[q]; }
+    {
+        std::vector<int32_t> at(iptr.begin(), iptr.end() - 1);
+        for (const Arc& a : arcs) isrc[(size_t)at[(size_t)a.dst]++] = a.src;
+    }
+    std::vector<uint8_t> fwd(nq0, 0), bwd(nq0, 0);
+    std::vector<int32_t> stack{0};
+    fwd[0] = 1;
+    while (!stack.empty()) {
+        const int32_t q = stack.back();
+        stack.pop_back();
+        for (int32_t j = optr[(size_t)q]; j < optr[(size_t)q + 1]; ++j)
+            if (!fwd[(size_t)arcs[(size_t)j].dst]) { fwd[(size_t)arcs[(size_t)j].dst] = 1; stack.push_back(arcs[(size_t)j].dst); }
+    }
+    for (size_t q = 0; q < nq0; ++q)
+        if (fin[q]) { bwd[q] = 1; stack.push_back((int32_t)q); }
+    while (!stack.empty()) {
+        const int32_t q = stack.back();
+        stack.pop_back();
+        for (int32_t j = iptr[(size_t)q]; j < iptr[(size_t)q + 1]; ++j)
+            if (!bwd[(size_t)isrc[(size_t)j]]) { bwd[(size_t)isrc[(size_t)j]] = 1; stack.push_back(isrc[(size_t)j]); }
+    }
+    if (!bwd[0]) return bad("the pattern's language is empty: no final state can be reached from state 0");
+    std::vector<int32_t> renum(nq0, -1);
+    int nQ = 0;
+    for (size_t q = 0; q < nq0; ++q)
+        if (fwd[q] && bwd[q]) renum[q] = nQ++;
+    std::vector<Arc> live;
+    for (const Arc& a : arcs)
+        if (renum[(size_t)a.src] >= 0 && renum[(size_t)a.dst] >= 0)
+            live.push_back(Arc{renum[(size_t)a.src], a.label, renum[(size_t)a.dst]});      // (still sorted by src, label)
+    // the eps states: the distinct (dst, label), ascending
+    std::vector<std::pair<int32_t, int32_t>> pairs;
+    for (const Arc& a : live) pairs.emplace_back(a.dst, a.label);
+    std::sort(pairs.begin(), pairs.end());
+    pairs.erase(std::unique(pairs.begin(), pairs.end()), pairs.end());
+    const int64_t S64 = (int64_t)nQ + (int64_t)pairs.size();
+    if (S64 > kPatMaxStates)
+        return bad("the pattern has " + str(S64) + " CTC states (" + str(nQ) + " DFA states + " + str((int64_t)pairs.size()) +
+                   " (state, label) pairs), HCTR_PAT_MAX_STATES is " + str(kPatMaxStates));
+    hctr_pat& x = *out;
+    x.C = C; x.nQ = nQ; x.S = (int)S64;
+    const size_t S = (size_t)S64;
+    auto eps = [&](int32_t q, int32_t c) {
+        return nQ + (int32_t)(std::lower_bound(pairs.begin(), pairs.end(), std::make_pair(q, c)) - pairs.begin());
+    };
+    std::vector<int32_t> pptr((size_t)nQ + 1, 0);     // the eps states of DFA state q are nQ + [pptr[q], pptr[q + 1])
+    for (const auto& p : pairs) ++pptr[(size_t)p.first + 1];
+    for (int q = 0; q < nQ; ++q) pptr[(size_t)q + 1] += pptr[(size_t)q];
+    x.label.assign(S, 0);
+    for (size_t i = 0; i < pairs.size(); ++i) x.label[(size_t)nQ + i] = pairs[i].second;
+    x.classes.assign(x.label.begin() + nQ, x.label.end());
+    std::sort(x.classes.begin(), x.classes.end());
+    x.classes.erase(std::unique(x.classes.begin(), x.classes.end()), x.classes.end());
+    x.slot.assign(S, 0);
+    for (size_t s = (size_t)nQ; s < S; ++s)
+        x.slot[s] = 1 + (int32_t)(std::lower_bound(x.classes.begin(), x.classes.end(), x.label[s]) - x.classes.begin());
+    // the arcs by (dst, label): the sources p of eps_(q,c)
+    std::vector<Arc> by_dst(live);
+    std::sort(by_dst.begin(), by_dst.end(), [](const Arc& a, const Arc& b) {
+        return a.dst != b.dst ? a.dst < b.dst : a.label != b.label ? a.label < b.label : a.src < b.src;
+    });
+    x.in_ptr.assign(1, 0);
+    std::vector<int32_t> srcs;
+    size_t k = 0;                                     // walks by_dst along with the pairs
+    for (size_t s = 0; s < S; ++s) {
+        srcs.clear();
+        srcs.push_back((int32_t)s);
+        if (s < (size_t)nQ) {
+            for (int32_t j = pptr[s]; j < pptr[s + 1]; ++j) srcs.push_back(nQ + j);
+        } else {
+            const int32_t q = pairs[s - (size_t)nQ].first, c = pairs[s - (size_t)nQ].second;
+            for (; k < by_dst.size() && by_dst[k].dst == q && by_dst[k].label == c; ++k) {
+                const int32_t p = by_dst[k].src;
+                srcs.push_back(p);
+                for (int32_t j = pptr[(size_t)p]; j < pptr[(size_t)p + 1]; ++j)
+                    if (pairs[(size_t)j].second != c) srcs.push_back(nQ + j);
+            }
+        }
+        std::sort(srcs.begin(), srcs.end());
+        if (x.in_src.size() + srcs.size() > (size_t)kPatMaxEdges)
+            return bad("the pattern has more than " + str(kPatMaxEdges) + " edges (HCTR_PAT_MAX_EDGES); " + str((int64_t)s) +
+                       " of its " + str(S64) + " CTC states reach that figure");
+        for (int32_t v : srcs) x.in_src.push_back((uint16_t)v);
+        x.in_ptr.push_back((int32_t)x.in_src.size());
+        x.max_deg = std::max(x.max_deg, (int)srcs.size());
+    }
+    std::vector<uint8_t> nfin((size_t)nQ, 0);
+    for (size_t q = 0; q < nq0; ++q)
+        if (renum[q] >= 0 && fin[q]) nfin[(size_t)renum[q]] = 1;
+    for (int q = 0; q < nQ; ++q)
+        if (nfin[(size_t)q]) x.accept.push_back(q);
+    for (size_t i = 0; i < pairs.size(); ++i)
+        if (nfin[(size_t)pairs[i].first]) x.accept.push_back(nQ + (int32_t)i);
+    x.start.assign(1, 0);
+    for (const Arc& a : live)
+        if (a.src == 0) x.start.push_back(eps(a.dst, a.label));
+    std::sort(x.start.begin(), x.start.end());
+    x.start.erase(std::unique(x.start.begin(), x.start.end()), x.start.end());
+    return true;
+}
+
+}  // namespace hctr

@@ -488,6 +488,456 @@ def lexicon_chunk_classes(lines, W):
     return int(_lib.load().hctr_lexicon_chunk_classes(int(lines), int(W)))
 
 
+PAT_MAX_STATES = 8192      # HCTR_PAT_MAX_STATES
+PAT_MAX_EDGES = 262144     # HCTR_PAT_MAX_EDGES
+
+
+class _Regex(object):
+    """The regular expressions ``Pattern.compile`` accepts, a subset of Python's ``re`` with ``re.fullmatch``'s meaning:
+    literals and ``\\`` escapes, ``.``, ``[...]`` / ``[^...]`` with code-point ranges, ``\\d``, ``( )`` (and ``(?: )``),
+    ``|``, ``?`` ``*`` ``+``, ``{m}`` ``{m,n}`` ``{m,}`` ``{,n}``. ``vocab`` maps a character to its label; ``.``,
+    negated sets and ranges mean the characters of ``vocab`` only. parse() returns the syntax tree: ("set", frozenset of
+    labels), ("cat", [nodes]), ("alt", [nodes]), ("rep", node, m, n or None)."""
+
+    SPECIAL = set(".[]()|?*+{}\\^$")
+
+    def __init__(self, expr, vocab):
+        self.s, self.i, self.vocab = expr, 0, vocab
+
+    def error(self, what):
+        return ValueError("pattern %r, position %d: %s" % (self.s, self.i, what))
+
+    def peek(self):
+        return self.s[self.i] if self.i < len(self.s) else ""
+
+    def take(self):
+        ch = self.peek()
+        if not ch:
+            raise self.error("unexpected end")
+        self.i += 1
+        return ch
+
+    def label(self, ch):
+        if ch not in self.vocab:
+            raise self.error("character %r is not in the vocabulary" % ch)
+        return self.vocab[ch]
+
+    def digits(self):
+        d = frozenset(self.vocab[ch] for ch in "0123456789" if ch in self.vocab)
+        if not d:
+            raise self.error("\\d: the vocabulary has no digit")
+        return d
+
+    def parse(self):
+        node = self.alt()
+        if self.i != len(self.s):
+            raise self.error("unbalanced ')'")
+        return node
+
+    def alt(self):
+        branches = [self.cat()]
+        while self.peek() == "|":
+            self.i += 1
+            branches.append(self.cat())
+        return branches[0] if len(branches) == 1 else ("alt", branches)
+
+    def cat(self):
+        items = []
+        while self.peek() not in ("", "|", ")"):
+            items.append(self.repeat(self.atom()))
+        return ("cat", items)
+
+    def number(self):
+        at = self.i
+        while self.peek().isdigit() and self.peek().isascii():
+            self.i += 1
+        return int(self.s[at:self.i]) if self.i > at else None
+
+    def repeat(self, node):
+        while True:
+            ch = self.peek()
+            if ch == "?":
+                m, n = 0, 1
+            elif ch == "*":
+                m, n = 0, None
+            elif ch == "+":
+                m, n = 1, None
+            elif ch == "{":
+                self.i += 1
+                m = self.number()
+                if self.peek() == ",":
+                    self.i += 1
+                    n = self.number()
+                    m = 0 if m is None else m
+                else:
+                    n = m
+                    if m is None:
+                        raise self.error("'{' needs a count")
+                if self.peek() != "}":
+                    raise self.error("malformed {m,n}")
+                if n is not None and n < m:
+                    raise self.error("{m,n} with n < m")
+            else:
+                return node
+            self.i += 1                        # the quantifier's last character
+            if self.peek() in ("?", "+", "*", "{"):
+                raise self.error("a quantifier after a quantifier is not supported")
+            node = ("rep", node, m, n)
+
+    def atom(self):
+        ch = self.take()
+        if ch == "(":
+            if self.s.startswith("?:", self.i):
+                self.i += 2
+            elif self.peek() == "?":
+                raise self.error("only (?: ) groups are supported")
+            node = self.alt()
+            if self.peek() != ")":
+                raise self.error("missing ')'")
+            self.i += 1
+            return node
+        if ch == "[":
+            return ("set", self.char_set())
+        if ch == ".":
+            return ("set", frozenset(self.vocab.values()))
+        if ch == "\\":
+            e = self.take()
+            if e == "d":
+                return ("set", self.digits())
+            if e.isalnum():
+                raise self.error("escape \\%s is not supported" % e)
+            return ("set", frozenset([self.label(e)]))
+        if ch in self.SPECIAL:
+            raise self.error("unexpected %r" % ch)
+        return ("set", frozenset([self.label(ch)]))
+
+    def char_set(self):
+        negate = self.peek() == "^"
+        if negate:
+            self.i += 1
+        members, first = set(), True
+        while True:
+            ch = self.take()
+            if ch == "]" and not first:
+                break
+            first = False
+            if ch == "\\":
+                e = self.take()
+                if e == "d":
+                    members |= self.digits()
+                    continue
+                if e.isalnum():
+                    raise self.error("escape \\%s is not supported" % e)
+                ch = e
+            if self.peek() == "-" and self.s[self.i + 1:self.i + 2] not in ("]", ""):
+                self.i += 1
+                hi = self.take()
+                if hi == "\\":
+                    hi = self.take()
+                if ord(hi) < ord(ch):
+                    raise self.error("bad character range %s-%s" % (ch, hi))
+                members |= set(v for k, v in self.vocab.items() if ord(ch) <= ord(k) <= ord(hi))
+            else:
+                members.add(self.label(ch))
+        if negate:
+            members = set(self.vocab.values()) - members
+        return frozenset(members)
+
+
+def _regex_to_dfa(tree):
+    """(arcs, finals, num_states) of the minimal DFA of a ``_Regex`` tree, its states numbered breadth-first from the start
+    over labels ascending - a function of the language, not of how it was spelt. arcs: int32 [n, 3] rows (src, label, dst)
+    sorted by (src, label). An empty language gives one state without finals."""
+    # atoms -> alphabet classes: labels with the same membership in every set of the expression behave alike
+    atoms, eps, tr = [], [[]], [[]]
+
+    def new():
+        eps.append([])
+        tr.append([])
+        if len(eps) > 200000:
+            raise ValueError("the pattern is too large (more than 200000 NFA states)")
+        return len(eps) - 1
+
+    def frag(node, s):
+        kind = node[0]
+        if kind == "set":
+            e = new()
+            atoms.append(node[1])
+            tr[s].append((len(atoms) - 1, e))
+            return e
+        if kind == "cat":
+            for child in node[1]:
+                s = frag(child, s)
+            return s
+        if kind == "alt":
+            e = new()
+            for child in node[1]:
+                a = new()
+                eps[s].append(a)
+                eps[frag(child, a)].append(e)
+            return e
+        _, child, m, n = node
+        for _ in range(m):
+            s = frag(child, s)
+        if n is None:
+            a, e = new(), new()
+            eps[s].append(a)
+            eps[frag(child, a)].append(a)
+            eps[a].append(e)
+            return e
+        e = new()
+        for _ in range(n - m):
+            eps[s].append(e)
+            s = frag(child, s)
+        eps[s].append(e)
+        return e
+
+    accept = frag(tree, 0)
+    sig = {}
+    for i, atom in enumerate(atoms):
+        for lab in atom:
+            sig[lab] = sig.get(lab, 0) | (1 << i)
+    by_sig = {}
+    for lab, v in sig.items():
+        by_sig.setdefault(v, []).append(lab)
+    classes = [np.array(sorted(v), np.int32) for v in by_sig.values()]
+    classes.sort(key=lambda c: int(c[0]))
+    atom_classes = [[k for k, c in enumerate(classes) if int(c[0]) in atom] for atom in atoms]
+
+    def closure(states):
+        seen, stack = set(states), list(states)
+        while stack:
+            for v in eps[stack.pop()]:
+                if v not in seen:
+                    seen.add(v)
+                    stack.append(v)
+        return frozenset(seen)
+
+    # subset construction over the classes
+    start = closure([0])
+    index, order, delta = {start: 0}, [start], []
+    q = 0
+    while q < len(order):
+        move = {}
+        for v in order[q]:
+            for ai, dst in tr[v]:
+                for k in atom_classes[ai]:
+                    move.setdefault(k, set()).add(dst)
+        row = {}
+        for k, dsts in move.items():
+            tgt = closure(dsts)
+            if tgt not in index:
+                index[tgt] = len(order)
+                order.append(tgt)
+                if len(order) > 50000:
+                    raise ValueError("the pattern is too large (more than 50000 DFA states before minimisation)")
+            row[k] = index[tgt]
+        delta.append(row)
+        q += 1
+    nq = len(order)
+    final = [accept in s for s in order]
+    # trim: the states that can reach a final state
+    back = [[] for _ in range(nq)]
+    for s, row in enumerate(delta):
+        for d in row.values():
+            back[d].append(s)
+    alive, stack = set(s for s in range(nq) if final[s]), [s for s in range(nq) if final[s]]
+    while stack:
+        for p in back[stack.pop()]:
+            if p not in alive:
+                alive.add(p)
+                stack.append(p)
+    if 0 not in alive:
+        return np.zeros((0, 3), np.int32), [], 1
+    # Moore's refinement on the trimmed (partial) automaton: a missing arc leads to the dead block -1
+    block = {s: (1 if final[s] else 0) for s in alive}
+    nk = len(classes)
+    while True:
+        keys = {}
+        new_block = {}
+        for s in sorted(alive):
+            row = delta[s]
+            key = (block[s],) + tuple(block[row[k]] if k in row and row[k] in alive else -1 for k in range(nk))
+            new_block[s] = keys.setdefault(key, len(keys))
+        stable = len(keys) == len(set(block.values()))
+        block = new_block
+        if stable:
+            break
+    rep = {}
+    for s in sorted(alive):
+        rep.setdefault(block[s], s)
+    # breadth-first numbering over labels ascending (the classes are sorted by their smallest label, and every label of
+    # a class leads to the same state, so the first label that reaches a state is its class's smallest)
+    number, queue = {block[0]: 0}, [block[0]]
+    rows = []
+    for blk in queue:
+        row = delta[rep[blk]]
+        out = sorted((int(classes[k][0]), k, block[d]) for k, d in row.items() if d in alive)
+        for _, _, d in out:
+            if d not in number:
+                number[d] = len(number)
+                queue.append(d)
+        rows.append([(k, d) for _, k, d in out])
+    arcs = []
+    for blk, row in zip(queue, rows):
+        for k, d in row:
+            a = np.empty((len(classes[k]), 3), np.int32)
+            a[:, 0], a[:, 1], a[:, 2] = number[blk], classes[k], number[d]
+            arcs.append(a)
+    arcs = np.concatenate(arcs) if arcs else np.zeros((0, 3), np.int32)
+    arcs = arcs[np.lexsort((arcs[:, 1], arcs[:, 0]))]
+    finals = sorted(number[b] for b in number if final[rep[b]])
+    return np.ascontiguousarray(arcs), finals, len(number)
+
+
+class Pattern(object):
+    """A pattern for pattern-constrained recognition (include/hctr_hip.h ``hctr_pat_build``): a deterministic finite
+    automaton over labels, lifted to CTC on the host (no GPU needed). ``arcs``: (src, label, dst) triples with labels in
+    [1, C-1] and at most one arc per (src, label); ``finals``: the final states; state 0 is the start; ``num_classes`` =
+    C. ``Pattern.compile(expr, codec)`` builds one from a regular expression. The object is immutable and serves any
+    number of contexts."""
+
+    def __init__(self, arcs, finals, num_states, num_classes, expr=None):
+        a = np.asarray(arcs, dtype=np.int64).reshape(-1, 3)
+        f = np.asarray(finals, dtype=np.int64).reshape(-1)
+        for v in (a, f):
+            if v.size and (v.min() < np.iinfo(np.int32).min or v.max() > np.iinfo(np.int32).max):
+                raise ValueError("arc or state out of the int32 range")
+        src, lab, dst = (np.ascontiguousarray(a[:, k], dtype=np.int32) for k in range(3))
+        f = np.ascontiguousarray(f, dtype=np.int32)
+        self.expr = expr
+        self.arcs, self.finals, self.num_states = np.stack([src, lab, dst], axis=1), f, int(num_states)      # as given
+        self.num_classes = int(num_classes)
+        lib = _lib.load()
+        h = ctypes.c_void_p()
+        rc = lib.hctr_pat_build(_lib.ptr(src), _lib.ptr(lab), _lib.ptr(dst), int(a.shape[0]), _lib.ptr(f), int(f.size),
+                                int(num_states), self.num_classes, ctypes.byref(h))
+        self._h = h if rc == 0 else None
+        _lib.check(rc, None)
+
+    @classmethod
+    def compile(cls, expr, codec):
+        """The pattern of the regular expression ``expr`` over ``codec``'s vocabulary; the whole line must match
+        (``re.fullmatch``). The syntax is ``_Regex``'s subset of ``re``. ``.``, negated sets and ranges mean the codec's
+        real characters (labels 1..C-2): <unknown> is never matched; a literal outside the vocabulary is a ValueError."""
+        chars = codec.characters
+        vocab = {ch: i for i, ch in enumerate(chars) if 1 <= i <= len(chars) - 2 and len(ch) == 1}
+        arcs, finals, nq = _regex_to_dfa(_Regex(expr, vocab).parse())
+        return cls(arcs, finals, nq, len(chars), expr=expr)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None):
+                _lib.load().hctr_pat_free(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def info(self):
+        """dict: dfa_states (after pruning), states (the CTC states), edges, classes (distinct), max_in_degree"""
+        v = [ctypes.c_int32() for _ in range(5)]
+        _lib.check(_lib.load().hctr_pat_info(self._h, *[ctypes.byref(x) for x in v]), None)
+        return dict(zip(("dfa_states", "states", "edges", "classes", "max_in_degree"), (int(x.value) for x in v)))
+
+    def tables(self):
+        """dict of numpy arrays: what ``hctr_pat_tables`` exports, the tables the kernel is given - state_label,
+        state_slot [S], in_ptr [S + 1], in_src uint16 [E], classes, accept, start."""
+        lib, i = _lib.load(), self.info()
+        na, ns = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(lib.hctr_pat_tables(self._h, None, None, None, None, None, ctypes.byref(na), None, ctypes.byref(ns), None),
+                   None)
+        t = {"state_label": np.zeros(i["states"], np.int32), "state_slot": np.zeros(i["states"], np.int32),
+             "in_ptr": np.zeros(i["states"] + 1, np.int32), "in_src": np.zeros(i["edges"], np.uint16),
+             "classes": np.zeros(i["classes"], np.int32), "accept": np.zeros(int(na.value), np.int32),
+             "start": np.zeros(int(ns.value), np.int32)}
+        _lib.check(lib.hctr_pat_tables(self._h, _lib.ptr(t["state_label"]), _lib.ptr(t["state_slot"]), _lib.ptr(t["in_ptr"]),
+                                       _lib.ptr(t["in_src"]), _lib.ptr(t["classes"]), None, _lib.ptr(t["accept"]), None,
+                                       _lib.ptr(t["start"])), None)
+        return t
+
+
+class PatternResult(object):
+    """Result of pattern-constrained recognition of B lines of W steps (numpy arrays, on the host; include/hctr_hip.h
+    ``hctr_pattern``): ``logp`` float32 [B], the log of the probability that the line's text matches the pattern;
+    ``best_logp`` float32 [B], the best matching path's log-probability; ``path`` int32 [B, W], its class per column (-1
+    beyond the line's length); ``labels`` int32 [B, W] / ``lengths`` int32 [B], the decoded text; ``starts`` / ``ends``
+    int32 [B, W] and ``logps`` float32 [B, W], each character's column span and the sum of its label's log-probabilities
+    over it; ``text_nll`` float32 [B], the CTC loss of the decoded text. A forward-only result holds ``logp`` alone (the
+    rest None). Where no path of the line's length matches, logp and best_logp are -inf, lengths 0, text_nll +inf."""
+
+    FIELDS = ("logp", "best_logp", "path", "labels", "lengths", "starts", "ends", "logps", "text_nll")
+
+    def __init__(self, logp, best_logp=None, path=None, labels=None, lengths=None, starts=None, ends=None, logps=None,
+                 text_nll=None):
+        self.logp, self.best_logp, self.path, self.labels, self.lengths = logp, best_logp, path, labels, lengths
+        self.starts, self.ends, self.logps, self.text_nll = starts, ends, logps, text_nll
+
+    def __len__(self):
+        return len(self.logp)
+
+    def label_lists(self):
+        return [self.labels[b, :int(self.lengths[b])].copy() for b in range(len(self))]
+
+    def texts(self, codec):
+        """the decoded text of every line ('' where nothing matches)"""
+        return codec.labels_to_text([l.tolist() for l in self.label_lists()])
+
+    def posterior(self):
+        """float64 [B]: exp(-text_nll - logp), the probability of the decoded text within the pattern (0 where nothing
+        matches)"""
+        with np.errstate(invalid="ignore", over="ignore"):
+            p = np.exp(-np.asarray(self.text_nll, np.float64) - np.asarray(self.logp, np.float64))
+        return np.where(np.isneginf(self.logp), 0.0, p)
+
+    def lines(self):
+        """yields per line the list of (label, start, end, confidence), one per character: its column span [start, end)
+        and the geometric mean of its probability over the span, exp(logp / (end - start))"""
+        for b in range(len(self)):
+            yield [(int(self.labels[b, j]), int(self.starts[b, j]), int(self.ends[b, j]),
+                    float(np.exp(np.float64(self.logps[b, j]) / (int(self.ends[b, j]) - int(self.starts[b, j])))))
+                   for j in range(int(self.lengths[b]))]
+
+
+def _pattern_outputs(pat, B, W, full):
+    if not isinstance(pat, Pattern):
+        raise ValueError("pat must be a ctc.Pattern")
+    i, f = np.int32, np.float32
+    logp = np.full(B, -np.inf, f)
+    if not full:
+        return (logp,) + (None,) * 8
+    return (logp, np.full(B, -np.inf, f), np.full((B, W), -1, i), np.zeros((B, W), i), np.zeros(B, i), np.zeros((B, W), i),
+            np.zeros((B, W), i), np.zeros((B, W), f), np.full(B, np.inf, f))
+
+
+def pattern_logits(ctx, logits, on_dev, pat, input_lengths=None, full=True):
+    """PatternResult of caller logits / log-probs in WBC layout (hctr_pattern_logits); ``full=False`` asks for logp
+    alone (the forward-only call)"""
+    if len(logits.shape) != 3:
+        raise ValueError("logits must be [W,B,C]")
+    W, B, C = (int(v) for v in logits.shape)
+    il = normalize_input_lengths(input_lengths, B)
+    out = _pattern_outputs(pat, B, W, full)
+    if B and W:
+        _lib.check(_lib.load().hctr_pattern_logits(ctx, pat._h, _lib.ptr(logits), on_dev, W, B, C, _lib.ptr(il),
+                                                   *[_lib.ptr(a) for a in out]), ctx)
+    return PatternResult(*out)
+
+
+def pattern_images(ctx, x, dt, on_dev, widths, B, W, pat, input_lengths=None, full=True):
+    """PatternResult of line images (hctr_pattern); x, dt, on_dev, widths as hctr_model._img_args / _widths give them."""
+    il = normalize_input_lengths(input_lengths, B)
+    out = _pattern_outputs(pat, B, W, full)
+    if B:
+        _lib.check(_lib.load().hctr_pattern(ctx, pat._h, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, _lib.ptr(il),
+                                            *[_lib.ptr(a) for a in out]), ctx)
+    return PatternResult(*out)
+
+
+def pattern_group_lines(S, D, W):
+    """lines one group holds for a pattern of S CTC states and D emission slots on W columns (hctr_pattern_group_lines)"""
+    return int(_lib.load().hctr_pattern_group_lines(int(S), int(D), int(W)))
+
+
 class Recognition(object):
     """Result of a greedy recognition of B lines of W steps (numpy arrays, on the host; include/hctr_hip.h
     ``hctr_recognize``): ``labels`` int32 [B, W] and ``lengths`` int32 [B], the decoded text as the greedy decode gives it
@@ -1221,6 +1671,28 @@ class LexiconRecognizer(_EngineBound):
             log_probs = log_probs.detach()
         logits, on_dev = ctc_codec._as_logits(log_probs)
         return lexicon_logits(self._context(), logits, on_dev, lex, n, input_lengths, scores)
+
+    __call__ = forward
+
+
+class PatternRecognizer(_EngineBound):
+    """Pattern-constrained recognition on the engine: ``PatternRecognizer().cuda(0)(log_probs_or_logits, pat,
+    input_lengths=None, full=True)`` with ``[T, B, C]`` input (numpy array or torch tensor, a CUDA tensor is read in
+    place) and ``pat`` a ``Pattern`` returns the ``PatternResult``: per line the log-probability that its text matches
+    the pattern and, with ``full``, the best matching reading with spans and confidences. Only blank=0 is supported."""
+
+    def __init__(self, blank=0):
+        if blank != 0:
+            raise NotImplementedError("the engine's CTC kernels use blank = 0 (the reference's codec)")
+        _EngineBound.__init__(self)
+        self.blank = blank
+
+    def forward(self, log_probs, pat, input_lengths=None, full=True):
+        from .codec import ctc_codec
+        if _is_torch(log_probs):
+            log_probs = log_probs.detach()
+        logits, on_dev = ctc_codec._as_logits(log_probs)
+        return pattern_logits(self._context(), logits, on_dev, pat, input_lengths, full)
 
     __call__ = forward
 

@@ -300,6 +300,19 @@ class hctr_model(object):
         x, dt, on_dev, B, W = self._img_args(input)
         return ctc.lexicon_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, lex, n, input_lengths, scores)
 
+    def pattern(self, input, pat, widths=None, input_lengths=None, full=True):
+        """Pattern-constrained recognition of line images, the logits never leaving the device: ``pat`` is a
+        ``ctc.Pattern`` (``Pattern.compile(expr, codec)`` or a DFA). Returns a ``ctc.PatternResult`` (numpy arrays):
+        ``logp`` [B], the log of the probability that the line's text matches the pattern - a sum over all CTC paths,
+        unpruned - and, with ``full``, the best matching reading: ``best_logp``, ``path``, ``labels`` / ``lengths``,
+        ``starts`` / ``ends`` / ``logps`` per character, ``text_nll``; ``texts(codec)``, ``posterior()``, ``lines()``.
+        ``input_lengths`` None = W for every line. In "auto" precision every line is scored in f16x3
+        (include/hctr_hip.h ``hctr_pattern``)."""
+        from . import ctc
+        ctx = self._require_ctx()
+        x, dt, on_dev, B, W = self._img_args(input)
+        return ctc.pattern_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, pat, input_lengths, full)
+
     def recognize(self, input, widths=None):
         """Forward + greedy decode with what an OCR interface reports beside the text, the logits never leaving the
         device: per character its pixel-column span, confidence and likeliest substitution, per line the greedy path's

@@ -380,6 +380,96 @@ int hctr_lexicon_logits(hctr_ctx* ctx, const hctr_lex* lex, const float* logits_
                         double* log_total, int32_t* count, float* scores);
 int hctr_lexicon_chunk_classes(int lines, int W);
 
+/* ---- pattern-constrained recognition on the device: CTC over a deterministic finite automaton ----------------------
+ * Reading a field whose admissible texts form an open set with a known shape (a date, an identity number, a phone
+ * number, an amount, a plate): the probability that the line's text matches the pattern - an exact sum over all CTC
+ * paths - and the best reading that matches it, with character spans and confidences. The reference has no
+ * counterpart. Spotting (one string's KMP automaton) and the lexicon (a trie) are special cases of this.
+ * Pattern: a DFA over labels. States 0..nQ-1, state 0 the start; arcs (src, label, dst) with label in [1, C-1] and at
+ *   most one arc per (src, label); a set of final states. L(A) = the label sequences that drive it from state 0 to a
+ *   final state (the empty sequence iff state 0 is final).
+ * hctr_pat_build (host only, no GPU, no context; errors are read with hctr_last_error(NULL)) validates determinism, the
+ *   label range, the state range and num_states >= 1, and prunes the DFA states that are not both reachable from state 0
+ *   and able to reach a final state (with their arcs); the survivors keep their relative order and state 0 is kept.
+ *   HCTR_ERR_ARG with a message for each of those, for an empty language, for more than HCTR_PAT_MAX_STATES CTC states
+ *   and for more than HCTR_PAT_MAX_EDGES edges (the message names the figure); HCTR_ERR_NOMEM; no exception crosses the
+ *   ABI. The object is immutable and may serve any number of contexts; a context uploads its tables on first use, keeps
+ *   the device copy of the pattern it used last (recognised by a serial number, not by address) and frees it with the
+ *   context.
+ * CTC states (after pruning): one blank state beta_q = q per DFA state q; one emitting state eps_(q,c) per distinct
+ *   (destination q, label c) among the arcs, numbered nQ, nQ + 1, .. in ascending (q, c) - arcs (p,c,q) and (p',c,q)
+ *   share it, their futures being identical. S = nQ + #pairs. label(beta_q) = 0, label(eps_(q,c)) = c.
+ * In-edges, each state's list sorted by source index ascending (the order in which the kernel visits them):
+ *   beta_q    <- beta_q and every eps_(q,.)
+ *   eps_(q,c) <- itself; beta_p for every arc (p,c,q); for each such p every eps_(p,c') with c' != c
+ * Start list: beta_0 and every eps_(q,c) with an arc (0,c,q), ascending. Accepting list: beta_q and every eps_(q,.) for
+ *   every final q, ascending.
+ * Emissions: lp_t(c) = float32((double)z_t[c] - lse_t), the loss's, bit for bit. T = input_lengths[b] in [1, W], NULL = W.
+ *   t = 0:  a_0(s) = v_0(s) = lp_0(label(s)) for the states of the start list, -inf elsewhere
+ *   t >= 1: a_t(s) = logsum over the in-edges of a_{t-1}(src) + lp_t(label(s))
+ *           v_t(s) = max    over the in-edges of v_{t-1}(src) + lp_t(label(s)); the backpointer is the first maximal
+ *           source in edge order, and the state's own index when every source is at -inf
+ *   logp[b]      = logsum of a_{T-1} over the accepting list, in list order: the log of the summed probability of every
+ *                  CTC path whose collapse is in L(A)
+ *   best_logp[b] = max of v_{T-1} over the accepting list, ties to the lowest state: the best such path
+ * Arithmetic: states are float32. logsum of x_1..x_n (in the order given): m = the float32 maximum; -inf if m is -inf;
+ *   else sum = the float64 sum, in that order, of (double)exp32(x_i - m), where x_i - m is a float32 subtraction and
+ *   exp32 the device's fast float32 exponential (the loss's); the result is the float32 sum m + log32((float)sum) with
+ *   the device's fast float32 logarithm. The emission is then added in float32. The max-plus recursion is exact float32
+ *   additions. No atomics; every reduction runs in the order stated. Because the automaton is deterministic every
+ *   accepted text has one arc sequence and every CTC path one state sequence: both recursions are exact.
+ *   Hence a pair's bits are a function of its line and the pattern's tables only: not of the other lines, the grouping
+ *   of lines (below), host or device pointers, repetition, or how the pattern was spelt when the tables are equal.
+ * Viterbi outputs (all host pointers, any may be NULL; when every one of best_logp .. text_nll is NULL the call runs the
+ *   sum alone, stores no backpointers, and logp has the bits of the full call's):
+ *   path int32 [B][W]: the class of the best accepted path per column, -1 for t >= T;
+ *   labels int32 [B][W], lengths int32 [B]: its collapse, the decoded text, which is in L(A);
+ *   span_start, span_end int32 [B][W], char_logp float32 [B][W]: per character its first column, the column after its
+ *   run, and the float32 sum of lp over the run in ascending t - layout and meaning of hctr_recognize: the first
+ *   lengths[b] valid, the rest zeros;
+ *   text_nll float32 [B]: the CTC loss of the decoded labels on the same logits, with the bits of
+ *   hctr_ctc_loss_logits given them as targets (the existing ctc_alpha over the pattern's own emissions);
+ *   NaN for a text longer than the loss's 2047 labels. exp(-text_nll - logp) is the posterior of the best text within
+ *   the pattern.
+ * No accepted path of length T (for example eight digits on 5 columns): logp = best_logp = -inf, path = -1 in every
+ *   column, lengths = 0, text_nll = +inf.
+ * hctr_pat_info: DFA states after pruning, CTC states S, edges E, distinct classes, the largest in-degree.
+ * hctr_pat_tables exports exactly what the kernel is given (any pointer may be NULL; call once for the counts):
+ *   state_label, state_slot int32 [S] (slot = the place of the label in the ascending class list, blank = 0);
+ *   in_ptr int32 [S + 1], in_src uint16 [E]; classes int32 [distinct classes]; accept int32 [num_accept];
+ *   start int32 [num_start].
+ * Lines are processed in groups of hctr_pattern_group_lines(S, D, W) lines, D = classes + 1: what keeps a group's
+ * emissions (4*W*D bytes a line) and backpointers (2*W*S bytes a line) within 2 GiB, at least 1; the environment
+ * variable HCTR_PAT_LINES overrides it at every call. Results do not depend on it, bit for bit.
+ * Errors of hctr_pattern*: HCTR_ERR_ARG with a message for a NULL pat, a pattern built for another C, an input length
+ * outside [1, W]; B == 0 is a no-op. HCTR_ERR_NOMEM leaves the context usable.
+ * Device scratch (the context's grow-only CTC scratch): per group 4*g*W*D emissions + 2*g*W*S backpointers + 8*g*W;
+ * 20*B*W for the per-column results, 4*B*D class tables; plus W*B*C floats for logits passed as a host pointer. The
+ * pattern's device copy (12 bytes per state + 2 per edge) is separate.
+ * Launches (hctr_last_profile): pattern_classes; per group ctc_lse, pattern, and with Viterbi outputs pattern_trace and,
+ * for text_nll, ctc_alpha.
+ * hctr_pattern runs the forward of img in internal passes on the stored-logits head exactly as hctr_lexicon does: mode 0
+ * f16, mode 1 f16x3, mode 2 EVERY line in f16x3, hctr_last_guard's figures left as they were. hctr_pattern_logits takes
+ * caller logits or log-probs in WBC layout, host or device pointer, and needs no weights. */
+#define HCTR_PAT_MAX_STATES 8192
+#define HCTR_PAT_MAX_EDGES 262144
+typedef struct hctr_pat hctr_pat;
+int hctr_pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const int32_t* arcs_dst, int num_arcs,
+                   const int32_t* finals, int num_finals, int num_states, int C, hctr_pat** out);
+void hctr_pat_free(hctr_pat* pat);
+int hctr_pat_info(const hctr_pat* pat, int32_t* dfa_states, int32_t* ctc_states, int32_t* num_edges, int32_t* num_classes,
+                  int32_t* max_in_degree);
+int hctr_pat_tables(const hctr_pat* pat, int32_t* state_label, int32_t* state_slot, int32_t* in_ptr, uint16_t* in_src,
+                    int32_t* classes, int32_t* num_accept, int32_t* accept, int32_t* num_start, int32_t* start);
+int hctr_pattern(hctr_ctx* ctx, const hctr_pat* pat, const void* img, int img_dtype, int img_on_device,
+                 const int32_t* widths, int B, int W, const int32_t* input_lengths, float* logp, float* best_logp,
+                 int32_t* path, int32_t* labels, int32_t* lengths, int32_t* span_start, int32_t* span_end,
+                 float* char_logp, float* text_nll);
+int hctr_pattern_logits(hctr_ctx* ctx, const hctr_pat* pat, const float* logits_wbc, int on_device, int W, int B, int C,
+                        const int32_t* input_lengths, float* logp, float* best_logp, int32_t* path, int32_t* labels,
+                        int32_t* lengths, int32_t* span_start, int32_t* span_end, float* char_logp, float* text_nll);
+int hctr_pattern_group_lines(int S, int D, int W);
+
 /* ---- greedy recognition: the decoded text with per-character spans, confidences and runners-up -------------------
  * What hctr_greedy / hctr_decode_greedy_logits decode, plus the figures the CTC family above gives only for a
  * transcription the caller already knows - in one pass over the logits, without a Viterbi recursion: the greedy path is

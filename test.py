@@ -47,9 +47,11 @@ def build_argparser():
     a.add_argument("--gpu", type=int, default=0)
     a.add_argument("-bm", "--benchmark-mode", dest="benchmark_mode", action="store_true")
     a.add_argument("-dm", "--decode-method", dest="decode_method", type=str, default="beam-search",
-                   choices=["greedy-search", "beam-search", "lexicon"])
+                   choices=["greedy-search", "beam-search", "lexicon", "pattern"])
     a.add_argument("--lexicon", dest="lexicon", type=str, default="",
                    help="-dm lexicon: a text file with one admissible text per line")
+    a.add_argument("--pattern", dest="pattern", type=str, default="",
+                   help="-dm pattern: a regular expression the whole line must match, e.g. '\\d{18}'")
     a.add_argument("-ss", "--skip-search", dest="skip_search", action="store_true")
     a.add_argument("-kp", "--kenlm-path", dest="kenlm_path", type=str, default="")
     a.add_argument("-utp", "--use-tfm-pred", dest="use_tfm_pred", action="store_true")
@@ -201,7 +203,18 @@ def load_lexicon(path, codec):
     return hctr_amd.Lexicon([e for e in entries if e], codec=codec)
 
 
-def recognise(model, codec, imgs, widths, lexicon=None):
+def load_pattern(expr, codec):
+    """-dm pattern --pattern EXPR: the compiled pattern (hctr_amd.Pattern.compile; the whole line must match)"""
+    import hctr_amd
+    if not expr:
+        raise ValueError("-dm pattern needs --pattern EXPR")
+    return hctr_amd.Pattern.compile(expr, codec)
+
+
+def recognise(model, codec, imgs, widths, lexicon=None, pattern=None):
+    if pattern is not None:             # per image: the best matching text, p(the line matches), p(that text | it matches)
+        res = model.pattern(imgs, pattern, widths=widths)
+        return [(t, float(np.exp(np.float64(lp))), float(p)) for t, lp, p in zip(res.texts(codec), res.logp, res.posterior())]
     if lexicon is not None:                                     # the best entry of the list per image
         res = model.lexicon(imgs, lexicon, n=1, widths=widths)
         return [t if t is not None else "" for t in res.best()]
@@ -221,13 +234,14 @@ def test(args):
     import hctr_amd
     pp = hctr_amd.preprocess
     lexicon = load_lexicon(args.lexicon, codec) if args.decode_method == "lexicon" else None
+    pattern = load_pattern(args.pattern, codec) if args.decode_method == "pattern" else None
     paths = list_inputs(args.input)
     batches = [paths[i * args.batch_size:(i + 1) * args.batch_size] for i in range(len(paths) // args.batch_size)]
     for i, (_, arrs) in enumerate(prefetched(batches, args.workers)):
         print("batch {} is being processed...".format(i))
         imgs, widths = pp.resize_lines(model, arrs, model.img_height, "test", "rgb", None, device_out=True)
         t0 = time.time()
-        result = recognise(model, codec, imgs, widths, lexicon)
+        result = recognise(model, codec, imgs, widths, lexicon, pattern)
         dt = time.time() - t0
         print("max_width: {}, throughput: {} ms/img".format(int(widths.max()), dt / args.batch_size * 1000))
         print("predicted results: {}".format(result))

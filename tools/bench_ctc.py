@@ -93,7 +93,16 @@ times lexicon recognition on the same caller logits (hctr_lexicon_logits, the 5 
 --entries synthetic entries of 2-6 labels, half of them cut from the lines' greedy texts, and in the same run the loss
 (hctr_ctc_loss_logits, each line's greedy text as its target), alternately after warm-up calls of each, medians with
 range, and the cost per (line, entry) next to the loss's per (line, target). --layers adds the device time of the call's
-launches, summed per name over the chunks of units (lexicon_classes, ctc_lse, lexicon_trie; lexicon_rank)."""
+launches, summed per name over the chunks of units (lexicon_classes, ctc_lse, lexicon_trie; lexicon_rank).
+
+    python tools/bench_ctc.py --pattern EXPR [--layers] ...
+
+times pattern-constrained recognition on the same caller logits (hctr_pattern_logits) for the regular expression EXPR,
+forward-only (logp alone) and full (every output fetched), and in the same run the loss (hctr_ctc_loss_logits, each
+line's greedy text as its target), alternately after warm-up calls of each, medians with range. The expression is
+compiled over a vocabulary whose labels 1..10 are the digits 0-9, 11-13 the year, month and day signs and the rest CJK
+code points, e.g. '\\d{18}', '\\d{4}\u5e74\\d{1,2}\u6708\\d{1,2}\u65e5', '.\\d{3}'. --layers adds the device time of each call's
+launches (pattern_classes, ctc_lse, pattern, pattern_trace, ctc_alpha) and the recursion's time per step."""
 import argparse
 import json
 import os
@@ -127,6 +136,7 @@ def main():
     ap.add_argument("--lexicon", action="store_true")
     ap.add_argument("--entries", type=int, default=10000)
     ap.add_argument("--unit-nodes", type=int, default=0, help="--lexicon: trie nodes per workgroup (0 = the default)")
+    ap.add_argument("--pattern", type=str, default="", help="a regular expression: time hctr_pattern_logits")
     ap.add_argument("--pairs", type=int, default=250)
     ap.add_argument("--host-lines", type=int, default=4)
     args = ap.parse_args()
@@ -157,6 +167,9 @@ def main():
         return
     if args.lexicon:
         print(json.dumps(lexicon(args, hctr_amd, m, imgs, labels, targets, tl)))
+        return
+    if args.pattern:
+        print(json.dumps(pattern(args, hctr_amd, m, imgs, targets, tl)))
         return
     if args.evaluate:
         print(json.dumps(evaluate(args, hctr_amd, m, imgs, labels)))
@@ -473,6 +486,79 @@ def lexicon(args, hctr_amd, m, imgs, labels, targets, tl):
         m.set_profiling(False)
         rec["loss_only_layers_ms"] = {k: round(v, 4) for k, v in fprof.items()}
         rec["lexicon_layers_ms"] = {k: round(v, 4) for k, v in lprof.items()}
+    return rec
+
+
+def pattern_characters(vocab):
+    """a vocabulary for --pattern: the digits, the year / month / day signs, then CJK code points from U+4E00"""
+    head = "0123456789\u5e74\u6708\u65e5"
+    out = list(head)
+    cp = 0x4E00
+    while len(out) < vocab:
+        if chr(cp) not in head:
+            out.append(chr(cp))
+        cp += 1
+    return "".join(out)
+
+
+def pattern(args, hctr_amd, m, imgs, targets, tl):
+    import torch
+    rc = hctr_amd.PatternRecognizer().attach(m)
+    mod = sys.modules[type(rc).__module__]
+    ctx = rc._context()
+    logits = m(imgs)                                             # device tensor [W, lines, C]
+    W, B, C = (int(v) for v in logits.shape)
+    t0 = time.perf_counter()
+    pat = mod.Pattern.compile(args.pattern, hctr_amd.ctc_codec(pattern_characters(C - 2)))
+    build_ms = 1e3 * (time.perf_counter() - t0)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def loss_only():
+        assert np.isfinite(mod.loss_logits(ctx, logits, 1, targets, tl, None)).all()
+
+    last = {}
+
+    def forward_only():
+        last["f"] = mod.pattern_logits(ctx, logits, 1, pat, None, False)
+
+    def full():
+        last["r"] = mod.pattern_logits(ctx, logits, 1, pat, None, True)
+
+    fns = (("loss_only", loss_only), ("pattern_forward", forward_only), ("pattern_full", full))
+    for _ in range(args.warmup):
+        for _, fn in fns:
+            fn()
+    ms = {k: [] for k, _ in fns}
+    for _ in range(args.steps):
+        for k, fn in fns:
+            ms[k].append(1e3 * timed(fn))
+    assert last["f"].logp.tobytes() == last["r"].logp.tobytes()
+    info = pat.info()
+    rec = {"mode": "pattern", "pattern": args.pattern, "lines": B, "width": W, "classes": C, "precision": args.precision,
+           "build_ms": round(build_ms, 1), "group_lines": mod.pattern_group_lines(info["states"], info["classes"] + 1, W),
+           "matching_lines": int(np.isfinite(last["r"].logp).sum())}
+    rec.update(info)
+    for k, v in ms.items():
+        rec[k + "_ms"] = [round(x, 3) for x in v]
+        rec[k + "_ms_median"] = round(float(np.median(v)), 3)
+    if args.layers:
+        m.set_profiling(True)
+        prof = {}
+        for k, fn in fns:
+            fn()
+            prof[k] = dict(m.last_profile())
+        m.set_profiling(False)
+        for k, v in prof.items():
+            rec[k + "_layers_ms"] = {n: round(x, 4) for n, x in v.items()}
+        groups = -(-B // rec["group_lines"])
+        for k in ("pattern_forward", "pattern_full"):        # a group's lines run side by side, the groups in turn
+            rec[k + "_us_per_step"] = round(1e3 * prof[k].get("pattern", 0.0) / (W * groups), 3)
     return rec
 
 
