@@ -3042,6 +3042,7 @@ hipError_t launch_beam_candidates(const int32_t* emit_cnt, const int32_t* emit_l
 
 // Log-sum-exp of the row p[0..C) by a 256-thread block (float32 max, float64 exp-sum and log), every thread's result.
 // One pass over the row: eight loads in flight per thread, a running (max, exp-sum) rescaled when the max grows.
+// A NaN anywhere in the row makes the result NaN: the exp-sum carries it, and `bad` where no sum was formed yet.
 // see(v, c) is handed every element a thread loads, in ascending c (greedy_rowstat_kernel's top-2; the loss passes
 // nothing, and its code is what it was).
 template <class See>
@@ -3051,6 +3052,7 @@ __device__ __forceinline__ double ctc_row_lse(const float* __restrict__ p, int C
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     float tm = -INFINITY;
     double ts = 0.0;
+    bool bad = false;                              // a NaN met while the running max was still -inf
     for (int c0 = tid; c0 < C; c0 += 8 * 256) {
         float v[8];
 #pragma unroll
@@ -3068,6 +3070,9 @@ __device__ __forceinline__ double ctc_row_lse(const float* __restrict__ p, int C
         if (tm != -INFINITY) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) ts += (double)expf(v[k] - tm);
+        } else {                                   // fmaxf drops a NaN: one among nothing but -inf must still count
+#pragma unroll
+            for (int k = 0; k < 8; ++k) bad |= v[k] != v[k];
         }
     }
     float mx = tm;
@@ -3076,8 +3081,8 @@ __device__ __forceinline__ double ctc_row_lse(const float* __restrict__ p, int C
     if (lane == 0) rv[wv] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(rv[0], rv[1]), fmaxf(rv[2], rv[3]));
-    const double s = block_sum_d(tm == -INFINITY ? 0.0 : ts * (double)expf(tm - mx), rd);
-    return (double)mx + log(s);
+    const double s = block_sum_d(bad ? (double)NAN : tm == -INFINITY ? 0.0 : ts * (double)expf(tm - mx), rd);
+    return (double)mx + log(s);                    // NaN for a row with a NaN or +inf; a row of nothing but -inf: -inf
 }
 
 // One 256-thread block per (t, line): log-sum-exp of the row in one pass over it, then the slots of D_b as
@@ -3540,7 +3545,8 @@ hipError_t launch_ctc_grad_rows(const float* x, int C, int B, int W, const CtcLi
 // s-2. The choice (0, 1 or 2 states down) of the lane's NS states is packed into one byte, state i at bits 2i, and
 // stored at bp[boff[gb] + t * ceil(S / NS) + lane index] for t >= 1: consecutive lanes, consecutive bytes. score[gb] is
 // the better of v_{T-1}(S-1) and v_{T-1}(S-2) (S-1 on a tie; state 0 for L = 0) and endst[gb] that state; a line marked
-// T = 0 gets -inf and -1.
+// T = 0 gets -inf and -1, and so does a line whose best score is -inf (masked logits leave it no path). A NaN score
+// (a non-finite logits row) stays NaN with the end state S-2 or S-1: comparisons with NaN are false.
 template <int NS_>
 struct CtcMax {
     static constexpr int NS = NS_;
@@ -3571,8 +3577,9 @@ struct CtcMax {
     }
     __device__ __forceinline__ void finish(int gb, int L, int S, float last, float prev) const {
         const bool end = L == 0 || last >= prev;
-        score[gb] = end ? last : prev;
-        endst[gb] = end ? S - 1 : S - 2;
+        const float best = end ? last : prev;
+        score[gb] = best;
+        endst[gb] = best == -INFINITY ? -1 : (end ? S - 1 : S - 2);    // every path masked out: no alignment
     }
 };
 
@@ -3590,7 +3597,8 @@ __global__ __launch_bounds__(64 * NW) void ctc_viterbi_kernel(const float* __res
 // window (independent byte loads, all in flight together), then every thread walks the chunk on LDS broadcasts with
 // the same scalar state; thread 0 stores the state of every step and, where the state changes, the span ends. After
 // the walk the steps are mapped to classes and the spans' log-probabilities summed (ascending t, float32) in parallel.
-// sh = log2 of the recursion instance's states per lane. Lines without an alignment: path and spans -1, logp -inf.
+// sh = log2 of the recursion instance's states per lane. Lines without an alignment (T = 0 or endst < 0): path and spans -1,
+// logp -inf.
 constexpr int kBtSteps = 32;
 __global__ __launch_bounds__(256) void ctc_backtrace_kernel(const float* __restrict__ emis, const CtcLines m, int b0, int W,
                                                             int sh, const int64_t* __restrict__ boff,
@@ -3612,7 +3620,7 @@ __global__ __launch_bounds__(256) void ctc_backtrace_kernel(const float* __restr
         en[j] = -1;
         lg[j] = -INFINITY;
     }
-    if (T == 0) {                                  // (block-uniform)
+    if (T == 0 || endst[gb] < 0) {                 // (block-uniform) infeasible by length, or every path is -inf
         for (int t = tid; t < W; t += 256) P[t] = -1;
         return;
     }
@@ -5425,7 +5433,8 @@ __global__ __launch_bounds__(kPatThreads) void pattern_kernel(const PatArgs a) {
         double sum = 0.0;
         if (m != -INFINITY)
             for (int j = 0; j < a.num_accept; ++j) sum += (double)__expf(pat_a(fin[min(max(a.accept[j], 0), S - 1)]) - m);
-        a.logp[gb] = pat_lse(m, sum);
+        const float lp = pat_lse(m, sum);
+        a.logp[gb] = lp > 0.f ? 0.f : lp;                 // a probability near 1 may round above 0; a NaN stays one
         if (VIT) {
             a.best[gb] = vm;
             a.endst[gb] = arg;

@@ -182,7 +182,8 @@ class CTCAlignment(object):
     ``scores`` float32 [B], the best path's log-probability; ``starts`` / ``ends`` int32 and ``logps`` float32
     [sum L], per target position the first step, the step after the last and the sum of the label's log-probabilities
     over them; ``offsets`` int64 [B + 1], where each line's positions begin; ``targets`` int32 [sum L]. A line with no
-    alignment has score -inf, -1 everywhere and logps -inf."""
+    alignment - too short for its targets, or every path through a masked (-inf) logit - has score -inf, -1 everywhere
+    and logps -inf."""
 
     def __init__(self, paths, scores, starts, ends, logps, targets, target_lengths):
         self.paths, self.scores = paths, scores
@@ -1613,7 +1614,11 @@ class CTCAligner(_EngineBound):
     """Forced alignment on the engine: ``CTCAligner().cuda(0)(log_probs_or_logits, targets, input_lengths,
     target_lengths)`` with the arguments of ``CTCLoss`` (``[T, B, C]`` numpy array or torch tensor, a CUDA tensor is read
     in place; targets 1-D concatenated or 2-D padded) returns the ``CTCAlignment`` of every line's best path: per
-    character its pixel-column span and log-probability, per line the path and its score. Only blank=0 is supported."""
+    character its pixel-column span and log-probability, per line the path and its score. Only blank=0 is supported.
+    Masked logits (-inf beside a finite logit in the row) mean probability 0: the best path avoids them, and a line
+    they leave no path is a line with no alignment. A line with a non-finite row (a NaN, a +inf, nothing but -inf) in
+    its input length has score NaN, a path and spans that are in range but mean nothing, and NaN for the ``logps`` of a
+    span that holds the row; the other lines are untouched (include/hctr_hip.h, "masked and non-finite logits")."""
 
     def __init__(self, blank=0):
         if blank != 0:
@@ -1635,7 +1640,11 @@ class KeywordSpotter(_EngineBound):
     """Keyword spotting on the engine: ``KeywordSpotter().cuda(0)(log_probs_or_logits, queries, input_lengths=None)``
     with ``[T, B, C]`` input (numpy array or torch tensor, a CUDA tensor is read in place) and ``queries`` a sequence of
     label sequences (1..32 labels each) returns the ``Spotting`` of every (line, query) pair: the posterior probability
-    that the line's text contains the query, and the best segment that reads it. Only blank=0 is supported."""
+    that the line's text contains the query, and the best segment that reads it. Only blank=0 is supported.
+    Masked logits (-inf beside a finite logit in the row) mean probability 0; a pair they leave no path gets -inf, -inf,
+    -1, -1. A line with a non-finite row (a NaN, a +inf, nothing but -inf) in its input length has ``logp`` NaN, and
+    its segment is the best of those that end before the row (or none): a segment never spans such a row. The other
+    lines are untouched (include/hctr_hip.h, "masked and non-finite logits")."""
 
     def __init__(self, blank=0):
         if blank != 0:
@@ -1657,7 +1666,11 @@ class LexiconRecognizer(_EngineBound):
     """Lexicon recognition on the engine: ``LexiconRecognizer().cuda(0)(log_probs_or_logits, lex, n=5,
     input_lengths=None, scores=False)`` with ``[T, B, C]`` input (numpy array or torch tensor, a CUDA tensor is read in
     place) and ``lex`` a ``Lexicon`` returns the ``LexiconResult``: per line the ``n`` best entries with their exact
-    log p(entry | line), ranks and the lexicon's total mass. Only blank=0 is supported."""
+    log p(entry | line), ranks and the lexicon's total mass. Only blank=0 is supported.
+    Masked logits (-inf beside a finite logit in the row) mean probability 0; an entry they leave no path scores -inf
+    and is left out of the ranking and of ``count``. A line with a non-finite row (a NaN, a +inf, nothing but -inf) in
+    its input length ranks nothing: ``count`` 0, ``log_total`` -inf, every score -inf or NaN. The other lines are
+    untouched (include/hctr_hip.h, "masked and non-finite logits")."""
 
     def __init__(self, blank=0):
         if blank != 0:
@@ -1679,7 +1692,11 @@ class PatternRecognizer(_EngineBound):
     """Pattern-constrained recognition on the engine: ``PatternRecognizer().cuda(0)(log_probs_or_logits, pat,
     input_lengths=None, full=True)`` with ``[T, B, C]`` input (numpy array or torch tensor, a CUDA tensor is read in
     place) and ``pat`` a ``Pattern`` returns the ``PatternResult``: per line the log-probability that its text matches
-    the pattern and, with ``full``, the best matching reading with spans and confidences. Only blank=0 is supported."""
+    the pattern and, with ``full``, the best matching reading with spans and confidences. Only blank=0 is supported.
+    Masked logits (-inf beside a finite logit in the row) mean probability 0; a line they leave no matching path, and a
+    line with a non-finite row (a NaN, a +inf, nothing but -inf) in its input length, get what a line gets that nothing
+    matches: ``logp`` = ``best_logp`` = -inf, path -1, lengths 0, ``text_nll`` +inf. The other lines are untouched
+    (include/hctr_hip.h, "masked and non-finite logits")."""
 
     def __init__(self, blank=0):
         if blank != 0:
@@ -1704,7 +1721,15 @@ class CTCLoss(_EngineBound):
     a ``grad_fn``: ``loss.backward()`` deposits ``w_b * (softmax - posterior occupancy)`` in the input's ``.grad``, the
     derivative in raw logits and, for log-probs, what torch's own ctc_loss hands to the ``log_softmax`` before it (which
     passes it through unchanged). ``loss_and_grad`` is the same without autograd. Bind it to a GPU with
-    ``.cuda(device)``, or share an hctr_model's engine context with ``.attach(model)``. Only blank=0 is supported."""
+    ``.cuda(device)``, or share an hctr_model's engine context with ``.attach(model)``. Only blank=0 is supported.
+    Masked logits (-inf beside a finite logit in the row) mean probability 0: the loss is the defined one, +inf for a
+    line whose every alignment goes through a masked entry (as for a line too short for its targets), and the gradient
+    at a masked entry is exactly 0. This DIFFERS FROM TORCH, whose ``ctc_loss(x.log_softmax(2), ...)`` returns a NaN
+    gradient for the whole tensor once one logit is -inf (and NaN at the masked entries when the log-probs are the
+    leaf). A line with a non-finite row (a NaN, a +inf, nothing but -inf) in its input length has a loss of NaN or +inf,
+    never a finite one: +inf, which ``zero_infinity`` turns into 0 with zero gradient rows, unless the row is one of the
+    line's last two (NaN, with NaN in the gradient). The other lines are untouched (include/hctr_hip.h, "masked and
+    non-finite logits")."""
 
     def __init__(self, blank=0, reduction="mean", zero_infinity=False):
         if blank != 0:

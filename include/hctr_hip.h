@@ -140,11 +140,44 @@ int hctr_beam_fetch_candidates(hctr_ctx* ctx, int64_t* cand_off, int32_t* cand_i
 int hctr_log_softmax(hctr_ctx* ctx, const float* logits_wbc, int on_device, int W, int B, int C,
                      float* out_host);
 
+/* ---- masked (-inf) and non-finite logits: what every *_logits entry point below makes of them ----------------------
+ * (hctr_ctc_loss_logits, hctr_ctc_loss_logits_grad, hctr_ctc_align_logits, hctr_spot_logits, hctr_lexicon_logits,
+ * hctr_pattern_logits, hctr_recognize_logits. The image entry points share the kernels; the engine's own logits are finite.)
+ * MASKED CLASS: a logit of -inf in a row that also holds a finite logit. The class has probability 0 in that column -
+ * the way to restrict a CTC model to a vocabulary, or to forbid the blank inside a forced region - and every result is
+ * the mathematically defined one, to the entry's stated precision; no result is NaN. "No alignment" covers a line whose
+ * every path has probability 0, whether or not it passes the length test (L + adjacent equal labels <= T): such a line
+ * gets exactly what a line that fails the length test gets -
+ *   loss +inf; gradient rows zero; alignment score -inf, path -1 everywhere, spans -1, span_logp -inf;
+ *   spotting -inf, -inf, -1, -1; a lexicon score of -inf and the entry left out of the ranking and of count;
+ *   pattern logp = best_logp = -inf, path -1, lengths 0, text_nll +inf.
+ * The gradient at a masked entry is exactly 0 (line_weight * (exp(-inf) - 0)); torch's ctc_loss differentiated through
+ * log_softmax returns NaN for the whole tensor there, and NaN at the masked entries with the log-probs as the leaf.
+ * NON-FINITE ROW: a row t < T of a line that holds a NaN or a +inf, or nothing but -inf. Its log-sum-exp is not a number
+ * (NaN; -inf for a row of nothing but -inf), so every log-probability of the row is NaN. The call returns HCTR_OK, the
+ * outputs of every other line are bit-identical to a call without the bad row, and the context stays usable. On the
+ * bad line no score is finite: each is NaN or the entry's "nothing" value, and every integer output is in range (path
+ * entries in [-1, C), spans in [-1, T], entry indices in [-1, N), counts in [0, n]) -
+ *   loss:       NaN when the row is one of the line's last two, else +inf (the recursion's max drops a NaN operand, and
+ *               two columns after the row every state is -inf); never finite.
+ *   gradient:   rows zero where the loss is +inf; where it is NaN, NaN in the bad row and in the columns of the blank and
+ *               of the line's own labels, line_weight * softmax elsewhere.
+ *   alignment:  score NaN; path, span_start, span_end in range and without meaning; span_logp NaN for a span that holds
+ *               the row.
+ *   spotting:   contain_logp NaN. The segment is the best among those that END BEFORE the row, bit for bit what a
+ *               call with input_lengths = t returns (-inf, -1, -1 where none does): a segment never spans a bad row.
+ *   lexicon:    every score -inf or NaN, no entry ranked: count 0, log_total -inf, top_entry -1.
+ *   pattern:    logp = best_logp = -inf, no path, lengths 0, text_nll +inf.
+ *   recognize:  as stated there (labels as the greedy decode gives them, the affected figures NaN).
+ * A row t >= T is never read: whatever it holds, the results are bit-identical. (hctr_recognize_logits has no lengths:
+ * every row counts.) Logits so large that float32 log-probabilities overflow are outside this contract. */
+
 /* ---- CTC loss on the device: replaces CTCLoss(zero_infinity=True) over preds.log_softmax(2) ------------
  * main.py:205 (criterion), :379-409 (targets from codec.encode, preds_sizes = [W] * B). The gradient: hctr_ctc_loss_logits_grad below.
  * nll[b] = -log sum over the alignments pi of line b's targets of prod_t softmax(z_t)[pi_t], with blank = class 0:
  * torch.nn.functional.ctc_loss(log_softmax(z), ..., blank=0, reduction='none', zero_infinity=False). A line with no
- * alignment (L + number of adjacent equal labels > T) gets +inf; a line with L = 0 gets -sum_t log p_t(blank).
+ * alignment (L + number of adjacent equal labels > T, or masked logits that leave every alignment the probability 0:
+ * see "masked and non-finite logits" above) gets +inf; a line with L = 0 gets -sum_t log p_t(blank).
  *   targets:        int32, the lines' labels back to back (what codec.encode returns), sum(target_lengths) entries;
  *                   every id in [1, C-1] (C-1 = the "<unknown>" id encode emits), else HCTR_ERR_ARG. Host pointer.
  *   target_lengths: int32 [B], >= 0; a line's 2L + 1 extended states must fit 4096 (L <= 2047) unless it has no alignment.
@@ -209,8 +242,9 @@ int hctr_ctc_loss_logits_grad(hctr_ctx* ctx, const float* logits_wbc, int on_dev
  *   span_logp:  float32: the sum of lp_t(label) over those steps, ascending t (exp(span_logp / (end - start)) is the
  *               geometric-mean probability, a per-character confidence), or NULL;
  *   score:      float32 [B], host, or NULL: v_{T-1}(end state), the best path's log-probability (<= -nll).
- * A line with no alignment (L + number of adjacent equal labels > T, the loss's test) gets score -inf, path -1
- * everywhere, spans -1 and span_logp -inf.
+ * A line with no alignment (L + number of adjacent equal labels > T, the loss's test; or a best score of -inf, when
+ * masked logits leave no path a probability above 0) gets score -inf, path -1 everywhere, spans -1 and span_logp -inf.
+ * A line with a non-finite row has a NaN score: see "masked and non-finite logits" above.
  * hctr_ctc_align runs the forward of img in internal passes and aligns the stored-logits head exactly as hctr_ctc_loss
  * scores it: mode 0 f16, mode 1 f16x3, mode 2 EVERY line in f16x3, hctr_last_guard's figures left as they were.
  * hctr_ctc_align_logits takes caller logits or log-probs in WBC layout, host or device pointer, and needs no weights.
@@ -416,7 +450,9 @@ int hctr_lexicon_chunk_classes(int lines, int W);
  *   else sum = the float64 sum, in that order, of (double)exp32(x_i - m), where x_i - m is a float32 subtraction and
  *   exp32 the device's fast float32 exponential (the loss's); the result is the float32 sum m + log32((float)sum) with
  *   the device's fast float32 logarithm. The emission is then added in float32. The max-plus recursion is exact float32
- *   additions. No atomics; every reduction runs in the order stated. Because the automaton is deterministic every
+ *   additions. logp[b] is returned as 0 where the final float32 sum rounds above 0 (a pattern that nearly every text of
+ *   the line matches): best_logp <= logp <= 0 always.
+ *   No atomics; every reduction runs in the order stated. Because the automaton is deterministic every
  *   accepted text has one arc sequence and every CTC path one state sequence: both recursions are exact.
  *   Hence a pair's bits are a function of its line and the pattern's tables only: not of the other lines, the grouping
  *   of lines (below), host or device pointers, repetition, or how the pattern was spelt when the tables are equal.

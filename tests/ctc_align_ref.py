@@ -6,7 +6,8 @@ lp_t(c) = z_t[c] - logsumexp(z_t) (float64 log-softmax, then rounded to ``dtype`
     v_0(0) = lp_0(blank), v_0(1) = lp_0(l_1), -inf elsewhere
     v_t(s) = max(v_{t-1}(s), v_{t-1}(s-1), [l_s != l_{s-2}] v_{t-1}(s-2)) + lp_t(class of s)      in ``dtype``
 Ties: among equal predecessors s, then s-1, then s-2; the end state is S-1 if v_{T-1}(S-1) >= v_{T-1}(S-2), else S-2
-(state 0 for L = 0). A line with L + adjacent repeats > T has no alignment.
+(state 0 for L = 0). A line with L + adjacent repeats > T has no alignment, and neither has a line whose best score is
+-inf (logits of -inf mask classes out; every path may go through one).
 """
 import numpy as np
 
@@ -40,10 +41,11 @@ def viterbi(logits, targets, dtype=np.float64):
     tg = np.asarray(targets, np.int64).reshape(-1)
     T, L = logits.shape[0], len(tg)
     lp64 = log_softmax64(logits)
+    none = {"states": None, "path": np.full(T, -1, np.int32), "score": dtype(-np.inf),
+            "starts": np.full(L, -1, np.int32), "ends": np.full(L, -1, np.int32),
+            "logps": np.full(L, -np.inf, dtype), "lp64": lp64}
     if not feasible(tg, T):
-        return {"states": None, "path": np.full(T, -1, np.int32), "score": dtype(-np.inf),
-                "starts": np.full(L, -1, np.int32), "ends": np.full(L, -1, np.int32),
-                "logps": np.full(L, -np.inf, dtype), "lp64": lp64}
+        return none
     S = 2 * L + 1
     ext = np.zeros(S, np.int64)
     ext[1::2] = tg
@@ -69,6 +71,8 @@ def viterbi(logits, targets, dtype=np.float64):
         back[t] = k
     s = S - 1 if (L == 0 or v[S - 1] >= v[S - 2]) else S - 2
     score = v[s]
+    if score == ninf:                                  # masked (-inf) logits leave the line no path
+        return none
     states = np.zeros(T, np.int64)
     for t in range(T - 1, -1, -1):
         states[t] = s
