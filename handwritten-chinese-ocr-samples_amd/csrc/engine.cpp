@@ -307,6 +307,11 @@ int logits_on_device(hctr_ctx* c, std::vector<void*>& pool, const float* logits,
     return HCTR_OK;
 }
 
+// a result's copy to the host, queued on the stream; nothing when the caller does not want it (dst null) or it is empty
+hipError_t fetch(hctr_ctx* c, void* dst, const void* src, size_t bytes) {
+    return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
+}
+
 // the end of a call that queued work: wait for the stream; a sync error does not mask an earlier one
 int synced(hctr_ctx* c, int rc) {
     hipError_t e = hipStreamSynchronize(c->stream);
@@ -1123,6 +1128,77 @@ int run_passes(hctr_ctx* c, const Batch& in, PassPolicy policy, PassFn pass) {
 }
 
 // ---------------------------------------------------------------------------------------------
+// the logits of a scoring call ("The pass skeleton"): their source, the rows of one pass, the driver
+// ---------------------------------------------------------------------------------------------
+struct Source {              // line images that go through the forward (img.img != null), or the caller's [W][B][C] logits
+    Batch img;
+    const float* wbc;        // on the host or the device
+    int on_device;
+    int B, W, C;
+    bool images() const { return img.img != nullptr; }
+};
+
+Source image_source(const hctr_ctx* c, const void* img, int dtype, int on_device, const int32_t* widths, int B, int W) {
+    return Source{Batch{img, dtype, on_device, widths, B, W}, nullptr, 0, B, W, c->num_classes};
+}
+
+Source logits_source(const float* wbc, int on_device, int W, int B, int C) { return Source{Batch{}, wbc, on_device, B, W, C}; }
+
+struct Rows {                // the logit rows of one pass: line b of the pass, column t lies at x + (b*sb + t*st) * ld
+    const float* x;
+    int64_t ld, sb, st;
+    int C;
+    Rows from_line(int l0) const { return Rows{x + (int64_t)l0 * sb * ld, ld, sb, st, C}; }
+};
+
+// The logit rows of pass p on the device: the forward of the pass's images into the workspace's stored logits, or the
+// caller's tensor, whose rows are r = t*B + b (a host tensor is uploaded into `pool`, the driver's).
+int pass_rows(hctr_ctx* c, const Source& src, const Pass& p, std::vector<void*>& pool, Rows* r) {
+    if (src.images()) {
+        TRY(forward_pass(c, src.img, p, HEAD_LOGITS));
+        *r = Rows{c->ws.logits, c->cpad, src.W, 1, c->num_classes};
+        return HCTR_OK;
+    }
+    const float* dev = nullptr;
+    TRY(logits_on_device(c, pool, src.wbc, src.on_device, (size_t)src.W * src.B * src.C, &dev));
+    *r = Rows{dev, src.C, 1, src.B, src.C};
+    return HCTR_OK;
+}
+
+// the emissions of the lines [b0, b0 + nb), the pass's lines 0 .. nb of r, under the tables m
+int lse_rows(Prof& pf, const Rows& r, const CtcLines& m, int b0, int nb, int W, float* emis) {
+    PROF_TRY(pf, "ctc_lse", launch_ctc_lse(r.x, r.ld, r.sb, r.st, r.C, m, b0, nb, W, emis, nullptr, pf.c->stream));
+    return HCTR_OK;
+}
+
+// The passes of a scoring call over its source, and its end. Images: PASS_EXACT passes (mode 2's guard certifies
+// argmaxes, not probabilities). Caller logits: one pass of all lines. pass(p, pool) queues one pass: the family's scratch
+// when p.first == 0 (no later pass is larger, so it is sized by p.nb), pass_rows, the launches on the rows. finish()
+// queues what follows the last pass: rankings, the copies back. `pool` holds the call's device temporaries and outlives
+// the wait the driver ends in; a failure ends the call at once, drained all the same. Pageable host tables that pass
+// or finish queue were staged before hipMemcpyAsync returned.
+template <class PassFn, class FinishFn>
+int source_passes(hctr_ctx* c, const Source& src, PassFn pass, FinishFn finish) {
+    std::vector<void*> pool;
+    PoolGuard pool_guard{pool};
+    return synced(c, [&]() -> int {
+        if (src.images()) {
+            TRY(run_passes(c, src.img, PASS_EXACT, [&](const Pass& p) -> int { return pass(p, pool); }));
+        } else {
+            prof_reset(c);
+            const std::vector<int> all = line_indices(src.B);
+            TRY(pass(Pass{all.data(), src.B, 0, src.B, false, nullptr}, pool));
+        }
+        return finish();
+    }());
+}
+
+template <class PassFn>
+int source_passes(hctr_ctx* c, const Source& src, PassFn pass) {
+    return source_passes(c, src, pass, [] { return HCTR_OK; });
+}
+
+// ---------------------------------------------------------------------------------------------
 // CTC loss (hctr_ctc_loss*): argument checks, the per-line tables of kernels.h CtcLines, scratch
 // ---------------------------------------------------------------------------------------------
 struct CtcHost {
@@ -1142,6 +1218,17 @@ int check_logits_args(hctr_ctx* c, int W, int B, int C, bool have_pointers) {
     if (!c) return HCTR_ERR_ARG;
     if (W < 0 || B < 0 || C < 2 || (B > 0 && W < 1)) return fail(c, HCTR_ERR_ARG, "bad logits shape W=%d B=%d C=%d", W, B, C);
     if (B > 0 && !have_pointers) return fail(c, HCTR_ERR_ARG, "NULL pointer");
+    return HCTR_OK;
+}
+
+// input_lengths (null: W for every line) held to [min_len, W], and the head of a family's upload made of them:
+// T[B] | zero[B]
+int lengths_head(hctr_ctx* c, int B, int W, const int32_t* input_lengths, int min_len, std::vector<int32_t>* up) {
+    for (int b = 0; b < B && input_lengths; ++b)
+        if (input_lengths[b] < min_len || input_lengths[b] > W)
+            return fail(c, HCTR_ERR_ARG, "input_lengths[%d]=%d outside [%d,%d]", b, input_lengths[b], min_len, W);
+    up->assign((size_t)2 * B, 0);
+    for (int b = 0; b < B; ++b) (*up)[(size_t)b] = input_lengths ? input_lengths[b] : W;
     return HCTR_OK;
 }
 
@@ -1302,41 +1389,71 @@ int align_launch(hctr_ctx* c, Prof& pf, const float* emis, const CtcLines& m, co
 
 int align_fetch(hctr_ctx* c, const AlignDev& a, int B, int W, const float* d_score, int32_t* path, int32_t* span_start,
                 int32_t* span_end, float* span_logp, float* score) {
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
-    HIP_TRY(c, fetch(path, a.d_path, (size_t)B * W * 4));
-    HIP_TRY(c, fetch(span_start, a.d_st, a.total * 4));
-    HIP_TRY(c, fetch(span_end, a.d_en, a.total * 4));
-    HIP_TRY(c, fetch(span_logp, a.d_lp, a.total * 4));
-    HIP_TRY(c, fetch(score, d_score, (size_t)B * 4));
+    HIP_TRY(c, fetch(c, path, a.d_path, (size_t)B * W * 4));
+    HIP_TRY(c, fetch(c, span_start, a.d_st, a.total * 4));      // (nothing to fetch when every target is empty)
+    HIP_TRY(c, fetch(c, span_end, a.d_en, a.total * 4));
+    HIP_TRY(c, fetch(c, span_logp, a.d_lp, a.total * 4));
+    HIP_TRY(c, fetch(c, score, d_score, (size_t)B * 4));
     return HCTR_OK;
 }
 
-// The image path of hctr_ctc_loss / hctr_ctc_align: the lines go through the forward in passes into stored logits and
-// from there into emissions. carve(extra) takes the call's `extra_b` further bytes of scratch;
-// after(pf, m, emis, res, b0, nb) queues what follows the emissions of the pass's lines [b0, b0 + nb), res[B] being the
-// per-line result; fetch(res) queues the copies back.
-template <class Carve, class After, class Fetch>
-int ctc_image_call(hctr_ctx* c, const Batch& in, const CtcHost& h, size_t extra_b, Carve carve, After after, Fetch fetch) {
+// hctr_ctc_loss*: `nll` is the caller's [B]
+int ctc_loss_call(hctr_ctx* c, const Source& src, const int32_t* targets, const int32_t* target_lengths,
+                  const int32_t* input_lengths, float* nll) {
+    const int B = src.B, W = src.W;
+    if (B == 0) return HCTR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    CtcHost h;
+    TRY(ctc_prepare(c, B, W, src.C, targets, target_lengths, input_lengths, &h));
     CtcLines m;
-    float *res = nullptr, *emis = nullptr;
-    // pageable host tables queued below were staged before hipMemcpyAsync returned
-    return synced(c, [&]() -> int {
-        TRY(run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
-            if (p.first == 0) {               // no later pass is larger: the scratch holds the emissions of one pass
-                char* extra = nullptr;
-                TRY(ctc_scratch(c, h, (size_t)p.nb * in.W * h.D, &m, &res, &emis, extra_b, &extra));
-                TRY(carve(extra));
-            }
-            TRY(forward_pass(c, in, p, HEAD_LOGITS));
+    float *d_nll = nullptr, *emis = nullptr;
+    return source_passes(
+        c, src,
+        [&](const Pass& p, std::vector<void*>& pool) -> int {
+            if (p.first == 0) TRY(ctc_scratch(c, h, (size_t)p.nb * W * h.D, &m, &d_nll, &emis));
+            Rows r;
+            TRY(pass_rows(c, src, p, pool, &r));
             Prof pf(c);
-            PROF_TRY(pf, "ctc_lse", launch_ctc_lse(c->ws.logits, c->cpad, in.W, 1, c->num_classes, m, p.first, p.nb,
-                                                   in.W, emis, nullptr, c->stream));
-            return after(pf, m, emis, res, p.first, p.nb);
-        }));
-        return fetch(res);
-    }());
+            TRY(lse_rows(pf, r, m, p.first, p.nb, W, emis));
+            PROF_TRY(pf, "ctc_alpha", launch_ctc_alpha(emis, m, p.first, p.nb, W, h.max_states, d_nll, nullptr, nullptr,
+                                                       c->stream));
+            return HCTR_OK;
+        },
+        [&]() -> int {
+            HIP_TRY(c, hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+            return HCTR_OK;
+        });
+}
+
+// hctr_ctc_align*: the outputs are the caller's host arrays, any may be null
+int ctc_align_call(hctr_ctx* c, const Source& src, const int32_t* targets, const int32_t* target_lengths,
+                   const int32_t* input_lengths, int32_t* path, int32_t* span_start, int32_t* span_end, float* span_logp,
+                   float* score) {
+    const int B = src.B, W = src.W;
+    if (B == 0) return HCTR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    CtcHost h;
+    TRY(ctc_prepare(c, B, W, src.C, targets, target_lengths, input_lengths, &h));
+    AlignDev a;
+    align_layout(h, W, &a);
+    CtcLines m;
+    float *d_score = nullptr, *emis = nullptr;
+    return source_passes(
+        c, src,
+        [&](const Pass& p, std::vector<void*>& pool) -> int {
+            if (p.first == 0) {
+                char* extra = nullptr;
+                TRY(ctc_scratch(c, h, (size_t)p.nb * W * h.D, &m, &d_score, &emis, a.bytes() + 16, &extra));
+                align_carve(extra, &a);
+                HIP_TRY(c, hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
+            }
+            Rows r;
+            TRY(pass_rows(c, src, p, pool, &r));
+            Prof pf(c);
+            TRY(lse_rows(pf, r, m, p.first, p.nb, W, emis));
+            return align_launch(c, pf, emis, m, h, a, p.first, p.nb, W, d_score);
+        },
+        [&] { return align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1457,14 +1574,10 @@ int spot_prepare(hctr_ctx* c, int B, int W, int C, const int32_t* queries, const
                 return fail(c, HCTR_ERR_ARG, "query id %d (query %d, position %d) outside [1,%d]", queries[o + j], k, j, C - 1);
         o += L;
     }
-    for (int b = 0; b < B && input_lengths; ++b)
-        if (input_lengths[b] < 0 || input_lengths[b] > W)
-            return fail(c, HCTR_ERR_ARG, "input_lengths[%d]=%d outside [0,%d]", b, input_lengths[b], W);
+    std::vector<int32_t>& up = h->up;
+    TRY(lengths_head(c, B, W, input_lengths, 0, &up));
     h->B = B; h->Q = Q;
     h->autos.resize((size_t)Q);
-    std::vector<int32_t>& up = h->up;
-    up.assign((size_t)2 * B, 0);
-    for (int b = 0; b < B; ++b) up[(size_t)b] = input_lengths ? input_lengths[b] : W;
     h->qoff_off = up.size();
     up.resize(up.size() + (size_t)Q);
     h->blob_off = up.size();
@@ -1548,12 +1661,11 @@ int spot_scratch(hctr_ctx* c, const SpotHost& h, int n, int W, SpotDev* d) {
     return HCTR_OK;
 }
 
-// the lines [b0, b0 + nb) whose logit rows lie at x + (b*sb + t*st) * ld: per chunk the emissions, then the recursions
-int spot_launch(hctr_ctx* c, const SpotHost& h, const SpotDev& d, const float* x, int64_t ld, int64_t sb, int64_t st,
-                int C, int b0, int nb, int W) {
+// the lines [b0, b0 + nb), whose logit rows are r: per chunk the emissions, then the recursions
+int spot_launch(hctr_ctx* c, const SpotHost& h, const SpotDev& d, const Rows& r, int b0, int nb, int W) {
     Prof pf(c);
     for (const SpotChunk& ch : h.chunks) {
-        PROF_TRY(pf, "ctc_lse", launch_ctc_lse(x, ld, sb, st, C, h.lines(d.up, ch), b0, nb, W, d.emis, nullptr, c->stream));
+        TRY(lse_rows(pf, r, h.lines(d.up, ch), b0, nb, W, d.emis));
         const SpotArgs a{d.emis, d.up, b0, nb, W, ch.D, d.up + h.blob_off, d.up + h.qoff_off, d.up + ch.pair_off,
                          d.up + ch.gslot_off, ch.n, h.Q, d.contain, d.seg, d.seg_start, d.seg_end};
         PROF_TRY(pf, "spot", launch_spot(a, c->stream));
@@ -1563,14 +1675,31 @@ int spot_launch(hctr_ctx* c, const SpotHost& h, const SpotDev& d, const float* x
 
 int spot_fetch(hctr_ctx* c, const SpotHost& h, const SpotDev& d, const SpotOut& o) {
     const size_t bytes = (size_t)h.B * h.Q * 4;
-    auto fetch = [&](void* dst, const void* src) {
-        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
-    HIP_TRY(c, fetch(o.contain, d.contain));
-    HIP_TRY(c, fetch(o.seg, d.seg));
-    HIP_TRY(c, fetch(o.seg_start, d.seg_start));
-    HIP_TRY(c, fetch(o.seg_end, d.seg_end));
+    HIP_TRY(c, fetch(c, o.contain, d.contain, bytes));
+    HIP_TRY(c, fetch(c, o.seg, d.seg, bytes));
+    HIP_TRY(c, fetch(c, o.seg_start, d.seg_start, bytes));
+    HIP_TRY(c, fetch(c, o.seg_end, d.seg_end, bytes));
     return HCTR_OK;
+}
+
+// hctr_spot*
+int spot_call(hctr_ctx* c, const Source& src, const int32_t* queries, const int32_t* query_lengths, int Q,
+              const int32_t* input_lengths, const SpotOut& o) {
+    const int B = src.B, W = src.W;
+    SpotHost h;
+    TRY(spot_prepare(c, B, W, src.C, queries, query_lengths, Q, input_lengths, B, &h));
+    if (B == 0) return HCTR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    SpotDev d;
+    return source_passes(
+        c, src,
+        [&](const Pass& p, std::vector<void*>& pool) -> int {
+            if (p.first == 0) TRY(spot_scratch(c, h, p.nb, W, &d));
+            Rows r;
+            TRY(pass_rows(c, src, p, pool, &r));
+            return spot_launch(c, h, d, r, p.first, p.nb, W);
+        },
+        [&] { return spot_fetch(c, h, d, o); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1592,24 +1721,47 @@ int lex_class_cap(int lines, int W) {
     return (int)std::min<int64_t>(1 << 20, std::max<int64_t>(64, ((int64_t)4 << 30) / (4 * rows)));
 }
 
+// the tables of a lexicon or a pattern as one device block of words: each table starts on a multiple of 64 words
+struct WordTaker {
+    size_t words = 0;
+    size_t operator()(size_t n) { const size_t at = words; words += (n + 63) & ~(size_t)63; return at; }
+};
+
+// The context's device copy (*dev, of the object with *serial) of a caller's lexicon or pattern: `image`, the tables of
+// the object with serial `want` packed on the host, replaces it. `what` names the object in the message.
+int tables_on_device(hctr_ctx* c, uint64_t* serial, int32_t** dev, uint64_t want, const std::vector<int32_t>& image,
+                     const char* what) {
+    *serial = 0;
+    if (*dev) (void)hipFree(*dev);
+    *dev = nullptr;
+    void* p = nullptr;
+    const hipError_t e = hipMalloc(&p, image.size() * 4);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(c, HCTR_ERR_NOMEM, "no device memory for the %s tables (%zu bytes): %s", what, image.size() * 4,
+                    hipGetErrorString(e));
+    }
+    *dev = (int32_t*)p;
+    HIP_TRY(c, hipMemcpyAsync(p, image.data(), image.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the image is this call's, the object the caller's)
+    *serial = want;
+    return HCTR_OK;
+}
+
 // the words of the device block: uoff | coff | node | kidx | eptr | elist | prior (float bits)
 struct LexLayout {
     size_t uoff, coff, node, kidx, eptr, elist, prior, words;
     explicit LexLayout(const hctr_lex& x) {
-        size_t o = 0;
-        auto take = [&](size_t n) { const size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
+        WordTaker take;
         uoff = take(x.uoff.size()); coff = take(x.coff.size()); node = take(x.node.size()); kidx = take(x.kidx.size());
         eptr = take(x.eptr.size()); elist = take(x.elist.size()); prior = take(x.prior.size());
-        words = o;
+        words = take.words;
     }
 };
 
 // the context's device copy of the call's lexicon: uploaded when the context holds another one (or none)
 int lex_on_device(hctr_ctx* c, const hctr_lex* x) {
     if (c->lex_serial == x->serial) return HCTR_OK;
-    c->lex_serial = 0;
-    if (c->lex_dev) (void)hipFree(c->lex_dev);
-    c->lex_dev = nullptr;
     const LexLayout lay(*x);
     std::vector<int32_t> img(lay.words, 0);
     std::copy(x->uoff.begin(), x->uoff.end(), img.begin() + lay.uoff);
@@ -1619,18 +1771,7 @@ int lex_on_device(hctr_ctx* c, const hctr_lex* x) {
     std::copy(x->eptr.begin(), x->eptr.end(), img.begin() + lay.eptr);
     std::copy(x->elist.begin(), x->elist.end(), img.begin() + lay.elist);
     memcpy(img.data() + lay.prior, x->prior.data(), x->prior.size() * 4);
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, lay.words * 4);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, HCTR_ERR_NOMEM, "no device memory for the lexicon tables (%zu bytes): %s", lay.words * 4,
-                    hipGetErrorString(e));
-    }
-    c->lex_dev = (int32_t*)p;
-    HIP_TRY(c, hipMemcpyAsync(p, img.data(), lay.words * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the image is this call's, the lexicon the caller's)
-    c->lex_serial = x->serial;
-    return HCTR_OK;
+    return tables_on_device(c, &c->lex_serial, &c->lex_dev, x->serial, img, "lexicon");
 }
 
 struct LexChunk {
@@ -1661,13 +1802,9 @@ int lex_prepare(hctr_ctx* c, const hctr_lex* lex, int B, int W, int C, const int
     if (lex->C != C) return fail(c, HCTR_ERR_ARG, "the lexicon was built for %d classes, the call has %d", lex->C, C);
     if (n < 1 || n > kLexMaxTop) return fail(c, HCTR_ERR_ARG, "n=%d outside [1,%d]", n, kLexMaxTop);
     if ((int64_t)std::max(B, 1) * lex->N > INT32_MAX) return fail(c, HCTR_ERR_ARG, "B*N=%lld too large", (long long)B * lex->N);
-    for (int b = 0; b < B && input_lengths; ++b)
-        if (input_lengths[b] < 1 || input_lengths[b] > W)
-            return fail(c, HCTR_ERR_ARG, "input_lengths[%d]=%d outside [1,%d]", b, input_lengths[b], W);
-    h->lex = lex; h->B = B; h->n = n;
     std::vector<int32_t>& up = h->up;
-    up.assign((size_t)2 * B, 0);
-    for (int b = 0; b < B; ++b) up[(size_t)b] = input_lengths ? input_lengths[b] : W;
+    TRY(lengths_head(c, B, W, input_lengths, 1, &up));
+    h->lex = lex; h->B = B; h->n = n;
     h->umap_off = up.size();
     up.resize(up.size() + lex->ucls.size(), 0);
     // chunks of consecutive units whose classes, with the blank, stay within the cap
@@ -1725,9 +1862,8 @@ int lex_scratch(hctr_ctx* c, const LexHost& h, int nl, int W, LexDev* d) {
     return HCTR_OK;
 }
 
-// the lines [b0, b0 + nb) whose logit rows lie at x + (b*sb + t*st) * ld: per chunk the emissions, then the trie
-int lex_launch(hctr_ctx* c, const LexHost& h, const LexDev& d, const float* x, int64_t ld, int64_t sb, int64_t st, int C,
-               int b0, int nb, int W) {
+// the lines [b0, b0 + nb), whose logit rows are r: per chunk the emissions, then the trie
+int lex_launch(hctr_ctx* c, const LexHost& h, const LexDev& d, const Rows& r, int b0, int nb, int W) {
     Prof pf(c);
     const hctr_lex& lx = *h.lex;
     const LexLayout lay(lx);
@@ -1735,7 +1871,7 @@ int lex_launch(hctr_ctx* c, const LexHost& h, const LexDev& d, const float* x, i
     for (const LexChunk& ch : h.chunks) {
         PROF_TRY(pf, "lexicon_classes", launch_lexicon_classes(d.up + ch.cls_off, ch.D, h.B, d.cls, d.nd, c->stream));
         const CtcLines m{d.up, d.up + h.B, d.up + h.B, d.nd, d.cls, d.up + h.B, ch.D};
-        PROF_TRY(pf, "ctc_lse", launch_ctc_lse(x, ld, sb, st, C, m, b0, nb, W, d.emis, nullptr, c->stream));
+        TRY(lse_rows(pf, r, m, b0, nb, W, d.emis));
         const LexArgs a{d.emis, d.up, b0, nb, W, ch.D, t + lay.uoff, t + lay.coff, t + lay.node, t + lay.kidx, t + lay.eptr,
                         t + lay.elist, d.up + h.umap_off, ch.u0, ch.nu, lx.max_unit, lx.N, d.score};
         PROF_TRY(pf, "lexicon_trie", launch_lexicon_trie(a, c->stream));
@@ -1750,17 +1886,34 @@ int lex_finish(hctr_ctx* c, const LexHost& h, const LexDev& d, const LexOut& o) 
     const float* prior = lx.has_prior ? (const float*)(c->lex_dev + LexLayout(lx).prior) : nullptr;
     PROF_TRY(pf, "lexicon_rank", launch_lexicon_rank(d.score, prior, h.B, lx.N, h.n, d.top_entry, d.top_logp, d.top_rank,
                                                      d.log_total, d.count, c->stream));
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
     const size_t B = (size_t)h.B, n = (size_t)h.n;
-    HIP_TRY(c, fetch(o.top_entry, d.top_entry, B * n * 4));
-    HIP_TRY(c, fetch(o.top_logp, d.top_logp, B * n * 4));
-    HIP_TRY(c, fetch(o.top_rank, d.top_rank, B * n * 8));
-    HIP_TRY(c, fetch(o.log_total, d.log_total, B * 8));
-    HIP_TRY(c, fetch(o.count, d.count, B * 4));
-    HIP_TRY(c, fetch(o.scores, d.score, B * lx.N * 4));
+    HIP_TRY(c, fetch(c, o.top_entry, d.top_entry, B * n * 4));
+    HIP_TRY(c, fetch(c, o.top_logp, d.top_logp, B * n * 4));
+    HIP_TRY(c, fetch(c, o.top_rank, d.top_rank, B * n * 8));
+    HIP_TRY(c, fetch(c, o.log_total, d.log_total, B * 8));
+    HIP_TRY(c, fetch(c, o.count, d.count, B * 4));
+    HIP_TRY(c, fetch(c, o.scores, d.score, B * lx.N * 4));
     return HCTR_OK;
+}
+
+// hctr_lexicon*
+int lex_call(hctr_ctx* c, const Source& src, const hctr_lex* lex, const int32_t* input_lengths, int n, const LexOut& o) {
+    const int B = src.B, W = src.W;
+    LexHost h;
+    TRY(lex_prepare(c, lex, B, W, src.C, input_lengths, n, B, &h));
+    if (B == 0) return HCTR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(lex_on_device(c, lex));
+    LexDev d;
+    return source_passes(
+        c, src,
+        [&](const Pass& p, std::vector<void*>& pool) -> int {
+            if (p.first == 0) TRY(lex_scratch(c, h, p.nb, W, &d));
+            Rows r;
+            TRY(pass_rows(c, src, p, pool, &r));
+            return lex_launch(c, h, d, r, p.first, p.nb, W);
+        },
+        [&] { return lex_finish(c, h, d, o); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1783,21 +1936,17 @@ int pat_group_lines(int S, int D, int W) {
 struct PatLayout {
     size_t slot, label, in_ptr, accept, start, cls, in_src, words;
     explicit PatLayout(const hctr_pat& x) {
-        size_t o = 0;
-        auto take = [&](size_t n) { const size_t at = o; o += (n + 63) & ~(size_t)63; return at; };
+        WordTaker take;
         slot = take(x.slot.size()); label = take(x.label.size()); in_ptr = take(x.in_ptr.size());
         accept = take(x.accept.size()); start = take(x.start.size()); cls = take(x.classes.size() + 1);
         in_src = take((x.in_src.size() + 1) / 2);
-        words = o;
+        words = take.words;
     }
 };
 
 // the context's device copy of the call's pattern: uploaded when the context holds another one (or none)
 int pat_on_device(hctr_ctx* c, const hctr_pat* x) {
     if (c->pat_serial == x->serial) return HCTR_OK;
-    c->pat_serial = 0;
-    if (c->pat_dev) (void)hipFree(c->pat_dev);
-    c->pat_dev = nullptr;
     const PatLayout lay(*x);
     std::vector<int32_t> img(lay.words, 0);
     std::copy(x->slot.begin(), x->slot.end(), img.begin() + lay.slot);
@@ -1807,18 +1956,7 @@ int pat_on_device(hctr_ctx* c, const hctr_pat* x) {
     std::copy(x->start.begin(), x->start.end(), img.begin() + lay.start);
     std::copy(x->classes.begin(), x->classes.end(), img.begin() + lay.cls + 1);
     memcpy(img.data() + lay.in_src, x->in_src.data(), x->in_src.size() * 2);
-    void* p = nullptr;
-    const hipError_t e = hipMalloc(&p, lay.words * 4);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(c, HCTR_ERR_NOMEM, "no device memory for the pattern tables (%zu bytes): %s", lay.words * 4,
-                    hipGetErrorString(e));
-    }
-    c->pat_dev = (int32_t*)p;
-    HIP_TRY(c, hipMemcpyAsync(p, img.data(), lay.words * 4, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the image is this call's, the pattern the caller's)
-    c->pat_serial = x->serial;
-    return HCTR_OK;
+    return tables_on_device(c, &c->pat_serial, &c->pat_dev, x->serial, img, "pattern");
 }
 
 struct PatOut {               // the caller's host outputs; any may be null
@@ -1840,13 +1978,9 @@ int pat_prepare(hctr_ctx* c, const hctr_pat* pat, int B, int W, int C, const int
                 PatHost* h) {
     if (!pat) return fail(c, HCTR_ERR_ARG, "pat is NULL");
     if (pat->C != C) return fail(c, HCTR_ERR_ARG, "the pattern was built for %d classes, the call has %d", pat->C, C);
-    for (int b = 0; b < B && input_lengths; ++b)
-        if (input_lengths[b] < 1 || input_lengths[b] > W)
-            return fail(c, HCTR_ERR_ARG, "input_lengths[%d]=%d outside [1,%d]", b, input_lengths[b], W);
+    TRY(lengths_head(c, B, W, input_lengths, 1, &h->up));
     h->pat = pat; h->B = B; h->D = (int)pat->classes.size() + 1; h->vit = o.viterbi();
     h->group = pat_group_lines(pat->S, h->D, W);
-    h->up.assign((size_t)2 * B, 0);
-    for (int b = 0; b < B; ++b) h->up[(size_t)b] = input_lengths ? input_lengths[b] : W;
     h->nll_fix.assign((size_t)B, 0);
     return HCTR_OK;
 }
@@ -1922,9 +2056,8 @@ int pat_text_nll(hctr_ctx* c, Prof& pf, PatHost& h, const PatDev& d, int gb0, in
     return HCTR_OK;
 }
 
-// the lines [b0, b0 + nb) whose logit rows lie at x + (b*sb + t*st) * ld, a group at a time: emissions, recursion, walk
-int pat_launch(hctr_ctx* c, PatHost& h, const PatDev& d, bool want_nll, const float* x, int64_t ld, int64_t sb, int64_t st,
-               int C, int b0, int nb, int W) {
+// the lines [b0, b0 + nb), whose logit rows are r, a group at a time: emissions, recursion, walk
+int pat_launch(hctr_ctx* c, PatHost& h, const PatDev& d, bool want_nll, const Rows& r, int b0, int nb, int W) {
     Prof pf(c);
     const hctr_pat& px = *h.pat;
     const PatLayout lay(px);
@@ -1933,8 +2066,7 @@ int pat_launch(hctr_ctx* c, PatHost& h, const PatDev& d, bool want_nll, const fl
     const CtcLines m{d.up, d.up + h.B, d.up + h.B, d.nd, d.cls, d.up + h.B, h.D};
     for (int l0 = 0; l0 < nb; l0 += d.g) {
         const int n = std::min(d.g, nb - l0), gb0 = b0 + l0;
-        PROF_TRY(pf, "ctc_lse", launch_ctc_lse(x + (int64_t)l0 * sb * ld, ld, sb, st, C, m, gb0, n, W, d.emis, nullptr,
-                                               c->stream));
+        TRY(lse_rows(pf, r.from_line(l0), m, gb0, n, W, d.emis));
         const PatArgs a{d.emis, d.up, gb0, n, W, h.D, px.S, px.edges(), t + lay.slot, t + lay.label, t + lay.in_ptr,
                         (const uint16_t*)(t + lay.in_src), t + lay.accept, t + lay.start, (int)px.accept.size(),
                         (int)px.start.size(), d.bp, d.logp, d.best, d.endst};
@@ -1949,19 +2081,16 @@ int pat_launch(hctr_ctx* c, PatHost& h, const PatDev& d, bool want_nll, const fl
 }
 
 int pat_finish(hctr_ctx* c, const PatHost& h, const PatDev& d, const PatOut& o, int W) {
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
     const size_t B = (size_t)h.B, cb = B * W * 4;
-    HIP_TRY(c, fetch(o.logp, d.logp, B * 4));
-    HIP_TRY(c, fetch(o.best, d.best, B * 4));
-    HIP_TRY(c, fetch(o.path, d.path, cb));
-    HIP_TRY(c, fetch(o.labels, d.labels, cb));
-    HIP_TRY(c, fetch(o.lengths, d.lengths, B * 4));
-    HIP_TRY(c, fetch(o.span_start, d.st, cb));
-    HIP_TRY(c, fetch(o.span_end, d.en, cb));
-    HIP_TRY(c, fetch(o.char_logp, d.clp, cb));
-    HIP_TRY(c, fetch(o.text_nll, d.nll, B * 4));
+    HIP_TRY(c, fetch(c, o.logp, d.logp, B * 4));
+    HIP_TRY(c, fetch(c, o.best, d.best, B * 4));
+    HIP_TRY(c, fetch(c, o.path, d.path, cb));
+    HIP_TRY(c, fetch(c, o.labels, d.labels, cb));
+    HIP_TRY(c, fetch(c, o.lengths, d.lengths, B * 4));
+    HIP_TRY(c, fetch(c, o.span_start, d.st, cb));
+    HIP_TRY(c, fetch(c, o.span_end, d.en, cb));
+    HIP_TRY(c, fetch(c, o.char_logp, d.clp, cb));
+    HIP_TRY(c, fetch(c, o.text_nll, d.nll, B * 4));
     if (!o.text_nll) return HCTR_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t b = 0; b < B; ++b) {
@@ -1969,6 +2098,26 @@ int pat_finish(hctr_ctx* c, const PatHost& h, const PatDev& d, const PatOut& o, 
         if (h.nll_fix[b] == 2) o.text_nll[b] = std::numeric_limits<float>::infinity();
     }
     return HCTR_OK;
+}
+
+// hctr_pattern*
+int pat_call(hctr_ctx* c, const Source& src, const hctr_pat* pat, const int32_t* input_lengths, const PatOut& o) {
+    const int B = src.B, W = src.W;
+    PatHost h;
+    TRY(pat_prepare(c, pat, B, W, src.C, input_lengths, o, &h));
+    if (B == 0) return HCTR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(pat_on_device(c, pat));
+    PatDev d;
+    return source_passes(
+        c, src,
+        [&](const Pass& p, std::vector<void*>& pool) -> int {
+            if (p.first == 0) TRY(pat_scratch(c, h, p.nb, W, &d));
+            Rows r;
+            TRY(pass_rows(c, src, p, pool, &r));
+            return pat_launch(c, h, d, o.text_nll != nullptr, r, p.first, p.nb, W);
+        },
+        [&] { return pat_finish(c, h, d, o, W); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1993,18 +2142,18 @@ struct RecCall {             // + where the batch's labels and lengths go on the
     }
 };
 
-// One pass of nb lines, [b0, b0 + nb) of the caller's batch, whose logit rows lie at x + (b*sb + t*st) * ld. The CTC
-// scratch holds lse[nb*W] first, which outlives the row figures and the spans; once those are on the host the tables,
-// nll and emissions of the decoded text take their place. Returns with the stream drained when text_nll is wanted.
-int rec_pass(hctr_ctx* c, const float* x, int64_t ld, int64_t sb, int64_t st, int C, int b0, int nb, int W,
-             const RecCall& rc) {
+// One pass of nb lines, [b0, b0 + nb) of the caller's batch, whose logit rows are r. The CTC scratch holds lse[nb*W]
+// first, which outlives the row figures and the spans; once those are on the host the tables, nll and emissions of the
+// decoded text take their place. Returns with the stream drained when text_nll is wanted.
+int rec_pass(hctr_ctx* c, const Rows& r, int b0, int nb, int W, const RecCall& rc) {
     const RecOut& o = rc.o;
+    const int C = r.C;
     int32_t *const h_lab = rc.h_lab, *const h_len = rc.h_len;
     const size_t n = (size_t)nb, col_b = align256(n * W * 4), line_b = align256(n * 4), lse_b = align256(n * W * 8);
     TRY(ctc_reserve(c, lse_b + 10 * col_b + 2 * line_b));
     double* d_lse = (double*)c->ctc_buf;
     char* q = c->ctc_buf + lse_b;
-    auto col = [&]() { char* r = q; q += col_b; return r; };
+    auto col = [&]() { char* at = q; q += col_b; return at; };
     int32_t *k1 = (int32_t*)col(), *k2 = (int32_t*)col();
     float *lp1 = (float*)col(), *lp2 = (float*)col();
     int32_t *d_lab = (int32_t*)col(), *d_st = (int32_t*)col(), *d_en = (int32_t*)col(), *d_alab = (int32_t*)col();
@@ -2012,24 +2161,22 @@ int rec_pass(hctr_ctx* c, const float* x, int64_t ld, int64_t sb, int64_t st, in
     int32_t* d_len = (int32_t*)q;
     float* d_plp = (float*)(q + line_b);
     Prof pf(c);
-    PROF_TRY(pf, "greedy_rowstat", launch_greedy_rowstat(x, ld, sb, st, C, nb, W, k1, k2, lp1, lp2, d_lse, c->stream));
+    PROF_TRY(pf, "greedy_rowstat", launch_greedy_rowstat(r.x, r.ld, r.sb, r.st, C, nb, W, k1, k2, lp1, lp2, d_lse,
+                                                         c->stream));
     PROF_TRY(pf, "greedy_spans", launch_greedy_spans(k1, k2, lp1, lp2, nb, W, C, d_lab, d_len, d_st, d_en, d_clp,
                                                      d_alab, d_alp, d_plp, c->stream));
     const size_t co = (size_t)b0 * W, cb = n * W * 4;
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
-    HIP_TRY(c, fetch(h_lab ? h_lab + co : nullptr, d_lab, cb));
-    HIP_TRY(c, fetch(h_len ? h_len + b0 : nullptr, d_len, n * 4));
-    HIP_TRY(c, fetch(o.span_start ? o.span_start + co : nullptr, d_st, cb));
-    HIP_TRY(c, fetch(o.span_end ? o.span_end + co : nullptr, d_en, cb));
-    HIP_TRY(c, fetch(o.char_logp ? o.char_logp + co : nullptr, d_clp, cb));
-    HIP_TRY(c, fetch(o.alt_label ? o.alt_label + co : nullptr, d_alab, cb));
-    HIP_TRY(c, fetch(o.alt_logp ? o.alt_logp + co : nullptr, d_alp, cb));
-    HIP_TRY(c, fetch(o.path_logp ? o.path_logp + b0 : nullptr, d_plp, n * 4));
+    HIP_TRY(c, fetch(c, h_lab ? h_lab + co : nullptr, d_lab, cb));
+    HIP_TRY(c, fetch(c, h_len ? h_len + b0 : nullptr, d_len, n * 4));
+    HIP_TRY(c, fetch(c, o.span_start ? o.span_start + co : nullptr, d_st, cb));
+    HIP_TRY(c, fetch(c, o.span_end ? o.span_end + co : nullptr, d_en, cb));
+    HIP_TRY(c, fetch(c, o.char_logp ? o.char_logp + co : nullptr, d_clp, cb));
+    HIP_TRY(c, fetch(c, o.alt_label ? o.alt_label + co : nullptr, d_alab, cb));
+    HIP_TRY(c, fetch(c, o.alt_logp ? o.alt_logp + co : nullptr, d_alp, cb));
+    HIP_TRY(c, fetch(c, o.path_logp ? o.path_logp + b0 : nullptr, d_plp, n * 4));
     if (!o.text_nll) return HCTR_OK;
     std::vector<float> plp(n);                 // a NaN here marks a line with a NaN row
-    HIP_TRY(c, fetch(plp.data(), d_plp, n * 4));
+    HIP_TRY(c, fetch(c, plp.data(), d_plp, n * 4));
     // the loss of the decoded text: its tables are built as the loss builds them, on labels that must be on the host
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     std::vector<int32_t> tg, tl((size_t)nb);
@@ -2048,7 +2195,7 @@ int rec_pass(hctr_ctx* c, const float* x, int64_t ld, int64_t sb, int64_t st, in
     float* d_nll = (float*)(c->ctc_buf + lse_b + tab_b);
     float* emis = (float*)(c->ctc_buf + lse_b + tab_b + line_b);
     HIP_TRY(c, hipMemcpyAsync(c->ctc_buf + lse_b, h.tab.data(), h.tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-    PROF_TRY(pf, "ctc_emis_gather", launch_ctc_emis_gather(x, ld, sb, st, m, 0, nb, W, d_lse, emis, c->stream));
+    PROF_TRY(pf, "ctc_emis_gather", launch_ctc_emis_gather(r.x, r.ld, r.sb, r.st, m, 0, nb, W, d_lse, emis, c->stream));
     PROF_TRY(pf, "ctc_alpha", launch_ctc_alpha(emis, m, 0, nb, W, h.max_states, d_nll, nullptr, nullptr, c->stream));
     HIP_TRY(c, hipMemcpyAsync(o.text_nll + b0, d_nll, n * 4, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -2057,6 +2204,18 @@ int rec_pass(hctr_ctx* c, const float* x, int64_t ld, int64_t sb, int64_t st, in
         if (tl[(size_t)b] != h_len[b0 + b] || plp[(size_t)b] != plp[(size_t)b])
             o.text_nll[b0 + b] = std::numeric_limits<float>::quiet_NaN();
     return HCTR_OK;
+}
+
+// hctr_recognize*: every pass sizes its own scratch and fetches its own lines
+int rec_call(hctr_ctx* c, const Source& src, const RecOut& o) {
+    if (src.B == 0) return HCTR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const RecCall rc(o, src.B, src.W);
+    return source_passes(c, src, [&](const Pass& p, std::vector<void*>& pool) -> int {
+        Rows r;
+        TRY(pass_rows(c, src, p, pool, &r));
+        return rec_pass(c, r, p.first, p.nb, src.W, rc);
+    });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2227,13 +2386,10 @@ int edit_launch(hctr_ctx* c, Prof& pf, EditCall* e, const int* lines, const int3
 }
 
 int edit_fetch(hctr_ctx* c, const EditCall& e, const EditOut& o) {
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        return dst && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
-    HIP_TRY(c, fetch(o.edits, e.d_edits, (size_t)e.B * 4));
-    HIP_TRY(c, fetch(o.counts, e.d_counts, (size_t)e.B * 16));
-    HIP_TRY(c, fetch(o.ref_map, e.d_rmap, e.total * 4));
-    HIP_TRY(c, fetch(o.hyp_map, e.d_hmap, (size_t)e.B * e.stride * 4));
+    HIP_TRY(c, fetch(c, o.edits, e.d_edits, (size_t)e.B * 4));
+    HIP_TRY(c, fetch(c, o.counts, e.d_counts, (size_t)e.B * 16));
+    HIP_TRY(c, fetch(c, o.ref_map, e.d_rmap, e.total * 4));
+    HIP_TRY(c, fetch(c, o.hyp_map, e.d_hmap, (size_t)e.B * e.stride * 4));
     return HCTR_OK;
 }
 
@@ -2248,15 +2404,15 @@ struct BeamLists {           // one pass's lists on the device, rows r = t*nb + 
     bool fused = false;                          // the lists came out of the head GEMM's epilogues (ws.emit_* hold them)
 };
 
-// Log-softmax + top-k of the pass's lines: the forward of `in` (or, with in == null, the caller's logits in WBC layout,
-// one pass of all lines), then the fused front end or the stored-logits kernels. Temporaries live in c->beam_allocs,
-// which the next pass (or the caller, at the end of its call) frees.
-int beam_lists_pass(hctr_ctx* c, const Batch* in, const Pass& p, const float* logits_wbc, int logits_on_device, int W,
-                    int C, int k, bool want_candidates, double thresh, BeamLists* out) {
+// Log-softmax + top-k of the pass's lines: the forward of the source's images (or the caller's logits in WBC layout, one
+// pass of all lines), then the fused front end or the stored-logits kernels. Temporaries live in c->beam_allocs, which
+// the next pass (or the caller, at the end of its call) frees.
+int beam_lists_pass(hctr_ctx* c, const Source& src, const Pass& p, int k, bool want_candidates, double thresh,
+                    BeamLists* out) {
     std::vector<void*>& pool = c->beam_allocs;
-    const int nb = p.nb;
+    const int nb = p.nb, W = src.W, C = src.C;
     const int64_t rows = (int64_t)nb * W;
-    const bool from_img = in != nullptr;
+    const bool from_img = src.images();
     free_pool(pool);
     const float* rowsrc = nullptr;
     int64_t ld = 0;
@@ -2265,16 +2421,12 @@ int beam_lists_pass(hctr_ctx* c, const Batch* in, const Pass& p, const float* lo
     // more than kBeamCap list slots (near-uniform logits) is redone through the stored-logits kernels.
     bool fused = from_img && c->fuse_beam && k <= kBeamMaxK && k <= head_parts(c);
     if (from_img) {
-        TRY(forward_pass(c, *in, p, fused ? HEAD_BEAM : HEAD_LOGITS));
+        TRY(forward_pass(c, src.img, p, fused ? HEAD_BEAM : HEAD_LOGITS));
         rowsrc = c->ws.logits; ld = c->cpad;
     } else {
-        float *up = nullptr, *rowsbuf = nullptr;
-        const float* dev = logits_wbc;
-        if (!logits_on_device) {
-            TRY(dev_alloc(c, pool, &up, (size_t)rows * C, false));
-            HIP_TRY(c, hipMemcpyAsync(up, logits_wbc, (size_t)rows * C * 4, hipMemcpyHostToDevice, c->stream));
-            dev = up;
-        }
+        float* rowsbuf = nullptr;
+        const float* dev = nullptr;
+        TRY(logits_on_device(c, pool, src.wbc, src.on_device, (size_t)rows * C, &dev));
         TRY(dev_alloc(c, pool, &rowsbuf, (size_t)rows * C, false));
         HIP_TRY(c, launch_wbc_to_rows(dev, nb, W, C, rowsbuf, C, c->stream));
         rowsrc = rowsbuf; ld = C;
@@ -2302,7 +2454,7 @@ int beam_lists_pass(hctr_ctx* c, const Batch* in, const Pass& p, const float* lo
             ++c->beam_fallbacks;
             Pass redo = p;
             redo.guard_dst = nullptr;      // (the guard figures came back with the fused forward)
-            TRY(forward_pass(c, *in, redo, HEAD_LOGITS));
+            TRY(forward_pass(c, src.img, redo, HEAD_LOGITS));
             rowsrc = c->ws.logits;
             TRY(own_outputs());
         }
@@ -2434,6 +2586,22 @@ int nbest_scratch(hctr_ctx* c, NbestCall* n, int lines) {
     return HCTR_OK;
 }
 
+// a search's results of the pass's lines [b0, b0 + nb), queued to the caller's rows; each exists in the searches that fill it
+int nbest_fetch(hctr_ctx* c, const NbestCall& n, int b0, int nb) {
+    const size_t ln = (size_t)nb * n.nbest, lo = (size_t)b0 * n.nbest;
+    HIP_TRY(c, fetch(c, n.o.labels ? n.o.labels + lo * n.W : nullptr, n.d_lab, ln * n.W * 4));
+    HIP_TRY(c, fetch(c, n.o.lengths ? n.o.lengths + lo : nullptr, n.d_len, ln * 4));
+    HIP_TRY(c, fetch(c, n.o.logp ? n.o.logp + lo : nullptr, n.d_logp, ln * 8));
+    HIP_TRY(c, fetch(c, n.o.score ? n.o.score + lo : nullptr, n.d_score, ln * 8));
+    HIP_TRY(c, fetch(c, n.o.count ? n.o.count + b0 : nullptr, n.d_cnt, (size_t)nb * 4));
+    if (n.lm || n.skip) HIP_TRY(c, fetch(c, n.o_lm ? n.o_lm + lo : nullptr, n.d_lm, ln * 8));
+    if (n.skip) {
+        HIP_TRY(c, fetch(c, n.o_status ? n.o_status + b0 : nullptr, n.d_status, (size_t)nb * 4));
+        HIP_TRY(c, fetch(c, n.o_ranked ? n.o_ranked + b0 : nullptr, n.d_ranked, (size_t)nb * 4));
+    }
+    return HCTR_OK;
+}
+
 // the search of the pass's lines [b0, b0 + nb) on their lists (rows r = t*nb + b), results queued to the caller's rows
 int nbest_launch(hctr_ctx* c, const NbestCall& n, const int32_t* d_idx, const float* d_lp, int b0, int nb) {
     const size_t ln = (size_t)nb * n.nbest;
@@ -2457,17 +2625,7 @@ int nbest_launch(hctr_ctx* c, const NbestCall& n, const int32_t* d_idx, const fl
     if (n.o.labels)
         PROF_TRY(pf, "prefix_backtrace", launch_prefix_backtrace(n.d_hist, d_steps, nb, n.W, n.beam, n.nbest, n.d_len,
                                                                  n.d_cnt, n.d_lab, c->stream));
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
-    const size_t lo = (size_t)b0 * n.nbest;
-    HIP_TRY(c, fetch(n.o.labels ? n.o.labels + lo * n.W : nullptr, n.d_lab, ln * n.W * 4));
-    HIP_TRY(c, fetch(n.o.lengths ? n.o.lengths + lo : nullptr, n.d_len, ln * 4));
-    HIP_TRY(c, fetch(n.o.logp ? n.o.logp + lo : nullptr, n.d_logp, ln * 8));
-    HIP_TRY(c, fetch(n.o.score ? n.o.score + lo : nullptr, n.d_score, ln * 8));
-    HIP_TRY(c, fetch(n.o.count ? n.o.count + b0 : nullptr, n.d_cnt, (size_t)nb * 4));
-    if (n.lm) HIP_TRY(c, fetch(n.o_lm ? n.o_lm + lo : nullptr, n.d_lm, ln * 8));
-    return HCTR_OK;
+    return nbest_fetch(c, n, b0, nb);
 }
 
 // the extra arguments of hctr_nbest_skip*: lm == null is the zero LM, lm_panelty then unused
@@ -2500,19 +2658,7 @@ int skip_launch(hctr_ctx* c, const NbestCall& n, const int32_t* d_top1, int ks, 
     if (n.o.labels)
         PROF_TRY(pf, "prefix_backtrace", launch_prefix_backtrace(n.d_hist, n.d_end, nb, n.W, n.beam, n.nbest, n.d_len,
                                                                  n.d_cnt, n.d_lab, c->stream));
-    auto fetch = [&](void* dst, const void* src, size_t bytes) {
-        return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream) : hipSuccess;
-    };
-    const size_t lo = (size_t)b0 * n.nbest;
-    HIP_TRY(c, fetch(n.o.labels ? n.o.labels + lo * n.W : nullptr, n.d_lab, ln * n.W * 4));
-    HIP_TRY(c, fetch(n.o.lengths ? n.o.lengths + lo : nullptr, n.d_len, ln * 4));
-    HIP_TRY(c, fetch(n.o.logp ? n.o.logp + lo : nullptr, n.d_logp, ln * 8));
-    HIP_TRY(c, fetch(n.o.score ? n.o.score + lo : nullptr, n.d_score, ln * 8));
-    HIP_TRY(c, fetch(n.o.count ? n.o.count + b0 : nullptr, n.d_cnt, (size_t)nb * 4));
-    HIP_TRY(c, fetch(n.o_lm ? n.o_lm + lo : nullptr, n.d_lm, ln * 8));
-    HIP_TRY(c, fetch(n.o_status ? n.o_status + b0 : nullptr, n.d_status, (size_t)nb * 4));
-    HIP_TRY(c, fetch(n.o_ranked ? n.o_ranked + b0 : nullptr, n.d_ranked, (size_t)nb * 4));
-    return HCTR_OK;
+    return nbest_fetch(c, n, b0, nb);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3036,7 +3182,8 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
         }
         if (k > C) return fail(c, HCTR_ERR_ARG, "k=%d exceeds C=%d", k, C);
         const double thresh = std::log(0.001);        // utils/ctc_codec.py:128
-        const Batch in{img, img_dtype, img_on_device, widths, B, W};
+        const Source src = from_img ? image_source(c, img, img_dtype, img_on_device, widths, B, W)
+                                    : logits_source(logits_wbc, logits_on_device, W, B, C);
         // candidate lists of one pass (lines in pass order); owner[line] = the pass whose lists are current for the line
         struct PassOut { std::vector<int> lines; std::vector<int64_t> loff; std::vector<int32_t> ci; std::vector<float> cl; };
         std::vector<PassOut> outs;
@@ -3050,8 +3197,7 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
             const int nb = p.nb;
             const int64_t rows = (int64_t)nb * W;
             BeamLists L;
-            TRY(beam_lists_pass(c, from_img ? &in : nullptr, p, logits_wbc, logits_on_device, W, C, k, want_candidates != 0,
-                                thresh, &L));
+            TRY(beam_lists_pass(c, src, p, k, want_candidates != 0, thresh, &L));
             const bool fused = L.fused;
             const float* rowsrc = L.rowsrc;
             const int64_t ld = L.ld;
@@ -3117,7 +3263,7 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
         // hctr_greedy - once more in f16x3, their rows of every output replaced); caller logits: one pass, no forward
         int rc;
         if (from_img) {
-            rc = run_passes(c, in, PASS_OWN, run_pass);
+            rc = run_passes(c, src.img, PASS_OWN, run_pass);
         } else {
             prof_reset(c);
             guard_clear(c);
@@ -3153,7 +3299,8 @@ int hctr_beam_frontend(hctr_ctx* c, const void* img, int img_dtype, int img_on_d
 
 // The three N-best entry points, each with and without an n-gram model: `lm` (null or the three extra arguments of
 // hctr_nbest_lm*) is all that tells the two apart. With lm->sweep they are the entry points of hctr_lm_sweep*: the same
-// checks, lists and passes, the sweep's scratch and launches in place of the single search's.
+// checks, lists and passes, the sweep's scratch and launches in place of the single search's. The caller's lists have a
+// body of their own (nbest_topk_impl); caller logits and line images share nbest_call.
 struct NbestLmArgs {
     const hctr_lm* lm;
     double lm_panelty;
@@ -3201,29 +3348,33 @@ static int nbest_topk_impl(hctr_ctx* c, const NbestLmArgs* lm, const int32_t* to
     });
 }
 
+// hctr_nbest* / hctr_nbest_lm* / hctr_lm_sweep* on a source: inside each pass the search runs on the front end's lists
+// where they lie; only its results go to the host
+static int nbest_call(hctr_ctx* c, const NbestLmArgs* lm, const Source& src, int k, int beam, int nbest, double len_bonus,
+                      const int32_t* input_lengths, const NbestOut& o) {
+    NbestCall n;
+    TRY(nbest_prepare(c, src.B, src.W, src.C, k, beam, nbest, len_bonus, input_lengths, o, &n));
+    if (lm) TRY(nbest_lm_prepare(c, &n, lm->lm, lm->lm_panelty, lm->lm_score));
+    SweepCall sw;
+    if (lm && lm->sweep) TRY(sweep_prepare(c, n, *lm->sweep, &sw));
+    if (src.B == 0) return HCTR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = source_passes(c, src, [&](const Pass& p, std::vector<void*>&) -> int {
+        if (p.first == 0) TRY(sw.on ? sweep_scratch(c, &n, &sw, p.nb) : nbest_scratch(c, &n, p.nb));
+        BeamLists L;
+        TRY(beam_lists_pass(c, src, p, k, false, std::log(0.001), &L));
+        return sw.on ? sweep_launch(c, n, sw, L.idx, L.lp, p.first, p.nb) : nbest_launch(c, n, L.idx, L.lp, p.first, p.nb);
+    });
+    free_pool(c->beam_allocs);
+    return sweep_finish(rc, sw);
+}
+
 static int nbest_logits_impl(hctr_ctx* c, const NbestLmArgs* lm, const float* logits_wbc, int on_device, int W, int B, int C,
                              int k, int beam, int nbest, double len_bonus, const int32_t* input_lengths,
                              const NbestOut& o) {
     return guard(c, [&]() -> int {
         TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
-        NbestCall n;
-        TRY(nbest_prepare(c, B, W, C, k, beam, nbest, len_bonus, input_lengths, o, &n));
-        if (lm) TRY(nbest_lm_prepare(c, &n, lm->lm, lm->lm_panelty, lm->lm_score));
-        SweepCall sw;
-        if (lm && lm->sweep) TRY(sweep_prepare(c, n, *lm->sweep, &sw));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        prof_reset(c);
-        const std::vector<int> all = line_indices(B);
-        const int rc = synced(c, [&]() -> int {
-            BeamLists L;
-            TRY(sw.on ? sweep_scratch(c, &n, &sw, B) : nbest_scratch(c, &n, B));
-            TRY(beam_lists_pass(c, nullptr, Pass{all.data(), B, 0, B, false, nullptr}, logits_wbc, on_device, W, C, k, false,
-                                std::log(0.001), &L));
-            return sw.on ? sweep_launch(c, n, sw, L.idx, L.lp, 0, B) : nbest_launch(c, n, L.idx, L.lp, 0, B);
-        }());
-        free_pool(c->beam_allocs);
-        return sweep_finish(rc, sw);
+        return nbest_call(c, lm, logits_source(logits_wbc, on_device, W, B, C), k, beam, nbest, len_bonus, input_lengths, o);
     });
 }
 
@@ -3232,23 +3383,8 @@ static int nbest_images_impl(hctr_ctx* c, const NbestLmArgs* lm, const void* img
                              const int32_t* input_lengths, const NbestOut& o) {
     return guard(c, [&]() -> int {
         TRY(check_forward_args(c, img, img_dtype, B, W));
-        NbestCall n;
-        TRY(nbest_prepare(c, B, W, c->num_classes, k, beam, nbest, len_bonus, input_lengths, o, &n));
-        if (lm) TRY(nbest_lm_prepare(c, &n, lm->lm, lm->lm_panelty, lm->lm_score));
-        SweepCall sw;
-        if (lm && lm->sweep) TRY(sweep_prepare(c, n, *lm->sweep, &sw));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        const Batch in{img, img_dtype, img_on_device, widths, B, W};
-        // inside each pass the search runs on the front end's lists where they lie; only its results go to the host
-        const int rc = synced(c, run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
-            if (p.first == 0) TRY(sw.on ? sweep_scratch(c, &n, &sw, p.nb) : nbest_scratch(c, &n, p.nb));      // no later pass is larger
-            BeamLists L;
-            TRY(beam_lists_pass(c, &in, p, nullptr, 0, W, n.C, k, false, std::log(0.001), &L));
-            return sw.on ? sweep_launch(c, n, sw, L.idx, L.lp, p.first, p.nb) : nbest_launch(c, n, L.idx, L.lp, p.first, p.nb);
-        }));
-        free_pool(c->beam_allocs);
-        return sweep_finish(rc, sw);
+        return nbest_call(c, lm, image_source(c, img, img_dtype, img_on_device, widths, B, W), k, beam, nbest, len_bonus,
+                          input_lengths, o);
     });
 }
 
@@ -3388,29 +3524,34 @@ int hctr_nbest_skip_lists(hctr_ctx* c, const hctr_lm* lm, const int32_t* top1_id
     });
 }
 
+// hctr_nbest_skip / hctr_nbest_skip_logits on a source: inside each pass the front end's lists stay where they lie, the
+// candidate counts included
+static int nbest_skip_call(hctr_ctx* c, const Source& src, const hctr_lm* lm, int beam, int nbest, double lm_panelty,
+                           double len_bonus, const int32_t* input_lengths, const NbestOut& o, double* lm_score,
+                           int32_t* status, int32_t* ranked) {
+    NbestCall n;
+    TRY(nbest_prepare(c, src.B, src.W, src.C, 1, beam, nbest, len_bonus, input_lengths, o, &n));
+    TRY(nbest_skip_prepare(c, &n, lm, lm_panelty, lm_score, status, ranked));
+    if (src.B == 0) return HCTR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const int rc = source_passes(c, src, [&](const Pass& p, std::vector<void*>&) -> int {
+        if (p.first == 0) TRY(nbest_scratch(c, &n, p.nb));
+        BeamLists L;
+        TRY(beam_lists_pass(c, src, p, 1, true, std::log(0.001), &L));
+        return skip_on_lists(c, n, L, p.first, p.nb);
+    });
+    free_pool(c->beam_allocs);
+    return rc;
+}
+
 int hctr_nbest_skip_logits(hctr_ctx* c, const hctr_lm* lm, const float* logits_wbc, int on_device, int W, int B, int C,
                            int beam, int nbest, double lm_panelty, double len_bonus, const int32_t* input_lengths,
                            int32_t* labels, int32_t* lengths, double* logp, double* score, int32_t* count, double* lm_score,
                            int32_t* status, int32_t* ranked) {
     return guard(c, [&]() -> int {
         TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
-        NbestCall n;
-        TRY(nbest_prepare(c, B, W, C, 1, beam, nbest, len_bonus, input_lengths, NbestOut{labels, lengths, logp, score, count},
-                          &n));
-        TRY(nbest_skip_prepare(c, &n, lm, lm_panelty, lm_score, status, ranked));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        prof_reset(c);
-        const std::vector<int> all = line_indices(B);
-        const int rc = synced(c, [&]() -> int {
-            BeamLists L;
-            TRY(nbest_scratch(c, &n, B));
-            TRY(beam_lists_pass(c, nullptr, Pass{all.data(), B, 0, B, false, nullptr}, logits_wbc, on_device, W, C, 1, true,
-                                std::log(0.001), &L));
-            return skip_on_lists(c, n, L, 0, B);
-        }());
-        free_pool(c->beam_allocs);
-        return rc;
+        return nbest_skip_call(c, logits_source(logits_wbc, on_device, W, B, C), lm, beam, nbest, lm_panelty, len_bonus,
+                               input_lengths, NbestOut{labels, lengths, logp, score, count}, lm_score, status, ranked);
     });
 }
 
@@ -3420,22 +3561,9 @@ int hctr_nbest_skip(hctr_ctx* c, const hctr_lm* lm, const void* img, int img_dty
                     int32_t* status, int32_t* ranked) {
     return guard(c, [&]() -> int {
         TRY(check_forward_args(c, img, img_dtype, B, W));
-        NbestCall n;
-        TRY(nbest_prepare(c, B, W, c->num_classes, 1, beam, nbest, len_bonus, input_lengths,
-                          NbestOut{labels, lengths, logp, score, count}, &n));
-        TRY(nbest_skip_prepare(c, &n, lm, lm_panelty, lm_score, status, ranked));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        const Batch in{img, img_dtype, img_on_device, widths, B, W};
-        // inside each pass the front end's lists stay where they lie, the candidate counts included
-        const int rc = synced(c, run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
-            if (p.first == 0) TRY(nbest_scratch(c, &n, p.nb));      // no later pass is larger
-            BeamLists L;
-            TRY(beam_lists_pass(c, &in, p, nullptr, 0, W, n.C, 1, true, std::log(0.001), &L));
-            return skip_on_lists(c, n, L, p.first, p.nb);
-        }));
-        free_pool(c->beam_allocs);
-        return rc;
+        return nbest_skip_call(c, image_source(c, img, img_dtype, img_on_device, widths, B, W), lm, beam, nbest, lm_panelty,
+                               len_bonus, input_lengths, NbestOut{labels, lengths, logp, score, count}, lm_score, status,
+                               ranked);
     });
 }
 
@@ -3443,22 +3571,9 @@ int hctr_ctc_loss(hctr_ctx* c, const void* img, int img_dtype, int img_on_device
                   const int32_t* targets, const int32_t* target_lengths, const int32_t* input_lengths, float* nll) {
     return guard(c, [&]() -> int {
         TRY(check_forward_args(c, img, img_dtype, B, W));
-        if (B == 0) return HCTR_OK;
-        if (!nll) return fail(c, HCTR_ERR_ARG, "nll is NULL");
-        HIP_TRY(c, hipSetDevice(c->device));
-        CtcHost h;
-        TRY(ctc_prepare(c, B, W, c->num_classes, targets, target_lengths, input_lengths, &h));
-        return ctc_image_call(
-            c, Batch{img, img_dtype, img_on_device, widths, B, W}, h, 0, [](char*) { return HCTR_OK; },
-            [&](Prof& pf, const CtcLines& m, const float* emis, float* d_nll, int b0, int nb) -> int {
-                PROF_TRY(pf, "ctc_alpha", launch_ctc_alpha(emis, m, b0, nb, W, h.max_states, d_nll, nullptr, nullptr,
-                                                           c->stream));
-                return HCTR_OK;
-            },
-            [&](const float* d_nll) -> int {
-                HIP_TRY(c, hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
-                return HCTR_OK;
-            });
+        if (B > 0 && !nll) return fail(c, HCTR_ERR_ARG, "nll is NULL");
+        return ctc_loss_call(c, image_source(c, img, img_dtype, img_on_device, widths, B, W), targets, target_lengths,
+                             input_lengths, nll);
     });
 }
 
@@ -3466,27 +3581,7 @@ int hctr_ctc_loss_logits(hctr_ctx* c, const float* logits_wbc, int on_device, in
                          const int32_t* target_lengths, const int32_t* input_lengths, float* nll) {
     return guard(c, [&]() -> int {
         TRY(check_logits_args(c, W, B, C, logits_wbc && nll));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        CtcHost h;
-        TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
-        prof_reset(c);
-        std::vector<void*> tmp;
-        PoolGuard tmp_guard{tmp};
-        return synced(c, [&]() -> int {
-            CtcLines m;
-            float *d_nll = nullptr, *emis = nullptr;
-            const float* dev = nullptr;
-            TRY(ctc_scratch(c, h, (size_t)B * W * h.D, &m, &d_nll, &emis));
-            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
-            Prof pf(c);
-            // rows of the WBC tensor are r = t*B + b
-            PROF_TRY(pf, "ctc_lse", launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, nullptr, c->stream));
-            PROF_TRY(pf, "ctc_alpha", launch_ctc_alpha(emis, m, 0, B, W, h.max_states, d_nll, nullptr, nullptr,
-                                                       c->stream));
-            HIP_TRY(c, hipMemcpyAsync(nll, d_nll, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
-            return HCTR_OK;
-        }());
+        return ctc_loss_call(c, logits_source(logits_wbc, on_device, W, B, C), targets, target_lengths, input_lengths, nll);
     });
 }
 
@@ -3568,25 +3663,8 @@ int hctr_ctc_align(hctr_ctx* c, const void* img, int img_dtype, int img_on_devic
                    int32_t* span_start, int32_t* span_end, float* span_logp, float* score) {
     return guard(c, [&]() -> int {
         TRY(check_forward_args(c, img, img_dtype, B, W));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        CtcHost h;
-        TRY(ctc_prepare(c, B, W, c->num_classes, targets, target_lengths, input_lengths, &h));
-        AlignDev a;
-        align_layout(h, W, &a);
-        return ctc_image_call(
-            c, Batch{img, img_dtype, img_on_device, widths, B, W}, h, a.bytes() + 16,
-            [&](char* extra) -> int {
-                align_carve(extra, &a);
-                HIP_TRY(c, hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
-                return HCTR_OK;
-            },
-            [&](Prof& pf, const CtcLines& m, const float* emis, float* d_score, int b0, int nb) {
-                return align_launch(c, pf, emis, m, h, a, b0, nb, W, d_score);
-            },
-            [&](const float* d_score) {
-                return align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
-            });
+        return ctc_align_call(c, image_source(c, img, img_dtype, img_on_device, widths, B, W), targets, target_lengths,
+                              input_lengths, path, span_start, span_end, span_logp, score);
     });
 }
 
@@ -3595,30 +3673,8 @@ int hctr_ctc_align_logits(hctr_ctx* c, const float* logits_wbc, int on_device, i
                           int32_t* span_end, float* span_logp, float* score) {
     return guard(c, [&]() -> int {
         TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        CtcHost h;
-        TRY(ctc_prepare(c, B, W, C, targets, target_lengths, input_lengths, &h));
-        prof_reset(c);
-        AlignDev a;
-        align_layout(h, W, &a);
-        std::vector<void*> tmp;
-        PoolGuard tmp_guard{tmp};
-        return synced(c, [&]() -> int {
-            CtcLines m;
-            float *d_score = nullptr, *emis = nullptr;
-            char* extra = nullptr;
-            const float* dev = nullptr;
-            TRY(ctc_scratch(c, h, (size_t)B * W * h.D, &m, &d_score, &emis, a.bytes() + 16, &extra));
-            align_carve(extra, &a);
-            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
-            HIP_TRY(c, hipMemcpyAsync(a.d_boff, a.boff.data(), (size_t)B * 8, hipMemcpyHostToDevice, c->stream));
-            Prof pf(c);
-            // rows of the WBC tensor are r = t*B + b
-            PROF_TRY(pf, "ctc_lse", launch_ctc_lse(dev, C, 1, B, C, m, 0, B, W, emis, nullptr, c->stream));
-            TRY(align_launch(c, pf, emis, m, h, a, 0, B, W, d_score));
-            return align_fetch(c, a, B, W, d_score, path, span_start, span_end, span_logp, score);
-        }());
+        return ctc_align_call(c, logits_source(logits_wbc, on_device, W, B, C), targets, target_lengths, input_lengths, path,
+                              span_start, span_end, span_logp, score);
     });
 }
 
@@ -3655,22 +3711,8 @@ int hctr_spot(hctr_ctx* c, const void* img, int img_dtype, int img_on_device, co
               float* contain_logp, float* seg_logp, int32_t* seg_start, int32_t* seg_end) {
     return guard(c, [&]() -> int {
         TRY(check_forward_args(c, img, img_dtype, B, W));
-        SpotHost h;
-        TRY(spot_prepare(c, B, W, c->num_classes, queries, query_lengths, Q, input_lengths, B, &h));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        const Batch in{img, img_dtype, img_on_device, widths, B, W};
-        SpotDev d;
-        // the pageable upload queued below was staged before hipMemcpyAsync returned. PASS_EXACT as hctr_ctc_loss: mode
-        // 2's guard certifies argmaxes, not probabilities
-        return synced(c, [&]() -> int {
-            TRY(run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
-                if (p.first == 0) TRY(spot_scratch(c, h, p.nb, W, &d));      // no later pass is larger
-                TRY(forward_pass(c, in, p, HEAD_LOGITS));
-                return spot_launch(c, h, d, c->ws.logits, c->cpad, W, 1, c->num_classes, p.first, p.nb, W);
-            }));
-            return spot_fetch(c, h, d, SpotOut{contain_logp, seg_logp, seg_start, seg_end});
-        }());
+        return spot_call(c, image_source(c, img, img_dtype, img_on_device, widths, B, W), queries, query_lengths, Q,
+                         input_lengths, SpotOut{contain_logp, seg_logp, seg_start, seg_end});
     });
 }
 
@@ -3679,21 +3721,8 @@ int hctr_spot_logits(hctr_ctx* c, const float* logits_wbc, int on_device, int W,
                      float* seg_logp, int32_t* seg_start, int32_t* seg_end) {
     return guard(c, [&]() -> int {
         TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
-        SpotHost h;
-        TRY(spot_prepare(c, B, W, C, queries, query_lengths, Q, input_lengths, B, &h));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        prof_reset(c);
-        std::vector<void*> tmp;
-        PoolGuard tmp_guard{tmp};
-        return synced(c, [&]() -> int {
-            SpotDev d;
-            const float* dev = nullptr;
-            TRY(spot_scratch(c, h, B, W, &d));
-            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
-            TRY(spot_launch(c, h, d, dev, C, 1, B, C, 0, B, W));      // rows of the WBC tensor are r = t*B + b
-            return spot_fetch(c, h, d, SpotOut{contain_logp, seg_logp, seg_start, seg_end});
-        }());
+        return spot_call(c, logits_source(logits_wbc, on_device, W, B, C), queries, query_lengths, Q, input_lengths,
+                         SpotOut{contain_logp, seg_logp, seg_start, seg_end});
     });
 }
 
@@ -3751,22 +3780,8 @@ int hctr_lexicon(hctr_ctx* c, const hctr_lex* lex, const void* img, int img_dtyp
                  float* top_logp, double* top_rank, double* log_total, int32_t* count, float* scores) {
     return guard(c, [&]() -> int {
         TRY(check_forward_args(c, img, img_dtype, B, W));
-        LexHost h;
-        TRY(lex_prepare(c, lex, B, W, c->num_classes, input_lengths, n, B, &h));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        TRY(lex_on_device(c, lex));
-        const Batch in{img, img_dtype, img_on_device, widths, B, W};
-        LexDev d;
-        // PASS_EXACT as hctr_ctc_loss: mode 2's guard certifies argmaxes, not probabilities
-        return synced(c, [&]() -> int {
-            TRY(run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
-                if (p.first == 0) TRY(lex_scratch(c, h, p.nb, W, &d));       // no later pass is larger
-                TRY(forward_pass(c, in, p, HEAD_LOGITS));
-                return lex_launch(c, h, d, c->ws.logits, c->cpad, W, 1, c->num_classes, p.first, p.nb, W);
-            }));
-            return lex_finish(c, h, d, LexOut{top_entry, top_logp, top_rank, log_total, count, scores});
-        }());
+        return lex_call(c, image_source(c, img, img_dtype, img_on_device, widths, B, W), lex, input_lengths, n,
+                        LexOut{top_entry, top_logp, top_rank, log_total, count, scores});
     });
 }
 
@@ -3775,22 +3790,8 @@ int hctr_lexicon_logits(hctr_ctx* c, const hctr_lex* lex, const float* logits_wb
                         double* log_total, int32_t* count, float* scores) {
     return guard(c, [&]() -> int {
         TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
-        LexHost h;
-        TRY(lex_prepare(c, lex, B, W, C, input_lengths, n, B, &h));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        prof_reset(c);
-        TRY(lex_on_device(c, lex));
-        std::vector<void*> tmp;
-        PoolGuard tmp_guard{tmp};
-        return synced(c, [&]() -> int {
-            LexDev d;
-            const float* dev = nullptr;
-            TRY(lex_scratch(c, h, B, W, &d));
-            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
-            TRY(lex_launch(c, h, d, dev, C, 1, B, C, 0, B, W));       // rows of the WBC tensor are r = t*B + b
-            return lex_finish(c, h, d, LexOut{top_entry, top_logp, top_rank, log_total, count, scores});
-        }());
+        return lex_call(c, logits_source(logits_wbc, on_device, W, B, C), lex, input_lengths, n,
+                        LexOut{top_entry, top_logp, top_rank, log_total, count, scores});
     });
 }
 
@@ -3846,24 +3847,8 @@ int hctr_pattern(hctr_ctx* c, const hctr_pat* pat, const void* img, int img_dtyp
                  float* char_logp, float* text_nll) {
     return guard(c, [&]() -> int {
         TRY(check_forward_args(c, img, img_dtype, B, W));
-        const PatOut o{logp, best_logp, path, labels, lengths, span_start, span_end, char_logp, text_nll};
-        PatHost h;
-        TRY(pat_prepare(c, pat, B, W, c->num_classes, input_lengths, o, &h));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        TRY(pat_on_device(c, pat));
-        const Batch in{img, img_dtype, img_on_device, widths, B, W};
-        PatDev d;
-        // PASS_EXACT as hctr_ctc_loss: mode 2's guard certifies argmaxes, not probabilities
-        return synced(c, [&]() -> int {
-            TRY(run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
-                if (p.first == 0) TRY(pat_scratch(c, h, p.nb, W, &d));       // no later pass is larger
-                TRY(forward_pass(c, in, p, HEAD_LOGITS));
-                return pat_launch(c, h, d, text_nll != nullptr, c->ws.logits, c->cpad, W, 1, c->num_classes, p.first,
-                                  p.nb, W);
-            }));
-            return pat_finish(c, h, d, o, W);
-        }());
+        return pat_call(c, image_source(c, img, img_dtype, img_on_device, widths, B, W), pat, input_lengths,
+                        PatOut{logp, best_logp, path, labels, lengths, span_start, span_end, char_logp, text_nll});
     });
 }
 
@@ -3872,23 +3857,8 @@ int hctr_pattern_logits(hctr_ctx* c, const hctr_pat* pat, const float* logits_wb
                         int32_t* lengths, int32_t* span_start, int32_t* span_end, float* char_logp, float* text_nll) {
     return guard(c, [&]() -> int {
         TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
-        const PatOut o{logp, best_logp, path, labels, lengths, span_start, span_end, char_logp, text_nll};
-        PatHost h;
-        TRY(pat_prepare(c, pat, B, W, C, input_lengths, o, &h));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        prof_reset(c);
-        TRY(pat_on_device(c, pat));
-        std::vector<void*> tmp;
-        PoolGuard tmp_guard{tmp};
-        return synced(c, [&]() -> int {
-            PatDev d;
-            const float* dev = nullptr;
-            TRY(pat_scratch(c, h, B, W, &d));
-            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
-            TRY(pat_launch(c, h, d, text_nll != nullptr, dev, C, 1, B, C, 0, B, W));      // rows of WBC: r = t*B + b
-            return pat_finish(c, h, d, o, W);
-        }());
+        return pat_call(c, logits_source(logits_wbc, on_device, W, B, C), pat, input_lengths,
+                        PatOut{logp, best_logp, path, labels, lengths, span_start, span_end, char_logp, text_nll});
     });
 }
 
@@ -3897,15 +3867,8 @@ int hctr_recognize(hctr_ctx* c, const void* img, int img_dtype, int img_on_devic
                    int32_t* alt_label, float* alt_logp, float* path_logp, float* text_nll) {
     return guard(c, [&]() -> int {
         TRY(check_forward_args(c, img, img_dtype, B, W));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        const Batch in{img, img_dtype, img_on_device, widths, B, W};
-        const RecCall rc({labels, lengths, span_start, span_end, char_logp, alt_label, alt_logp, path_logp, text_nll}, B, W);
-        // PASS_EXACT as hctr_ctc_loss: mode 2's guard certifies argmaxes, not confidences
-        return synced(c, run_passes(c, in, PASS_EXACT, [&](const Pass& p) -> int {
-            TRY(forward_pass(c, in, p, HEAD_LOGITS));
-            return rec_pass(c, c->ws.logits, c->cpad, W, 1, c->num_classes, p.first, p.nb, W, rc);
-        }));
+        return rec_call(c, image_source(c, img, img_dtype, img_on_device, widths, B, W),
+                        RecOut{labels, lengths, span_start, span_end, char_logp, alt_label, alt_logp, path_logp, text_nll});
     });
 }
 
@@ -3914,17 +3877,8 @@ int hctr_recognize_logits(hctr_ctx* c, const float* logits_wbc, int on_device, i
                           float* alt_logp, float* path_logp, float* text_nll) {
     return guard(c, [&]() -> int {
         TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
-        if (B == 0) return HCTR_OK;
-        HIP_TRY(c, hipSetDevice(c->device));
-        prof_reset(c);
-        const RecCall rc({labels, lengths, span_start, span_end, char_logp, alt_label, alt_logp, path_logp, text_nll}, B, W);
-        std::vector<void*> tmp;
-        PoolGuard tmp_guard{tmp};
-        return synced(c, [&]() -> int {
-            const float* dev = nullptr;
-            TRY(logits_on_device(c, tmp, logits_wbc, on_device, (size_t)W * B * C, &dev));
-            return rec_pass(c, dev, C, 1, B, C, 0, B, W, rc);      // rows of the WBC tensor are r = t*B + b
-        }());
+        return rec_call(c, logits_source(logits_wbc, on_device, W, B, C),
+                        RecOut{labels, lengths, span_start, span_end, char_logp, alt_label, alt_logp, path_logp, text_nll});
     });
 }
 
