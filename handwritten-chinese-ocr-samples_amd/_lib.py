@@ -186,6 +186,8 @@ SIGNATURES = [
     ("hctr_lexicon_chunk_classes", _I, [_I, _I]),
     # pattern recognition: arcs_src, arcs_label, arcs_dst, num_arcs, finals, num_finals, num_states, C, out
     ("hctr_pat_build", _I, [_VP, _VP, _VP, _I, _VP, _I, _I, _I, ctypes.POINTER(_VP)]),
+    ("hctr_pat_build_sets", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _I, _I, _I, ctypes.POINTER(_VP)]),
+    ("hctr_pat_kind", _I, [_VP]),
     ("hctr_pat_free", None, [_VP]),
     ("hctr_pat_info", _I, [_VP] * 6),
     ("hctr_pat_tables", _I, [_VP] * 10),

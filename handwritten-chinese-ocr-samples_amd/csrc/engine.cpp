@@ -1944,9 +1944,41 @@ struct PatLayout {
     }
 };
 
+// the set form's block: slot | label | meta (2 words a state) | blk_ptr | in_arc | finals | cls (0, then the classes)
+struct PatSetLayout {
+    size_t slot, label, meta, blk_ptr, in_arc, finals, cls, words;
+    explicit PatSetLayout(const hctr_pat& x) {
+        WordTaker take;
+        slot = take(x.slot.size()); label = take(x.label.size()); meta = take(x.meta.size());
+        blk_ptr = take(x.blk_ptr.size()); in_arc = take(x.in_arc.size()); finals = take(x.finals.size());
+        cls = take(x.classes.size() + 1);
+        words = take.words;
+    }
+};
+
+// whether a set pattern's two step buffers live in LDS: when they fit beside the block totals, unless HCTR_PATSET_LDS=0
+// keeps them in the call's scratch (for the tests: results do not depend on it)
+bool pat_set_lds(const hctr_pat& x, bool vit) {
+    const char* e = getenv("HCTR_PATSET_LDS");
+    if (e && atoi(e) == 0 && *e) return false;
+    return pattern_set_states_in_lds(x.S, x.nQ, vit);
+}
+
 // the context's device copy of the call's pattern: uploaded when the context holds another one (or none)
 int pat_on_device(hctr_ctx* c, const hctr_pat* x) {
     if (c->pat_serial == x->serial) return HCTR_OK;
+    if (x->kind) {
+        const PatSetLayout lay(*x);
+        std::vector<int32_t> img(lay.words, 0);
+        std::copy(x->slot.begin(), x->slot.end(), img.begin() + lay.slot);
+        std::copy(x->label.begin(), x->label.end(), img.begin() + lay.label);
+        memcpy(img.data() + lay.meta, x->meta.data(), x->meta.size() * 4);
+        std::copy(x->blk_ptr.begin(), x->blk_ptr.end(), img.begin() + lay.blk_ptr);
+        memcpy(img.data() + lay.in_arc, x->in_arc.data(), x->in_arc.size() * 4);
+        std::copy(x->finals.begin(), x->finals.end(), img.begin() + lay.finals);
+        std::copy(x->classes.begin(), x->classes.end(), img.begin() + lay.cls + 1);
+        return tables_on_device(c, &c->pat_serial, &c->pat_dev, x->serial, img, "pattern");
+    }
     const PatLayout lay(*x);
     std::vector<int32_t> img(lay.words, 0);
     std::copy(x->slot.begin(), x->slot.end(), img.begin() + lay.slot);
@@ -1990,20 +2022,22 @@ struct PatDev {
     int32_t *cls = nullptr, *nd = nullptr, *endst = nullptr, *lengths = nullptr, *path = nullptr, *labels = nullptr,
             *st = nullptr, *en = nullptr, *nll_tab = nullptr;
     float *logp = nullptr, *best = nullptr, *nll = nullptr, *clp = nullptr, *lpv = nullptr, *emis = nullptr;
+    float* states = nullptr;      // a set pattern's step buffers, 16*S bytes a line, when they are not in LDS
     uint16_t* bp = nullptr;
     int g = 1;                    // lines per group of this call's launches
 };
 
 // scratch of a pattern call that launches nl lines at a time, in groups of g = min(group, nl): the upload, the class
 // tables, the per-line and per-column results of all B lines, and per group the walk's scratch, the tables of the
-// decoded texts' loss, the emissions and the backpointers
+// decoded texts' loss, the emissions, the backpointers and a set pattern's step buffers that are not in LDS
 int pat_scratch(hctr_ctx* c, const PatHost& h, int nl, int W, PatDev* d) {
     const size_t B = (size_t)h.B, g = (size_t)std::max(1, std::min(h.group, nl)), S = (size_t)h.pat->S;
     const size_t up_b = align256(h.up.size() * 4), cls_b = align256(B * h.D * 4), b4 = align256(B * 4),
                  col_b = h.vit ? align256(B * W * 4) : 0, lpv_b = h.vit ? align256(g * W * 4) : 0,
                  tab_b = h.vit ? align256((3 * g + g * W) * 4) : 0, emis_b = align256(g * W * h.D * 4),
-                 bp_b = h.vit ? align256(g * W * S * 2) : 0;
-    TRY(ctc_reserve(c, up_b + cls_b + 6 * b4 + 5 * col_b + lpv_b + tab_b + emis_b + bp_b));
+                 bp_b = h.vit ? align256(g * W * S * 2) : 0,
+                 st_b = h.pat->kind && !pat_set_lds(*h.pat, h.vit) ? align256(g * S * 16) : 0;
+    TRY(ctc_reserve(c, up_b + cls_b + 6 * b4 + 5 * col_b + lpv_b + tab_b + emis_b + bp_b + st_b));
     char* p = c->ctc_buf;
     auto take = [&](size_t bytes) { char* r = p; p += bytes; return r; };
     d->g = (int)g;
@@ -2018,6 +2052,7 @@ int pat_scratch(hctr_ctx* c, const PatHost& h, int nl, int W, PatDev* d) {
     d->nll_tab = (int32_t*)take(tab_b);
     d->emis = (float*)take(emis_b);
     d->bp = (uint16_t*)take(bp_b);
+    d->states = st_b ? (float*)take(st_b) : nullptr;
     HIP_TRY(c, hipMemcpyAsync(c->ctc_buf, h.up.data(), h.up.size() * 4, hipMemcpyHostToDevice, c->stream));
     return HCTR_OK;
 }
@@ -2061,18 +2096,28 @@ int pat_launch(hctr_ctx* c, PatHost& h, const PatDev& d, bool want_nll, const Ro
     Prof pf(c);
     const hctr_pat& px = *h.pat;
     const PatLayout lay(px);
+    const PatSetLayout slay(px);
     const int32_t* t = c->pat_dev;
-    PROF_TRY(pf, "pattern_classes", launch_lexicon_classes(t + lay.cls, h.D, h.B, d.cls, d.nd, c->stream));
+    const size_t cls = px.kind ? slay.cls : lay.cls, slot = px.kind ? slay.slot : lay.slot,
+                 label = px.kind ? slay.label : lay.label;
+    PROF_TRY(pf, "pattern_classes", launch_lexicon_classes(t + cls, h.D, h.B, d.cls, d.nd, c->stream));
     const CtcLines m{d.up, d.up + h.B, d.up + h.B, d.nd, d.cls, d.up + h.B, h.D};
     for (int l0 = 0; l0 < nb; l0 += d.g) {
         const int n = std::min(d.g, nb - l0), gb0 = b0 + l0;
         TRY(lse_rows(pf, r.from_line(l0), m, gb0, n, W, d.emis));
-        const PatArgs a{d.emis, d.up, gb0, n, W, h.D, px.S, px.edges(), t + lay.slot, t + lay.label, t + lay.in_ptr,
-                        (const uint16_t*)(t + lay.in_src), t + lay.accept, t + lay.start, (int)px.accept.size(),
-                        (int)px.start.size(), d.bp, d.logp, d.best, d.endst};
-        PROF_TRY(pf, "pattern", launch_pattern(a, h.vit, c->stream));
+        if (px.kind) {
+            const PatSetArgs a{d.emis, d.up, gb0, n, W, h.D, px.S, px.nQ, (const uint32_t*)(t + slay.meta), t + slay.blk_ptr,
+                               (const uint32_t*)(t + slay.in_arc), t + slay.finals, (int)px.finals.size(), d.states, d.bp,
+                               d.logp, d.best, d.endst};
+            PROF_TRY(pf, "pattern_set", launch_pattern_set(a, h.vit, c->stream));
+        } else {
+            const PatArgs a{d.emis, d.up, gb0, n, W, h.D, px.S, px.edges(), t + lay.slot, t + lay.label, t + lay.in_ptr,
+                            (const uint16_t*)(t + lay.in_src), t + lay.accept, t + lay.start, (int)px.accept.size(),
+                            (int)px.start.size(), d.bp, d.logp, d.best, d.endst};
+            PROF_TRY(pf, "pattern", launch_pattern(a, h.vit, c->stream));
+        }
         if (!h.vit) continue;
-        const PatTraceArgs ta{d.emis, d.up, gb0, n, W, h.D, px.S, t + lay.slot, t + lay.label, d.bp, d.endst, d.lpv,
+        const PatTraceArgs ta{d.emis, d.up, gb0, n, W, h.D, px.S, t + slot, t + label, d.bp, d.endst, d.lpv,
                               d.path, d.labels, d.lengths, d.st, d.en, d.clp};
         PROF_TRY(pf, "pattern_trace", launch_pattern_trace(ta, c->stream));
         if (want_nll) TRY(pat_text_nll(c, pf, h, d, gb0, n, W));
@@ -3797,21 +3842,44 @@ int hctr_lexicon_logits(hctr_ctx* c, const hctr_lex* lex, const float* logits_wb
 
 int hctr_pattern_group_lines(int S, int D, int W) { return pat_group_lines(S, D, W); }
 
+static uint64_t next_pat_serial() {          // one sequence for both kinds: a context tells patterns apart by it
+    static std::atomic<uint64_t> serial{0};
+    return ++serial;
+}
+
 int hctr_pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const int32_t* arcs_dst, int num_arcs,
                    const int32_t* finals, int num_finals, int num_states, int C, hctr_pat** out) {
     if (out) *out = nullptr;
     return guard((hctr_ctx*)nullptr, [&]() -> int {
         if (!out) return fail(nullptr, HCTR_ERR_ARG, "hctr_pat_build: out is NULL");
-        static std::atomic<uint64_t> serial{0};
         std::unique_ptr<hctr_pat> x(new hctr_pat());
         std::string msg;
         if (!pat_build(arcs_src, arcs_label, arcs_dst, num_arcs, finals, num_finals, num_states, C, x.get(), &msg))
             return fail(nullptr, HCTR_ERR_ARG, "%s", msg.c_str());
-        x->serial = ++serial;
+        x->serial = next_pat_serial();
         *out = x.release();
         return HCTR_OK;
     });
 }
+
+int hctr_pat_build_sets(const int32_t* arcs_src, const int32_t* arcs_set, const int32_t* arcs_dst, int num_arcs,
+                        const int32_t* set_ptr, const int32_t* set_labels, int num_sets, const int32_t* finals,
+                        int num_finals, int num_states, int C, hctr_pat** out) {
+    if (out) *out = nullptr;
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!out) return fail(nullptr, HCTR_ERR_ARG, "hctr_pat_build_sets: out is NULL");
+        std::unique_ptr<hctr_pat> x(new hctr_pat());
+        std::string msg;
+        if (!pat_build_sets(arcs_src, arcs_set, arcs_dst, num_arcs, set_ptr, set_labels, num_sets, finals, num_finals,
+                            num_states, C, x.get(), &msg))
+            return fail(nullptr, HCTR_ERR_ARG, "%s", msg.c_str());
+        x->serial = next_pat_serial();
+        *out = x.release();
+        return HCTR_OK;
+    });
+}
+
+int hctr_pat_kind(const hctr_pat* pat) { return pat ? pat->kind : HCTR_ERR_ARG; }
 
 void hctr_pat_free(hctr_pat* pat) { delete pat; }
 
@@ -3832,6 +3900,8 @@ int hctr_pat_tables(const hctr_pat* pat, int32_t* state_label, int32_t* state_sl
                     int32_t* classes, int32_t* num_accept, int32_t* accept, int32_t* num_start, int32_t* start) {
     return guard((hctr_ctx*)nullptr, [&]() -> int {
         if (!pat) return fail(nullptr, HCTR_ERR_ARG, "pat is NULL");
+        if (pat->kind)
+            return fail(nullptr, HCTR_ERR_ARG, "hctr_pat_tables: a set pattern (hctr_pat_build_sets) has no edge list");
         auto put = [](auto* dst, const auto& v) { if (dst) std::copy(v.begin(), v.end(), dst); };
         put(state_label, pat->label); put(state_slot, pat->slot); put(in_ptr, pat->in_ptr); put(in_src, pat->in_src);
         put(classes, pat->classes); put(accept, pat->accept); put(start, pat->start);

@@ -440,6 +440,28 @@ struct PatTraceArgs {
 };
 hipError_t launch_pattern_trace(const PatTraceArgs& a, hipStream_t s);
 
+// the set form of a pattern (pat_build_sets): the same recursions in block form - per step the totals of every block
+// (beta_p and every eps_(p,.)), then the states from the totals of their source blocks. Outputs as PatArgs's.
+struct PatSetArgs {
+    const float* emis;        // [nb][W][D]
+    const int32_t* T;         // [B]
+    int b0, nb, W, D, S, nQ;
+    const uint32_t* meta;     // [2 * S] slot | in-arcs << 16 | start << 31; the first in-arc
+    const int32_t* blk_ptr;   // [nQ + 1] the eps states of block p are nQ + [blk_ptr[p], blk_ptr[p + 1])
+    const uint32_t* in_arc;   // p | (eps_(p,c) or 0xFFFF) << 16, ascending p
+    const int32_t* finals;    // [num_finals] the final DFA states, ascending
+    int num_finals;
+    float* states;            // [nb][2][S] float2 when the step buffers do not fit in LDS (or are kept out), else unused
+    uint16_t* bp;
+    float* logp;
+    float* best;
+    int32_t* endst;
+};
+// whether launch_pattern_set keeps the two step buffers of a pattern of S states and nQ blocks in LDS
+// (HCTR_PATSET_LDS=0: never)
+bool pattern_set_states_in_lds(int S, int nQ, bool viterbi);
+hipError_t launch_pattern_set(const PatSetArgs& a, bool viterbi, hipStream_t s);
+
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {
     int64_t src_off;          // byte offset of the image inside the packed source buffer

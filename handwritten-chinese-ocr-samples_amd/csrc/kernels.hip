@@ -5543,9 +5543,254 @@ __global__ __launch_bounds__(256) void pattern_trace_kernel(const PatTraceArgs a
 
 hipError_t launch_pattern_trace(const PatTraceArgs& a, hipStream_t s) {
     if (a.nb <= 0) return hipSuccess;
-    if (a.S < 1 || a.S > kPatMaxStates || a.D < 1 || a.W < 1) return hipErrorInvalidValue;
+    if (a.S < 1 || a.S > kPatSetMaxStates || a.D < 1 || a.W < 1) return hipErrorInvalidValue;
     hipLaunchKernelGGL(pattern_trace_kernel, dim3((unsigned)a.nb), dim3(256), 0, s, a);
     return hipGetLastError();
+}
+
+// -------------------------------------------------------------------------------------------
+// The set form (pat_build_sets): the same two recursions over the same CTC states, in block form. The block of DFA
+// state p is beta_p and every eps_(p,.). Every state is fed by whole blocks less at most one state each:
+//   beta_q    <- block q
+//   eps_(q,c) <- itself, and for every arc (p, A, q) with c in A: block p without eps_(p,c)
+// so a step is the totals of every block over the buffer just written, then every state from the totals of its source
+// blocks: O(S + in-arcs) a step, whatever the sets hold.
+// Totals of block p (one wave per block; blocks w, w + waves, .. are wave w's): lane l takes the members l, l + 64, ..
+// in ascending order (member 0 = beta_p, member j = the block's j-th eps state), the 64 lanes combine by the butterfly
+// over the lane offsets 32, 16, 8, 4, 2, 1. Two passes: m = the float32 maximum and i* = the lowest state that holds it
+// (and, with VIT, the two best v with their states, ties to the lower state); then all = the float64 sum of
+// (double)__expf(a - m) over the members and rest = the same sum without i*. The order is a function of the tables only.
+// A source term of eps_(q,c) from block p: X = rest if eps_(p,c) is i*, all - (double)__expf(a(eps_(p,c)) - m) if it
+// exists otherwise (the maximal term survives: nothing cancels), all if it does not; y = m + __logf((float)X), -inf
+// where X is 0 or m is -inf. The state is pattern_kernel's n-ary log-sum over [its own value, y of each in-arc in
+// ascending p], plus the emission. beta_q = m + __logf((float)all) of its block, plus the emission.
+// Max: the candidate of block p is its best v, or its second best where the best is eps_(p,c) itself; among the own
+// value and the candidates the greatest wins, ties to the lowest state - pattern_kernel's first maximal source in
+// ascending order, so every Viterbi output has its bits.
+// One workgroup per line, two barriers a step. The two step buffers are in LDS behind the totals (SLDS) or in the call's
+// scratch, which only this workgroup touches. The emissions of a thread's first four states are in flight over the
+// totals. No atomics; thread 0 reduces the final blocks in ascending q.
+// -------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool pat_better(float xa, int ia, float xb, int ib) { return xa > xb || (xa == xb && ia < ib); }
+
+template <bool VIT, bool SLDS>
+__global__ __launch_bounds__(kPatThreads) void pattern_set_kernel(const PatSetArgs a) {
+    using PS = PatState<VIT>;
+    using St = typename PS::type;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int S = a.S, nQ = a.nQ, D = a.D, b = blockIdx.x, gb = a.b0 + b, tid = threadIdx.x, nt = blockDim.x;
+    const int lane = tid & 63, wave = tid >> 6, nw = nt >> 6;
+    const int T = min(max(a.T[gb], 1), a.W);              // (the host admits 1 <= T <= W only)
+    double* t_all = (double*)smem;                        // the totals of the previous step's blocks, [nQ] each
+    double* t_rest = t_all + nQ;
+    float* t_m = (float*)(t_rest + nQ);
+    int* t_i = (int*)(t_m + nQ);
+    float* t_v1 = (float*)(t_i + nQ);                     // (VIT only)
+    float* t_v2 = t_v1 + nQ;
+    int* t_i1 = (int*)(t_v2 + nQ);
+    int* t_i2 = t_i1 + nQ;
+    St* st = SLDS ? (St*)(smem + (size_t)nQ * (VIT ? 40 : 24)) : (St*)(a.states + (int64_t)b * 4 * S);      // [2][S]
+    const float* base = a.emis + (int64_t)b * a.W * D;
+    uint16_t* bpl = VIT ? a.bp + (int64_t)b * a.W * S : nullptr;
+    const uint2* meta = (const uint2*)a.meta;
+    uint2 mt[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) mt[i] = tid + i * nt < S ? meta[tid + i * nt] : make_uint2(0u, 0u);
+    for (int s = tid; s < S; s += nt) {
+        const unsigned x = meta[s].x;
+        const float lp = x >> 31 ? base[x & 0xFFFFu] : -INFINITY;
+        st[s] = PS::make(lp, lp);
+        if (VIT) bpl[s] = (uint16_t)s;
+    }
+    __syncthreads();
+    for (int t = 1; t <= T; ++t) {                        // t = T: the totals of the last step alone
+        const St* prev = st + ((t - 1) & 1) * S;
+        const float* row = base + (int64_t)min(t, T - 1) * D;
+        float e4[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) e4[i] = row[mt[i].x & 0xFFFFu];
+        for (int p = wave; p < nQ; p += nw) {
+            const int e0 = nQ + a.blk_ptr[p], n = 1 + a.blk_ptr[p + 1] - a.blk_ptr[p];
+            float m = -INFINITY, v1 = -INFINITY, v2 = -INFINITY;
+            int im = 0x7FFFFFFF, i1 = -1, i2 = -1;
+            for (int j = lane; j < n; j += 64) {
+                const int idx = j ? e0 + j - 1 : p;
+                const St x = prev[idx];
+                if (pat_a(x) > m) {
+                    m = pat_a(x);
+                    im = idx;
+                }
+                if (VIT) {
+                    const float xv = pat_v(x);
+                    if (xv > v1) {
+                        v2 = v1; i2 = i1;
+                        v1 = xv; i1 = idx;
+                    } else if (xv > v2) {
+                        v2 = xv; i2 = idx;
+                    }
+                }
+            }
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) {
+                const float om = __shfl_xor(m, off);
+                const int oi = __shfl_xor(im, off);
+                if (pat_better(om, oi, m, im)) {
+                    m = om;
+                    im = oi;
+                }
+                if (VIT) {
+                    const float ov1 = __shfl_xor(v1, off), ov2 = __shfl_xor(v2, off);
+                    const int oi1 = __shfl_xor(i1, off), oi2 = __shfl_xor(i2, off);
+                    if (pat_better(ov1, oi1, v1, i1)) {
+                        const bool k = pat_better(v1, i1, ov2, oi2);
+                        v2 = k ? v1 : ov2; i2 = k ? i1 : oi2;
+                        v1 = ov1; i1 = oi1;
+                    } else {
+                        const bool k = pat_better(ov1, oi1, v2, i2);
+                        v2 = k ? ov1 : v2; i2 = k ? oi1 : i2;
+                    }
+                }
+            }
+            double all = 0.0, rest = 0.0;
+            if (m > -INFINITY) {                           // (wave-uniform)
+                for (int j = lane; j < n; j += 64) {
+                    const int idx = j ? e0 + j - 1 : p;
+                    const double ex = (double)__expf(pat_a(prev[idx]) - m);
+                    all += ex;
+                    if (idx != im) rest += ex;
+                }
+#pragma unroll
+                for (int off = 32; off >= 1; off >>= 1) {
+                    all += __shfl_xor(all, off);
+                    rest += __shfl_xor(rest, off);
+                }
+            } else {
+                im = p;
+            }
+            if (lane == 0) {
+                t_all[p] = all; t_rest[p] = rest; t_m[p] = m; t_i[p] = im;
+                if (VIT) { t_v1[p] = v1; t_v2[p] = v2; t_i1[p] = i1; t_i2[p] = i2; }
+            }
+        }
+        __syncthreads();
+        if (t == T) break;
+        St* cur = st + (t & 1) * S;
+        // a source term: block p's total without the state ex (0xFFFF: the block holds no such state)
+        auto term = [&](unsigned p, unsigned ex) -> float {
+            const float mp = t_m[p];
+            if (!(mp > -INFINITY)) return -INFINITY;
+            const double X = ex == 0xFFFFu        ? t_all[p]
+                             : (int)ex == t_i[p] ? t_rest[p]
+                                                 : t_all[p] - (double)__expf(pat_a(prev[ex]) - mp);
+            return X > 0.0 ? mp + __logf((float)X) : -INFINITY;
+        };
+        auto update = [&](int s, uint2 ms, float e) {
+            float aa, vv = -INFINITY;
+            int arg = s;
+            if (s < nQ) {
+                aa = pat_lse(t_m[s], t_all[s]);
+                if (VIT) {
+                    vv = t_v1[s];
+                    if (vv > -INFINITY) arg = t_i1[s];
+                }
+            } else {
+                const St own = prev[s];
+                const unsigned deg = (ms.x >> 16) & 0x7FFFu, first = ms.y;
+                float m = fmaxf(-INFINITY, pat_a(own));
+                if (VIT && pat_v(own) > vv) vv = pat_v(own);
+                for (unsigned k = 0; k < deg; ++k) {
+                    const unsigned w = a.in_arc[first + k], p = w & 0xFFFFu, ex = w >> 16;
+                    m = fmaxf(m, term(p, ex));
+                    if (VIT) {
+                        const bool top = t_i1[p] == (int)ex;
+                        const float cv = top ? t_v2[p] : t_v1[p];
+                        const int ci = top ? t_i2[p] : t_i1[p];
+                        if (cv > vv || (cv == vv && cv > -INFINITY && ci < arg)) {
+                            vv = cv;
+                            arg = ci;
+                        }
+                    }
+                }
+                double sum = 0.0;
+                if (m != -INFINITY) {
+                    sum = (double)__expf(pat_a(own) - m);
+                    for (unsigned k = 0; k < deg; ++k) {
+                        const unsigned w = a.in_arc[first + k];
+                        sum += (double)__expf(term(w & 0xFFFFu, w >> 16) - m);
+                    }
+                }
+                aa = pat_lse(m, sum);
+            }
+            cur[s] = PS::make(aa + e, vv + e);
+            if (VIT) bpl[(int64_t)t * S + s] = (uint16_t)arg;
+        };
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (tid + i * nt < S) update(tid + i * nt, mt[i], e4[i]);
+        for (int s = tid + 4 * nt; s < S; s += nt) {
+            const uint2 ms = meta[s];
+            update(s, ms, row[ms.x & 0xFFFFu]);
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        float m = -INFINITY, vm = -INFINITY;
+        int arg = -1;
+        for (int j = 0; j < a.num_finals; ++j) {
+            const int q = min(max(a.finals[j], 0), nQ - 1);
+            m = fmaxf(m, pat_lse(t_m[q], t_all[q]));
+            if (VIT) {
+                const float cv = t_v1[q];
+                const int ci = t_i1[q];
+                if (cv > vm || (cv == vm && cv > -INFINITY && ci < arg)) {
+                    vm = cv;
+                    arg = ci;
+                }
+            }
+        }
+        double sum = 0.0;
+        if (m != -INFINITY)
+            for (int j = 0; j < a.num_finals; ++j) {
+                const int q = min(max(a.finals[j], 0), nQ - 1);
+                sum += (double)__expf(pat_lse(t_m[q], t_all[q]) - m);
+            }
+        const float lp = pat_lse(m, sum);
+        a.logp[gb] = lp > 0.f ? 0.f : lp;                 // a probability near 1 may round above 0; a NaN stays one
+        if (VIT) {
+            a.best[gb] = vm;
+            a.endst[gb] = arg;
+        }
+    }
+}
+
+static int pattern_set_lds(int S, int nQ, bool viterbi, bool states) {
+    const int64_t bytes = (int64_t)nQ * (viterbi ? 40 : 24) + (states ? 2 * (int64_t)S * (viterbi ? 8 : 4) : 0);
+    return bytes > kPatLds ? -1 : (int)bytes;
+}
+
+bool pattern_set_states_in_lds(int S, int nQ, bool viterbi) { return pattern_set_lds(S, nQ, viterbi, true) >= 0; }
+
+template <bool VIT, bool SLDS>
+static hipError_t launch_pattern_set_t(const PatSetArgs& a, hipStream_t s) {
+    static bool raised[64] = {};
+    const int lds = pattern_set_lds(a.S, a.nQ, VIT, SLDS);
+    if (lds < 0 || (!SLDS && !a.states)) return hipErrorInvalidValue;
+    // a thread per state up to 1024, and a wave per block up to 16: the results do not depend on it
+    const int threads = std::min(kPatThreads, std::max((a.S + 63) / 64, std::min(a.nQ, 16)) * 64);
+    hipError_t e = raise_lds_limit((const void*)pattern_set_kernel<VIT, SLDS>, kPatLds, raised);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((pattern_set_kernel<VIT, SLDS>), dim3((unsigned)a.nb), dim3(threads), lds, s, a);
+    return hipGetLastError();
+}
+
+// a.states == nullptr: the step buffers in LDS (the caller has asked pattern_set_states_in_lds)
+hipError_t launch_pattern_set(const PatSetArgs& a, bool viterbi, hipStream_t s) {
+    if (a.nb <= 0) return hipSuccess;
+    if (a.S < 1 || a.S > kPatSetMaxStates || a.nQ < 1 || a.nQ > kPatSetMaxDfaStates || a.nQ > a.S || a.D < 1 ||
+        a.D > 0xFFFF || a.W < 1 || a.num_finals < 1)
+        return hipErrorInvalidValue;
+    if (viterbi) return a.states ? launch_pattern_set_t<true, false>(a, s) : launch_pattern_set_t<true, true>(a, s);
+    return a.states ? launch_pattern_set_t<false, false>(a, s) : launch_pattern_set_t<false, true>(a, s);
 }
 
 }  // namespace hctr

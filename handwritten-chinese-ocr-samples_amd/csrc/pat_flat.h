@@ -23,11 +23,16 @@ namespace hctr {
 
 constexpr int kPatMaxStates = 8192;              // HCTR_PAT_MAX_STATES
 constexpr int kPatMaxEdges = 262144;             // HCTR_PAT_MAX_EDGES
+constexpr int kPatSetMaxStates = 65535;          // HCTR_PATSET_MAX_STATES (backpointers are uint16; 65535 = "no state")
+constexpr int kPatSetMaxDfaStates = 4096;        // HCTR_PATSET_MAX_DFA_STATES (the block totals live in LDS)
+constexpr int kPatSetMaxInArcs = 1 << 20;        // HCTR_PATSET_MAX_INARCS
+constexpr uint32_t kPatSetNone = 0xFFFFu;        // an in-arc whose source block has no state of the label
 
 }  // namespace hctr
 
 struct hctr_pat {
     int C = 0, nQ = 0, S = 0, max_deg = 0;
+    int kind = 0;                                // 0 = explicit edges (pat_build), 1 = label-set arcs (pat_build_sets)
     uint64_t serial = 0;
     std::vector<int32_t> classes;                // the distinct labels, ascending
     std::vector<int32_t> label, slot;            // [S] label (0 = blank); its place in (0, classes..)
@@ -35,7 +40,14 @@ struct hctr_pat {
     std::vector<uint16_t> in_src;                // [E] a state's sources, ascending
     std::vector<int32_t> accept;                 // the accepting states, ascending
     std::vector<int32_t> start;                  // beta_0, then the eps states of the arcs that leave state 0, ascending
-    int edges() const { return (int)in_src.size(); }
+    // kind 1 only (label, slot and classes as above; in_ptr, in_src, accept and start stay empty). The block of DFA
+    // state p is beta_p = p and its eps states nQ + [blk_ptr[p], blk_ptr[p + 1]), in ascending label.
+    std::vector<int32_t> blk_ptr;                // [nQ + 1]
+    std::vector<uint32_t> meta;                  // [2 * S] per state: slot | in-arcs << 16 | start << 31; its first in-arc
+    std::vector<uint32_t> in_arc;                // [R] per eps_(q,c) the p with an arc (p, A, q), c in A, ascending:
+                                                 // p | (eps_(p,c) or kPatSetNone) << 16
+    std::vector<int32_t> finals;                 // the final DFA states, ascending
+    int edges() const { return kind ? (int)in_arc.size() : (int)in_src.size(); }
 };
 
 namespace hctr {
@@ -177,6 +189,178 @@ inline bool pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const 
         if (a.src == 0) x.start.push_back(eps(a.dst, a.label));
     std::sort(x.start.begin(), x.start.end());
     x.start.erase(std::unique(x.start.begin(), x.start.end()), x.start.end());
+    return true;
+}
+
+// The set form: arcs (src, set, dst) that carry label sets, set k = set_labels[set_ptr[k] .. set_ptr[k + 1]). The
+// language and the CTC lift (the states and their numbering) are those of pat_build on the same automaton with every
+// arc expanded into single-label arcs; what is built instead of the edge list is, per eps_(q,c), the source DFA states p
+// with an arc (p, A, q), c in A - pattern_set_kernel sums a block (beta_p and every eps_(p,.)) once per step and takes
+// the one state of the block that may not feed eps_(q,c), eps_(p,c), out of the total.
+inline bool pat_build_sets(const int32_t* arcs_src, const int32_t* arcs_set, const int32_t* arcs_dst, int num_arcs,
+                           const int32_t* set_ptr, const int32_t* set_labels, int num_sets, const int32_t* finals,
+                           int num_finals, int num_states, int C, hctr_pat* out, std::string* msg) {
+    auto bad = [&](const std::string& m) { *msg = "hctr_pat_build_sets: " + m; return false; };
+    auto str = [](int64_t v) { return std::to_string(v); };
+    if (num_arcs < 0 || num_finals < 0 || num_sets < 0) return bad("negative count");
+    if (num_arcs > 0 && (!arcs_src || !arcs_set || !arcs_dst)) return bad("arcs_src / arcs_set / arcs_dst is NULL");
+    if (num_sets > 0 && (!set_ptr || !set_labels)) return bad("set_ptr / set_labels is NULL");
+    if (num_finals > 0 && !finals) return bad("finals is NULL");
+    if (C < 2) return bad("need C >= 2 classes, got C=" + str(C));
+    if (num_states < 1) return bad("need num_states >= 1, got " + str(num_states));
+    if (num_states > (1 << 24)) return bad("num_states=" + str(num_states) + " exceeds " + str(1 << 24));
+    if (num_sets > 0 && set_ptr[0] != 0) return bad("set_ptr[0] must be 0, got " + str(set_ptr[0]));
+    for (int k = 0; k < num_sets; ++k) {
+        const int32_t f = set_ptr[k], l = set_ptr[k + 1];
+        if (l <= f) return bad("set " + str(k) + " is empty");
+        for (int32_t j = f; j < l; ++j) {
+            if (set_labels[j] < 1 || set_labels[j] > C - 1)
+                return bad("label " + str(set_labels[j]) + " (set " + str(k) + ") outside [1," + str(C - 1) + "]");
+            if (j > f && set_labels[j] <= set_labels[j - 1])
+                return bad("the labels of set " + str(k) + " are not ascending: " + str(set_labels[j - 1]) + " before " +
+                           str(set_labels[j]));
+        }
+    }
+    const size_t nq0 = (size_t)num_states;
+    struct Arc { int32_t src, set, dst; };
+    std::vector<Arc> arcs((size_t)num_arcs);
+    for (int i = 0; i < num_arcs; ++i) {
+        const Arc a{arcs_src[i], arcs_set[i], arcs_dst[i]};
+        if (a.src < 0 || a.src >= num_states || a.dst < 0 || a.dst >= num_states)
+            return bad("arc " + str(i) + " (" + str(a.src) + " -> " + str(a.dst) + ") names a state outside [0," +
+                       str(num_states - 1) + "]");
+        if (a.set < 0 || a.set >= num_sets)
+            return bad("arc " + str(i) + " names set " + str(a.set) + " outside [0," + str((int64_t)num_sets - 1) + "]");
+        arcs[(size_t)i] = a;
+    }
+    std::sort(arcs.begin(), arcs.end(), [](const Arc& a, const Arc& b) {
+        return a.src != b.src ? a.src < b.src : a.dst != b.dst ? a.dst < b.dst : a.set < b.set;
+    });
+    {   // determinism: the sets that leave one state are pairwise disjoint
+        std::vector<int32_t> seen((size_t)C, -1);
+        for (const Arc& a : arcs)
+            for (int32_t j = set_ptr[a.set]; j < set_ptr[a.set + 1]; ++j) {
+                if (seen[(size_t)set_labels[j]] == a.src)
+                    return bad("not deterministic: the sets of two arcs that leave state " + str(a.src) + " overlap on label " +
+                               str(set_labels[j]));
+                seen[(size_t)set_labels[j]] = a.src;
+            }
+    }
+    std::vector<uint8_t> fin(nq0, 0);
+    for (int i = 0; i < num_finals; ++i) {
+        if (finals[i] < 0 || finals[i] >= num_states)
+            return bad("finals[" + str(i) + "]=" + str(finals[i]) + " outside [0," + str(num_states - 1) + "]");
+        fin[(size_t)finals[i]] = 1;
+    }
+    // prune: forward from state 0, backward from the final states
+    std::vector<int32_t> optr(nq0 + 1, 0), iptr(nq0 + 1, 0), isrc(arcs.size());
+    for (const Arc& a : arcs) { ++optr[(size_t)a.src + 1]; ++iptr[(size_t)a.dst + 1]; }
+    for (size_t q = 0; q < nq0; ++q) { optr[q + 1] += optr[q]; iptr[q + 1] += iptr[q]; }
+    {
+        std::vector<int32_t> at(iptr.begin(), iptr.end() - 1);
+        for (const Arc& a : arcs) isrc[(size_t)at[(size_t)a.dst]++] = a.src;
+    }
+    std::vector<uint8_t> fwd(nq0, 0), bwd(nq0, 0);
+    std::vector<int32_t> stack{0};
+    fwd[0] = 1;
+    while (!stack.empty()) {
+        const int32_t q = stack.back();
+        stack.pop_back();
+        for (int32_t j = optr[(size_t)q]; j < optr[(size_t)q + 1]; ++j)
+            if (!fwd[(size_t)arcs[(size_t)j].dst]) { fwd[(size_t)arcs[(size_t)j].dst] = 1; stack.push_back(arcs[(size_t)j].dst); }
+    }
+    for (size_t q = 0; q < nq0; ++q)
+        if (fin[q]) { bwd[q] = 1; stack.push_back((int32_t)q); }
+    while (!stack.empty()) {
+        const int32_t q = stack.back();
+        stack.pop_back();
+        for (int32_t j = iptr[(size_t)q]; j < iptr[(size_t)q + 1]; ++j)
+            if (!bwd[(size_t)isrc[(size_t)j]]) { bwd[(size_t)isrc[(size_t)j]] = 1; stack.push_back(isrc[(size_t)j]); }
+    }
+    if (!bwd[0]) return bad("the pattern's language is empty: no final state can be reached from state 0");
+    std::vector<int32_t> renum(nq0, -1);
+    int nQ = 0;
+    for (size_t q = 0; q < nq0; ++q)
+        if (fwd[q] && bwd[q]) renum[q] = nQ++;
+    if (nQ > kPatSetMaxDfaStates)
+        return bad("the pattern has " + str(nQ) + " DFA states, HCTR_PATSET_MAX_DFA_STATES is " + str(kPatSetMaxDfaStates));
+    std::vector<Arc> live;                            // by (dst, src): the order of every state's in-arcs
+    for (const Arc& a : arcs)
+        if (renum[(size_t)a.src] >= 0 && renum[(size_t)a.dst] >= 0)
+            live.push_back(Arc{renum[(size_t)a.src], a.set, renum[(size_t)a.dst]});
+    std::stable_sort(live.begin(), live.end(), [](const Arc& a, const Arc& b) {
+        return a.dst != b.dst ? a.dst < b.dst : a.src < b.src;
+    });
+    // the eps states: per destination q the union of the sets of the arcs into q, ascending
+    hctr_pat& x = *out;
+    x.kind = 1; x.C = C; x.nQ = nQ;
+    x.blk_ptr.assign((size_t)nQ + 1, 0);
+    std::vector<int32_t> plab;                        // the label of eps state nQ + i
+    {
+        std::vector<int32_t> seen((size_t)C, -1), got;
+        size_t k = 0;
+        for (int q = 0; q < nQ; ++q) {
+            got.clear();
+            for (; k < live.size() && live[k].dst == q; ++k)
+                for (int32_t j = set_ptr[live[k].set]; j < set_ptr[live[k].set + 1]; ++j)
+                    if (seen[(size_t)set_labels[j]] != q) { seen[(size_t)set_labels[j]] = q; got.push_back(set_labels[j]); }
+            std::sort(got.begin(), got.end());
+            plab.insert(plab.end(), got.begin(), got.end());
+            x.blk_ptr[(size_t)q + 1] = (int32_t)plab.size();
+            if ((int64_t)nQ + (int64_t)plab.size() > kPatSetMaxStates)
+                return bad("the pattern has more than " + str(kPatSetMaxStates) + " CTC states (HCTR_PATSET_MAX_STATES): " +
+                           str(nQ) + " DFA states + " + str((int64_t)plab.size()) + " (state, label) pairs up to DFA state " +
+                           str(q) + " of " + str(nQ));
+        }
+    }
+    const size_t S = (size_t)nQ + plab.size();
+    x.S = (int)S;
+    x.label.assign(S, 0);
+    std::copy(plab.begin(), plab.end(), x.label.begin() + nQ);
+    x.classes = plab;
+    std::sort(x.classes.begin(), x.classes.end());
+    x.classes.erase(std::unique(x.classes.begin(), x.classes.end()), x.classes.end());
+    if (x.classes.size() > 0xFFFFu) return bad("the pattern uses " + str((int64_t)x.classes.size()) + " classes, more than 65535");
+    x.slot.assign(S, 0);
+    for (size_t s = (size_t)nQ; s < S; ++s)
+        x.slot[s] = 1 + (int32_t)(std::lower_bound(x.classes.begin(), x.classes.end(), x.label[s]) - x.classes.begin());
+    auto eps = [&](int32_t q, int32_t c) -> uint32_t {      // eps_(q,c), or kPatSetNone
+        const int32_t *f = plab.data() + x.blk_ptr[(size_t)q], *l = plab.data() + x.blk_ptr[(size_t)q + 1];
+        const int32_t* at = std::lower_bound(f, l, c);
+        return at != l && *at == c ? (uint32_t)(nQ + (at - plab.data())) : kPatSetNone;
+    };
+    // the reduced in-arcs: count, then fill in the arcs' order (ascending source within a destination)
+    std::vector<int64_t> deg(S, 0);
+    int64_t R = 0;
+    for (const Arc& a : live) R += set_ptr[a.set + 1] - set_ptr[a.set];
+    if (R > kPatSetMaxInArcs)
+        return bad("the pattern has " + str(R) + " in-arcs ((state, label) pairs summed over their source states), "
+                   "HCTR_PATSET_MAX_INARCS is " + str(kPatSetMaxInArcs));
+    for (const Arc& a : live)
+        for (int32_t j = set_ptr[a.set]; j < set_ptr[a.set + 1]; ++j) ++deg[eps(a.dst, set_labels[j])];
+    std::vector<uint32_t> first(S + 1, 0);
+    for (size_t s = 0; s < S; ++s) first[s + 1] = first[s] + (uint32_t)deg[s];
+    x.in_arc.assign((size_t)R, 0);
+    {
+        std::vector<uint32_t> at(first.begin(), first.end() - 1);
+        for (const Arc& a : live)
+            for (int32_t j = set_ptr[a.set]; j < set_ptr[a.set + 1]; ++j) {
+                const int32_t c = set_labels[j];
+                x.in_arc[at[eps(a.dst, c)]++] = (uint32_t)a.src | eps(a.src, c) << 16;
+            }
+    }
+    x.meta.assign(2 * S, 0);
+    for (size_t s = 0; s < S; ++s) {
+        x.meta[2 * s] = (uint32_t)x.slot[s] | (uint32_t)deg[s] << 16;      // (deg <= nQ <= 4096 < 2^15)
+        x.meta[2 * s + 1] = first[s];
+        x.max_deg = std::max(x.max_deg, (int)deg[s]);
+    }
+    x.meta[0] |= 1u << 31;                            // the start list: beta_0 and the eps states of the arcs that leave 0
+    for (const Arc& a : live)
+        if (a.src == 0)
+            for (int32_t j = set_ptr[a.set]; j < set_ptr[a.set + 1]; ++j) x.meta[2 * (size_t)eps(a.dst, set_labels[j])] |= 1u << 31;
+    for (size_t q = 0; q < nq0; ++q)
+        if (renum[q] >= 0 && fin[q]) x.finals.push_back(renum[q]);
     return true;
 }
 

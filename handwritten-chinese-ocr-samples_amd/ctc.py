@@ -645,10 +645,12 @@ class _Regex(object):
         return frozenset(members)
 
 
-def _regex_to_dfa(tree):
+def _regex_to_dfa(tree, sets=False):
     """(arcs, finals, num_states) of the minimal DFA of a ``_Regex`` tree, its states numbered breadth-first from the start
     over labels ascending - a function of the language, not of how it was spelt. arcs: int32 [n, 3] rows (src, label, dst)
-    sorted by (src, label). An empty language gives one state without finals."""
+    sorted by (src, label). An empty language gives one state without finals. ``sets=True``: (arcs, sets, finals,
+    num_states) with the arcs before they are expanded - rows (src, set, dst) sorted by (src, the set's smallest label),
+    ``sets`` the list of ascending int32 label arrays (the expression's alphabet classes) they index."""
     # atoms -> alphabet classes: labels with the same membership in every set of the expression behave alike
     atoms, eps, tr = [], [[]], [[]]
 
@@ -749,7 +751,7 @@ def _regex_to_dfa(tree):
                 alive.add(p)
                 stack.append(p)
     if 0 not in alive:
-        return np.zeros((0, 3), np.int32), [], 1
+        return (np.zeros((0, 3), np.int32), [], [], 1) if sets else (np.zeros((0, 3), np.int32), [], 1)
     # Moore's refinement on the trimmed (partial) automaton: a missing arc leads to the dead block -1
     block = {s: (1 if final[s] else 0) for s in alive}
     nk = len(classes)
@@ -779,6 +781,10 @@ def _regex_to_dfa(tree):
                 number[d] = len(number)
                 queue.append(d)
         rows.append([(k, d) for _, k, d in out])
+    finals = sorted(number[b] for b in number if final[rep[b]])
+    if sets:
+        arcs = np.array([(number[blk], k, number[d]) for blk, row in zip(queue, rows) for k, d in row], np.int32)
+        return np.ascontiguousarray(arcs.reshape(-1, 3)), classes, finals, len(number)
     arcs = []
     for blk, row in zip(queue, rows):
         for k, d in row:
@@ -787,8 +793,21 @@ def _regex_to_dfa(tree):
             arcs.append(a)
     arcs = np.concatenate(arcs) if arcs else np.zeros((0, 3), np.int32)
     arcs = arcs[np.lexsort((arcs[:, 1], arcs[:, 0]))]
-    finals = sorted(number[b] for b in number if final[rep[b]])
     return np.ascontiguousarray(arcs), finals, len(number)
+
+
+_PAT_MAX_EDGES = 262144                                    # HCTR_PAT_MAX_EDGES
+
+
+def _expand_arcs(arcs, sets):
+    """the single-label arcs of set arcs: int32 [n, 3] rows (src, label, dst) sorted by (src, label)"""
+    out = []
+    for p, k, q in np.asarray(arcs).reshape(-1, 3):
+        a = np.empty((len(sets[k]), 3), np.int32)
+        a[:, 0], a[:, 1], a[:, 2] = p, sets[k], q
+        out.append(a)
+    out = np.concatenate(out) if out else np.zeros((0, 3), np.int32)
+    return np.ascontiguousarray(out[np.lexsort((out[:, 1], out[:, 0]))])
 
 
 class Pattern(object):
@@ -796,9 +815,15 @@ class Pattern(object):
     automaton over labels, lifted to CTC on the host (no GPU needed). ``arcs``: (src, label, dst) triples with labels in
     [1, C-1] and at most one arc per (src, label); ``finals``: the final states; state 0 is the start; ``num_classes`` =
     C. ``Pattern.compile(expr, codec)`` builds one from a regular expression. The object is immutable and serves any
-    number of contexts."""
+    number of contexts. ``Pattern.from_sets`` builds the set form (``hctr_pat_build_sets``): arcs that carry label sets,
+    the same language and results without the explicit edge list - what a wildcard over a large vocabulary needs.
+    ``kind`` is 0 for the explicit form, 1 for the set form."""
 
-    def __init__(self, arcs, finals, num_states, num_classes, expr=None):
+    def __init__(self, arcs, finals, num_states, num_classes, expr=None, sets=None):
+        if sets is not None:
+            self._init_sets(arcs, sets, finals, num_states, num_classes, expr)
+            return
+        self.sets = None
         a = np.asarray(arcs, dtype=np.int64).reshape(-1, 3)
         f = np.asarray(finals, dtype=np.int64).reshape(-1)
         for v in (a, f):
@@ -816,15 +841,68 @@ class Pattern(object):
         self._h = h if rc == 0 else None
         _lib.check(rc, None)
 
+    def _init_sets(self, arcs, sets, finals, num_states, num_classes, expr):
+        a = np.asarray(arcs, dtype=np.int64).reshape(-1, 3)
+        f = np.asarray(finals, dtype=np.int64).reshape(-1)
+        sets = [np.asarray(v, dtype=np.int64).reshape(-1) for v in sets]
+        for v in [a, f] + sets:
+            if v.size and (v.min() < np.iinfo(np.int32).min or v.max() > np.iinfo(np.int32).max):
+                raise ValueError("arc, state or label out of the int32 range")
+        src, st, dst = (np.ascontiguousarray(a[:, k], dtype=np.int32) for k in range(3))
+        f = np.ascontiguousarray(f, dtype=np.int32)
+        ptr = np.concatenate([[0], np.cumsum([len(v) for v in sets])]).astype(np.int32)
+        lab = np.ascontiguousarray(np.concatenate(sets) if sets else np.zeros(0), dtype=np.int32)
+        self.expr = expr
+        self.arcs, self.finals, self.num_states = np.stack([src, st, dst], axis=1), f, int(num_states)      # as given
+        self.sets = [v.astype(np.int32) for v in sets]
+        self.num_classes = int(num_classes)
+        lib = _lib.load()
+        h = ctypes.c_void_p()
+        rc = lib.hctr_pat_build_sets(_lib.ptr(src), _lib.ptr(st), _lib.ptr(dst), int(a.shape[0]), _lib.ptr(ptr), _lib.ptr(lab),
+                                     len(sets), _lib.ptr(f), int(f.size), int(num_states), self.num_classes, ctypes.byref(h))
+        self._h = h if rc == 0 else None
+        _lib.check(rc, None)
+
     @classmethod
-    def compile(cls, expr, codec):
+    def from_sets(cls, arcs, sets, finals, num_states, num_classes, expr=None):
+        """The set form: ``arcs`` (src, set, dst) triples, ``sets`` the list of label sets they index - each ascending,
+        non-empty, within [1, C-1]; the sets of the arcs that leave one state are pairwise disjoint."""
+        return cls(arcs, finals, num_states, num_classes, expr=expr, sets=list(sets))
+
+    @classmethod
+    def compile(cls, expr, codec, sets=None):
         """The pattern of the regular expression ``expr`` over ``codec``'s vocabulary; the whole line must match
         (``re.fullmatch``). The syntax is ``_Regex``'s subset of ``re``. ``.``, negated sets and ranges mean the codec's
-        real characters (labels 1..C-2): <unknown> is never matched; a literal outside the vocabulary is a ValueError."""
+        real characters (labels 1..C-2): <unknown> is never matched; a literal outside the vocabulary is a ValueError.
+        ``sets=False``: the explicit form; ``True``: the set form, from the expression's alphabet classes; ``None``: the
+        explicit form whenever it builds, the set form where the explicit build is refused for a limit."""
         chars = codec.characters
         vocab = {ch: i for i, ch in enumerate(chars) if 1 <= i <= len(chars) - 2 and len(ch) == 1}
-        arcs, finals, nq = _regex_to_dfa(_Regex(expr, vocab).parse())
-        return cls(arcs, finals, nq, len(chars), expr=expr)
+        arcs, classes, finals, nq = _regex_to_dfa(_Regex(expr, vocab).parse(), sets=True)
+        if sets:
+            return cls.from_sets(arcs, classes, finals, nq, len(chars), expr=expr)
+        # the explicit form's limits, decided before the arcs are expanded (a refused build may have 10^8 of them)
+        expanded = sum(len(classes[k]) for k in arcs[:, 1])
+        if sets is None and expanded > 4 * _PAT_MAX_EDGES:
+            return cls.from_sets(arcs, classes, finals, nq, len(chars), expr=expr)
+        try:
+            return cls(_expand_arcs(arcs, classes), finals, nq, len(chars), expr=expr)
+        except ValueError as exc:
+            if sets is None and ("HCTR_PAT_MAX_STATES" in str(exc) or "HCTR_PAT_MAX_EDGES" in str(exc)):
+                return cls.from_sets(arcs, classes, finals, nq, len(chars), expr=expr)
+            raise
+
+    @property
+    def kind(self):
+        """0 = the explicit form, 1 = the set form (``hctr_pat_kind``)"""
+        return int(_lib.load().hctr_pat_kind(self._h))
+
+    def expanded_arcs(self):
+        """int32 [n, 3]: the single-label arcs (src, label, dst) of the same automaton, sorted by (src, label) - the set
+        arcs expanded (for tests on small vocabularies), the arcs as given for the explicit form"""
+        if self.sets is None:
+            return self.arcs
+        return _expand_arcs(self.arcs, self.sets)
 
     def __del__(self):
         try:
@@ -835,7 +913,9 @@ class Pattern(object):
             pass
 
     def info(self):
-        """dict: dfa_states (after pruning), states (the CTC states), edges, classes (distinct), max_in_degree"""
+        """dict: dfa_states (after pruning), states (the CTC states), edges, classes (distinct), max_in_degree. For the
+        set form ``edges`` counts the reduced in-arcs (one per eps state and source DFA state) and ``max_in_degree`` the
+        most of them one state has."""
         v = [ctypes.c_int32() for _ in range(5)]
         _lib.check(_lib.load().hctr_pat_info(self._h, *[ctypes.byref(x) for x in v]), None)
         return dict(zip(("dfa_states", "states", "edges", "classes", "max_in_degree"), (int(x.value) for x in v)))

@@ -486,12 +486,67 @@ int hctr_lexicon_chunk_classes(int lines, int W);
  * for text_nll, ctc_alpha.
  * hctr_pattern runs the forward of img in internal passes on the stored-logits head exactly as hctr_lexicon does: mode 0
  * f16, mode 1 f16x3, mode 2 EVERY line in f16x3, hctr_last_guard's figures left as they were. hctr_pattern_logits takes
- * caller logits or log-probs in WBC layout, host or device pointer, and needs no weights. */
+ * caller logits or log-probs in WBC layout, host or device pointer, and needs no weights.
+ *
+ * THE SET FORM (hctr_pat_build_sets): arcs (src, set, dst) that carry label sets - a wildcard, a negated class, a name
+ * field over the whole vocabulary - without the explicit edge list, whose size is what refuses such patterns above.
+ *   Set k is set_labels[set_ptr[k] .. set_ptr[k + 1]): non-empty, labels ascending, in [1, C-1]. The sets of the arcs that
+ *   leave one state are pairwise disjoint (determinism); several arcs between one pair of states are allowed.
+ *   The language, the pruning, the CTC states and their numbering (beta_q = q, then eps_(q,c) in ascending (q, c)), the
+ *   start and accepting states, the emissions and the meaning of every output are exactly those of hctr_pat_build on the
+ *   same automaton with every arc expanded into single-label arcs. Only the tables and the order of the sums differ.
+ *   The object is the same hctr_pat: hctr_pat_kind tells the forms apart, hctr_pattern* dispatch on it, hctr_pat_free
+ *   frees both. Errors as hctr_pat_build's, one message each: an empty set, a label out of range, labels not ascending,
+ *   an arc that names no set or no state, overlapping sets leaving one state, an empty language, an exceeded limit
+ *   (the message names the figure).
+ * Limits (nothing is approximated: a pattern beyond one is refused): HCTR_PATSET_MAX_STATES = 65535 CTC states (eight
+ *   full-vocabulary positions; backpointers stay uint16), HCTR_PATSET_MAX_DFA_STATES = 4096 DFA states after pruning (the
+ *   block totals of a step live in LDS, 40 bytes a block), HCTR_PATSET_MAX_INARCS = 1048576 entries of the reduced
+ *   in-arc table: one entry per (state eps_(q,c), source DFA state p with an arc (p, A, q), c in A).
+ * hctr_pat_info on a set pattern: dfa_states, ctc_states and num_classes as above; num_edges = the entries of the
+ *   reduced in-arc table; max_in_degree = the most entries one state has (the most DFA states that feed one eps state).
+ *   hctr_pat_tables on a set pattern returns HCTR_ERR_ARG: the edge list is what this form never builds.
+ * The recursion in block form. The block of DFA state p is beta_p and every eps_(p,.). A state is fed by whole blocks
+ *   less at most one state each: beta_q by block q; eps_(q,c) by itself and, for every arc (p, A, q) with c in A, by
+ *   block p without eps_(p,c) (where the block holds such a state). Work per step is O(S + in-arcs).
+ *   Block totals over a_{t-1}, per block p: its members in ascending state order are beta_p, then its eps states. Lane l
+ *   of 64 takes the members l, l + 64, l + 128, .. in that order; the 64 lanes then combine by the butterfly over the lane
+ *   distances 32, 16, 8, 4, 2, 1 (lane l with lane l xor d). m_p = the float32 maximum; i*_p = the lowest state that
+ *   holds it; all_p = the float64 sum of (double)exp32(a - m_p) over the members, rest_p = the same sum without i*_p
+ *   (both 0 where m_p is -inf). The order is a function of the tables alone: not of the thread count, of where the step
+ *   buffers live, or of the grouping of lines.
+ *   Tot_p = m_p + log32((float)all_p), -inf where m_p is. The source term of eps_(q,c) from block p is
+ *   y = m_p + log32((float)X) with X = rest_p where eps_(p,c) is i*_p; all_p - (double)exp32(a(eps_(p,c)) - m_p) where
+ *   eps_(p,c) exists and is not i*_p (the maximal term survives the subtraction: nothing cancels); all_p where it does
+ *   not exist; y = -inf where X <= 0 or m_p is -inf.
+ *   a_t(beta_q) = Tot_q + lp_t(0). a_t(eps_(q,c)) = the logsum above (the explicit form's n-ary logsum) over [its own
+ *   a_{t-1}, then y of each in-arc in ascending p] + lp_t(c). logp[b] = that logsum over Tot_q of the final q, ascending,
+ *   returned as 0 where it rounds above 0. logp is within the family's rule of the explicit form's, not bit-equal.
+ *   Max: per block the two best v_{t-1} with their states, ties to the lower state. The candidate of block p for
+ *   eps_(q,c) is the best, or the runner-up where the best is eps_(p,c) itself; among the own value and the candidates
+ *   the greatest wins, ties to the lowest state; all at -inf: the state's own index. That is the explicit form's first
+ *   maximal source in ascending order and the additions are exact, so best_logp, path, labels, lengths, span_start,
+ *   span_end, char_logp and text_nll have the explicit form's bits wherever both forms build.
+ *   When every Viterbi output is NULL the sum runs alone and logp has the full call's bits.
+ * One workgroup per line, no atomics, no workgroup waits on another. The two step buffers of (a, v) live in LDS when
+ *   they fit beside the block totals (16*S + 40*nQ <= 160 KB; 8*S + 24*nQ forward-only), else in the context's CTC
+ *   scratch; the environment variable HCTR_PATSET_LDS=0, read at every call, keeps them in scratch. Results do not
+ *   depend on it, bit for bit. hctr_pattern_group_lines is unchanged. Device scratch as above, plus 16*g*S for the step
+ *   buffers kept out of LDS; the device copy is 20 bytes per state + 4 per DFA state + 4 per in-arc. Launches:
+ *   pattern_set in the place of pattern.
+ * Masked and non-finite logits: as stated above for hctr_pattern_logits, for both forms. */
 #define HCTR_PAT_MAX_STATES 8192
 #define HCTR_PAT_MAX_EDGES 262144
 typedef struct hctr_pat hctr_pat;
 int hctr_pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const int32_t* arcs_dst, int num_arcs,
                    const int32_t* finals, int num_finals, int num_states, int C, hctr_pat** out);
+#define HCTR_PATSET_MAX_STATES 65535
+#define HCTR_PATSET_MAX_DFA_STATES 4096
+#define HCTR_PATSET_MAX_INARCS 1048576
+int hctr_pat_build_sets(const int32_t* arcs_src, const int32_t* arcs_set, const int32_t* arcs_dst, int num_arcs,
+                        const int32_t* set_ptr, const int32_t* set_labels, int num_sets, const int32_t* finals,
+                        int num_finals, int num_states, int C, hctr_pat** out);
+int hctr_pat_kind(const hctr_pat* pat);      /* 0 = hctr_pat_build's, 1 = hctr_pat_build_sets's; HCTR_ERR_ARG for NULL */
 void hctr_pat_free(hctr_pat* pat);
 int hctr_pat_info(const hctr_pat* pat, int32_t* dfa_states, int32_t* ctc_states, int32_t* num_edges, int32_t* num_classes,
                   int32_t* max_in_degree);

@@ -102,7 +102,10 @@ forward-only (logp alone) and full (every output fetched), and in the same run t
 line's greedy text as its target), alternately after warm-up calls of each, medians with range. The expression is
 compiled over a vocabulary whose labels 1..10 are the digits 0-9, 11-13 the year, month and day signs and the rest CJK
 code points, e.g. '\\d{18}', '\\d{4}\u5e74\\d{1,2}\u6708\\d{1,2}\u65e5', '.\\d{3}'. --layers adds the device time of each call's
-launches (pattern_classes, ctc_lse, pattern, pattern_trace, ctc_alpha) and the recursion's time per step."""
+launches (pattern_classes, ctc_lse, pattern, pattern_trace, ctc_alpha) and the recursion's time per step. --sets builds
+the set form (label-set arcs, the launch pattern_set), which a wildcard over the whole vocabulary needs ('.{2,4}',
+'.*\u5e74.*'); where the explicit form builds as well ('.\\d{3}') both are timed alternately in the one process and their
+Viterbi outputs compared bit for bit."""
 import argparse
 import json
 import os
@@ -137,6 +140,8 @@ def main():
     ap.add_argument("--entries", type=int, default=10000)
     ap.add_argument("--unit-nodes", type=int, default=0, help="--lexicon: trie nodes per workgroup (0 = the default)")
     ap.add_argument("--pattern", type=str, default="", help="a regular expression: time hctr_pattern_logits")
+    ap.add_argument("--sets", action="store_true", help="with --pattern: build the set form (label-set arcs); where the "
+                    "explicit form builds too, it is timed alternately in the same process")
     ap.add_argument("--pairs", type=int, default=250)
     ap.add_argument("--host-lines", type=int, default=4)
     args = ap.parse_args()
@@ -509,8 +514,15 @@ def pattern(args, hctr_amd, m, imgs, targets, tl):
     logits = m(imgs)                                             # device tensor [W, lines, C]
     W, B, C = (int(v) for v in logits.shape)
     t0 = time.perf_counter()
-    pat = mod.Pattern.compile(args.pattern, hctr_amd.ctc_codec(pattern_characters(C - 2)))
+    codec = hctr_amd.ctc_codec(pattern_characters(C - 2))
+    pat = mod.Pattern.compile(args.pattern, codec, sets=True if args.sets else None)
     build_ms = 1e3 * (time.perf_counter() - t0)
+    explicit = None
+    if args.sets:
+        try:
+            explicit = mod.Pattern.compile(args.pattern, codec, sets=False)
+        except ValueError:
+            pass                                                 # beyond the explicit form's limits
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -531,6 +543,9 @@ def pattern(args, hctr_amd, m, imgs, targets, tl):
         last["r"] = mod.pattern_logits(ctx, logits, 1, pat, None, True)
 
     fns = (("loss_only", loss_only), ("pattern_forward", forward_only), ("pattern_full", full))
+    if explicit is not None:
+        fns += (("explicit_forward", lambda: last.update(ef=mod.pattern_logits(ctx, logits, 1, explicit, None, False))),
+                ("explicit_full", lambda: last.update(er=mod.pattern_logits(ctx, logits, 1, explicit, None, True))))
     for _ in range(args.warmup):
         for _, fn in fns:
             fn()
@@ -540,7 +555,10 @@ def pattern(args, hctr_amd, m, imgs, targets, tl):
             ms[k].append(1e3 * timed(fn))
     assert last["f"].logp.tobytes() == last["r"].logp.tobytes()
     info = pat.info()
-    rec = {"mode": "pattern", "pattern": args.pattern, "lines": B, "width": W, "classes": C, "precision": args.precision,
+    if explicit is not None:                                     # the Viterbi outputs of the two forms: the same bits
+        for f in last["r"].FIELDS[1:]:
+            assert getattr(last["r"], f).tobytes() == getattr(last["er"], f).tobytes(), f
+    rec = {"mode": "pattern", "pattern": args.pattern, "kind": pat.kind, "lines": B, "width": W, "classes": C, "precision": args.precision,
            "build_ms": round(build_ms, 1), "group_lines": mod.pattern_group_lines(info["states"], info["classes"] + 1, W),
            "matching_lines": int(np.isfinite(last["r"].logp).sum())}
     rec.update(info)
@@ -557,8 +575,10 @@ def pattern(args, hctr_amd, m, imgs, targets, tl):
         for k, v in prof.items():
             rec[k + "_layers_ms"] = {n: round(x, 4) for n, x in v.items()}
         groups = -(-B // rec["group_lines"])
-        for k in ("pattern_forward", "pattern_full"):        # a group's lines run side by side, the groups in turn
-            rec[k + "_us_per_step"] = round(1e3 * prof[k].get("pattern", 0.0) / (W * groups), 3)
+        for k in prof:                                       # a group's lines run side by side, the groups in turn
+            if k != "loss_only":
+                kernel = "pattern" if k.startswith("explicit") or not pat.kind else "pattern_set"
+                rec[k + "_us_per_step"] = round(1e3 * prof[k].get(kernel, 0.0) / (W * groups), 3)
     return rec
 
 
