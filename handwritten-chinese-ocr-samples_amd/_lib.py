@@ -156,6 +156,7 @@ SIGNATURES = [
     ("hctr_finalize_weights", _I, [_VP]),
     ("hctr_set_precision", _I, [_VP, _I]),
     ("hctr_set_guard", _I, [_VP, ctypes.c_double, ctypes.c_double]),
+    ("hctr_get_guard", _I, [_VP, c_f64p, c_f64p]),
     ("hctr_last_guard", _I, [_VP, c_i64p, c_i64p, _VP, _VP, _VP, _I64]),
     ("hctr_lines_per_pass", _I, [_VP, _I, _I, _I]),
     ("hctr_workspace_stats", _I, [_VP, c_i64p, c_i64p, c_i64p]),

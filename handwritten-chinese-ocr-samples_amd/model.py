@@ -28,10 +28,10 @@ class hctr_model(object):
     def __init__(self, num_classes=7375, precision="f16"):
         """``precision`` (an engine option, not part of the reference surface): "f16" (default; fp16 storage/MFMA, fp32
         accumulate), "f16x3" (hi+lo split pairs, ~3x the work, fp32-grade logits) or "auto" (guarded: every line in f16,
-        and the lines with a column whose top-1/top-2 logit margin is within twice the f16 logit tolerance once more in
-        f16x3 - the f16x3 mode's text wherever f16 cannot certify its own, f16 speed on peaky logits; see
-        include/hctr_hip.h ``hctr_set_precision``). A model built with "auto" holds both weight sets and can be switched
-        between all three modes afterwards (``set_precision``)."""
+        and the lines with a column whose top-1/top-2 logit margin is within twice the guard's own per-line tolerance
+        (``set_guard``) once more in f16x3 - the f16x3 mode's text wherever f16 cannot certify its own, f16 speed on
+        peaky logits; see include/hctr_hip.h ``hctr_set_precision``). A model built with "auto" holds both weight sets
+        and can be switched between all three modes afterwards (``set_precision``)."""
         if precision not in _PRECISIONS:
             raise ValueError("precision must be 'f16', 'f16x3' or 'auto'")
         self.precision = precision
@@ -410,11 +410,20 @@ class hctr_model(object):
             self.precision = precision
         return self
 
-    def set_guard(self, rel=0.01, abs=0.05):
+    def set_guard(self, rel=0.018, abs=0.05):
         """Criterion of the "auto" mode: a line is run again in f16x3 unless every column's top-1/top-2 logit margin
-        exceeds 2 * (rel * max|logit of the line| + abs)."""
+        exceeds 2 * (rel * max|logit of the line| + abs). The defaults are the engine's (csrc/engine.cpp ``guard_rel`` /
+        ``guard_abs``, what ``guard()`` returns on a fresh model): the guard's own per-line tolerance, 1.5 x the largest
+        per-line relative f16-versus-f16x3 logit error measured on the engine ("Guard defaults"),
+        valid for checkpoints whose per-line relative f16 error stays below ``rel``."""
         _lib.check(_lib.load().hctr_set_guard(self._require_ctx(), float(rel), float(abs)), self._ctx)
         return self
+
+    def guard(self):
+        """(rel, abs) of the "auto" mode's criterion as the engine holds them now."""
+        rel, ab = ctypes.c_double(0.0), ctypes.c_double(0.0)
+        _lib.check(_lib.load().hctr_get_guard(self._require_ctx(), ctypes.byref(rel), ctypes.byref(ab)), self._ctx)
+        return rel.value, ab.value
 
     def last_guard(self):
         """Figures of the last call in "auto" mode: dict(lines, flagged, flags[uint8], min_margin[float32],

@@ -79,13 +79,21 @@ int hctr_finalize_weights(hctr_ctx* ctx);
  * Before hctr_finalize_weights the mode decides which weight set(s) are built (0: f16, 1: f16x3, 2: both);
  * afterwards it may still be changed among the modes whose set(s) are resident (a context finalized in
  * mode 2 serves all three).
- * hctr_set_guard: rel / abs of mode 2's criterion (defaults 0.01 / 0.05 = the f16 logit tolerance the parity
- *     suite asserts, tests/test_gpu_parity.py LOGIT_RTOL / LOGIT_ATOL).
+ * hctr_set_guard / hctr_get_guard: rel / abs of mode 2's criterion (either output pointer may be NULL). The
+ *     tolerance is the guard's OWN, taken per line: the certificate holds for a checkpoint whose f16 logits are
+ *     within rel * (max|logit| of THAT line) + abs of the fp32-grade ones. It is not the parity suite's f16
+ *     tolerance (tests/test_gpu_parity.py scales by the batch-wide max|logit|, a looser bound). The defaults
+ *     (csrc/engine.cpp guard_rel / guard_abs, the one place that defines them; a fresh context's hctr_get_guard
+ *     returns them) are derived from the per-line f16-versus-f16x3 error measured on the engine: rel = 1.5 x
+ *     the largest max|f16 - f16x3| / max|logit of the line| seen, abs = 0.05 ("Guard
+ *     defaults"; tests/test_gpu_guard.py asserts the premise per line). A checkpoint whose per-line relative
+ *     f16 error is larger needs a larger rel.
  * hctr_last_guard: figures of the last mode-2 call, per line of its batch: flags[i] = 1 if line i was
  *     run again in f16x3, min_margin[i] = its smallest column margin, scale[i] = its largest |logit| (f16 sweep).
  *     Any output pointer may be NULL; at most cap entries are written. */
 int hctr_set_precision(hctr_ctx* ctx, int mode);
 int hctr_set_guard(hctr_ctx* ctx, double rel, double abs_tol);
+int hctr_get_guard(hctr_ctx* ctx, double* rel, double* abs_tol);
 int hctr_last_guard(hctr_ctx* ctx, int64_t* lines, int64_t* flagged, uint8_t* flags, float* min_margin,
                     float* scale, int64_t cap);
 

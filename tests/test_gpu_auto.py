@@ -1,7 +1,8 @@
 """GPU tests (-m gpu) of the guarded precision mode (``precision="auto"``, C ABI ``hctr_set_precision(ctx, 2)``):
 every line runs in f16; the fused head also yields each column's top-1/top-2 logit margin; a line with a column whose
-margin is within twice the f16 logit tolerance (LOGIT_RTOL * max|logit of the line| + LOGIT_ATOL - the tolerance
-tests/test_gpu_parity.py asserts for f16) is run again in f16x3 at the same padded width.
+margin is within twice the guard's own tolerance (rel * max|logit of the line| + abs; rel / abs are read from the engine,
+model.guard(), and tests/test_gpu_guard.py asserts the premise behind them line by line) is run again in f16x3 at the
+same padded width.
 
 What must hold:
   * the text of auto mode EQUALS the text of f16x3 mode on every fixture (flagged lines ARE f16x3 results; an unflagged
@@ -20,9 +21,6 @@ import pytest
 from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
-
-LOGIT_RTOL, LOGIT_ATOL = 0.01, 0.05          # = tests/test_gpu_parity.py (and the engine's guard defaults)
-
 
 @pytest.fixture(scope="module")
 def auto_random(pkg, synth, state_dict):
@@ -74,7 +72,8 @@ def test_auto_equals_f16x3_and_guard_figures_are_the_f16_margins(pkg, synth, aut
     lg16 = m(imgs, widths=wd)
     mg, sc = _np_guard(lg16)
     assert np.array_equal(g["min_margin"], mg.astype(np.float32)) and np.array_equal(g["scale"], sc.astype(np.float32))
-    thr = 2.0 * (LOGIT_RTOL * sc.astype(np.float64) + LOGIT_ATOL)
+    rel, ab = m.guard()
+    thr = 2.0 * (rel * sc.astype(np.float64) + ab)
     assert np.array_equal(g["flags"].astype(bool), ~(mg.astype(np.float64) > thr))
     # logits in auto mode: flagged lines carry the f16x3 logits, the others the f16 ones, bit for bit
     m.set_precision("f16x3")
@@ -96,13 +95,14 @@ def test_guard_thresholds_and_mode_switching(pkg, synth, auto_random, state_dict
     t = _texts(pkg, synth, m, imgs)
     cd = pkg.ctc_codec(synth.characters())
     m.set_precision("auto")
+    defaults = m.guard()
     try:
         m.set_guard(0.0, 0.0)                         # only exact ties / NaNs are uncertain: nothing is re-run
         assert cd.labels_to_text(m.greedy(imgs)) == t["f16"] and m.last_guard()["flagged"] == 0
         m.set_guard(1e6, 0.0)                         # everything is uncertain: the f16x3 text
         assert cd.labels_to_text(m.greedy(imgs)) == t["f16x3"] and m.last_guard()["flagged"] == 3
     finally:
-        m.set_guard(LOGIT_RTOL, LOGIT_ATOL)
+        m.set_guard(*defaults)
     with pytest.raises(ValueError):
         m.set_guard(-1.0, 0.0)
     # after a call in another mode the figures are empty
@@ -132,7 +132,7 @@ def test_guard_thresholds_and_mode_switching(pkg, synth, auto_random, state_dict
         del ms
     finally:
         os.environ.pop("HCTR_MAX_COLS", None)
-        m.set_guard(LOGIT_RTOL, LOGIT_ATOL)
+        m.set_guard(*defaults)
 
 
 def _runs(idx):
@@ -147,6 +147,7 @@ def test_partly_flagged_batch_in_several_passes_equals_one_pass(pkg, synth, auto
     m = auto_random
     imgs = synth.make_line_images(7, 150, 79)
     m.set_precision("auto")
+    defaults = m.guard()
     m.greedy(imgs)
     mg = m.last_guard()["min_margin"].astype(np.float64)
     srt = np.sort(mg)
@@ -202,7 +203,7 @@ def test_partly_flagged_batch_in_several_passes_equals_one_pass(pkg, synth, auto
         if old_cols is not None:
             os.environ["HCTR_MAX_COLS"] = old_cols
         m.set_precision("auto")
-        m.set_guard(LOGIT_RTOL, LOGIT_ATOL)
+        m.set_guard(*defaults)
         del ms
 
 
@@ -220,7 +221,9 @@ def test_auto_mode_config2_trained_checkpoint_equals_the_real_reference(pkg, syn
     assert cd.labels_to_text(m.greedy(imgs)) == meta["greedy"]
     gd = m.last_guard()
     assert gd["lines"] == 64 and 0 <= gd["flagged"] <= 12, gd["flagged"]       # reference margins: 5-6 lines below the bound
-    tol = LOGIT_RTOL * float(np.abs(g["max"]).max()) + LOGIT_ATOL
+    rel, ab = m.guard()
+    print("flagged %d of %d lines at rel %g, abs %g: %s" % (gd["flagged"], gd["lines"], rel, ab, np.flatnonzero(gd["flags"]).tolist()))
+    tol = rel * float(np.abs(g["max"]).max()) + ab
     assert np.abs(gd["min_margin"] - g["margin"].min(axis=1)).max() <= 2 * tol
     # the engine's margin is within 2 * tol of the reference's, so a line whose REFERENCE margins all exceed 4 * tol
     # cannot be flagged (the flag threshold is at most 2 * tol)
@@ -272,6 +275,7 @@ def test_auto_mode_config5_beam_strings_equal_the_real_reference(pkg, synth, aut
     with open(os.path.join(GOLDEN, "c5_beam_lines.json"), encoding="utf-8") as f:
         gold = json.load(f)
     m = auto_trained
+    defaults = m.guard()
     imgs = synth.make_font_lines(gold["lines"], gold["width"], gold["seed"])
     cd = pkg.ctc_codec(synth.characters()).attach(m)
     fes = {}
@@ -308,7 +312,7 @@ def test_auto_mode_config5_beam_strings_equal_the_real_reference(pkg, synth, aut
         n = int(fe["cand_off"][-1])
         assert np.array_equal(fe["cand_idx"][:n], fes["f16x3"]["cand_idx"][:n])
     finally:
-        m.set_guard(LOGIT_RTOL, LOGIT_ATOL)
+        m.set_guard(*defaults)
 
 
 def test_auto_mode_nan_and_ties_are_flagged(pkg, synth, state_dict):
