@@ -2306,12 +2306,12 @@ int greedy_passes(hctr_ctx* c, const Batch& in, int32_t* labels, int32_t* length
     });
 }
 
-// the re-run lines' labels, up to each length, into the caller's rows (the stream is drained)
+// the re-run lines' labels into the caller's rows (the stream is drained): whole rows, zeros beyond each length as
+// ctc_collapse wrote them, so that nothing of the first sweep's longer text stays behind
 void greedy_scatter(hctr_ctx* c, const std::vector<int>& redo, int W, int32_t* labels, int32_t* lengths) {
     for (size_t i = 0; i < redo.size() && lengths; ++i) {
-        const int n = c->h_lengths[i];
-        lengths[redo[i]] = n;
-        if (n > 0 && labels) memcpy(labels + (size_t)redo[i] * W, c->h_labels.data() + i * W, (size_t)n * 4);
+        lengths[redo[i]] = c->h_lengths[i];
+        if (labels) memcpy(labels + (size_t)redo[i] * W, c->h_labels.data() + i * W, (size_t)W * 4);
     }
 }
 

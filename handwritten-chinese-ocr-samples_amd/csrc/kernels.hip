@@ -2625,6 +2625,8 @@ __global__ __launch_bounds__(64) void ctc_collapse_kernel(const int32_t* __restr
         if (keep) o[base + __popcll(m & ((1ull << lane) - 1ull))] = cur;
         base += __popcll(m);
     }
+    // the callers copy the whole [B][W] array out: the places beyond the text are zeros, not what the buffer held
+    for (int t = base + lane; t < W; t += 64) o[t] = 0;
     if (lane == 0) lengths[b] = base;
 }
 

@@ -112,7 +112,8 @@ int hctr_forward_logits(hctr_ctx* ctx, const void* img, int img_dtype, int img_o
 /* ---- fused forward + greedy decode: replaces model(x) -> codec.decode(...) greedy ------------
  * test.py:191-194 with utils/ctc_codec.py:70-99. Logits never leave the device; argmax takes the
  * first maximum (np.argmax), a column is kept iff idx!=0 && idx!=C-1 && idx!=previous raw idx.
- * labels: int32 [B][W] (first lengths[b] entries valid), lengths: int32 [B]; host pointers. */
+ * labels: int32 [B][W] (first lengths[b] entries valid, the rest written as zeros), lengths: int32 [B]; host pointers.
+ * The same holds for the labels of hctr_decode_greedy_logits and hctr_evaluate*: the whole array is written. */
 int hctr_greedy(hctr_ctx* ctx, const void* img, int img_dtype, int img_on_device,
                 const int32_t* widths, int B, int W,
                 int32_t* labels, int32_t* lengths);
@@ -467,7 +468,7 @@ int hctr_lexicon_chunk_classes(int lines, int W);
  * Viterbi outputs (all host pointers, any may be NULL; when every one of best_logp .. text_nll is NULL the call runs the
  *   sum alone, stores no backpointers, and logp has the bits of the full call's):
  *   path int32 [B][W]: the class of the best accepted path per column, -1 for t >= T;
- *   labels int32 [B][W], lengths int32 [B]: its collapse, the decoded text, which is in L(A);
+ *   labels int32 [B][W], lengths int32 [B]: its collapse, the decoded text, which is in L(A) (zeros beyond lengths[b]);
  *   span_start, span_end int32 [B][W], char_logp float32 [B][W]: per character its first column, the column after its
  *   run, and the float32 sum of lp over the run in ascending t - layout and meaning of hctr_recognize: the first
  *   lengths[b] valid, the rest zeros;

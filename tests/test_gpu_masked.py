@@ -144,10 +144,10 @@ def _pad(path, Wc):
     return list(path) + [-1] * (Wc - len(path))
 
 
-@pytest.mark.parametrize("name", NAMES)
-def test_scores_against_float64(name, results):
+def check_scores_against_float64(name, r):
+    """the scores, paths, spans, rankings and decoded labels of `r`, a ``run_all`` result of the case `name`, against the
+    case's float64 oracle (also what tests/test_gpu_history.py holds its first-call results to)"""
     c, o = mc.get(name)
-    r = results(name)
     Wc, B, _ = c["logits"].shape
     _check_scores(r["nll"][0], o["nll"], name + " loss", "loss")
     assert r["grad.nll"][0].tobytes() == r["nll"][0].tobytes()
@@ -204,6 +204,11 @@ def test_scores_against_float64(name, results):
         lp = np.float64(r["rec.alt_logps"][0])
         assert np.isneginf(lp).any(), "no runner-up of a single-class row was reported"
     print("largest errors so far:", {k: "%.3e at %.2f" % v for k, v in sorted(WORST.items())})
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_scores_against_float64(name, results):
+    check_scores_against_float64(name, results(name))
 
 
 def test_no_alignment_outputs(results):
