@@ -27,6 +27,10 @@ Public surface = the reference's surface for this path:
                Pattern (a DFA over labels, or Pattern.compile of a regular expression) by one CTC forward over the
                automaton, and the best matching reading with spans and confidences; PatternResult is its result and that
                of hctr_model.pattern / ctc_codec.pattern          (engine-backed; no counterpart)
+  WordRecognizer  word-sequence recognition on logits: the line is a sequence of entries of a Lexicon - which, and
+               where: the best segmentation by token passing over the lexicon's trie, with per-entry log priors and a
+               word bonus; WordsResult is its result and that of hctr_model.words / ctc_codec.words
+                                                                    (engine-backed; no counterpart)
   LMSweep      result of hctr_model.lm_sweep / ctc_codec.lm_sweep: edit distances of the LM-scored 1-best under a grid of
                (lm_panelty, len_bonus) pairs; LMSweepTotals adds batches up and answers the reference's test.py -gs
 plus ``synth`` (deterministic synthetic checkpoints / line images) and ``build`` / ``load_library``.
@@ -36,7 +40,7 @@ from ._lib import build, load as load_library  # noqa: F401
 from .codec import ArpaLM, ToyBigramLM, ZeroLM, ctc_codec  # noqa: F401
 from .ctc import (CTCAligner, CTCAlignment, CTCLoss, Evaluation, KeywordSpotter, LMSweep, LMSweepTotals, NBest,  # noqa: F401
                   Lexicon, LexiconRecognizer, LexiconResult, Pattern, PatternRecognizer, PatternResult, Recognition,
-                  Spotting)
+                  Spotting, WordRecognizer, WordsResult)
 from .model import hctr_model  # noqa: F401
 
 _EDIT_BOUND = None
@@ -53,4 +57,4 @@ def edit_distance(hyps, refs, device=0):
         _EDIT_BOUND = ctc._EngineBound().cuda(device)
     return ctc.edit_distance_sequences(_EDIT_BOUND._context(), list(hyps), list(refs), maps=False).edits
 
-__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "Recognition", "Evaluation", "NBest", "LMSweep", "LMSweepTotals", "KeywordSpotter", "Spotting", "Lexicon", "LexiconRecognizer", "LexiconResult", "Pattern", "PatternRecognizer", "PatternResult", "edit_distance", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]
+__all__ = ["hctr_model", "ctc_codec", "CTCLoss", "CTCAligner", "CTCAlignment", "Recognition", "Evaluation", "NBest", "LMSweep", "LMSweepTotals", "KeywordSpotter", "Spotting", "Lexicon", "LexiconRecognizer", "LexiconResult", "Pattern", "PatternRecognizer", "PatternResult", "WordRecognizer", "WordsResult", "edit_distance", "ZeroLM", "ToyBigramLM", "ArpaLM", "synth", "preprocess", "build", "load_library"]

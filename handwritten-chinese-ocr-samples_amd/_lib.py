@@ -27,7 +27,7 @@ U8, F32, I64 = 0, 1, 2
 
 def _headers():
     return [os.path.join(CSRC, "kernels.h"), os.path.join(CSRC, "ngram_lm.h"), os.path.join(CSRC, "lm_flat.h"),
-            os.path.join(CSRC, "lex_flat.h"), os.path.join(CSRC, "pat_flat.h"), HEADER]
+            os.path.join(CSRC, "lex_flat.h"), os.path.join(CSRC, "lex_words.h"), os.path.join(CSRC, "pat_flat.h"), HEADER]
 
 
 def _deps():
@@ -185,6 +185,11 @@ SIGNATURES = [
     ("hctr_lexicon", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_lexicon_logits", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_lexicon_chunk_classes", _I, [_I, _I]),
+    # word-sequence recognition: lex, word_bonus, num_nodes, num_classes, node, slot, entry, weight, classes
+    ("hctr_lex_word_tables", _I, [_VP, ctypes.c_float] + [_VP] * 7),
+    # ctx, lex, ..., input_lengths, word_bonus, max_words, score, count, words, starts, labels, lengths, text_nll
+    ("hctr_words", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _VP, ctypes.c_float, _I] + [_VP] * 7),
+    ("hctr_words_logits", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP, ctypes.c_float, _I] + [_VP] * 7),
     # pattern recognition: arcs_src, arcs_label, arcs_dst, num_arcs, finals, num_finals, num_states, C, out
     ("hctr_pat_build", _I, [_VP, _VP, _VP, _I, _VP, _I, _I, _I, ctypes.POINTER(_VP)]),
     ("hctr_pat_build_sets", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _I, _I, _I, ctypes.POINTER(_VP)]),

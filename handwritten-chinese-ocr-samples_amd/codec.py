@@ -275,6 +275,19 @@ class ctc_codec(object):
         res = ctc.pattern_logits(self._context(), logits, on_dev, pat, input_lengths, full)
         return (res.texts(self) if full else None), res
 
+    def words(self, preds, lex, word_bonus=0.0, max_words=None, input_lengths=None):
+        """Word-sequence recognition of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) against ``lex``,
+        a ``ctc.Lexicon``: the best segmentation of every line into entries. Returns ``(word_lists, result)``: per line
+        the list of its words as the lexicon was given them (empty where nothing fits) and the ``ctc.WordsResult`` with
+        scores, starts, the concatenated text and its loss (include/hctr_hip.h ``hctr_words_logits``)."""
+        from . import ctc
+        logits, on_dev = self._as_logits(preds)
+        C = int(logits.shape[2])
+        if C != len(self.characters):
+            raise ValueError("logits have %d classes, codec has %d" % (C, len(self.characters)))
+        res = ctc.words_logits(self._context(), logits, on_dev, lex, word_bonus, max_words, input_lengths)
+        return [[w[1] for w in line] for line in res.lines(lex)], res
+
     def nbest(self, preds, n=5, beam=10, depth=10, len_bonus=0.0, input_lengths=None, lm=None, lm_panelty=2.0,
               skip_search=False):
         """The ``n`` best texts of every line of ``preds`` (what ``decode`` takes; a CUDA tensor is read in place) with

@@ -213,6 +213,15 @@ struct hctr_ctx {
     // device copy of the most recently used hctr_pat (hctr_pattern*): its tables in one block, likewise
     int32_t* pat_dev = nullptr;
     uint64_t pat_serial = 0;
+    // device copy of the word tables (hctr_words*) of the most recently used hctr_lex and word_bonus, likewise
+    // and the host tables they were packed from (words_tab_serial = 0: none), kept so that a call on the same lexicon and
+    // bonus builds nothing
+    int32_t* words_dev = nullptr;
+    uint64_t words_serial = 0;
+    float words_bonus = 0.f;
+    WordTables words_tab;
+    uint64_t words_tab_serial = 0;
+    float words_tab_bonus = 0.f;
 };
 
 namespace {
@@ -1924,6 +1933,254 @@ int lex_call(hctr_ctx* c, const Source& src, const hctr_lex* lex, const int32_t*
 }
 
 // ---------------------------------------------------------------------------------------------
+// the loss of a decoded text over the emissions it was decoded from (hctr_pattern*, hctr_words*)
+// ---------------------------------------------------------------------------------------------
+// what a call that decodes texts in groups of lines keeps for their loss: the object's classes (ascending; every class
+// a decoded text uses is among them) with D = classes + 1 emission slots, the call's upload (T[B] first), the group's
+// decoded labels [B][W] and lengths [B] on the device, a per-line flag [B] (a line whose flag is below `have` has no
+// text), the group's tables and emissions, and nll [B]. fix [B]: 0 = the kernel's nll, 1 = NaN (the text exceeds the
+// loss's labels), 2 = +inf (no text).
+struct TextNll {
+    const std::vector<int32_t>* classes;
+    int D;
+    const std::vector<int32_t>* up;
+    const int32_t *labels, *lengths, *flag;
+    int have;
+    int32_t* tab;
+    const float* emis;
+    float* nll;
+    std::vector<uint8_t>* fix;
+};
+
+// The loss of the decoded texts of the group's lines [gb0, gb0 + n), over the group's own emissions: the loss's tables
+// point into the object's classes and ctc_alpha reads what ctc_lse wrote for the object - the loss's emissions, bit for
+// bit. The labels must be on the host: drains the stream.
+int text_nll_group(hctr_ctx* c, Prof& pf, const TextNll& x, int gb0, int n, int W) {
+    std::vector<int32_t> lab((size_t)n * W), len((size_t)n), flag((size_t)n);
+    HIP_TRY(c, hipMemcpyAsync(lab.data(), x.labels + (size_t)gb0 * W, lab.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(len.data(), x.lengths + gb0, len.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(flag.data(), x.flag + gb0, flag.size() * 4, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const std::vector<int32_t>& cls = *x.classes;
+    std::vector<int32_t> tab((size_t)3 * n);
+    int max_states = 1;
+    for (int b = 0; b < n; ++b) {
+        const int L = std::min(std::max(len[(size_t)b], 0), W);
+        const bool none = flag[(size_t)b] < x.have, fits = 2 * (int64_t)L + 1 <= kCtcMaxStates;
+        (*x.fix)[(size_t)gb0 + b] = none ? 2 : fits ? 0 : 1;
+        const bool run = !none && fits;
+        tab[(size_t)b] = run ? (*x.up)[(size_t)gb0 + b] : 0;          // T = 0: the kernel reads nothing of the line
+        tab[(size_t)n + b] = run ? L : 0;
+        tab[(size_t)2 * n + b] = (int32_t)(tab.size() - 3 * (size_t)n);
+        for (int j = 0; j < L && run; ++j) {
+            const size_t k = (size_t)(std::lower_bound(cls.begin(), cls.end(), lab[(size_t)b * W + j]) - cls.begin());
+            tab.push_back(1 + (int32_t)std::min(k, cls.size() - 1));
+        }
+        if (run) max_states = std::max(max_states, 2 * L + 1);
+    }
+    HIP_TRY(c, hipMemcpyAsync(x.tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
+    const int32_t* t = x.tab;
+    const CtcLines m{t, t + n, t + 2 * n, t, t, t + 3 * n, x.D};
+    PROF_TRY(pf, "ctc_alpha", launch_ctc_alpha(x.emis, m, 0, n, W, max_states, x.nll + gb0, nullptr, nullptr, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));          // (tab is this function's)
+    return HCTR_OK;
+}
+
+// text_nll on the host once it is fetched: the lines whose figure is not the kernel's
+void text_nll_fix(const std::vector<uint8_t>& fix, float* text_nll) {
+    for (size_t b = 0; b < fix.size(); ++b) {
+        if (fix[b] == 1) text_nll[b] = std::numeric_limits<float>::quiet_NaN();
+        if (fix[b] == 2) text_nll[b] = std::numeric_limits<float>::infinity();
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// word-sequence recognition (hctr_words*): the device copy of the word tables, the groups of lines that share one block
+// of emissions, records and step buffers, scratch
+// ---------------------------------------------------------------------------------------------
+// whether a trie's two step buffers live in LDS: when they fit, unless HCTR_WORDS_LDS=0 keeps them in the call's scratch
+// (for the tests: results do not depend on it)
+bool words_lds(int nodes) {
+    const char* e = getenv("HCTR_WORDS_LDS");
+    if (e && *e && atoi(e) == 0) return false;
+    return nodes <= kWordsLdsNodes;
+}
+
+// lines one group holds: HCTR_WORDS_LINES, else what keeps a group's emissions (4*W*D bytes a line), records (32*W) and
+// scratch-form step buffers (32*nodes) within the 4 GiB of the lexicon call's emissions, at least 1. Results do not
+// depend on it.
+int words_group_lines(int nodes, int D, int W, bool lds) {
+    if (const char* e = getenv("HCTR_WORDS_LINES")) {
+        const int v = atoi(e);
+        if (v >= 1) return v;
+    }
+    const int64_t per = (int64_t)std::max(W, 1) * (4 * (int64_t)std::max(D, 1) + 32) + (lds ? 0 : 32 * (int64_t)nodes);
+    return (int)std::min<int64_t>(1 << 20, std::max<int64_t>(1, ((int64_t)4 << 30) / per));
+}
+
+// the words of the device block: node | slot | entry | weight (float bits) | cls
+struct WordsLayout {
+    size_t node, slot, entry, weight, cls, words;
+    explicit WordsLayout(const WordTables& t) {
+        WordTaker take;
+        node = take(t.node.size()); slot = take(t.slot.size()); entry = take(t.entry.size());
+        weight = take(t.weight.size()); cls = take(t.cls.size());
+        words = take.words;
+    }
+};
+
+struct WordsOut {             // the caller's host outputs; any may be null
+    float* score;
+    int32_t *count, *words, *starts, *labels, *lengths;
+    float* text_nll;
+};
+
+struct WordsHost {
+    const hctr_lex* lex = nullptr;
+    const WordTables* tab = nullptr;      // the context's
+    int B = 0, D = 1, max_words = 1, group = 1;
+    bool lds = true;
+    std::vector<int32_t> up;      // the call's upload: T[B] | zero[B]
+    std::vector<uint8_t> nll_fix; // [B] text_nll: 0 = the kernel's, 1 = NaN (the text exceeds the loss's labels), 2 = +inf
+};
+
+int words_prepare(hctr_ctx* c, const hctr_lex* lex, float word_bonus, int max_words, int B, int W, int C,
+                  const int32_t* input_lengths, WordsHost* h) {
+    if (!lex) return fail(c, HCTR_ERR_ARG, "lex is NULL");
+    if (lex->C != C) return fail(c, HCTR_ERR_ARG, "the lexicon was built for %d classes, the call has %d", lex->C, C);
+    if (max_words < 1 || max_words > std::max(W, 1)) return fail(c, HCTR_ERR_ARG, "max_words=%d outside [1,%d]", max_words, W);
+    if ((int64_t)std::max(B, 1) * std::max(max_words, W) > INT32_MAX)
+        return fail(c, HCTR_ERR_ARG, "B*W=%lld too large", (long long)B * W);
+    if (c->words_tab_serial != lex->serial || memcmp(&c->words_tab_bonus, &word_bonus, 4) != 0) {
+        c->words_tab_serial = 0;
+        std::string msg;
+        if (!word_tables(*lex, word_bonus, &c->words_tab, &msg)) return fail(c, HCTR_ERR_ARG, "%s", msg.c_str());
+        c->words_tab_serial = lex->serial;
+        c->words_tab_bonus = word_bonus;
+    }
+    h->tab = &c->words_tab;
+    TRY(lengths_head(c, B, W, input_lengths, 1, &h->up));
+    h->lex = lex; h->B = B; h->D = h->tab->D(); h->max_words = max_words;
+    h->lds = words_lds(h->tab->nodes());
+    h->group = words_group_lines(h->tab->nodes(), h->D, W, h->lds);
+    h->nll_fix.assign((size_t)B, 0);
+    return HCTR_OK;
+}
+
+// the context's device copy of the call's word tables: uploaded when the context holds another lexicon's or bonus's
+int words_on_device(hctr_ctx* c, const WordsHost& h, float word_bonus) {
+    if (c->words_serial == h.lex->serial && memcmp(&c->words_bonus, &word_bonus, 4) == 0) return HCTR_OK;
+    const WordTables& t = *h.tab;
+    const WordsLayout lay(t);
+    std::vector<int32_t> img(lay.words, 0);
+    std::copy(t.node.begin(), t.node.end(), img.begin() + lay.node);
+    std::copy(t.slot.begin(), t.slot.end(), img.begin() + lay.slot);
+    std::copy(t.entry.begin(), t.entry.end(), img.begin() + lay.entry);
+    memcpy(img.data() + lay.weight, t.weight.data(), t.weight.size() * 4);
+    std::copy(t.cls.begin(), t.cls.end(), img.begin() + lay.cls);
+    c->words_bonus = word_bonus;
+    return tables_on_device(c, &c->words_serial, &c->words_dev, h.lex->serial, img, "word");
+}
+
+struct WordsDev {
+    const int32_t* up = nullptr;
+    int32_t *cls = nullptr, *nd = nullptr, *count = nullptr, *lengths = nullptr, *words = nullptr, *starts = nullptr,
+            *labels = nullptr, *nll_tab = nullptr;
+    float *score = nullptr, *nll = nullptr, *emis = nullptr;
+    WordsRec* rec = nullptr;
+    void* states = nullptr;       // the scratch form's step buffers, 32*nodes bytes a line
+    int g = 1;                    // lines per group of this call's launches
+};
+
+// scratch of a words call that launches nl lines at a time, in groups of g = min(group, nl): the upload, the class
+// tables, the results of all B lines, and per group the tables of the texts' loss, the emissions, the records and the
+// step buffers that are not in LDS
+int words_scratch(hctr_ctx* c, const WordsHost& h, int nl, int W, WordsDev* d) {
+    const size_t B = (size_t)h.B, g = (size_t)std::max(1, std::min(h.group, nl)), nn = (size_t)h.tab->nodes();
+    const size_t up_b = align256(h.up.size() * 4), cls_b = align256(B * h.D * 4), b4 = align256(B * 4),
+                 w_b = align256(B * h.max_words * 4), col_b = align256(B * W * 4), tab_b = align256((3 * g + g * W) * 4),
+                 emis_b = align256(g * W * h.D * 4), rec_b = align256(g * W * 2 * sizeof(WordsRec)),
+                 st_b = h.lds ? 0 : align256(g * 2 * nn * 16);
+    TRY(ctc_reserve(c, up_b + cls_b + 5 * b4 + 2 * w_b + col_b + tab_b + emis_b + rec_b + st_b));
+    char* p = c->ctc_buf;
+    auto take = [&](size_t bytes) { char* r = p; p += bytes; return r; };
+    d->g = (int)g;
+    d->up = (const int32_t*)take(up_b);
+    d->cls = (int32_t*)take(cls_b);
+    d->nd = (int32_t*)take(b4);
+    d->score = (float*)take(b4); d->nll = (float*)take(b4);
+    d->count = (int32_t*)take(b4); d->lengths = (int32_t*)take(b4);
+    d->words = (int32_t*)take(w_b); d->starts = (int32_t*)take(w_b);
+    d->labels = (int32_t*)take(col_b);
+    d->nll_tab = (int32_t*)take(tab_b);
+    d->emis = (float*)take(emis_b);
+    d->rec = (WordsRec*)take(rec_b);
+    d->states = st_b ? (void*)take(st_b) : nullptr;
+    HIP_TRY(c, hipMemcpyAsync(c->ctc_buf, h.up.data(), h.up.size() * 4, hipMemcpyHostToDevice, c->stream));
+    return HCTR_OK;
+}
+
+// the lines [b0, b0 + nb), whose logit rows are r, a group at a time: emissions, recursion, walk
+int words_launch(hctr_ctx* c, WordsHost& h, const WordsDev& d, bool want_nll, const Rows& r, int b0, int nb, int W) {
+    Prof pf(c);
+    const WordsLayout lay(*h.tab);
+    const int32_t* t = c->words_dev;
+    const int nn = h.tab->nodes();
+    PROF_TRY(pf, "lexicon_classes", launch_lexicon_classes(t + lay.cls, h.D, h.B, d.cls, d.nd, c->stream));
+    const CtcLines m{d.up, d.up + h.B, d.up + h.B, d.nd, d.cls, d.up + h.B, h.D};
+    for (int l0 = 0; l0 < nb; l0 += d.g) {
+        const int n = std::min(d.g, nb - l0), gb0 = b0 + l0;
+        TRY(lse_rows(pf, r.from_line(l0), m, gb0, n, W, d.emis));
+        const WordsArgs a{d.emis, d.up, gb0, n, W, h.D, nn, t + lay.node, t + lay.slot, t + lay.entry,
+                          (const float*)(t + lay.weight), d.states, d.rec};
+        PROF_TRY(pf, "words_trie", launch_words_trie(a, c->stream));
+        const WordsTraceArgs ta{d.rec, d.up, gb0, n, W, nn, h.max_words, t + lay.node, t + lay.slot, t + lay.entry,
+                                t + lay.cls, d.score, d.count, d.words, d.starts, d.labels, d.lengths};
+        PROF_TRY(pf, "words_backtrace", launch_words_backtrace(ta, c->stream));
+        if (want_nll)
+            TRY(text_nll_group(c, pf, TextNll{&h.lex->classes, h.D, &h.up, d.labels, d.lengths, d.count, 1, d.nll_tab,
+                                              d.emis, d.nll, &h.nll_fix}, gb0, n, W));
+    }
+    return HCTR_OK;
+}
+
+int words_finish(hctr_ctx* c, const WordsHost& h, const WordsDev& d, const WordsOut& o, int W) {
+    const size_t B = (size_t)h.B;
+    HIP_TRY(c, fetch(c, o.score, d.score, B * 4));
+    HIP_TRY(c, fetch(c, o.count, d.count, B * 4));
+    HIP_TRY(c, fetch(c, o.words, d.words, B * h.max_words * 4));
+    HIP_TRY(c, fetch(c, o.starts, d.starts, B * h.max_words * 4));
+    HIP_TRY(c, fetch(c, o.labels, d.labels, B * W * 4));
+    HIP_TRY(c, fetch(c, o.lengths, d.lengths, B * 4));
+    HIP_TRY(c, fetch(c, o.text_nll, d.nll, B * 4));
+    if (!o.text_nll) return HCTR_OK;
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    text_nll_fix(h.nll_fix, o.text_nll);
+    return HCTR_OK;
+}
+
+// hctr_words*
+int words_call(hctr_ctx* c, const Source& src, const hctr_lex* lex, float word_bonus, int max_words,
+               const int32_t* input_lengths, const WordsOut& o) {
+    const int B = src.B, W = src.W;
+    WordsHost h;
+    TRY(words_prepare(c, lex, word_bonus, max_words, B, W, src.C, input_lengths, &h));
+    if (B == 0) return HCTR_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    TRY(words_on_device(c, h, word_bonus));
+    WordsDev d;
+    return source_passes(
+        c, src,
+        [&](const Pass& p, std::vector<void*>& pool) -> int {
+            if (p.first == 0) TRY(words_scratch(c, h, p.nb, W, &d));
+            Rows r;
+            TRY(pass_rows(c, src, p, pool, &r));
+            return words_launch(c, h, d, o.text_nll != nullptr, r, p.first, p.nb, W);
+        },
+        [&] { return words_finish(c, h, d, o, W); });
+}
+
+// ---------------------------------------------------------------------------------------------
 // pattern-constrained recognition (hctr_pattern*): the device copy of the pattern, the groups of lines that share one
 // block of emissions and backpointers, scratch
 // ---------------------------------------------------------------------------------------------
@@ -2064,40 +2321,6 @@ int pat_scratch(hctr_ctx* c, const PatHost& h, int nl, int W, PatDev* d) {
     return HCTR_OK;
 }
 
-// the loss of the decoded texts of the group's lines [gb0, gb0 + n), over the group's own emissions: the pattern's
-// classes hold every class a decoded text uses, so the loss's tables point into them and ctc_alpha reads what ctc_lse
-// wrote for the pattern - the loss's emissions, bit for bit. The labels must be on the host: drains the stream.
-int pat_text_nll(hctr_ctx* c, Prof& pf, PatHost& h, const PatDev& d, int gb0, int n, int W) {
-    std::vector<int32_t> lab((size_t)n * W), len((size_t)n), end((size_t)n);
-    HIP_TRY(c, hipMemcpyAsync(lab.data(), d.labels + (size_t)gb0 * W, lab.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(len.data(), d.lengths + gb0, len.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(end.data(), d.endst + gb0, end.size() * 4, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const hctr_pat& x = *h.pat;
-    std::vector<int32_t> tab((size_t)3 * n);
-    int max_states = 1;
-    for (int b = 0; b < n; ++b) {
-        const int L = std::min(std::max(len[(size_t)b], 0), W);
-        const bool none = end[(size_t)b] < 0, fits = 2 * (int64_t)L + 1 <= kCtcMaxStates;
-        h.nll_fix[(size_t)gb0 + b] = none ? 2 : fits ? 0 : 1;
-        const bool run = !none && fits;
-        tab[(size_t)b] = run ? h.up[(size_t)gb0 + b] : 0;             // T = 0: the kernel reads nothing of the line
-        tab[(size_t)n + b] = run ? L : 0;
-        tab[(size_t)2 * n + b] = (int32_t)(tab.size() - 3 * (size_t)n);
-        for (int j = 0; j < L && run; ++j) {
-            const int32_t cl = lab[(size_t)b * W + j];
-            tab.push_back(1 + (int32_t)(std::lower_bound(x.classes.begin(), x.classes.end(), cl) - x.classes.begin()));
-        }
-        if (run) max_states = std::max(max_states, 2 * L + 1);
-    }
-    HIP_TRY(c, hipMemcpyAsync(d.nll_tab, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, c->stream));
-    const int32_t* t = d.nll_tab;
-    const CtcLines m{t, t + n, t + 2 * n, t, t, t + 3 * n, h.D};
-    PROF_TRY(pf, "ctc_alpha", launch_ctc_alpha(d.emis, m, 0, n, W, max_states, d.nll + gb0, nullptr, nullptr, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));          // (tab is this function's)
-    return HCTR_OK;
-}
-
 // the lines [b0, b0 + nb), whose logit rows are r, a group at a time: emissions, recursion, walk
 int pat_launch(hctr_ctx* c, PatHost& h, const PatDev& d, bool want_nll, const Rows& r, int b0, int nb, int W) {
     Prof pf(c);
@@ -2127,7 +2350,9 @@ int pat_launch(hctr_ctx* c, PatHost& h, const PatDev& d, bool want_nll, const Ro
         const PatTraceArgs ta{d.emis, d.up, gb0, n, W, h.D, px.S, t + slot, t + label, d.bp, d.endst, d.lpv,
                               d.path, d.labels, d.lengths, d.st, d.en, d.clp};
         PROF_TRY(pf, "pattern_trace", launch_pattern_trace(ta, c->stream));
-        if (want_nll) TRY(pat_text_nll(c, pf, h, d, gb0, n, W));
+        if (want_nll)
+            TRY(text_nll_group(c, pf, TextNll{&px.classes, h.D, &h.up, d.labels, d.lengths, d.endst, 0, d.nll_tab, d.emis,
+                                              d.nll, &h.nll_fix}, gb0, n, W));
     }
     return HCTR_OK;
 }
@@ -2145,10 +2370,7 @@ int pat_finish(hctr_ctx* c, const PatHost& h, const PatDev& d, const PatOut& o, 
     HIP_TRY(c, fetch(c, o.text_nll, d.nll, B * 4));
     if (!o.text_nll) return HCTR_OK;
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    for (size_t b = 0; b < B; ++b) {
-        if (h.nll_fix[b] == 1) o.text_nll[b] = std::numeric_limits<float>::quiet_NaN();
-        if (h.nll_fix[b] == 2) o.text_nll[b] = std::numeric_limits<float>::infinity();
-    }
+    text_nll_fix(h.nll_fix, o.text_nll);
     return HCTR_OK;
 }
 
@@ -2952,6 +3174,7 @@ void hctr_destroy(hctr_ctx* c) {
     if (c->lm_words) (void)hipFree(c->lm_words);
     if (c->lex_dev) (void)hipFree(c->lex_dev);
     if (c->pat_dev) (void)hipFree(c->pat_dev);
+    if (c->words_dev) (void)hipFree(c->words_dev);
     if (c->stamp_buf) (void)hipFree(c->stamp_buf);
     for (hipEvent_t e : c->ev_pool) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
@@ -3853,6 +4076,41 @@ int hctr_lexicon_logits(hctr_ctx* c, const hctr_lex* lex, const float* logits_wb
         TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
         return lex_call(c, logits_source(logits_wbc, on_device, W, B, C), lex, input_lengths, n,
                         LexOut{top_entry, top_logp, top_rank, log_total, count, scores});
+    });
+}
+
+int hctr_lex_word_tables(const hctr_lex* lex, float word_bonus, int32_t* num_nodes, int32_t* num_classes, int32_t* node,
+                         int32_t* slot, int32_t* entry, float* weight, int32_t* classes) {
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!lex) return fail(nullptr, HCTR_ERR_ARG, "lex is NULL");
+        WordTables t;
+        std::string msg;
+        if (!word_tables(*lex, word_bonus, &t, &msg)) return fail(nullptr, HCTR_ERR_ARG, "hctr_lex_word_tables: %s", msg.c_str());
+        auto put = [](auto* dst, const auto& v) { if (dst) std::copy(v.begin(), v.end(), dst); };
+        if (num_nodes) *num_nodes = t.nodes();
+        if (num_classes) *num_classes = t.D();
+        put(node, t.node); put(slot, t.slot); put(entry, t.entry); put(weight, t.weight); put(classes, t.cls);
+        return HCTR_OK;
+    });
+}
+
+int hctr_words(hctr_ctx* c, const hctr_lex* lex, const void* img, int img_dtype, int img_on_device, const int32_t* widths,
+               int B, int W, const int32_t* input_lengths, float word_bonus, int max_words, float* score, int32_t* count,
+               int32_t* words, int32_t* starts, int32_t* labels, int32_t* lengths, float* text_nll) {
+    return guard(c, [&]() -> int {
+        TRY(check_forward_args(c, img, img_dtype, B, W));
+        return words_call(c, image_source(c, img, img_dtype, img_on_device, widths, B, W), lex, word_bonus, max_words,
+                          input_lengths, WordsOut{score, count, words, starts, labels, lengths, text_nll});
+    });
+}
+
+int hctr_words_logits(hctr_ctx* c, const hctr_lex* lex, const float* logits_wbc, int on_device, int W, int B, int C,
+                      const int32_t* input_lengths, float word_bonus, int max_words, float* score, int32_t* count,
+                      int32_t* words, int32_t* starts, int32_t* labels, int32_t* lengths, float* text_nll) {
+    return guard(c, [&]() -> int {
+        TRY(check_logits_args(c, W, B, C, logits_wbc != nullptr));
+        return words_call(c, logits_source(logits_wbc, on_device, W, B, C), lex, word_bonus, max_words, input_lengths,
+                          WordsOut{score, count, words, starts, labels, lengths, text_nll});
     });
 }
 

@@ -6,6 +6,7 @@
 
 #include "lm_flat.h"
 #include "lex_flat.h"
+#include "lex_words.h"
 #include "pat_flat.h"
 
 namespace hctr {
@@ -461,6 +462,37 @@ struct PatSetArgs {
 // (HCTR_PATSET_LDS=0: never)
 bool pattern_set_states_in_lds(int S, int nQ, bool viterbi);
 hipError_t launch_pattern_set(const PatSetArgs& a, bool viterbi, hipStream_t s);
+
+// ---- word-sequence recognition (hctr_words*): token passing over the looped trie (lex_words.h), Viterbi, one workgroup
+// per line over the emissions of launch_ctc_lse; then the walk back over the columns' exit records. ----
+struct WordsRec {             // an exit record: the best way to end a word after a column (16 bytes)
+    float score;              // a(state) + x_v; -inf = none
+    int32_t node;             // the end node v
+    int32_t last;             // the emission slot of the column's label: slot[v], or 0 for the blank state
+    uint32_t origin;          // the winning state's origin: s << 2 | k
+};
+struct WordsArgs {
+    const float* emis;        // [nb][W][D]
+    const int32_t* T;         // [B] columns that count, indexed by b0 + b
+    int b0, nb, W, D, nn;     // nn trie nodes, the root included
+    const int32_t* node;      // [nn] parent | kLexSkip | kLexFirst
+    const int32_t* slot;      // [nn]
+    const int32_t* entry;     // [nn] e_v or -1
+    const float* weight;      // [nn] x_v
+    void* states;             // [nb][2][nn] 16-byte states of the scratch form; null: the step buffers live in LDS
+    WordsRec* rec;            // [nb][W][2]
+};
+constexpr int kWordsLdsNodes = 4096;          // the largest trie whose step buffers fit LDS
+hipError_t launch_words_trie(const WordsArgs& a, hipStream_t s);
+struct WordsTraceArgs {
+    const WordsRec* rec;      // [nb][W][2]
+    const int32_t* T;
+    int b0, nb, W, nn, max_words;
+    const int32_t *node, *slot, *entry, *cls;
+    float* score;             // [B]
+    int32_t *count, *words, *starts, *labels, *lengths;      // [B], [B][max_words] x 2, [B][W], [B]
+};
+hipError_t launch_words_backtrace(const WordsTraceArgs& a, hipStream_t s);
 
 // ---- line preprocessing (preprocess.hip): cv2.resize(..., INTER_AREA) of ragged u8 images to height out_h ----
 struct ResizeLine {

@@ -5795,4 +5795,304 @@ hipError_t launch_pattern_set(const PatSetArgs& a, bool viterbi, hipStream_t s) 
     return a.states ? launch_pattern_set_t<false, false>(a, s) : launch_pattern_set_t<false, true>(a, s);
 }
 
+// -------------------------------------------------------------------------------------------
+// Word-sequence recognition (hctr_words*): the best segmentation of a line into lexicon entries, by token passing over
+// the lexicon's trie with the word ends looped back to the root (include/hctr_hip.h has the definition). Viterbi only:
+//   a'(n_u) = max(a(n_u), a(b_0), pick.score) + lp_t(c_u)            u a child of the root
+//   a'(n_v) = max(a(n_v), a(b_p), [c_p != c_v] a(n_p)) + lp_t(c_v)   deeper nodes
+//   a'(b_v) = max(a(b_v), a(n_v)) + lp_t(0),  a'(b_0) = a(b_0) + lp_t(0)
+// in float32, the earlier-listed source winning ties (a later one must be strictly greater, so a NaN state stays NaN and
+// wins nothing). A state carries its origin (s << 2 | k): the column of the current word's first label and which exit
+// record of column s - 1 it came from (0 = the line's start or b_0). After every column the end nodes' states are
+// reduced to two exit records, R1 the best of (a(n_v) + x_v, last = slot_v) and (a(b_v) + x_v, last = 0) by (score
+// descending, blank first, node ascending), R2 the best whose `last` differs from R1's: a root's child takes R1 unless
+// R1 ended on the child's own label, the CTC rule that equal labels need a blank between them. The pair is a mergeable
+// summary - the pair of a union is found among the parts' four records - so the reduction tree does not matter: a
+// thread folds its nodes, a wave merges by shuffles, the waves' partials meet in LDS and every thread merges them.
+// One workgroup per line, one barrier per column: it publishes the column's states and the waves' partials together.
+// Two storage forms with one body (words_step) and the same bits: NPT > 0 keeps the two step buffers in LDS (16 bytes a
+// state, 32 a node) with a thread's NPT nodes' tables in registers and their emissions of the next PF columns in flight;
+// NPT = 0 keeps them in the call's scratch and a thread walks its nodes tid, tid + 1024, .. per column. No atomics.
+// -------------------------------------------------------------------------------------------
+constexpr int kWordsThreads = 1024, kWordsPF = 4;
+constexpr int32_t kWordsEnd = 1 << 28;                    // in a thread's copy of node[v]: an entry ends on v
+
+struct __attribute__((aligned(16))) WordsSt {
+    float n, b;
+    uint32_t on, ob;
+};
+struct WordsPair {                                        // R1 and R2, field by field (they stay in registers)
+    float s1;
+    int n1, l1;
+    uint32_t o1;
+    float s2;
+    int n2, l2;
+    uint32_t o2;
+};
+
+__device__ __forceinline__ WordsPair words_none() {
+    return WordsPair{-INFINITY, 0x7FFFFFFF, -1, 0u, -INFINITY, 0x7FFFFFFF, -1, 0u};
+}
+
+// (score descending, blank first, node ascending)
+__device__ __forceinline__ bool words_better(float xs, int xn, int xl, float ys, int yn, int yl) {
+    if (xs != ys) return xs > ys;
+    const bool xz = xl == 0, yz = yl == 0;
+    if (xz != yz) return xz;
+    return xn < yn;
+}
+
+// a candidate joins the pair; one at -inf or NaN is none
+__device__ __forceinline__ void words_put(WordsPair& p, float s, int n, int l, uint32_t o) {
+    if (!(s > -INFINITY)) return;
+    if (words_better(s, n, l, p.s1, p.n1, p.l1)) {
+        if (p.l1 != l) {
+            p.s2 = p.s1; p.n2 = p.n1; p.l2 = p.l1; p.o2 = p.o1;
+        }
+        p.s1 = s; p.n1 = n; p.l1 = l; p.o1 = o;
+    } else if (l != p.l1 && words_better(s, n, l, p.s2, p.n2, p.l2)) {
+        p.s2 = s; p.n2 = n; p.l2 = l; p.o2 = o;
+    }
+}
+
+// the states of node v after column t >= 1 from the previous buffer and the records of column t - 1; its exits join fold
+__device__ __forceinline__ WordsSt words_step(int v, int word, int slot, float x, int t, float e, float eb,
+                                              const WordsSt* prev, int nn, const WordsPair& R, WordsPair& fold) {
+    const WordsSt self = prev[v];
+    if (v == 0) return WordsSt{-INFINITY, self.b + eb, 0u, 0u};      // the root: b_0 alone
+    const WordsSt p = prev[min(word & kLexParMask, nn - 1)];
+    float m = self.n;
+    uint32_t om = self.on;
+    if (word & kLexFirst) {
+        if (p.b > m) {
+            m = p.b;
+            om = (uint32_t)t << 2;
+        }
+        const bool one = R.l1 != slot;
+        const float ps = one ? R.s1 : R.s2;
+        if (ps > m) {
+            m = ps;
+            om = (uint32_t)t << 2 | (one ? 1u : 2u);
+        }
+    } else {
+        if (p.b > m) {
+            m = p.b;
+            om = p.ob;
+        }
+        if ((word & kLexSkip) && p.n > m) {
+            m = p.n;
+            om = p.on;
+        }
+    }
+    float mb = self.b;
+    uint32_t ob = self.ob;
+    if (self.n > mb) {
+        mb = self.n;
+        ob = self.on;
+    }
+    const WordsSt o{m + e, mb + eb, om, ob};
+    if (word & kWordsEnd) {
+        words_put(fold, o.n + x, v, slot, o.on);
+        words_put(fold, o.b + x, v, 0, o.ob);
+    }
+    return o;
+}
+
+// column 0
+__device__ __forceinline__ WordsSt words_first(int v, int word, int slot, float x, const float* row, WordsPair& fold) {
+    WordsSt o{-INFINITY, -INFINITY, 0u, 0u};
+    if (v == 0) o.b = row[0];
+    else if (word & kLexFirst) o.n = row[slot];
+    if (word & kWordsEnd) words_put(fold, o.n + x, v, slot, 0u);
+    return o;
+}
+
+// a column's end: the waves' pairs meet in LDS behind the barrier that also publishes the column's states; every thread
+// merges the partials and returns the column's records, thread 0 stores them
+__device__ __forceinline__ WordsPair words_close(int t, WordsPair fold, WordsRec (*part)[kWordsThreads / 64][2],
+                                                 WordsRec* rec) {
+    const int tid = threadIdx.x, nw = blockDim.x >> 6;
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+        const float s1 = __shfl_xor(fold.s1, m, 64), s2 = __shfl_xor(fold.s2, m, 64);
+        const int n1 = __shfl_xor(fold.n1, m, 64), n2 = __shfl_xor(fold.n2, m, 64);
+        const int l1 = __shfl_xor(fold.l1, m, 64), l2 = __shfl_xor(fold.l2, m, 64);
+        const int o1 = __shfl_xor((int)fold.o1, m, 64), o2 = __shfl_xor((int)fold.o2, m, 64);
+        words_put(fold, s1, n1, l1, (uint32_t)o1);
+        words_put(fold, s2, n2, l2, (uint32_t)o2);
+    }
+    if ((tid & 63) == 0) {
+        part[t & 1][tid >> 6][0] = WordsRec{fold.s1, fold.n1, fold.l1, fold.o1};
+        part[t & 1][tid >> 6][1] = WordsRec{fold.s2, fold.n2, fold.l2, fold.o2};
+    }
+    __syncthreads();
+    WordsPair R = words_none();
+    for (int w = 0; w < nw; ++w) {
+        const WordsRec p1 = part[t & 1][w][0], p2 = part[t & 1][w][1];
+        words_put(R, p1.score, p1.node, p1.last, p1.origin);
+        words_put(R, p2.score, p2.node, p2.last, p2.origin);
+    }
+    if (tid == 0) {
+        rec[2 * t] = WordsRec{R.s1, R.n1, R.l1, R.o1};
+        rec[2 * t + 1] = WordsRec{R.s2, R.n2, R.l2, R.o2};
+    }
+    return R;
+}
+
+template <int NPT>
+__global__ __launch_bounds__(kWordsThreads) void words_trie_kernel(const WordsArgs a) {
+    constexpr bool LDS = NPT > 0;
+    constexpr int NR = LDS ? NPT : 1;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ WordsRec part[2][kWordsThreads / 64][2];
+    const int b = blockIdx.x, gb = a.b0 + b, tid = threadIdx.x, nt = blockDim.x, nn = a.nn, D = a.D;
+    const int T = min(max(a.T[gb], 1), a.W);              // (the host admits 1 <= T <= W only)
+    WordsSt* st = LDS ? (WordsSt*)smem : (WordsSt*)a.states + (int64_t)b * 2 * nn;
+    const float* base = a.emis + (int64_t)b * a.W * D;
+    WordsRec* rec = a.rec + (int64_t)b * a.W * 2;
+    WordsPair fold = words_none();
+    if constexpr (LDS) {
+        int word[NR], slot[NR];
+        float x[NR];
+#pragma unroll
+        for (int i = 0; i < NR; ++i) {
+            const int v = tid + i * nt;
+            const bool live = v < nn;
+            word[i] = live ? a.node[v] | (a.entry[v] >= 0 ? kWordsEnd : 0) : 0;
+            slot[i] = live ? a.slot[v] : 0;
+            x[i] = live ? a.weight[v] : 0.f;
+            if (live) st[v] = words_first(v, word[i], slot[i], x[i], base, fold);
+        }
+        float e[kWordsPF][NR], eb[kWordsPF];
+#pragma unroll
+        for (int k = 0; k < kWordsPF; ++k) {
+            const float* r = base + (int64_t)min(1 + k, T - 1) * D;
+            ctc_ring_load(r, slot, e[k]);
+            eb[k] = r[0];
+        }
+        WordsPair R = words_close(0, fold, part, rec);
+        for (int t0 = 1; t0 < T; t0 += kWordsPF) {
+#pragma unroll
+            for (int k = 0; k < kWordsPF; ++k) {
+                const int t = t0 + k;
+                if (t < T) {                               // (block-uniform)
+                    const WordsSt* prev = st + ((t - 1) & 1) * nn;
+                    WordsSt* cur = st + (t & 1) * nn;
+                    fold = words_none();
+#pragma unroll
+                    for (int i = 0; i < NR; ++i) {
+                        const int v = tid + i * nt;
+                        if (v < nn) cur[v] = words_step(v, word[i], slot[i], x[i], t, e[k][i], eb[k], prev, nn, R, fold);
+                    }
+                    R = words_close(t, fold, part, rec);
+                }
+                const float* r = base + (int64_t)min(t + kWordsPF, T - 1) * D;      // refill the slot just used
+                ctc_ring_load(r, slot, e[k]);
+                eb[k] = r[0];
+            }
+        }
+    } else {
+        for (int v = tid; v < nn; v += nt)
+            st[v] = words_first(v, a.node[v] | (a.entry[v] >= 0 ? kWordsEnd : 0), a.slot[v], a.weight[v], base, fold);
+        WordsPair R = words_close(0, fold, part, rec);
+        for (int t = 1; t < T; ++t) {
+            const WordsSt* prev = st + ((t - 1) & 1) * nn;
+            WordsSt* cur = st + (t & 1) * nn;
+            const float* r = base + (int64_t)t * D;
+            const float eb = r[0];
+            fold = words_none();
+            for (int v = tid; v < nn; v += nt) {
+                const int sl = a.slot[v];
+                cur[v] = words_step(v, a.node[v] | (a.entry[v] >= 0 ? kWordsEnd : 0), sl, a.weight[v], t, r[sl], eb, prev, nn,
+                                    R, fold);
+            }
+            R = words_close(t, fold, part, rec);
+        }
+    }
+}
+
+template <int NPT>
+static hipError_t launch_words_trie_t(const WordsArgs& a, int threads, hipStream_t s) {
+    static bool raised[64] = {};
+    const int lds = NPT > 0 ? 2 * a.nn * (int)sizeof(WordsSt) : 0;
+    if (NPT > 0) {
+        hipError_t e = raise_lds_limit((const void*)words_trie_kernel<NPT>, 2 * kWordsLdsNodes * (int)sizeof(WordsSt), raised);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(words_trie_kernel<NPT>, dim3((unsigned)a.nb), dim3(threads), lds, s, a);
+    return hipGetLastError();
+}
+
+// a.states == nullptr: the step buffers in LDS (nn <= kWordsLdsNodes)
+hipError_t launch_words_trie(const WordsArgs& a, hipStream_t s) {
+    if (a.nb <= 0) return hipSuccess;
+    if (a.nn < 2 || a.nn > kWordsMaxNodes || a.D < 2 || a.W < 1 || a.W >= (1 << 30) || !a.rec) return hipErrorInvalidValue;
+    if (a.states) return launch_words_trie_t<0>(a, kWordsThreads, s);
+    if (a.nn > kWordsLdsNodes) return hipErrorInvalidValue;
+    if (a.nn <= kWordsThreads) return launch_words_trie_t<1>(a, (a.nn + 63) / 64 * 64, s);
+    if (a.nn <= 2 * kWordsThreads) return launch_words_trie_t<2>(a, kWordsThreads, s);
+    return launch_words_trie_t<4>(a, kWordsThreads, s);
+}
+
+// One workgroup of 64 per line: all lanes clear the line's outputs, then lane 0 walks the records from R1(T - 1) back to
+// the line's start twice, once to count the words and the labels, once to fill. A record of column s - 1 is followed
+// only when 1 <= s <= the column of the record before it, a node is used only inside [1, nn), and a spelling is at most
+// kLexMaxLen parents long: every index is in range whatever the records hold, and the walk ends within T steps.
+__global__ __launch_bounds__(64) void words_backtrace_kernel(const WordsTraceArgs a) {
+    const int b = blockIdx.x, gb = a.b0 + b, lane = threadIdx.x, W = a.W, nn = a.nn, mw = a.max_words;
+    const int T = min(max(a.T[gb], 1), W);
+    int32_t* words = a.words + (int64_t)gb * mw;
+    int32_t* starts = a.starts + (int64_t)gb * mw;
+    int32_t* labels = a.labels + (int64_t)gb * W;
+    for (int j = lane; j < mw; j += 64) {
+        words[j] = -1;
+        starts[j] = -1;
+    }
+    for (int j = lane; j < W; j += 64) labels[j] = 0;
+    __syncthreads();
+    if (lane != 0) return;
+    const WordsRec* rec = a.rec + (int64_t)b * W * 2;
+    const WordsRec end = rec[2 * (T - 1)];
+    int cnt = 0, L = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        WordsRec r = end;
+        int col = T - 1, i = cnt, pos = min(L, W);
+        for (int it = 0; it < T; ++it) {
+            if (!(r.score > -INFINITY) || r.node < 1 || r.node >= nn) break;
+            const int s = (int)(r.origin >> 2), k = (int)(r.origin & 3u);
+            int len = 0;
+            for (int u = r.node; u > 0 && len < kLexMaxLen; u = min(a.node[u] & kLexParMask, nn - 1)) {
+                if (pass) {
+                    --pos;
+                    if (pos >= 0 && pos < W) labels[pos] = a.cls[a.slot[u]];
+                }
+                ++len;
+            }
+            if (pass) {
+                --i;
+                if (i >= 0 && i < mw) {
+                    words[i] = a.entry[r.node];
+                    starts[i] = s;
+                }
+            } else {
+                ++cnt;
+                L += len;
+            }
+            if (k < 1 || k > 2 || s < 1 || s > col) break;
+            col = s - 1;
+            r = rec[2 * col + (k - 1)];
+        }
+    }
+    a.count[gb] = cnt;
+    a.lengths[gb] = min(L, W);
+    a.score[gb] = cnt > 0 ? end.score : -INFINITY;
+}
+
+hipError_t launch_words_backtrace(const WordsTraceArgs& a, hipStream_t s) {
+    if (a.nb <= 0) return hipSuccess;
+    if (a.nn < 2 || a.nn > kWordsMaxNodes || a.W < 1 || a.max_words < 1) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(words_backtrace_kernel, dim3((unsigned)a.nb), dim3(64), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace hctr

@@ -489,6 +489,106 @@ def lexicon_chunk_classes(lines, W):
     return int(_lib.load().hctr_lexicon_chunk_classes(int(lines), int(W)))
 
 
+WORDS_MAX_NODES = 65536    # HCTR_WORDS_MAX_NODES
+WORDS_LDS_NODES = 4096     # HCTR_WORDS_LDS_NODES
+
+
+def lex_word_tables(lex, word_bonus=0.0):
+    """dict of numpy arrays: what ``hctr_lex_word_tables`` exports for word-sequence recognition - per trie node ``node``
+    (parent | LEX_SKIP | LEX_FIRST), ``slot``, ``entry`` (e_v or -1) and ``weight`` (x_v), and ``classes`` (0, then the
+    distinct labels ascending)."""
+    if not isinstance(lex, Lexicon):
+        raise ValueError("lex must be a ctc.Lexicon")
+    lib = _lib.load()
+    nn, nc = ctypes.c_int32(), ctypes.c_int32()
+    _lib.check(lib.hctr_lex_word_tables(lex._h, float(word_bonus), ctypes.byref(nn), ctypes.byref(nc), None, None, None, None,
+                                        None), None)
+    nn, nc = int(nn.value), int(nc.value)
+    t = {"node": np.zeros(nn, np.int32), "slot": np.zeros(nn, np.int32), "entry": np.zeros(nn, np.int32),
+         "weight": np.zeros(nn, np.float32), "classes": np.zeros(nc, np.int32)}
+    _lib.check(lib.hctr_lex_word_tables(lex._h, float(word_bonus), None, None, _lib.ptr(t["node"]), _lib.ptr(t["slot"]),
+                                        _lib.ptr(t["entry"]), _lib.ptr(t["weight"]), _lib.ptr(t["classes"])), None)
+    return t
+
+
+class WordsResult(object):
+    """Result of word-sequence recognition of B lines of W steps (numpy arrays, on the host; include/hctr_hip.h
+    ``hctr_words``): ``score`` float32 [B], the best path's log-probability plus the weights of its words; ``count`` int32
+    [B], the number of words (it may exceed the returned ones); ``words`` / ``starts`` int32 [B, max_words], the entries
+    in line order and the column at which each begins (-1 in unused places); ``labels`` int32 [B, W] / ``lengths`` int32
+    [B], the concatenated text; ``text_nll`` float32 [B], the CTC loss of that text. Where no sequence of entries fits the
+    line, score is -inf, count 0, lengths 0, text_nll +inf."""
+
+    def __init__(self, score, count, words, starts, labels, lengths, text_nll, input_lengths=None):
+        self.score, self.count, self.words, self.starts = score, count, words, starts
+        self.labels, self.lengths, self.text_nll = labels, lengths, text_nll
+        self.input_lengths = input_lengths
+
+    def __len__(self):
+        return len(self.score)
+
+    def label_lists(self):
+        return [self.labels[b, :int(self.lengths[b])].copy() for b in range(len(self))]
+
+    def texts(self, codec):
+        """the concatenated text of every line ('' where nothing fits)"""
+        return codec.labels_to_text([l.tolist() for l in self.label_lists()])
+
+    def posterior(self):
+        """float64 [B]: exp(-text_nll), the probability of the concatenated text given the line (0 where nothing fits)"""
+        with np.errstate(invalid="ignore", over="ignore"):
+            p = np.exp(-np.asarray(self.text_nll, np.float64))
+        return np.where(self.count > 0, p, 0.0)
+
+    def lines(self, lex):
+        """yields per line the list of (entry_index, entry, start, end) of its returned words: the entry as the lexicon
+        was given it and its column span [start, end) - up to the next word's start, or the line's length for the line's
+        last word; None for the end of the last returned word when ``count`` exceeds ``max_words``"""
+        for b in range(len(self)):
+            n = min(int(self.count[b]), self.words.shape[1])
+            T = int(self.input_lengths[b]) if self.input_lengths is not None else int(self.labels.shape[1])
+            out = []
+            for j in range(n):
+                end = int(self.starts[b, j + 1]) if j + 1 < n else T if n == int(self.count[b]) else None
+                out.append((int(self.words[b, j]), lex.entry(int(self.words[b, j])), int(self.starts[b, j]), end))
+            yield out
+
+
+def _words_outputs(lex, B, W, max_words):
+    if not isinstance(lex, Lexicon):
+        raise ValueError("lex must be a ctc.Lexicon")
+    mw = W if max_words is None else int(max_words)
+    if B and W and (mw < 1 or mw > W):
+        raise ValueError("max_words must be in 1..%d, got %d" % (W, mw))
+    mw = max(mw, 1)
+    i, f = np.int32, np.float32
+    return mw, (np.full(B, -np.inf, f), np.zeros(B, i), np.full((B, mw), -1, i), np.full((B, mw), -1, i),
+                np.zeros((B, W), i), np.zeros(B, i), np.full(B, np.inf, f))
+
+
+def words_logits(ctx, logits, on_dev, lex, word_bonus=0.0, max_words=None, input_lengths=None):
+    """WordsResult of caller logits / log-probs in WBC layout (hctr_words_logits)"""
+    if len(logits.shape) != 3:
+        raise ValueError("logits must be [W,B,C]")
+    W, B, C = (int(v) for v in logits.shape)
+    il = normalize_input_lengths(input_lengths, B)
+    mw, out = _words_outputs(lex, B, W, max_words)
+    if B and W:
+        _lib.check(_lib.load().hctr_words_logits(ctx, lex._h, _lib.ptr(logits), on_dev, W, B, C, _lib.ptr(il),
+                                                 float(word_bonus), mw, *[_lib.ptr(a) for a in out]), ctx)
+    return WordsResult(*out, input_lengths=il if il is not None else np.full(B, W, np.int32))
+
+
+def words_images(ctx, x, dt, on_dev, widths, B, W, lex, word_bonus=0.0, max_words=None, input_lengths=None):
+    """WordsResult of line images (hctr_words); x, dt, on_dev, widths as hctr_model._img_args / _widths give them."""
+    il = normalize_input_lengths(input_lengths, B)
+    mw, out = _words_outputs(lex, B, W, max_words)
+    if B:
+        _lib.check(_lib.load().hctr_words(ctx, lex._h, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, _lib.ptr(il),
+                                          float(word_bonus), mw, *[_lib.ptr(a) for a in out]), ctx)
+    return WordsResult(*out, input_lengths=il if il is not None else np.full(B, W, np.int32))
+
+
 PAT_MAX_STATES = 8192      # HCTR_PAT_MAX_STATES
 PAT_MAX_EDGES = 262144     # HCTR_PAT_MAX_EDGES
 
@@ -1764,6 +1864,31 @@ class LexiconRecognizer(_EngineBound):
             log_probs = log_probs.detach()
         logits, on_dev = ctc_codec._as_logits(log_probs)
         return lexicon_logits(self._context(), logits, on_dev, lex, n, input_lengths, scores)
+
+    __call__ = forward
+
+
+class WordRecognizer(_EngineBound):
+    """Word-sequence recognition on the engine: ``WordRecognizer().cuda(0)(log_probs_or_logits, lex, word_bonus=0.0,
+    max_words=None, input_lengths=None)`` with ``[T, B, C]`` input (numpy array or torch tensor, a CUDA tensor is read in
+    place) and ``lex`` a ``Lexicon`` returns the ``WordsResult``: per line the best segmentation into entries with the
+    column at which each word begins, the concatenated text and its loss. Only blank=0 is supported.
+    Masked logits (-inf beside a finite logit in the row) mean probability 0; a line they leave no sequence of entries,
+    and a line with a non-finite row (a NaN, a +inf, nothing but -inf) in its input length, get ``count`` 0, ``score``
+    -inf, ``text_nll`` +inf. The other lines are untouched (include/hctr_hip.h, "masked and non-finite logits")."""
+
+    def __init__(self, blank=0):
+        if blank != 0:
+            raise NotImplementedError("the engine's CTC kernels use blank = 0 (the reference's codec)")
+        _EngineBound.__init__(self)
+        self.blank = blank
+
+    def forward(self, log_probs, lex, word_bonus=0.0, max_words=None, input_lengths=None):
+        from .codec import ctc_codec
+        if _is_torch(log_probs):
+            log_probs = log_probs.detach()
+        logits, on_dev = ctc_codec._as_logits(log_probs)
+        return words_logits(self._context(), logits, on_dev, lex, word_bonus, max_words, input_lengths)
 
     __call__ = forward
 

@@ -313,6 +313,18 @@ class hctr_model(object):
         x, dt, on_dev, B, W = self._img_args(input)
         return ctc.pattern_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, pat, input_lengths, full)
 
+    def words(self, input, lex, word_bonus=0.0, max_words=None, widths=None, input_lengths=None):
+        """Word-sequence recognition of line images, the logits never leaving the device: the line is a sequence of
+        entries of ``lex`` (a ``ctc.Lexicon``) - which, and where. Returns a ``ctc.WordsResult`` (numpy arrays): ``score``
+        [B], the best path's log-probability plus each word's log prior and ``word_bonus``; ``count`` [B]; ``words`` /
+        ``starts`` [B, max_words] (None = W); ``labels`` / ``lengths``, the concatenated text; ``text_nll``;
+        ``lines(lex)``, ``texts(codec)``, ``posterior()``. ``input_lengths`` None = W for every line. In "auto" precision
+        every line is scored in f16x3 (include/hctr_hip.h ``hctr_words``)."""
+        from . import ctc
+        ctx = self._require_ctx()
+        x, dt, on_dev, B, W = self._img_args(input)
+        return ctc.words_images(ctx, x, dt, on_dev, self._widths(widths, B), B, W, lex, word_bonus, max_words, input_lengths)
+
     def recognize(self, input, widths=None):
         """Forward + greedy decode with what an OCR interface reports beside the text, the logits never leaving the
         device: per character its pixel-column span, confidence and likeliest substitution, per line the greedy path's

@@ -423,6 +423,69 @@ int hctr_lexicon_logits(hctr_ctx* ctx, const hctr_lex* lex, const float* logits_
                         double* log_total, int32_t* count, float* scores);
 int hctr_lexicon_chunk_classes(int lines, int W);
 
+/* ---- word-sequence recognition on the device: the best segmentation of a line into lexicon entries ----------------
+ * The line is a sequence of words from a closed vocabulary - which words, and where? Token passing over the lexicon's
+ * trie with every word end looped back to the root, Viterbi (max) only: a sum over the looped trie would count a text
+ * once per segmentation, the best path and its best segmentation are defined for any lexicon.
+ * Inputs: a hctr_lex as hctr_lex_build makes it (only the global trie is used: parent, label, entry_node, the priors;
+ * the partition into units plays no part); word_bonus, float32, finite: the word insertion bonus or penalty;
+ * input_lengths as everywhere (T in [1, W], NULL = W).
+ * Emissions: lp_t(c) = float32((double)z_t[c] - lse_t), the loss's, over the lexicon's distinct classes plus the blank.
+ * Node weight: for a node v on which at least one entry ends, e_v is the entry with the largest log_prior among those
+ * ending on v (ties to the lower index; no other can ever win), x_v = float32((double)log_prior[e_v] + (double)word_bonus).
+ * States: b_0 (leading blanks, no word begun) and n_v, b_v for every non-root node as for hctr_lexicon. Each carries a
+ * float32 score a and an origin (s, k): s the column at which the current word's first label was first emitted, k where
+ * the word came from - 0 the line's start or b_0, 1 or 2 which exit record of column s - 1.
+ * Exit records of column t, from the states after it: the candidates are (a(n_v) + x_v, last = c_v) and (a(b_v) + x_v,
+ * last = 0) of every end node v, those at -inf left out; total order: score descending, then last == 0 first, then node
+ * ascending. R1(t) is the best candidate, R2(t) the best whose last differs from R1(t).last. Each keeps score, node, last
+ * and the winning state's origin. The pair is a mergeable summary: any reduction tree gives the same records.
+ * Recursion, all float32, max then one add, the earlier-listed source winning equal scores:
+ *   t = 0:  a(b_0) = lp_0(0); a(n_u) = lp_0(c_u), origin (0, 0), for the root's children u; -inf elsewhere
+ *   root's children u:  pick = R1(t-1) if R1(t-1).last != c_u, else R2(t-1)
+ *                       a'(n_u) = max(a(n_u), a(b_0), pick.score) + lp_t(c_u); the origin is kept from n_u, or becomes
+ *                       (t, 0) from b_0, (t, 1|2) from the record
+ *   deeper v, parent p: a'(n_v) = max(a(n_v), a(b_p), [c_p != c_v] a(n_p)) + lp_t(c_v), the origin copied from the winner
+ *   a'(b_v) = max(a(b_v), a(n_v)) + lp_t(0);  a'(b_0) = a(b_0) + lp_t(0)
+ * "pick skips a record whose last label equals c_u" is the CTC rule that two equal labels need a blank between them,
+ * applied across the word boundary.
+ * Result: score[b] = R1(T-1).score, -inf if there is no candidate. The words come from walking origins back from
+ * R1(T-1): word e_v, origin (s, k) -> record k of column s - 1, until k = 0; word_start = s of each word. A word's span
+ * is [its start, the next word's start), [start, T) for the last: inter-word blanks belong to the preceding word, leading
+ * blanks to none. Outputs, host pointers, any may be NULL: score float32 [B]; count int32 [B], the true number of words
+ * even beyond max_words; words, starts int32 [B][max_words], the first min(count, max_words) words in line order, unused
+ * places -1; labels [B][W] / lengths [B], the concatenated text (unused places 0); text_nll float32 [B], the CTC loss of
+ * that text on the same emissions by the loss's kernels as hctr_pattern does for its reading (NaN for a text beyond the
+ * loss's labels), so exp(-text_nll) is the text's posterior.
+ * Masked and non-finite logits as stated above: a -inf beside a finite logit is probability 0; a line with a non-finite
+ * row inside its length returns count 0, score -inf, text_nll +inf (a NaN state wins no comparison and is no candidate),
+ * other lines are untouched, and no index is derived from a logit.
+ * Limits and errors: 1 <= max_words <= W; the trie has at most HCTR_WORDS_MAX_NODES nodes (the root included), a larger
+ * one is refused with HCTR_ERR_ARG and a message naming both numbers; a NULL lex, a lexicon built for another C, a
+ * non-finite word_bonus, an input length outside [1, W]: HCTR_ERR_ARG with a message. B == 0 is a no-op.
+ * HCTR_ERR_NOMEM leaves the context usable.
+ * hctr_lex_word_tables (host only) exports what the kernel is given, [num_nodes] each: node = parent | HCTR_LEX_SKIP |
+ * HCTR_LEX_FIRST; slot = the place of the node's label in classes; entry = e_v or -1; weight = x_v (0 where no entry
+ * ends); classes [num_classes] = 0 (the blank), then the distinct labels ascending. Any pointer may be NULL.
+ * Two storage forms with the same bits: tries of up to HCTR_WORDS_LDS_NODES nodes keep the two step buffers in LDS,
+ * larger ones (and every one under HCTR_WORDS_LDS=0, read at every call) in the call's scratch. Lines run in groups that
+ * keep emissions, records and step buffers within 4 GiB (HCTR_WORDS_LINES overrides the group's lines).
+ * Launches (hctr_last_profile): lexicon_classes, then per group ctc_lse, words_trie, words_backtrace and, for text_nll,
+ * ctc_alpha. hctr_words runs the forward of img in internal passes exactly as hctr_lexicon does (mode 0 f16, mode 1
+ * f16x3, mode 2 EVERY line in f16x3, hctr_last_guard's figures left as they were); hctr_words_logits takes caller logits
+ * or log-probs in WBC layout, host or device pointer, and needs no weights. */
+#define HCTR_WORDS_MAX_NODES 65536
+#define HCTR_WORDS_LDS_NODES 4096
+int hctr_lex_word_tables(const hctr_lex* lex, float word_bonus, int32_t* num_nodes, int32_t* num_classes, int32_t* node,
+                         int32_t* slot, int32_t* entry, float* weight, int32_t* classes);
+int hctr_words(hctr_ctx* ctx, const hctr_lex* lex, const void* img, int img_dtype, int img_on_device,
+               const int32_t* widths, int B, int W, const int32_t* input_lengths, float word_bonus, int max_words,
+               float* score, int32_t* count, int32_t* words, int32_t* starts, int32_t* labels, int32_t* lengths,
+               float* text_nll);
+int hctr_words_logits(hctr_ctx* ctx, const hctr_lex* lex, const float* logits_wbc, int on_device, int W, int B, int C,
+                      const int32_t* input_lengths, float word_bonus, int max_words, float* score, int32_t* count,
+                      int32_t* words, int32_t* starts, int32_t* labels, int32_t* lengths, float* text_nll);
+
 /* ---- pattern-constrained recognition on the device: CTC over a deterministic finite automaton ----------------------
  * Reading a field whose admissible texts form an open set with a known shape (a date, an identity number, a phone
  * number, an amount, a plate): the probability that the line's text matches the pattern - an exact sum over all CTC

@@ -47,9 +47,11 @@ def build_argparser():
     a.add_argument("--gpu", type=int, default=0)
     a.add_argument("-bm", "--benchmark-mode", dest="benchmark_mode", action="store_true")
     a.add_argument("-dm", "--decode-method", dest="decode_method", type=str, default="beam-search",
-                   choices=["greedy-search", "beam-search", "lexicon", "pattern"])
+                   choices=["greedy-search", "beam-search", "lexicon", "pattern", "words"])
     a.add_argument("--lexicon", dest="lexicon", type=str, default="",
-                   help="-dm lexicon: a text file with one admissible text per line")
+                   help="-dm lexicon / -dm words: a text file with one admissible text (one word) per line")
+    a.add_argument("--word-bonus", dest="word_bonus", type=float, default=0.0,
+                   help="-dm words: added to the score per word (negative: a penalty)")
     a.add_argument("--pattern", dest="pattern", type=str, default="",
                    help="-dm pattern: a regular expression the whole line must match, e.g. '\\d{18}'")
     a.add_argument("-ss", "--skip-search", dest="skip_search", action="store_true")
@@ -194,7 +196,8 @@ def build(args):
 
 
 def load_lexicon(path, codec):
-    """-dm lexicon --lexicon FILE: the closed list of admissible texts, one per line (empty lines are skipped)"""
+    """-dm lexicon / -dm words --lexicon FILE: the closed list of admissible texts, one per line (empty lines are
+    skipped)"""
     import hctr_amd
     if not path or not os.path.isfile(path):
         raise FileNotFoundError("-dm lexicon needs --lexicon FILE with one entry per line")
@@ -211,7 +214,10 @@ def load_pattern(expr, codec):
     return hctr_amd.Pattern.compile(expr, codec)
 
 
-def recognise(model, codec, imgs, widths, lexicon=None, pattern=None):
+def recognise(model, codec, imgs, widths, lexicon=None, pattern=None, word_bonus=None):
+    if word_bonus is not None:          # per image: the words of the best segmentation into entries, separated by /
+        res = model.words(imgs, lexicon, word_bonus, widths=widths)
+        return ["/".join(w[1] for w in line) for line in res.lines(lexicon)]
     if pattern is not None:             # per image: the best matching text, p(the line matches), p(that text | it matches)
         res = model.pattern(imgs, pattern, widths=widths)
         return [(t, float(np.exp(np.float64(lp))), float(p)) for t, lp, p in zip(res.texts(codec), res.logp, res.posterior())]
@@ -233,7 +239,8 @@ def test(args):
         return benchmark(model, codec, args)
     import hctr_amd
     pp = hctr_amd.preprocess
-    lexicon = load_lexicon(args.lexicon, codec) if args.decode_method == "lexicon" else None
+    lexicon = load_lexicon(args.lexicon, codec) if args.decode_method in ("lexicon", "words") else None
+    word_bonus = args.word_bonus if args.decode_method == "words" else None
     pattern = load_pattern(args.pattern, codec) if args.decode_method == "pattern" else None
     paths = list_inputs(args.input)
     batches = [paths[i * args.batch_size:(i + 1) * args.batch_size] for i in range(len(paths) // args.batch_size)]
@@ -241,7 +248,7 @@ def test(args):
         print("batch {} is being processed...".format(i))
         imgs, widths = pp.resize_lines(model, arrs, model.img_height, "test", "rgb", None, device_out=True)
         t0 = time.time()
-        result = recognise(model, codec, imgs, widths, lexicon, pattern)
+        result = recognise(model, codec, imgs, widths, lexicon, pattern, word_bonus)
         dt = time.time() - t0
         print("max_width: {}, throughput: {} ms/img".format(int(widths.max()), dt / args.batch_size * 1000))
         print("predicted results: {}".format(result))

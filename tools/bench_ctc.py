@@ -95,6 +95,15 @@ times lexicon recognition on the same caller logits (hctr_lexicon_logits, the 5 
 range, and the cost per (line, entry) next to the loss's per (line, target). --layers adds the device time of the call's
 launches, summed per name over the chunks of units (lexicon_classes, ctc_lse, lexicon_trie; lexicon_rank).
 
+    python tools/bench_ctc.py --words [--entries 1000] [--layers] ...
+
+times word-sequence recognition (hctr_words_logits, every output fetched) against lexicon recognition
+(hctr_lexicon_logits, the 5 best) on the same lexicon of --entries synthetic entries (as --lexicon's), the same caller
+logits and in the same process, alternately after warm-up calls of each, medians with range; --entries 1000 gives a trie
+of about 3 900 nodes (the LDS form), 10 000 one of about 34 000 (the scratch form). --layers adds the device time of each
+call's launches (lexicon_classes, ctc_lse, words_trie, words_backtrace, ctc_alpha against lexicon_trie, lexicon_rank) and
+the recursions' time per column.
+
     python tools/bench_ctc.py --pattern EXPR [--layers] ...
 
 times pattern-constrained recognition on the same caller logits (hctr_pattern_logits) for the regular expression EXPR,
@@ -137,6 +146,7 @@ def main():
     ap.add_argument("--spot", action="store_true")
     ap.add_argument("--queries", type=int, default=16)
     ap.add_argument("--lexicon", action="store_true")
+    ap.add_argument("--words", action="store_true")
     ap.add_argument("--entries", type=int, default=10000)
     ap.add_argument("--unit-nodes", type=int, default=0, help="--lexicon: trie nodes per workgroup (0 = the default)")
     ap.add_argument("--pattern", type=str, default="", help="a regular expression: time hctr_pattern_logits")
@@ -169,6 +179,9 @@ def main():
         return
     if args.spot:
         print(json.dumps(spot(args, hctr_amd, m, imgs, labels, targets, tl)))
+        return
+    if args.words:
+        print(json.dumps(words(args, hctr_amd, m, imgs, labels)))
         return
     if args.lexicon:
         print(json.dumps(lexicon(args, hctr_amd, m, imgs, labels, targets, tl)))
@@ -491,6 +504,61 @@ def lexicon(args, hctr_amd, m, imgs, labels, targets, tl):
         m.set_profiling(False)
         rec["loss_only_layers_ms"] = {k: round(v, 4) for k, v in fprof.items()}
         rec["lexicon_layers_ms"] = {k: round(v, 4) for k, v in lprof.items()}
+    return rec
+
+
+def words(args, hctr_amd, m, imgs, labels):
+    import torch
+    rc = hctr_amd.WordRecognizer().attach(m)
+    mod = sys.modules[type(rc).__module__]
+    ctx = rc._context()
+    logits = m(imgs)                                             # device tensor [W, lines, C]
+    W, B, C = (int(v) for v in logits.shape)
+    lex = mod.Lexicon(lexicon_entries(labels, C, args.entries), num_classes=C)
+
+    def timed(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    last = {}
+
+    def lexicon_all():
+        last["lexicon"] = mod.lexicon_logits(ctx, logits, 1, lex, 5, None, False)
+
+    def words_all():
+        last["words"] = mod.words_logits(ctx, logits, 1, lex, 0.0, None, None)
+
+    fns = (("lexicon", lexicon_all), ("words", words_all))
+    for _ in range(args.warmup):
+        for _, fn in fns:
+            fn()
+    ms = {k: [] for k, _ in fns}
+    for _ in range(args.steps):
+        for k, fn in fns:
+            ms[k].append(1e3 * timed(fn))
+    rec = {"mode": "words", "lines": B, "width": W, "classes": C, "precision": args.precision,
+           "form": "LDS" if lex.info()["nodes"] <= mod.WORDS_LDS_NODES and os.environ.get("HCTR_WORDS_LDS", "1") != "0"
+           else "scratch"}
+    rec.update(lex.info())
+    for k, v in ms.items():
+        rec[k + "_ms"] = [round(x, 3) for x in v]
+        rec[k + "_ms_median"] = round(float(np.median(v)), 3)
+    rec["lines_with_words"] = int((last["words"].count > 0).sum())
+    rec["mean_words"] = round(float(last["words"].count.mean()), 1)
+    if args.layers:
+        m.set_profiling(True)
+        lexicon_all()
+        lprof = dict(m.last_profile())
+        words_all()
+        wprof = dict(m.last_profile())
+        m.set_profiling(False)
+        rec["lexicon_layers_ms"] = {k: round(v, 4) for k, v in lprof.items()}
+        rec["words_layers_ms"] = {k: round(v, 4) for k, v in wprof.items()}
+        rec["lexicon_trie_us_per_step"] = round(1e3 * lprof.get("lexicon_trie", 0.0) / W, 3)
+        rec["words_trie_us_per_step"] = round(1e3 * wprof.get("words_trie", 0.0) / W, 3)
     return rec
 
 
