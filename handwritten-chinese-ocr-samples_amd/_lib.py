@@ -193,6 +193,9 @@ SIGNATURES = [
     # pattern recognition: arcs_src, arcs_label, arcs_dst, num_arcs, finals, num_finals, num_states, C, out
     ("hctr_pat_build", _I, [_VP, _VP, _VP, _I, _VP, _I, _I, _I, ctypes.POINTER(_VP)]),
     ("hctr_pat_build_sets", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _I, _I, _I, ctypes.POINTER(_VP)]),
+    ("hctr_pat_build_weighted", _I, [_VP, _VP, _VP, _VP, _I, _VP, _VP, _I, _I, _I, ctypes.POINTER(_VP)]),
+    ("hctr_pat_weights", _I, [_VP, _VP, _VP, _VP]),
+    ("hctr_pat_text_weight", _I, [_VP, _VP, _I, ctypes.POINTER(ctypes.c_double)]),
     ("hctr_pat_kind", _I, [_VP]),
     ("hctr_pat_free", None, [_VP]),
     ("hctr_pat_info", _I, [_VP] * 6),
@@ -201,6 +204,7 @@ SIGNATURES = [
     ("hctr_pattern", _I, [_VP, _VP, _VP, _I, _I, _VP, _I, _I, _VP] + [_VP] * 9),
     ("hctr_pattern_logits", _I, [_VP, _VP, _VP, _I, _I, _I, _I, _VP] + [_VP] * 9),
     ("hctr_pattern_group_lines", _I, [_I, _I, _I]),
+    ("hctr_pattern_instance", _I, [_I, _I, _I, _I]),
     ("hctr_recognize", _I, [_VP, _VP, _I, _I, _VP, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_recognize_logits", _I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("hctr_edit_distance", _I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP, _VP, _VP, _VP]),

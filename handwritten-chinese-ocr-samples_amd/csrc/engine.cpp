@@ -2196,14 +2196,16 @@ int pat_group_lines(int S, int D, int W) {
     return (int)std::min<int64_t>(1 << 20, std::max<int64_t>(1, kPatGroupBytes / per));
 }
 
-// the words of the device block: slot | label | in_ptr | accept | start | cls (0, then the classes) | in_src (uint16)
+// the words of the device block: slot | label | in_ptr | accept | start | cls (0, then the classes) | in_src (uint16),
+// and for a weighted pattern (kind 2) | in_w | accept_w | start_w (float)
 struct PatLayout {
-    size_t slot, label, in_ptr, accept, start, cls, in_src, words;
+    size_t slot, label, in_ptr, accept, start, cls, in_src, in_w, accept_w, start_w, words;
     explicit PatLayout(const hctr_pat& x) {
         WordTaker take;
         slot = take(x.slot.size()); label = take(x.label.size()); in_ptr = take(x.in_ptr.size());
         accept = take(x.accept.size()); start = take(x.start.size()); cls = take(x.classes.size() + 1);
         in_src = take((x.in_src.size() + 1) / 2);
+        in_w = take(x.in_w.size()); accept_w = take(x.accept_w.size()); start_w = take(x.start_w.size());
         words = take.words;
     }
 };
@@ -2231,7 +2233,7 @@ bool pat_set_lds(const hctr_pat& x, bool vit) {
 // the context's device copy of the call's pattern: uploaded when the context holds another one (or none)
 int pat_on_device(hctr_ctx* c, const hctr_pat* x) {
     if (c->pat_serial == x->serial) return HCTR_OK;
-    if (x->kind) {
+    if (x->kind == 1) {
         const PatSetLayout lay(*x);
         std::vector<int32_t> img(lay.words, 0);
         std::copy(x->slot.begin(), x->slot.end(), img.begin() + lay.slot);
@@ -2252,6 +2254,11 @@ int pat_on_device(hctr_ctx* c, const hctr_pat* x) {
     std::copy(x->start.begin(), x->start.end(), img.begin() + lay.start);
     std::copy(x->classes.begin(), x->classes.end(), img.begin() + lay.cls + 1);
     memcpy(img.data() + lay.in_src, x->in_src.data(), x->in_src.size() * 2);
+    if (x->kind == 2) {
+        memcpy(img.data() + lay.in_w, x->in_w.data(), x->in_w.size() * 4);
+        memcpy(img.data() + lay.accept_w, x->accept_w.data(), x->accept_w.size() * 4);
+        memcpy(img.data() + lay.start_w, x->start_w.data(), x->start_w.size() * 4);
+    }
     return tables_on_device(c, &c->pat_serial, &c->pat_dev, x->serial, img, "pattern");
 }
 
@@ -2300,7 +2307,7 @@ int pat_scratch(hctr_ctx* c, const PatHost& h, int nl, int W, PatDev* d) {
                  col_b = h.vit ? align256(B * W * 4) : 0, lpv_b = h.vit ? align256(g * W * 4) : 0,
                  tab_b = h.vit ? align256((3 * g + g * W) * 4) : 0, emis_b = align256(g * W * h.D * 4),
                  bp_b = h.vit ? align256(g * W * S * 2) : 0,
-                 st_b = h.pat->kind && !pat_set_lds(*h.pat, h.vit) ? align256(g * S * 16) : 0;
+                 st_b = h.pat->kind == 1 && !pat_set_lds(*h.pat, h.vit) ? align256(g * S * 16) : 0;
     TRY(ctc_reserve(c, up_b + cls_b + 6 * b4 + 5 * col_b + lpv_b + tab_b + emis_b + bp_b + st_b));
     char* p = c->ctc_buf;
     auto take = [&](size_t bytes) { char* r = p; p += bytes; return r; };
@@ -2328,14 +2335,14 @@ int pat_launch(hctr_ctx* c, PatHost& h, const PatDev& d, bool want_nll, const Ro
     const PatLayout lay(px);
     const PatSetLayout slay(px);
     const int32_t* t = c->pat_dev;
-    const size_t cls = px.kind ? slay.cls : lay.cls, slot = px.kind ? slay.slot : lay.slot,
-                 label = px.kind ? slay.label : lay.label;
+    const bool sets = px.kind == 1;
+    const size_t cls = sets ? slay.cls : lay.cls, slot = sets ? slay.slot : lay.slot, label = sets ? slay.label : lay.label;
     PROF_TRY(pf, "pattern_classes", launch_lexicon_classes(t + cls, h.D, h.B, d.cls, d.nd, c->stream));
     const CtcLines m{d.up, d.up + h.B, d.up + h.B, d.nd, d.cls, d.up + h.B, h.D};
     for (int l0 = 0; l0 < nb; l0 += d.g) {
         const int n = std::min(d.g, nb - l0), gb0 = b0 + l0;
         TRY(lse_rows(pf, r.from_line(l0), m, gb0, n, W, d.emis));
-        if (px.kind) {
+        if (sets) {
             const PatSetArgs a{d.emis, d.up, gb0, n, W, h.D, px.S, px.nQ, (const uint32_t*)(t + slay.meta), t + slay.blk_ptr,
                                (const uint32_t*)(t + slay.in_arc), t + slay.finals, (int)px.finals.size(), d.states, d.bp,
                                d.logp, d.best, d.endst};
@@ -2344,7 +2351,13 @@ int pat_launch(hctr_ctx* c, PatHost& h, const PatDev& d, bool want_nll, const Ro
             const PatArgs a{d.emis, d.up, gb0, n, W, h.D, px.S, px.edges(), t + lay.slot, t + lay.label, t + lay.in_ptr,
                             (const uint16_t*)(t + lay.in_src), t + lay.accept, t + lay.start, (int)px.accept.size(),
                             (int)px.start.size(), d.bp, d.logp, d.best, d.endst};
-            PROF_TRY(pf, "pattern", launch_pattern(a, h.vit, c->stream));
+            if (px.kind == 2) {
+                const PatWeights w{(const float*)(t + lay.in_w), (const float*)(t + lay.accept_w),
+                                   (const float*)(t + lay.start_w)};
+                PROF_TRY(pf, "pattern_w", launch_pattern_weighted(a, w, h.vit, c->stream));
+            } else {
+                PROF_TRY(pf, "pattern", launch_pattern(a, h.vit, c->stream));
+            }
         }
         if (!h.vit) continue;
         const PatTraceArgs ta{d.emis, d.up, gb0, n, W, h.D, px.S, t + slot, t + label, d.bp, d.endst, d.lpv,
@@ -4116,7 +4129,13 @@ int hctr_words_logits(hctr_ctx* c, const hctr_lex* lex, const float* logits_wbc,
 
 int hctr_pattern_group_lines(int S, int D, int W) { return pat_group_lines(S, D, W); }
 
-static uint64_t next_pat_serial() {          // one sequence for both kinds: a context tells patterns apart by it
+int hctr_pattern_instance(int S, int E, int viterbi, int weighted) {
+    if (S < 1 || S > kPatMaxStates || E < 0 || E > kPatMaxEdges) return HCTR_ERR_ARG;
+    return pattern_states_per_thread(S) | (pattern_edges_in_lds(S, E, viterbi != 0) ? 16 : 0) |
+           (weighted && pattern_weights_in_lds(S, E, viterbi != 0) ? 32 : 0);
+}
+
+static uint64_t next_pat_serial() {          // one sequence for every kind: a context tells patterns apart by it
     static std::atomic<uint64_t> serial{0};
     return ++serial;
 }
@@ -4132,6 +4151,45 @@ int hctr_pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const int
             return fail(nullptr, HCTR_ERR_ARG, "%s", msg.c_str());
         x->serial = next_pat_serial();
         *out = x.release();
+        return HCTR_OK;
+    });
+}
+
+int hctr_pat_build_weighted(const int32_t* arcs_src, const int32_t* arcs_label, const int32_t* arcs_dst,
+                            const float* arcs_weight, int num_arcs, const int32_t* finals, const float* final_weight,
+                            int num_finals, int num_states, int C, hctr_pat** out) {
+    if (out) *out = nullptr;
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!out) return fail(nullptr, HCTR_ERR_ARG, "hctr_pat_build_weighted: out is NULL");
+        std::unique_ptr<hctr_pat> x(new hctr_pat());
+        std::string msg;
+        if (!pat_build_weighted(arcs_src, arcs_label, arcs_dst, arcs_weight, num_arcs, finals, final_weight, num_finals,
+                                num_states, C, x.get(), &msg))
+            return fail(nullptr, HCTR_ERR_ARG, "%s", msg.c_str());
+        x->serial = next_pat_serial();
+        *out = x.release();
+        return HCTR_OK;
+    });
+}
+
+int hctr_pat_weights(const hctr_pat* pat, float* in_w, float* accept_w, float* start_w) {
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!pat) return fail(nullptr, HCTR_ERR_ARG, "pat is NULL");
+        if (pat->kind != 2)
+            return fail(nullptr, HCTR_ERR_ARG, "hctr_pat_weights: the pattern has no weights (hctr_pat_build_weighted builds one that has)");
+        auto put = [](float* dst, const std::vector<float>& v) { if (dst) std::copy(v.begin(), v.end(), dst); };
+        put(in_w, pat->in_w); put(accept_w, pat->accept_w); put(start_w, pat->start_w);
+        return HCTR_OK;
+    });
+}
+
+int hctr_pat_text_weight(const hctr_pat* pat, const int32_t* labels, int n, double* w) {
+    return guard((hctr_ctx*)nullptr, [&]() -> int {
+        if (!pat) return fail(nullptr, HCTR_ERR_ARG, "pat is NULL");
+        if (pat->kind != 2)
+            return fail(nullptr, HCTR_ERR_ARG, "hctr_pat_text_weight: the pattern has no weights (hctr_pat_build_weighted builds one that has)");
+        if (n < 0 || (n > 0 && !labels) || !w) return fail(nullptr, HCTR_ERR_ARG, "hctr_pat_text_weight: labels / w is NULL or n < 0");
+        *w = pat_text_weight(*pat, labels, n);
         return HCTR_OK;
     });
 }
@@ -4174,7 +4232,7 @@ int hctr_pat_tables(const hctr_pat* pat, int32_t* state_label, int32_t* state_sl
                     int32_t* classes, int32_t* num_accept, int32_t* accept, int32_t* num_start, int32_t* start) {
     return guard((hctr_ctx*)nullptr, [&]() -> int {
         if (!pat) return fail(nullptr, HCTR_ERR_ARG, "pat is NULL");
-        if (pat->kind)
+        if (pat->kind == 1)
             return fail(nullptr, HCTR_ERR_ARG, "hctr_pat_tables: a set pattern (hctr_pat_build_sets) has no edge list");
         auto put = [](auto* dst, const auto& v) { if (dst) std::copy(v.begin(), v.end(), dst); };
         put(state_label, pat->label); put(state_slot, pat->slot); put(in_ptr, pat->in_ptr); put(in_src, pat->in_src);

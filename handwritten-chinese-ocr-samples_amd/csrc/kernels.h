@@ -423,6 +423,20 @@ struct PatArgs {
 hipError_t launch_pattern(const PatArgs& a, bool viterbi, hipStream_t s);
 // whether launch_pattern stages the edge list of a pattern of S states and E edges in LDS
 bool pattern_edges_in_lds(int S, int E, bool viterbi);
+// NPT of the instance launch_pattern / launch_pattern_weighted run for S states: 1, 2, 4 or 8
+int pattern_states_per_thread(int S);
+// a weighted pattern (kind 2): PatArgs plus one float per in-edge, per accepting state and per start state.
+//   x_j = a_{t-1}(src_j) + in_w[j] (one float32 addition), then the log-sum and the max over the x_j as above;
+//   t = 0: lp_0 + start_w; the end: over a_{T-1}(s) + accept_w; logp is not clamped to 0.
+struct PatWeights {
+    const float* in_w = nullptr;      // [E] parallel to in_src
+    const float* accept_w = nullptr;  // [num_accept]
+    const float* start_w = nullptr;   // [num_start]
+};
+hipError_t launch_pattern_weighted(const PatArgs& a, const PatWeights& w, bool viterbi, hipStream_t s);
+// whether launch_pattern_weighted stages the edge weights in LDS beside the edge list (2*S*(8 or 4) + 6*E <= 160 KiB);
+// else the edge list alone where pattern_edges_in_lds says so, and the weights are read through L2
+bool pattern_weights_in_lds(int S, int E, bool viterbi);
 // the walk back from endst over bp, and what follows from the path, all [B][W] indexed by b0 + b: path = the class per
 // column (-1 for t >= T and for a line without an accepted path); labels / lengths = its collapse; span_start, span_end
 // = each character's first column and the column after its run; char_logp = the float32 sum of its emissions in

@@ -5339,22 +5339,34 @@ __device__ __forceinline__ float pat_a(float x) { return x; }
 __device__ __forceinline__ float pat_a(float2 x) { return x.x; }
 __device__ __forceinline__ float pat_v(float) { return -INFINITY; }
 __device__ __forceinline__ float pat_v(float2 x) { return x.y; }
+__device__ __forceinline__ float pat_add(float x, float w) { return x + w; }
+__device__ __forceinline__ float2 pat_add(float2 x, float w) { return make_float2(x.x + w, x.y + w); }
 __device__ __forceinline__ float pat_lse(float m, double sum) { return m == -INFINITY ? -INFINITY : m + __logf((float)sum); }
 
-template <int NPT, bool VIT, bool ELDS>
-__global__ __launch_bounds__(kPatThreads) void pattern_kernel(const PatArgs a) {
+// WGT (kind 2, PatWeights): every in-edge adds its float32 weight to its source's value before the max and the sum, the
+// start list and the accepting list add theirs, and logp is not clamped (it is no probability). WLDS (with ELDS) stages
+// the edge weights in LDS between the states and the edge list. Without WGT, w is not read and the code is kind 0's.
+template <int NPT, bool VIT, bool ELDS, bool WGT, bool WLDS>
+__device__ __forceinline__ void pattern_body(const PatArgs& a, const PatWeights& w) {
     using PS = PatState<VIT>;
     using St = typename PS::type;
     constexpr int PF = NPT >= 8 ? 1 : NPT >= 4 ? 2 : 4;      // ring depth: NPT * PF emissions in flight per thread
+    constexpr int UNR = WGT && !VIT && NPT >= 8 ? 1 : 2;     // edge loops: unrolled by 2 that instance spills (20 bytes)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     St* st = (St*)smem;                                   // [2][S]: the previous and the current step
     const int S = a.S, D = a.D, b = blockIdx.x, gb = a.b0 + b, tid = threadIdx.x, nt = blockDim.x;
     const int T = min(max(a.T[gb], 1), a.W);              // (the host admits 1 <= T <= W only)
     const uint16_t* es = a.in_src;
+    const float* ew = w.in_w;
     if (ELDS) {
-        uint16_t* l = (uint16_t*)(smem + 2 * (size_t)S * sizeof(St));
+        uint16_t* l = (uint16_t*)(smem + 2 * (size_t)S * sizeof(St) + (WGT && WLDS ? 4 * (size_t)a.E : 0));
         for (int j = tid; j < a.E; j += nt) l[j] = a.in_src[j];
         es = l;
+    }
+    if (WGT && WLDS) {
+        float* l = (float*)(smem + 2 * (size_t)S * sizeof(St));
+        for (int j = tid; j < a.E; j += nt) l[j] = w.in_w[j];
+        ew = l;
     }
     const float* base = a.emis + (int64_t)b * a.W * D;
     uint16_t* bpl = VIT ? a.bp + (int64_t)b * a.W * S : nullptr;
@@ -5374,7 +5386,7 @@ __global__ __launch_bounds__(kPatThreads) void pattern_kernel(const PatArgs a) {
     __syncthreads();
     for (int j = tid; j < a.num_start; j += nt) {
         const int s = min(max(a.start[j], 0), S - 1);
-        const float lp = base[a.slot[s]];
+        const float lp = WGT ? base[a.slot[s]] + w.start_w[j] : base[a.slot[s]];
         st[s] = PS::make(lp, lp);
     }
     float e[PF][NPT];
@@ -5395,10 +5407,10 @@ __global__ __launch_bounds__(kPatThreads) void pattern_kernel(const PatArgs a) {
                         const int e0 = (int)(edges[i] & 0x3FFFFu), e1 = e0 + (int)(edges[i] >> 18);
                         float m = -INFINITY, vm = -INFINITY;
                         int arg = s;
-#pragma unroll 2
+#pragma unroll UNR
                         for (int j = e0; j < e1; ++j) {
                             const int src = es[j];
-                            const St p = prev[src];
+                            const St p = WGT ? pat_add(prev[src], ew[j]) : prev[src];
                             m = fmaxf(m, pat_a(p));
                             if (VIT && pat_v(p) > vm) {
                                 vm = pat_v(p);
@@ -5407,8 +5419,9 @@ __global__ __launch_bounds__(kPatThreads) void pattern_kernel(const PatArgs a) {
                         }
                         double sum = 0.0;
                         if (m != -INFINITY) {
-#pragma unroll 2
-                            for (int j = e0; j < e1; ++j) sum += (double)__expf(pat_a(prev[es[j]]) - m);
+#pragma unroll UNR
+                            for (int j = e0; j < e1; ++j)
+                                sum += (double)__expf((WGT ? pat_a(prev[es[j]]) + ew[j] : pat_a(prev[es[j]])) - m);
                         }
                         cur[s] = PS::make(pat_lse(m, sum) + e[k][i], vm + e[k][i]);
                         if (VIT) bpl[(int64_t)t * S + s] = (uint16_t)arg;
@@ -5425,7 +5438,7 @@ __global__ __launch_bounds__(kPatThreads) void pattern_kernel(const PatArgs a) {
         int arg = -1;
         for (int j = 0; j < a.num_accept; ++j) {
             const int s = min(max(a.accept[j], 0), S - 1);
-            const St p = fin[s];
+            const St p = WGT ? pat_add(fin[s], w.accept_w[j]) : fin[s];
             m = fmaxf(m, pat_a(p));
             if (VIT && pat_v(p) > vm) {
                 vm = pat_v(p);
@@ -5434,14 +5447,27 @@ __global__ __launch_bounds__(kPatThreads) void pattern_kernel(const PatArgs a) {
         }
         double sum = 0.0;
         if (m != -INFINITY)
-            for (int j = 0; j < a.num_accept; ++j) sum += (double)__expf(pat_a(fin[min(max(a.accept[j], 0), S - 1)]) - m);
+            for (int j = 0; j < a.num_accept; ++j) {
+                const float x = pat_a(fin[min(max(a.accept[j], 0), S - 1)]);
+                sum += (double)__expf((WGT ? x + w.accept_w[j] : x) - m);
+            }
         const float lp = pat_lse(m, sum);
-        a.logp[gb] = lp > 0.f ? 0.f : lp;                 // a probability near 1 may round above 0; a NaN stays one
+        a.logp[gb] = !WGT && lp > 0.f ? 0.f : lp;         // a probability near 1 may round above 0; a NaN stays one
         if (VIT) {
             a.best[gb] = vm;
             a.endst[gb] = arg;
         }
     }
+}
+
+template <int NPT, bool VIT, bool ELDS>
+__global__ __launch_bounds__(kPatThreads) void pattern_kernel(const PatArgs a) {
+    pattern_body<NPT, VIT, ELDS, false, false>(a, PatWeights{});
+}
+
+template <int NPT, bool VIT, bool ELDS, bool WLDS>
+__global__ __launch_bounds__(kPatThreads) void pattern_w_kernel(const PatArgs a, const PatWeights w) {
+    pattern_body<NPT, VIT, ELDS, true, WLDS>(a, w);
 }
 
 static int pattern_npt(int S) { return S <= kPatThreads ? 1 : S <= 2 * kPatThreads ? 2 : S <= 4 * kPatThreads ? 4 : 8; }
@@ -5479,6 +5505,45 @@ hipError_t launch_pattern(const PatArgs& a, bool viterbi, hipStream_t s) {
         case 2: return launch_pattern_n<2>(a, viterbi, s);
         case 4: return launch_pattern_n<4>(a, viterbi, s);
         default: return launch_pattern_n<8>(a, viterbi, s);
+    }
+}
+
+int pattern_states_per_thread(int S) { return pattern_npt(S); }
+
+bool pattern_weights_in_lds(int S, int E, bool viterbi) {
+    return 2 * (int64_t)S * (viterbi ? 8 : 4) + 6 * (int64_t)E <= kPatLds;
+}
+
+template <int NPT, bool VIT, bool ELDS, bool WLDS>
+static hipError_t launch_pattern_w_t(const PatArgs& a, const PatWeights& w, hipStream_t s) {
+    static bool raised[64] = {};
+    const int threads = ((a.S + NPT - 1) / NPT + 63) / 64 * 64;
+    const int lds = 2 * a.S * (VIT ? 8 : 4) + (ELDS ? 2 * a.E : 0) + (WLDS ? 4 * a.E : 0);
+    if (threads > kPatThreads || lds > kPatLds) return hipErrorInvalidValue;
+    hipError_t e = raise_lds_limit((const void*)pattern_w_kernel<NPT, VIT, ELDS, WLDS>, kPatLds, raised);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((pattern_w_kernel<NPT, VIT, ELDS, WLDS>), dim3((unsigned)a.nb), dim3(threads), lds, s, a, w);
+    return hipGetLastError();
+}
+
+// the weights in LDS (then the edges are too), else the edges alone where they fit, else both through L2
+template <int NPT, bool VIT>
+static hipError_t launch_pattern_w_n(const PatArgs& a, const PatWeights& w, hipStream_t s) {
+    if (pattern_weights_in_lds(a.S, a.E, VIT)) return launch_pattern_w_t<NPT, VIT, true, true>(a, w, s);
+    if (pattern_edges_in_lds(a.S, a.E, VIT)) return launch_pattern_w_t<NPT, VIT, true, false>(a, w, s);
+    return launch_pattern_w_t<NPT, VIT, false, false>(a, w, s);
+}
+
+hipError_t launch_pattern_weighted(const PatArgs& a, const PatWeights& w, bool viterbi, hipStream_t s) {
+    if (a.nb <= 0) return hipSuccess;
+    if (a.S < 1 || a.S > kPatMaxStates || a.E < a.S || a.E > kPatMaxEdges || a.D < 1 || a.W < 1 || a.num_accept < 1 ||
+        a.num_start < 1 || !w.in_w || !w.accept_w || !w.start_w)
+        return hipErrorInvalidValue;
+    switch (pattern_npt(a.S)) {
+        case 1: return viterbi ? launch_pattern_w_n<1, true>(a, w, s) : launch_pattern_w_n<1, false>(a, w, s);
+        case 2: return viterbi ? launch_pattern_w_n<2, true>(a, w, s) : launch_pattern_w_n<2, false>(a, w, s);
+        case 4: return viterbi ? launch_pattern_w_n<4, true>(a, w, s) : launch_pattern_w_n<4, false>(a, w, s);
+        default: return viterbi ? launch_pattern_w_n<8, true>(a, w, s) : launch_pattern_w_n<8, false>(a, w, s);
     }
 }
 

@@ -11,7 +11,12 @@
 // the text read so far leads to q). Arcs (p,c,q) and (p',c,q) share eps_(q,c): their futures are the same.
 // In-edges, sorted by source ascending: beta_q <- beta_q, every eps_(q,.);  eps_(q,c) <- itself, beta_p for every arc
 // (p,c,q), and for each such p every eps_(p,c') with c' != c.
+// Weighted (kind 2, pat_build_weighted): the same automaton and tables with one float per arc and per final state. The
+// weight of arc (p,c,q) sits on every in-edge of eps_(q,c) whose source is beta_p or an eps_(p,.) - every source belongs
+// to one DFA state, so one edge has one weight - and, for p = 0, on eps_(q,c)'s place in the start list; self edges and
+// the in-edges of beta states weigh 0; an accepting state carries the final weight of its DFA state.
 #pragma once
+#include <cmath>
 #include <stdint.h>
 
 #include <algorithm>
@@ -32,7 +37,8 @@ constexpr uint32_t kPatSetNone = 0xFFFFu;        // an in-arc whose source block
 
 struct hctr_pat {
     int C = 0, nQ = 0, S = 0, max_deg = 0;
-    int kind = 0;                                // 0 = explicit edges (pat_build), 1 = label-set arcs (pat_build_sets)
+    int kind = 0;                                // 0 = explicit edges (pat_build), 1 = label-set arcs (pat_build_sets),
+                                                 // 2 = explicit edges with weights (pat_build_weighted)
     uint64_t serial = 0;
     std::vector<int32_t> classes;                // the distinct labels, ascending
     std::vector<int32_t> label, slot;            // [S] label (0 = blank); its place in (0, classes..)
@@ -47,15 +53,27 @@ struct hctr_pat {
     std::vector<uint32_t> in_arc;                // [R] per eps_(q,c) the p with an arc (p, A, q), c in A, ascending:
                                                  // p | (eps_(p,c) or kPatSetNone) << 16
     std::vector<int32_t> finals;                 // the final DFA states, ascending
-    int edges() const { return kind ? (int)in_arc.size() : (int)in_src.size(); }
+    // kind 2 only, beside the tables of kind 0
+    std::vector<float> in_w, accept_w, start_w;  // parallel to in_src, accept, start
+    struct WArc { int32_t src, label, dst; float w; };
+    std::vector<WArc> warcs;                     // the pruned automaton's arcs by (src, label), renumbered
+    std::vector<int32_t> warc_ptr;               // [nQ + 1] the arcs that leave state p are warcs[warc_ptr[p] .. warc_ptr[p + 1])
+    std::vector<uint8_t> is_final;               // [nQ]
+    std::vector<float> final_w;                  // [nQ] (0 where the state is not final)
+    int edges() const { return kind == 1 ? (int)in_arc.size() : (int)in_src.size(); }
 };
 
 namespace hctr {
 
-// builds *out from checked arguments; false with a message for the caller's mistakes (std::bad_alloc passes through)
-inline bool pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const int32_t* arcs_dst, int num_arcs,
-                      const int32_t* finals, int num_finals, int num_states, int C, hctr_pat* out, std::string* msg) {
-    auto bad = [&](const std::string& m) { *msg = "hctr_pat_build: " + m; return false; };
+inline std::string pat_float_str(float v) { return std::isnan(v) ? "nan" : v > 0 ? "+inf" : "-inf"; }      // (of a non-finite v)
+
+// pat_build and pat_build_weighted: *out from checked arguments; false with a message under `who` for the caller's
+// mistakes (std::bad_alloc passes through). weighted = false ignores the weight arguments and leaves kind 0.
+inline bool pat_build_explicit(const char* who, bool weighted, const int32_t* arcs_src, const int32_t* arcs_label,
+                               const int32_t* arcs_dst, const float* arcs_weight, int num_arcs, const int32_t* finals,
+                               const float* final_weight, int num_finals, int num_states, int C, hctr_pat* out,
+                               std::string* msg) {
+    auto bad = [&](const std::string& m) { *msg = std::string(who) + ": " + m; return false; };
     auto str = [](int64_t v) { return std::to_string(v); };
     if (num_arcs < 0 || num_finals < 0) return bad("negative count");
     if (num_arcs > 0 && (!arcs_src || !arcs_label || !arcs_dst)) return bad("arcs_src / arcs_label / arcs_dst is NULL");
@@ -64,15 +82,18 @@ inline bool pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const 
     if (num_states < 1) return bad("need num_states >= 1, got " + str(num_states));
     if (num_states > (1 << 24)) return bad("num_states=" + str(num_states) + " exceeds " + str(1 << 24));
     const size_t nq0 = (size_t)num_states;
-    struct Arc { int32_t src, label, dst; };
+    using Arc = hctr_pat::WArc;
     std::vector<Arc> arcs((size_t)num_arcs);
     for (int i = 0; i < num_arcs; ++i) {
-        const Arc a{arcs_src[i], arcs_label[i], arcs_dst[i]};
+        const Arc a{arcs_src[i], arcs_label[i], arcs_dst[i], weighted && arcs_weight ? arcs_weight[i] : 0.f};
         if (a.src < 0 || a.src >= num_states || a.dst < 0 || a.dst >= num_states)
             return bad("arc " + str(i) + " (" + str(a.src) + " -> " + str(a.dst) + ") names a state outside [0," +
                        str(num_states - 1) + "]");
         if (a.label < 1 || a.label > C - 1)
             return bad("label " + str(a.label) + " (arc " + str(i) + ") outside [1," + str(C - 1) + "]");
+        if (!std::isfinite(a.w))
+            return bad("arcs_weight[" + str(i) + "] is " + pat_float_str(a.w) +
+                       ": a weight must be finite (an arc that cannot be taken is left out)");
         arcs[(size_t)i] = a;
     }
     std::sort(arcs.begin(), arcs.end(), [](const Arc& a, const Arc& b) {
@@ -82,9 +103,20 @@ inline bool pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const 
         if (arcs[i].src == arcs[i - 1].src && arcs[i].label == arcs[i - 1].label)
             return bad("not deterministic: two arcs leave state " + str(arcs[i].src) + " on label " + str(arcs[i].label));
     std::vector<uint8_t> fin(nq0, 0);
+    std::vector<float> finw(weighted ? nq0 : 0, 0.f);
     for (int i = 0; i < num_finals; ++i) {
         if (finals[i] < 0 || finals[i] >= num_states)
             return bad("finals[" + str(i) + "]=" + str(finals[i]) + " outside [0," + str(num_states - 1) + "]");
+        if (weighted) {
+            const float w = final_weight ? final_weight[i] : 0.f;
+            if (!std::isfinite(w))
+                return bad("final_weight[" + str(i) + "] is " + pat_float_str(w) +
+                           ": a weight must be finite (a state that cannot end a text is not final)");
+            if (fin[(size_t)finals[i]] && finw[(size_t)finals[i]] != w)
+                return bad("final state " + str(finals[i]) + " is listed twice with different weights (" +
+                           std::to_string(finw[(size_t)finals[i]]) + " and " + std::to_string(w) + ")");
+            finw[(size_t)finals[i]] = w;
+        }
         fin[(size_t)finals[i]] = 1;
     }
     // prune: forward from state 0, backward from the final states
@@ -120,7 +152,7 @@ inline bool pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const 
     std::vector<Arc> live;
     for (const Arc& a : arcs)
         if (renum[(size_t)a.src] >= 0 && renum[(size_t)a.dst] >= 0)
-            live.push_back(Arc{renum[(size_t)a.src], a.label, renum[(size_t)a.dst]});      // (still sorted by src, label)
+            live.push_back(Arc{renum[(size_t)a.src], a.label, renum[(size_t)a.dst], a.w});      // (still sorted by src, label)
     // the eps states: the distinct (dst, label), ascending
     std::vector<std::pair<int32_t, int32_t>> pairs;
     for (const Arc& a : live) pairs.emplace_back(a.dst, a.label);
@@ -131,7 +163,7 @@ inline bool pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const 
         return bad("the pattern has " + str(S64) + " CTC states (" + str(nQ) + " DFA states + " + str((int64_t)pairs.size()) +
                    " (state, label) pairs), HCTR_PAT_MAX_STATES is " + str(kPatMaxStates));
     hctr_pat& x = *out;
-    x.C = C; x.nQ = nQ; x.S = (int)S64;
+    x.kind = weighted ? 2 : 0; x.C = C; x.nQ = nQ; x.S = (int)S64;
     const size_t S = (size_t)S64;
     auto eps = [&](int32_t q, int32_t c) {
         return nQ + (int32_t)(std::lower_bound(pairs.begin(), pairs.end(), std::make_pair(q, c)) - pairs.begin());
@@ -153,27 +185,30 @@ inline bool pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const 
         return a.dst != b.dst ? a.dst < b.dst : a.label != b.label ? a.label < b.label : a.src < b.src;
     });
     x.in_ptr.assign(1, 0);
-    std::vector<int32_t> srcs;
+    std::vector<std::pair<int32_t, float>> srcs;      // (source, the edge's weight); the sources of a state are distinct
     size_t k = 0;                                     // walks by_dst along with the pairs
     for (size_t s = 0; s < S; ++s) {
         srcs.clear();
-        srcs.push_back((int32_t)s);
+        srcs.emplace_back((int32_t)s, 0.f);
         if (s < (size_t)nQ) {
-            for (int32_t j = pptr[s]; j < pptr[s + 1]; ++j) srcs.push_back(nQ + j);
+            for (int32_t j = pptr[s]; j < pptr[s + 1]; ++j) srcs.emplace_back(nQ + j, 0.f);
         } else {
             const int32_t q = pairs[s - (size_t)nQ].first, c = pairs[s - (size_t)nQ].second;
             for (; k < by_dst.size() && by_dst[k].dst == q && by_dst[k].label == c; ++k) {
                 const int32_t p = by_dst[k].src;
-                srcs.push_back(p);
+                srcs.emplace_back(p, by_dst[k].w);
                 for (int32_t j = pptr[(size_t)p]; j < pptr[(size_t)p + 1]; ++j)
-                    if (pairs[(size_t)j].second != c) srcs.push_back(nQ + j);
+                    if (pairs[(size_t)j].second != c) srcs.emplace_back(nQ + j, by_dst[k].w);
             }
         }
-        std::sort(srcs.begin(), srcs.end());
+        std::sort(srcs.begin(), srcs.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
         if (x.in_src.size() + srcs.size() > (size_t)kPatMaxEdges)
             return bad("the pattern has more than " + str(kPatMaxEdges) + " edges (HCTR_PAT_MAX_EDGES); " + str((int64_t)s) +
                        " of its " + str(S64) + " CTC states reach that figure");
-        for (int32_t v : srcs) x.in_src.push_back((uint16_t)v);
+        for (const auto& v : srcs) {
+            x.in_src.push_back((uint16_t)v.first);
+            if (weighted) x.in_w.push_back(v.second);
+        }
         x.in_ptr.push_back((int32_t)x.in_src.size());
         x.max_deg = std::max(x.max_deg, (int)srcs.size());
     }
@@ -189,7 +224,51 @@ inline bool pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const 
         if (a.src == 0) x.start.push_back(eps(a.dst, a.label));
     std::sort(x.start.begin(), x.start.end());
     x.start.erase(std::unique(x.start.begin(), x.start.end()), x.start.end());
+    if (!weighted) return true;
+    x.is_final = nfin;
+    x.final_w.assign((size_t)nQ, 0.f);
+    for (size_t q = 0; q < nq0; ++q)
+        if (renum[q] >= 0 && fin[q]) x.final_w[(size_t)renum[q]] = finw[q];
+    for (int32_t s : x.accept) x.accept_w.push_back(x.final_w[(size_t)(s < nQ ? s : pairs[(size_t)(s - nQ)].first)]);
+    x.start_w.assign(x.start.size(), 0.f);            // (0, c) names one arc: one weight per start state
+    for (const Arc& a : live)
+        if (a.src == 0)
+            x.start_w[(size_t)(std::lower_bound(x.start.begin(), x.start.end(), eps(a.dst, a.label)) - x.start.begin())] = a.w;
+    x.warc_ptr.assign((size_t)nQ + 1, 0);
+    for (const Arc& a : live) ++x.warc_ptr[(size_t)a.src + 1];
+    for (int q = 0; q < nQ; ++q) x.warc_ptr[(size_t)q + 1] += x.warc_ptr[(size_t)q];
+    x.warcs = std::move(live);
     return true;
+}
+
+inline bool pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const int32_t* arcs_dst, int num_arcs,
+                      const int32_t* finals, int num_finals, int num_states, int C, hctr_pat* out, std::string* msg) {
+    return pat_build_explicit("hctr_pat_build", false, arcs_src, arcs_label, arcs_dst, nullptr, num_arcs, finals, nullptr,
+                              num_finals, num_states, C, out, msg);
+}
+
+// kind 2: pat_build's automaton and tables with a finite weight per arc and per final state (NULL = zeros)
+inline bool pat_build_weighted(const int32_t* arcs_src, const int32_t* arcs_label, const int32_t* arcs_dst,
+                               const float* arcs_weight, int num_arcs, const int32_t* finals, const float* final_weight,
+                               int num_finals, int num_states, int C, hctr_pat* out, std::string* msg) {
+    return pat_build_explicit("hctr_pat_build_weighted", true, arcs_src, arcs_label, arcs_dst, arcs_weight, num_arcs, finals,
+                              final_weight, num_finals, num_states, C, out, msg);
+}
+
+// the weight of a text under a kind-2 pattern: the float64 sum, in text order, of its arcs' float32 weights, then the
+// final weight of the state it ends in; -inf for a text outside the language
+inline double pat_text_weight(const hctr_pat& x, const int32_t* labels, int n) {
+    double w = 0.0;
+    int32_t q = 0;
+    for (int i = 0; i < n; ++i) {
+        const hctr_pat::WArc *f = x.warcs.data() + x.warc_ptr[(size_t)q], *l = x.warcs.data() + x.warc_ptr[(size_t)q + 1];
+        const hctr_pat::WArc* at =
+            std::lower_bound(f, l, labels[i], [](const hctr_pat::WArc& a, int32_t c) { return a.label < c; });
+        if (at == l || at->label != labels[i]) return -INFINITY;
+        w += (double)at->w;
+        q = at->dst;
+    }
+    return x.is_final[(size_t)q] ? w + (double)x.final_w[(size_t)q] : -INFINITY;
 }
 
 // The set form: arcs (src, set, dst) that carry label sets, set k = set_labels[set_ptr[k] .. set_ptr[k + 1]). The

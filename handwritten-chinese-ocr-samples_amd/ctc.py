@@ -917,10 +917,17 @@ class Pattern(object):
     C. ``Pattern.compile(expr, codec)`` builds one from a regular expression. The object is immutable and serves any
     number of contexts. ``Pattern.from_sets`` builds the set form (``hctr_pat_build_sets``): arcs that carry label sets,
     the same language and results without the explicit edge list - what a wildcard over a large vocabulary needs.
-    ``kind`` is 0 for the explicit form, 1 for the set form."""
+    ``kind`` is 0 for the explicit form, 1 for the set form, 2 for the weighted form. ``weights`` (one float per arc)
+    and ``final_weights`` (one per entry of ``finals``) build the weighted form (``hctr_pat_build_weighted``; either
+    may be None = zeros): a text's weight is the sum of its arcs' weights plus its final state's, ``logp`` becomes
+    log sum p(text | line) * exp(w(text)) and the best reading maximises path log-probability + w(text). Weights are
+    finite; an arc that cannot be taken is left out. ``Pattern.compile(..., label_weights=)`` and ``Pattern.bigram``
+    build such patterns."""
 
-    def __init__(self, arcs, finals, num_states, num_classes, expr=None, sets=None):
+    def __init__(self, arcs, finals, num_states, num_classes, expr=None, sets=None, weights=None, final_weights=None):
         if sets is not None:
+            if weights is not None or final_weights is not None:
+                raise ValueError("the set form carries no weights: build the explicit form (sets=None)")
             self._init_sets(arcs, sets, finals, num_states, num_classes, expr)
             return
         self.sets = None
@@ -936,8 +943,24 @@ class Pattern(object):
         self.num_classes = int(num_classes)
         lib = _lib.load()
         h = ctypes.c_void_p()
-        rc = lib.hctr_pat_build(_lib.ptr(src), _lib.ptr(lab), _lib.ptr(dst), int(a.shape[0]), _lib.ptr(f), int(f.size),
-                                int(num_states), self.num_classes, ctypes.byref(h))
+        self.weights_given = self.final_weights_given = None
+        if weights is None and final_weights is None:
+            rc = lib.hctr_pat_build(_lib.ptr(src), _lib.ptr(lab), _lib.ptr(dst), int(a.shape[0]), _lib.ptr(f), int(f.size),
+                                    int(num_states), self.num_classes, ctypes.byref(h))
+        else:
+            w = fw = None
+            if weights is not None:
+                w = np.ascontiguousarray(np.asarray(weights, dtype=np.float32).reshape(-1))
+                if w.size != a.shape[0]:
+                    raise ValueError("%d weights for %d arcs" % (w.size, a.shape[0]))
+            if final_weights is not None:
+                fw = np.ascontiguousarray(np.asarray(final_weights, dtype=np.float32).reshape(-1))
+                if fw.size != f.size:
+                    raise ValueError("%d final weights for %d final states" % (fw.size, f.size))
+            self.weights_given, self.final_weights_given = w, fw
+            rc = lib.hctr_pat_build_weighted(_lib.ptr(src), _lib.ptr(lab), _lib.ptr(dst), _lib.ptr(w), int(a.shape[0]),
+                                             _lib.ptr(f), _lib.ptr(fw), int(f.size), int(num_states), self.num_classes,
+                                             ctypes.byref(h))
         self._h = h if rc == 0 else None
         _lib.check(rc, None)
 
@@ -970,14 +993,39 @@ class Pattern(object):
         return cls(arcs, finals, num_states, num_classes, expr=expr, sets=list(sets))
 
     @classmethod
-    def compile(cls, expr, codec, sets=None):
+    def compile(cls, expr, codec, sets=None, label_weights=None):
         """The pattern of the regular expression ``expr`` over ``codec``'s vocabulary; the whole line must match
         (``re.fullmatch``). The syntax is ``_Regex``'s subset of ``re``. ``.``, negated sets and ranges mean the codec's
         real characters (labels 1..C-2): <unknown> is never matched; a literal outside the vocabulary is a ValueError.
         ``sets=False``: the explicit form; ``True``: the set form, from the expression's alphabet classes; ``None``: the
-        explicit form whenever it builds, the set form where the explicit build is refused for a limit."""
+        explicit form whenever it builds, the set form where the explicit build is refused for a limit.
+        ``label_weights``: a scalar (a bonus per character), a dict character -> weight (0 for the others) or an array
+        [C]; every arc on label c weighs ``label_weights[c]``, so a text's weight is the sum over its characters whatever
+        automaton the expression gave. Always the explicit (weighted) form: ``sets=True`` is a ValueError, and so is a
+        pattern that only the set form could hold, with the builder's message."""
         chars = codec.characters
         vocab = {ch: i for i, ch in enumerate(chars) if 1 <= i <= len(chars) - 2 and len(ch) == 1}
+        if label_weights is not None:
+            if sets:
+                raise ValueError("label_weights need the explicit form: the set form (sets=True) carries no weights")
+            if isinstance(label_weights, dict):
+                lw = np.zeros(len(chars), np.float32)
+                for ch, v in label_weights.items():
+                    if ch not in vocab:
+                        raise ValueError("label_weights names %r, which is not a character of the codec" % (ch,))
+                    lw[vocab[ch]] = v
+            elif np.ndim(label_weights) == 0:
+                lw = np.full(len(chars), label_weights, np.float32)
+            else:
+                lw = np.asarray(label_weights, dtype=np.float32).reshape(-1)
+                if lw.size != len(chars):
+                    raise ValueError("label_weights has %d entries, the codec %d classes" % (lw.size, len(chars)))
+            arcs, classes, finals, nq = _regex_to_dfa(_Regex(expr, vocab).parse(), sets=True)
+            if sum(len(classes[k]) for k in arcs[:, 1]) > 4 * _PAT_MAX_EDGES:
+                raise ValueError("hctr_pat_build_weighted: the pattern has more than %d edges (HCTR_PAT_MAX_EDGES): only the "
+                                 "set form, which carries no weights, could hold it" % _PAT_MAX_EDGES)
+            full = _expand_arcs(arcs, classes)
+            return cls(full, finals, nq, len(chars), expr=expr, weights=lw[full[:, 1]])
         arcs, classes, finals, nq = _regex_to_dfa(_Regex(expr, vocab).parse(), sets=True)
         if sets:
             return cls.from_sets(arcs, classes, finals, nq, len(chars), expr=expr)
@@ -992,10 +1040,69 @@ class Pattern(object):
                 return cls.from_sets(arcs, classes, finals, nq, len(chars), expr=expr)
             raise
 
+    @classmethod
+    def bigram(cls, labels, trans, init=None, final=None, num_classes=None):
+        """The weighted pattern of a label bigram over the n distinct ``labels``: every non-empty text over them, weighted
+        ``init[i]`` for its first label ``labels[i]``, ``trans[j][i]`` for ``labels[i]`` after ``labels[j]`` and
+        ``final[i]`` for ending on ``labels[i]`` (None = zeros). State 0 is the start, state i + 1 "the last label was
+        labels[i]". A -inf entry of ``trans`` or ``init`` leaves the arc out. Dense, it has 2n + 1 CTC states and
+        2n^2 + 3n + 1 edges: n <= 361 fits HCTR_PAT_MAX_EDGES."""
+        lab = np.asarray(labels, dtype=np.int64).reshape(-1)
+        n = int(lab.size)
+        if num_classes is None:
+            raise ValueError("num_classes is required")
+        if n < 1 or len(set(lab.tolist())) != n:
+            raise ValueError("labels must be n >= 1 distinct labels")
+        tr = np.asarray(trans, dtype=np.float32)
+        if tr.shape != (n, n):
+            raise ValueError("trans must be [n, n] = [%d, %d], got %s" % (n, n, tr.shape))
+        ini = np.zeros(n, np.float32) if init is None else np.asarray(init, dtype=np.float32).reshape(-1)
+        fin = np.zeros(n, np.float32) if final is None else np.asarray(final, dtype=np.float32).reshape(-1)
+        if ini.size != n or fin.size != n:
+            raise ValueError("init and final must have n = %d entries" % n)
+        w = np.concatenate([ini[None, :], tr], axis=0)                  # [n + 1, n]: row = source state, column = label
+        src, col = np.nonzero(~np.isneginf(w))
+        arcs = np.stack([src, lab[col], col + 1], axis=1)
+        return cls(arcs, np.arange(1, n + 1), n + 1, int(num_classes), weights=w[src, col], final_weights=fin)
+
     @property
     def kind(self):
-        """0 = the explicit form, 1 = the set form (``hctr_pat_kind``)"""
+        """0 = the explicit form, 1 = the set form, 2 = the weighted form (``hctr_pat_kind``)"""
         return int(_lib.load().hctr_pat_kind(self._h))
+
+    @property
+    def weighted(self):
+        return self.kind == 2
+
+    def instance(self, full=True):
+        """(states per thread, edge list in LDS, edge weights in LDS): the kernel instance a call with (``full``) or
+        without the Viterbi outputs runs for this explicit or weighted pattern (``hctr_pattern_instance``, a pure
+        function of the pattern's sizes)"""
+        if self.kind == 1:
+            raise ValueError("the set form has one kernel shape: no instance to select")
+        i = self.info()
+        v = int(_lib.load().hctr_pattern_instance(i["states"], i["edges"], int(bool(full)), int(self.kind == 2)))
+        return v & 15, bool(v & 16), bool(v & 32)
+
+    def weights(self):
+        """dict of float32 arrays: what ``hctr_pat_weights`` exports, the weights the kernel is given beside ``tables()`` -
+        in_w [E] parallel to in_src, accept_w parallel to accept, start_w parallel to start"""
+        lib, i = _lib.load(), self.info()
+        if self.kind != 2:
+            _lib.check(lib.hctr_pat_weights(self._h, None, None, None), None)
+        t = self.tables()
+        w = {"in_w": np.zeros(i["edges"], np.float32), "accept_w": np.zeros(t["accept"].size, np.float32),
+             "start_w": np.zeros(t["start"].size, np.float32)}
+        _lib.check(lib.hctr_pat_weights(self._h, _lib.ptr(w["in_w"]), _lib.ptr(w["accept_w"]), _lib.ptr(w["start_w"])), None)
+        return w
+
+    def text_weight(self, labels):
+        """float: the weight of the text ``labels`` (``hctr_pat_text_weight``): the float64 sum of its arcs' float32
+        weights and its final state's; -inf for a text outside the pattern's language"""
+        lab = np.ascontiguousarray(np.asarray(labels, dtype=np.int32).reshape(-1))
+        w = ctypes.c_double()
+        _lib.check(_lib.load().hctr_pat_text_weight(self._h, _lib.ptr(lab), int(lab.size), ctypes.byref(w)), None)
+        return float(w.value)
 
     def expanded_arcs(self):
         """int32 [n, 3]: the single-label arcs (src, label, dst) of the same automaton, sorted by (src, label) - the set
@@ -1044,14 +1151,17 @@ class PatternResult(object):
     beyond the line's length); ``labels`` int32 [B, W] / ``lengths`` int32 [B], the decoded text; ``starts`` / ``ends``
     int32 [B, W] and ``logps`` float32 [B, W], each character's column span and the sum of its label's log-probabilities
     over it; ``text_nll`` float32 [B], the CTC loss of the decoded text. A forward-only result holds ``logp`` alone (the
-    rest None). Where no path of the line's length matches, logp and best_logp are -inf, lengths 0, text_nll +inf."""
+    rest None). Where no path of the line's length matches, logp and best_logp are -inf, lengths 0, text_nll +inf.
+    ``weights`` float64 [B]: the decoded texts' weights under a weighted pattern (``Pattern.text_weight``; NaN where no
+    path was accepted), zeros for an unweighted one; no field of the device call."""
 
     FIELDS = ("logp", "best_logp", "path", "labels", "lengths", "starts", "ends", "logps", "text_nll")
 
     def __init__(self, logp, best_logp=None, path=None, labels=None, lengths=None, starts=None, ends=None, logps=None,
-                 text_nll=None):
+                 text_nll=None, weights=None):
         self.logp, self.best_logp, self.path, self.labels, self.lengths = logp, best_logp, path, labels, lengths
         self.starts, self.ends, self.logps, self.text_nll = starts, ends, logps, text_nll
+        self.weights = weights
 
     def __len__(self):
         return len(self.logp)
@@ -1064,10 +1174,11 @@ class PatternResult(object):
         return codec.labels_to_text([l.tolist() for l in self.label_lists()])
 
     def posterior(self):
-        """float64 [B]: exp(-text_nll - logp), the probability of the decoded text within the pattern (0 where nothing
-        matches)"""
+        """float64 [B]: exp(-text_nll + weight - logp), the probability of the decoded text within the pattern, under its
+        weights where it has any (0 where nothing matches)"""
+        w = np.zeros(len(self)) if self.weights is None else np.where(np.isnan(self.weights), 0.0, self.weights)
         with np.errstate(invalid="ignore", over="ignore"):
-            p = np.exp(-np.asarray(self.text_nll, np.float64) - np.asarray(self.logp, np.float64))
+            p = np.exp(-np.asarray(self.text_nll, np.float64) + w - np.asarray(self.logp, np.float64))
         return np.where(np.isneginf(self.logp), 0.0, p)
 
     def lines(self):
@@ -1090,6 +1201,19 @@ def _pattern_outputs(pat, B, W, full):
             np.zeros((B, W), i), np.zeros((B, W), f), np.full(B, np.inf, f))
 
 
+def _pattern_result(pat, out):
+    """the PatternResult of a call's outputs, with the decoded texts' weights (host side)"""
+    res = PatternResult(*out)
+    if res.lengths is None:
+        return res
+    res.weights = np.zeros(len(res), np.float64)
+    if pat.kind == 2:
+        for b in range(len(res)):
+            res.weights[b] = (pat.text_weight(res.labels[b, :int(res.lengths[b])]) if np.isfinite(res.best_logp[b])
+                              else np.nan)
+    return res
+
+
 def pattern_logits(ctx, logits, on_dev, pat, input_lengths=None, full=True):
     """PatternResult of caller logits / log-probs in WBC layout (hctr_pattern_logits); ``full=False`` asks for logp
     alone (the forward-only call)"""
@@ -1101,7 +1225,7 @@ def pattern_logits(ctx, logits, on_dev, pat, input_lengths=None, full=True):
     if B and W:
         _lib.check(_lib.load().hctr_pattern_logits(ctx, pat._h, _lib.ptr(logits), on_dev, W, B, C, _lib.ptr(il),
                                                    *[_lib.ptr(a) for a in out]), ctx)
-    return PatternResult(*out)
+    return _pattern_result(pat, out)
 
 
 def pattern_images(ctx, x, dt, on_dev, widths, B, W, pat, input_lengths=None, full=True):
@@ -1111,7 +1235,7 @@ def pattern_images(ctx, x, dt, on_dev, widths, B, W, pat, input_lengths=None, fu
     if B:
         _lib.check(_lib.load().hctr_pattern(ctx, pat._h, _lib.ptr(x), dt, on_dev, _lib.ptr(widths), B, W, _lib.ptr(il),
                                             *[_lib.ptr(a) for a in out]), ctx)
-    return PatternResult(*out)
+    return _pattern_result(pat, out)
 
 
 def pattern_group_lines(S, D, W):

@@ -606,7 +606,45 @@ int hctr_words_logits(hctr_ctx* ctx, const hctr_lex* lex, const float* logits_wb
  *   depend on it, bit for bit. hctr_pattern_group_lines is unchanged. Device scratch as above, plus 16*g*S for the step
  *   buffers kept out of LDS; the device copy is 20 bytes per state + 4 per DFA state + 4 per in-arc. Launches:
  *   pattern_set in the place of pattern.
- * Masked and non-finite logits: as stated above for hctr_pattern_logits, for both forms. */
+ *
+ * WEIGHTED ARCS (hctr_pat_build_weighted, hctr_pat_kind == 2): one float32 weight per arc and per final state - a prior
+ * over the pattern's texts (a character bonus, a bigram, log priors of alternatives). The automaton is deterministic,
+ * so a text has one arc sequence and one weight: w(text) = the sum of the weights of the arcs it takes plus the weight
+ * of the final state it ends in.
+ *   logp[b]      = log of the sum over the texts of L(A) of p(text | line) * exp(w(text)): no probability, and not
+ *                  clamped to 0;
+ *   best_logp[b] = the best accepted path's log-probability plus the weight of its text; best_logp <= logp still.
+ *   Validation, pruning, CTC states, numbering, in-edges, accepting list, start list and the limits are hctr_pat_build's
+ *   on the same arcs: hctr_pat_tables returns the tables of the kind-0 pattern of that automaton, byte for byte.
+ *   arcs_weight == NULL or final_weight == NULL means zeros. Every weight must be finite: NaN, +inf and -inf are
+ *   refused (an arc that cannot be taken is left out); a final state listed twice with different weights is refused.
+ *   Every error of hctr_pat_build and these, one message each, under the prefix "hctr_pat_build_weighted:".
+ * hctr_pat_weights exports what the kernel is given beside the tables (any pointer may be NULL):
+ *   in_w float32 [E], parallel to in_src: for a state eps_(q,c) and a source beta_p or eps_(p,c'), the weight of arc
+ *   (p,c,q) - every source belongs to one DFA state p, so this is one value even where several arcs share eps_(q,c); 0
+ *   for a state's self edge and for every in-edge of a beta state;
+ *   accept_w float32 [num_accept]: the final weight of the DFA state the accepting state belongs to;
+ *   start_w float32 [num_start]: 0 for beta_0, the weight of arc (0,c,q) for eps_(q,c).
+ *   Weights on pruned arcs and states are dropped. HCTR_ERR_ARG on a pattern of kind 0 or 1.
+ * hctr_pat_text_weight: *w = the float64 sum, in text order, of the float32 weights of the arcs the n labels take from
+ *   state 0, plus the final weight of the state reached; -inf (with HCTR_OK) for a text outside L(A). HCTR_ERR_ARG on a
+ *   pattern of kind 0 or 1.
+ * Arithmetic (the recursion, the order of every reduction and the tie rules are the explicit form's above):
+ *   t = 0:  a_0(s) = v_0(s) = lp_0(label(s)) + start_w(s), one float32 addition, on the start list;
+ *   t >= 1: x_j = a_{t-1}(src_j) + in_w[j], one float32 addition per in-edge; a_t(s) = the logsum above over the x_j
+ *           in edge order (float32 max, float64 sum of (double)exp32(x_j - m), m + log32((float)sum)) + lp_t(label(s));
+ *           v_t(s) = max_j (v_{t-1}(src_j) + in_w[j]) + lp_t(label(s)), the backpointer the first maximal edge, the
+ *           state's own index when every source is at -inf;
+ *   end:    the logsum and the max over a_{T-1}(s) + accept_w(s), v_{T-1}(s) + accept_w(s) in list order, ties to the
+ *           lowest state.
+ *   With every weight 0 every output has the bits of the kind-0 pattern's, except that logp is not clamped.
+ *   path .. char_logp describe the best weighted path; char_logp stays the sum of emissions and text_nll the plain CTC
+ *   loss of the decoded text: exp(-text_nll + w(text) - logp) is the text's posterior under the weights.
+ * The edge weights are staged in LDS beside the edge list when 2*S*(8 or 4) + 6*E <= 160 KB, else read through L2 (the
+ *   edge list alone stays in LDS where it fits as for kind 0). Results do not depend on it. The device copy grows by 4
+ *   bytes per edge, accepting state and start state. Launches: pattern_w in the place of pattern. Grouping,
+ *   HCTR_PAT_LINES, scratch and the errors of hctr_pattern* are unchanged.
+ * Masked and non-finite logits: as stated above for hctr_pattern_logits, for every form. */
 #define HCTR_PAT_MAX_STATES 8192
 #define HCTR_PAT_MAX_EDGES 262144
 typedef struct hctr_pat hctr_pat;
@@ -618,7 +656,13 @@ int hctr_pat_build(const int32_t* arcs_src, const int32_t* arcs_label, const int
 int hctr_pat_build_sets(const int32_t* arcs_src, const int32_t* arcs_set, const int32_t* arcs_dst, int num_arcs,
                         const int32_t* set_ptr, const int32_t* set_labels, int num_sets, const int32_t* finals,
                         int num_finals, int num_states, int C, hctr_pat** out);
-int hctr_pat_kind(const hctr_pat* pat);      /* 0 = hctr_pat_build's, 1 = hctr_pat_build_sets's; HCTR_ERR_ARG for NULL */
+int hctr_pat_build_weighted(const int32_t* arcs_src, const int32_t* arcs_label, const int32_t* arcs_dst,
+                            const float* arcs_weight, int num_arcs, const int32_t* finals, const float* final_weight,
+                            int num_finals, int num_states, int C, hctr_pat** out);
+int hctr_pat_weights(const hctr_pat* pat, float* in_w, float* accept_w, float* start_w);
+int hctr_pat_text_weight(const hctr_pat* pat, const int32_t* labels, int n, double* w);
+/* 0 = hctr_pat_build's, 1 = hctr_pat_build_sets's, 2 = hctr_pat_build_weighted's; HCTR_ERR_ARG for NULL */
+int hctr_pat_kind(const hctr_pat* pat);
 void hctr_pat_free(hctr_pat* pat);
 int hctr_pat_info(const hctr_pat* pat, int32_t* dfa_states, int32_t* ctc_states, int32_t* num_edges, int32_t* num_classes,
                   int32_t* max_in_degree);
@@ -632,6 +676,10 @@ int hctr_pattern_logits(hctr_ctx* ctx, const hctr_pat* pat, const float* logits_
                         const int32_t* input_lengths, float* logp, float* best_logp, int32_t* path, int32_t* labels,
                         int32_t* lengths, int32_t* span_start, int32_t* span_end, float* char_logp, float* text_nll);
 int hctr_pattern_group_lines(int S, int D, int W);
+/* the kernel instance an explicit (weighted != 0: a weighted) pattern of S CTC states and E edges runs, a pure function:
+ * states per thread (1, 2, 4 or 8) | 16 where the edge list is staged in LDS | 32 where the edge weights are too;
+ * HCTR_ERR_ARG beyond the limits. For tests that mean to reach one instance. */
+int hctr_pattern_instance(int S, int E, int viterbi, int weighted);
 
 /* ---- greedy recognition: the decoded text with per-character spans, confidences and runners-up -------------------
  * What hctr_greedy / hctr_decode_greedy_logits decode, plus the figures the CTC family above gives only for a

@@ -54,6 +54,9 @@ def build_argparser():
                    help="-dm words: added to the score per word (negative: a penalty)")
     a.add_argument("--pattern", dest="pattern", type=str, default="",
                    help="-dm pattern: a regular expression the whole line must match, e.g. '\\d{18}'")
+    a.add_argument("--char-bonus", dest="char_bonus", type=float, default=0.0,
+                   help="-dm pattern: a weight per character of the reading (the len_bonus of the searches, in an exact "
+                        "search); 0.0 builds the unweighted pattern")
     a.add_argument("-ss", "--skip-search", dest="skip_search", action="store_true")
     a.add_argument("-kp", "--kenlm-path", dest="kenlm_path", type=str, default="")
     a.add_argument("-utp", "--use-tfm-pred", dest="use_tfm_pred", action="store_true")
@@ -206,12 +209,15 @@ def load_lexicon(path, codec):
     return hctr_amd.Lexicon([e for e in entries if e], codec=codec)
 
 
-def load_pattern(expr, codec):
-    """-dm pattern --pattern EXPR: the compiled pattern (hctr_amd.Pattern.compile; the whole line must match)"""
+def load_pattern(expr, codec, char_bonus=0.0):
+    """-dm pattern --pattern EXPR [--char-bonus X]: the compiled pattern (hctr_amd.Pattern.compile; the whole line must
+    match), with X on every arc where X is not 0"""
     import hctr_amd
     if not expr:
         raise ValueError("-dm pattern needs --pattern EXPR")
-    return hctr_amd.Pattern.compile(expr, codec)
+    if char_bonus == 0.0:
+        return hctr_amd.Pattern.compile(expr, codec)
+    return hctr_amd.Pattern.compile(expr, codec, label_weights=char_bonus)
 
 
 def recognise(model, codec, imgs, widths, lexicon=None, pattern=None, word_bonus=None):
@@ -241,7 +247,7 @@ def test(args):
     pp = hctr_amd.preprocess
     lexicon = load_lexicon(args.lexicon, codec) if args.decode_method in ("lexicon", "words") else None
     word_bonus = args.word_bonus if args.decode_method == "words" else None
-    pattern = load_pattern(args.pattern, codec) if args.decode_method == "pattern" else None
+    pattern = load_pattern(args.pattern, codec, args.char_bonus) if args.decode_method == "pattern" else None
     paths = list_inputs(args.input)
     batches = [paths[i * args.batch_size:(i + 1) * args.batch_size] for i in range(len(paths) // args.batch_size)]
     for i, (_, arrs) in enumerate(prefetched(batches, args.workers)):

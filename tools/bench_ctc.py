@@ -114,7 +114,9 @@ code points, e.g. '\\d{18}', '\\d{4}\u5e74\\d{1,2}\u6708\\d{1,2}\u65e5', '.\\d{3
 launches (pattern_classes, ctc_lse, pattern, pattern_trace, ctc_alpha) and the recursion's time per step. --sets builds
 the set form (label-set arcs, the launch pattern_set), which a wildcard over the whole vocabulary needs ('.{2,4}',
 '.*\u5e74.*'); where the explicit form builds as well ('.\\d{3}') both are timed alternately in the one process and their
-Viterbi outputs compared bit for bit."""
+Viterbi outputs compared bit for bit. --char-bonus X (with --pattern) builds the weighted form with X on every arc
+(Pattern.compile(label_weights=X), the launch pattern_w) and --bigram N the dense weighted bigram over labels 1..N
+(Pattern.bigram, random weights); the unweighted pattern of the same automaton is timed alternately in the same run."""
 import argparse
 import json
 import os
@@ -152,6 +154,10 @@ def main():
     ap.add_argument("--pattern", type=str, default="", help="a regular expression: time hctr_pattern_logits")
     ap.add_argument("--sets", action="store_true", help="with --pattern: build the set form (label-set arcs); where the "
                     "explicit form builds too, it is timed alternately in the same process")
+    ap.add_argument("--char-bonus", type=float, default=0.0, help="with --pattern: a weight per character (the weighted "
+                    "form); the unweighted pattern is timed alternately in the same process")
+    ap.add_argument("--bigram", type=int, default=0, help="time the dense weighted bigram over labels 1..N beside the "
+                    "unweighted pattern of the same automaton")
     ap.add_argument("--pairs", type=int, default=250)
     ap.add_argument("--host-lines", type=int, default=4)
     args = ap.parse_args()
@@ -186,7 +192,7 @@ def main():
     if args.lexicon:
         print(json.dumps(lexicon(args, hctr_amd, m, imgs, labels, targets, tl)))
         return
-    if args.pattern:
+    if args.pattern or args.bigram:
         print(json.dumps(pattern(args, hctr_amd, m, imgs, targets, tl)))
         return
     if args.evaluate:
@@ -583,10 +589,19 @@ def pattern(args, hctr_amd, m, imgs, targets, tl):
     W, B, C = (int(v) for v in logits.shape)
     t0 = time.perf_counter()
     codec = hctr_amd.ctc_codec(pattern_characters(C - 2))
-    pat = mod.Pattern.compile(args.pattern, codec, sets=True if args.sets else None)
+    unweighted = None
+    if args.bigram:
+        rng, n = np.random.RandomState(7), args.bigram
+        pat = mod.Pattern.bigram(np.arange(1, n + 1), rng.randn(n, n), rng.randn(n), rng.randn(n), num_classes=C)
+    elif args.char_bonus != 0.0:
+        pat = mod.Pattern.compile(args.pattern, codec, label_weights=args.char_bonus)
+    else:
+        pat = mod.Pattern.compile(args.pattern, codec, sets=True if args.sets else None)
     build_ms = 1e3 * (time.perf_counter() - t0)
+    if pat.kind == 2:
+        unweighted = mod.Pattern(pat.arcs, pat.finals, pat.num_states, C)
     explicit = None
-    if args.sets:
+    if args.sets and pat.kind == 1:
         try:
             explicit = mod.Pattern.compile(args.pattern, codec, sets=False)
         except ValueError:
@@ -614,6 +629,9 @@ def pattern(args, hctr_amd, m, imgs, targets, tl):
     if explicit is not None:
         fns += (("explicit_forward", lambda: last.update(ef=mod.pattern_logits(ctx, logits, 1, explicit, None, False))),
                 ("explicit_full", lambda: last.update(er=mod.pattern_logits(ctx, logits, 1, explicit, None, True))))
+    if unweighted is not None:
+        fns += (("unweighted_forward", lambda: last.update(uf=mod.pattern_logits(ctx, logits, 1, unweighted, None, False))),
+                ("unweighted_full", lambda: last.update(ur=mod.pattern_logits(ctx, logits, 1, unweighted, None, True))))
     for _ in range(args.warmup):
         for _, fn in fns:
             fn()
@@ -626,7 +644,8 @@ def pattern(args, hctr_amd, m, imgs, targets, tl):
     if explicit is not None:                                     # the Viterbi outputs of the two forms: the same bits
         for f in last["r"].FIELDS[1:]:
             assert getattr(last["r"], f).tobytes() == getattr(last["er"], f).tobytes(), f
-    rec = {"mode": "pattern", "pattern": args.pattern, "kind": pat.kind, "lines": B, "width": W, "classes": C, "precision": args.precision,
+    rec = {"mode": "pattern", "pattern": args.pattern or "bigram %d" % args.bigram, "kind": pat.kind,
+           "instance": list(pat.instance(True)) + list(pat.instance(False)) if pat.kind != 1 else None, "lines": B, "width": W, "classes": C, "precision": args.precision,
            "build_ms": round(build_ms, 1), "group_lines": mod.pattern_group_lines(info["states"], info["classes"] + 1, W),
            "matching_lines": int(np.isfinite(last["r"].logp).sum())}
     rec.update(info)
@@ -645,7 +664,8 @@ def pattern(args, hctr_amd, m, imgs, targets, tl):
         groups = -(-B // rec["group_lines"])
         for k in prof:                                       # a group's lines run side by side, the groups in turn
             if k != "loss_only":
-                kernel = "pattern" if k.startswith("explicit") or not pat.kind else "pattern_set"
+                kernel = ("pattern" if k.startswith("explicit") or k.startswith("unweighted") or not pat.kind else
+                          "pattern_set" if pat.kind == 1 else "pattern_w")
                 rec[k + "_us_per_step"] = round(1e3 * prof[k].get(kernel, 0.0) / (W * groups), 3)
     return rec
 
