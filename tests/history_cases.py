@@ -14,11 +14,19 @@ this file adds no oracle of its own.
   * the "defaults, ragged, OOV" row of tests/test_gpu_nbest_lm.py's CASES (T = 63, B = 3, C = 18): the logits that module's
     ``lists_of`` builds its lists from, for nbest_logits, nbest_topk, nbest_logits(lm=), nbest_skip_logits (zero LM and
     model) and lm_sweep_logits over a 2 x 2 grid, against tests/nbest_ref.py, lm_beam_ref.py, skip_beam_ref.py and
-    lm_sweep_ref.py.
+    lm_sweep_ref.py;
+  * word-sequence recognition on `vocab` with its lexicon entries (two need the masked class 9), seeded priors and a word
+    bonus of -0.5, against tests/words_ref.py: a trie of 27 nodes, the one-node-per-thread LDS instance;
+  * `vocab`'s ``union`` and ``live_plus`` patterns as weighted (kind 2) patterns with seeded arc and final weights in
+    [-2, 2], against tests/pattern_w_ref.py, and the forward-only (``full=False``, logp alone) instances of the plain and
+    the weighted ``union``.
 
 Dirtiers: legal calls that leave hostile bytes in the context's scratch and are larger (``big``), then smaller
 (``small``), than every probe in every dimension a scratch layout is carved by. ``big`` holds three non-finite lines
-(masked_cases.POISON_KINDS' inputs: one NaN, one +inf, one row of nothing but -inf), whose contract is HCTR_OK.
+(masked_cases.POISON_KINDS' inputs: one NaN, one +inf, one row of nothing but -inf), whose contract is HCTR_OK. Its words
+calls run a lexicon of more than 4096 trie nodes (the scratch form, which sizes step buffers in the block) and then its
+small one (the LDS form's records); its ``literal`` and ``union`` patterns run once more with weights, with and without
+the Viterbi outputs.
 ``dims`` states the dimensions; tests/test_history_host.py asserts the ordering numerically.
 """
 import functools
@@ -32,7 +40,9 @@ import masked_cases as mc
 import nbest_ref as nr
 import pattern_ref
 import pattern_set_ref
+import pattern_w_ref
 import recognize_ref
+import words_ref
 
 NBEST_NAME = "defaults, ragged, OOV"
 SWEEP_ALPHAS, SWEEP_BETAS = (0.0, 2.0), (-1.5, 5.8)
@@ -40,6 +50,9 @@ PATSET_W, PATSET_LENGTHS = 48, [48, 33, 5, 1]
 BIG_W, BIG_B, BIG_C = 160, 8, 64
 BIG_BAD = {1: "nan", 4: "posinf", 6: "row_neginf"}         # line -> the kind of its non-finite row (row BAD_T)
 BAD_T, BAD_C = 7, 3
+WORDS_BONUS, WORDS_PRIOR_SEED = -0.5, 9960
+PATW_SEEDS = {"union": 9972, "live_plus": 9973}            # of the probes' arc and final weights, uniform in [-2, 2]
+BIG_WORDS_BONUS, BIG_WORDS_NODES = 0.75, (4200, 6000)      # the big dirtier's word bonus; its large trie's nodes lie between
 EDIT_SYMBOLS = (0x7FC00000, -1, 2 ** 31 - 1, -2 ** 31)     # a float NaN's bits, all ones, INT32_MAX, INT32_MIN
 
 # the probes in ascending order of the CTC scratch they need: what the `grow` history runs them in. The figures are
@@ -50,11 +63,15 @@ PROBES = ["edit",                   # 4 * (H + L) per line and the backpointers 
           "loss",                   # 4 * B*W*D emissions (D <= 6) + 8 * B*W: 7 KB
           "spot",                   # emissions of the queries' 8 classes + 16 * B*Q: 7 KB
           "align",                  # emissions + backpointers + 4 * B*W + 12 * sum L: 8 KB
+          "pattern.union.fwd",      # forward only: 4 * B*W*D emissions at D = 9 and the class tables, no backpointers: 8 KB
+          "pattern_w.union.fwd",
           "recognize",              # 8 * B*W + 40 * B*W: 10 KB
           "grad",                   # the loss's + 4 * sum T (2L + 1) alpha rows: 13 KB
           "recognize_wide",         # 9.3 KB, then 13.8 KB for the text's emissions (`recognize_needs`, exact)
-          "pattern.literal",        # 4 * W*D + 2 * W*S per line, S = 11 .. 70
-          "pattern.masked_literal", "pattern.live_plus", "pattern.union",
+          "pattern.literal",        # 4 * W*D + 2 * W*S per line, S = 11 .. 53, + 20 * B*W: 15 KB .. 34 KB
+          "pattern.masked_literal", "pattern.live_plus", "pattern_w.live_plus",
+          "words",                  # 4 * B*W*D emissions at D = 9 + 32 * B*W records + 12 * B*W words, starts, labels: 17 KB
+          "pattern.union", "pattern_w.union",
           "lexicon",                # emissions + the trie's 2 * 30 states per line and step + B*N scores: 30 KB
           "nbest_topk",             # 8 * T*B*k lists + 8 * T*B*beam history: 30 KB
           "nbest_logits",           # + the rows of the front end, 4 * T*B*C: 45 KB
@@ -84,6 +101,44 @@ def _shape(z):
 def vocab():
     """(case, oracle) of masked_cases' `vocab`"""
     return mc.get("vocab")
+
+
+def _ctc():
+    """the package's ctc module (host side: building a Lexicon needs no GPU)"""
+    import importlib
+    from conftest import PKG
+    return importlib.import_module(PKG + ".ctc")
+
+
+@functools.lru_cache(maxsize=None)
+def words():
+    """the words probe: dict(entries, priors float32, bonus, want) - masked_cases.entries(vocab), seeded priors, and
+    words_ref.words' (score, words, starts) per line"""
+    c, _ = vocab()
+    es = mc.entries(c)
+    pr = (np.random.RandomState(WORDS_PRIOR_SEED).randn(len(es)) * 0.5).astype(np.float32)
+    return dict(entries=es, priors=pr, bonus=WORDS_BONUS, want=words_ref.words(c["logits"], es, pr, WORDS_BONUS, c["il"]))
+
+
+def _weights(seed, arcs, finals):
+    rng = np.random.RandomState(seed)
+    return rng.uniform(-2, 2, len(arcs)).astype(np.float32), rng.uniform(-2, 2, len(finals)).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def pattern_w():
+    """the weighted probes: name -> dict(arcs, finals, states, weights, final_weights, tab, want) - `vocab`'s ``union`` and
+    ``live_plus`` automata with seeded float32 weights, pattern_w_ref's tables of them and its (logp, best_logp, path) per
+    line"""
+    c, _ = vocab()
+    out = {}
+    for name, seed in PATW_SEEDS.items():
+        arcs, finals, ns = mc.patterns(c)[name]
+        w, fw = _weights(seed, arcs, finals)
+        tab = pattern_w_ref.tables(arcs, finals, ns, w, fw)
+        out[name] = dict(arcs=arcs, finals=finals, states=ns, weights=w, final_weights=fw, tab=tab,
+                         want=pattern_w_ref.run(c["logits"], tab, c["il"]))
+    return out
 
 
 @functools.lru_cache(maxsize=None)
@@ -220,6 +275,11 @@ def probe_dims():
     out["lexicon"] = dict(v, count=len(o["entries"]), **_seq_dims(o["entries"]))
     for pname, (arcs, finals, ns) in pats.items():
         out["pattern." + pname] = dict(v, states=int(ns), **_arc_dims(arcs))
+    for name in ("pattern_w.union", "pattern_w.live_plus", "pattern.union.fwd", "pattern_w.union.fwd"):
+        out[name] = dict(out["pattern." + name.split(".")[1]])
+    wd = words()
+    lex = _ctc().Lexicon(wd["entries"], num_classes=mc.C, priors=wd["priors"])
+    out["words"] = dict(v, count=len(wd["entries"]), nodes=int(lex.info()["nodes"]), **_seq_dims(wd["entries"]))
     out["pattern_set"] = dict(_shape(ps["logits"]), states=ps["num_states"],
                               **_arc_dims(pattern_set_ref.expand(ps["arcs"], ps["sets"])))
     out["edit"] = dict(B=len(ed["refs"]), stride=int(ed["hyp"].shape[1]), **_seq_dims(ed["refs"]))
@@ -242,8 +302,10 @@ def _edit_batch(pairs):
 @functools.lru_cache(maxsize=None)
 def big():
     """dict: logits [160, 8, 64] with the three bad lines, clean (the same without them), il, lines / targets / tl,
-    queries, entries, patterns name -> (arcs, finals, states), set_pattern (arcs, sets, finals, states), edit (hyps,
-    refs), search dict(n, beam, depth). Texts as masked_cases.ladder() makes its L = 70 line, over 63 live labels; line 0
+    queries, entries, patterns name -> (arcs, finals, states), pattern_weights name -> (arc weights, final weights),
+    set_pattern (arcs, sets, finals, states), edit (hyps, refs), search dict(n, beam, depth), words_entries (random
+    entries of 1 - 4 of the 63 live labels, as tests/test_gpu_words.py's ``grown`` makes them, whose trie has more than
+    4096 nodes: the scratch form) and words_bonus. Texts as masked_cases.ladder() makes its L = 70 line, over 63 live labels; line 0
     holds every one of them"""
     rng = np.random.RandomState(9800)
     live = list(range(1, BIG_C))
@@ -288,16 +350,22 @@ def big():
     pairs = [(ref.tolist(), noisy(280)), (ref.tolist(), noisy(310)), ([], noisy(5)), (ref[:7].tolist(), []),
              (ref[:150].tolist(), noisy(150)), (ref.tolist(), noisy(300))]
     hyps, refs = _edit_batch(pairs)
-    case.update(clean=clean, queries=queries, entries=entries,
-                patterns={"literal": pattern_ref.literal(lines[0]), "union": pattern_ref.trie(entries)},
-                set_pattern=([(0, 0, 1), (1, 0, 1)], [every], [1], 2), edit=(hyps, refs), search=dict(n=32, beam=32, depth=32))
+    patterns = {"literal": pattern_ref.literal(lines[0]), "union": pattern_ref.trie(entries)}
+    wrng, words_entries = np.random.RandomState(9801), []
+    while len(words_ref.build_trie(words_entries or [[1]])[0]) < BIG_WORDS_NODES[0]:
+        words_entries += [[int(v) for v in wrng.randint(1, BIG_C, size=wrng.randint(1, 5))] for _ in range(200)]
+    case.update(clean=clean, queries=queries, entries=entries, patterns=patterns,
+                pattern_weights={k: _weights(9810 + i, p[0], p[1]) for i, (k, p) in enumerate(patterns.items())},
+                set_pattern=([(0, 0, 1), (1, 0, 1)], [every], [1], 2), edit=(hyps, refs), search=dict(n=32, beam=32, depth=32),
+                words_entries=words_entries, words_bonus=BIG_WORDS_BONUS)
     return case
 
 
 @functools.lru_cache(maxsize=None)
 def small():
     """the same families at B = 1, W = 2, C = 3, masked_cases.single(5)'s way: row 0 keeps one live class. `clean` is the
-    same without the mask. One query, one entry, one-state patterns that loop on label 1."""
+    same without the mask. One query, one entry (the lexicon of its words call too: a trie of two nodes), one-state
+    patterns that loop on label 1, once more with a weight."""
     rng = np.random.RandomState(9900)
     lines, il = [[1]], [2]
     paths = [mc.planted_path(lines[0], 2, lead=0, run=1)]
@@ -307,14 +375,17 @@ def small():
     z[0, 0, 2:] = -np.inf
     case = mc._case("history_small", lines, il, paths, z)
     case.update(clean=clean, queries=[[1]], entries=[[1]], patterns={"loop": ([(0, 1, 0)], [0], 1)},
-                set_pattern=([(0, 0, 0)], [[1]], [0], 1), edit=([[1]], [[2]]), search=dict(n=1, beam=2, depth=2))
+                pattern_weights={"loop": (np.array([-1.5], np.float32), np.array([0.5], np.float32))},
+                set_pattern=([(0, 0, 0)], [[1]], [0], 1), edit=([[1]], [[2]]), search=dict(n=1, beam=2, depth=2),
+                words_entries=None, words_bonus=0.25)
     return case
 
 
 def dirtier_dims(d, worst):
     """every dimension of a dirtier's calls, the largest (worst = max, the big dirtier) or smallest (min) over them"""
     hyps, refs = d["edit"]
-    seqs = [d["lines"], d["queries"], d["entries"], refs]
+    lexica = [d["entries"]] + ([d["words_entries"]] if d["words_entries"] else [])      # of the words calls
+    seqs = [d["lines"], d["queries"], refs] + lexica
     arcs = [a for a, _, _ in d["patterns"].values()] + [pattern_set_ref.expand(d["set_pattern"][0], d["set_pattern"][1])]
     states = [ns for _, _, ns in d["patterns"].values()] + [d["set_pattern"][3]]
     out = dict(_shape(d["logits"]))
@@ -322,7 +393,8 @@ def dirtier_dims(d, worst):
         out[key] = worst([_seq_dims([s for s in ss if len(s)] or [[]])[key] for ss in seqs])
     out["total"] = worst([out["total"]] + [_arc_dims(a)["total"] for a in arcs])
     out["distinct"] = worst([out["distinct"]] + [_arc_dims(a)["distinct"] for a in arcs])
-    out["count"] = worst([len(d["queries"]), len(d["entries"])])
+    out["count"] = worst([len(d["queries"])] + [len(es) for es in lexica])
+    out["nodes"] = worst([len(words_ref.build_trie(es)[0]) for es in lexica])
     out["states"] = worst(states)
     out["B"] = worst([out["B"], len(refs)])
     out["stride"] = max(len(h) for h in hyps)

@@ -11,9 +11,11 @@ existing rules in the check of the first-call results against the existing oracl
   * base: each probe as the first call on a new context, checked against its oracle (a result that is history-independent
     but wrong must not pass);
   * dirty: on one context the big dirtier (larger than every probe in every carved dimension, three non-finite lines, so
-    that emissions, alpha / beta rows, log-sum-exps and gradient scratch hold NaN and inf; int32 extremes in the edit
-    tables; the widest search), then the probe - for every probe, host and device pointers, and under the four layout
-    switches HCTR_SPOT_CLASSES=4, HCTR_LEX_CLASSES=4, HCTR_PAT_LINES=1, HCTR_PATSET_LDS=0;
+    that emissions, alpha / beta rows, log-sum-exps, gradient scratch, the words call's step buffers and exit records
+    hold NaN and inf; int32 extremes in the edit tables; the widest search), then the probe - for every probe, host and
+    device pointers, and under the layout switches HCTR_SPOT_CLASSES=4, HCTR_LEX_CLASSES=4, HCTR_PAT_LINES=1,
+    HCTR_PATSET_LDS=0, HCTR_WORDS_LDS=0 and HCTR_WORDS_LINES=1; the words probe also right after each of the big
+    dirtier's two words calls, whose records and step buffers then lie where it carves its own;
   * grow: on one context the small dirtier (B = 1, W = 2, C = 3), then the probes in ascending order of (estimated)
     scratch need, so that the block grows under them; each probe also right after the small dirtier on a context of its
     own; and the wide recognition probe from blocks of known size, where the call grows the block between its two
@@ -21,7 +23,9 @@ existing rules in the check of the first-call results against the existing oracl
   * mixed: on one context all probes in order, in reverse order, and each twice in a row;
   * the fills include/hctr_hip.h documents beyond the valid part of an output, asserted on the dirty results;
   * the cached tables: two lexicons and two patterns alternating, a pattern freed and another built, one object on two
-    contexts;
+    contexts; one lexicon through the exact-lexicon and the words call in turn (three device copies under one serial),
+    under two bonuses, two lexicons through the words call, a lexicon freed and another built, and patterns of kind 0,
+    2, 1, 2 (forward only), 0 in a row on the dirty context, the kind-0 and kind-2 ones with equal tables;
   * the image entries of two models: the second runs the first's calls reversed, each after a call of another family at
     another shape and once after the big dirtier, and returns the first's bytes, guard figures included.
 """
@@ -43,13 +47,18 @@ import skip_beam_ref as skr
 import test_gpu_masked as tm
 import test_gpu_nbest_skip as tskip
 import test_gpu_pattern_set as tps
+import test_gpu_pattern_w as tpw
+import test_gpu_words as tw
 
 pytestmark = pytest.mark.gpu
 
 PAT_NAMES = ("literal", "masked_literal", "union", "live_plus")
+PATW_PROBES = ["pattern_w.union", "pattern_w.live_plus", "pattern.union.fwd", "pattern_w.union.fwd"]
 SWITCHES = [("HCTR_SPOT_CLASSES", "4", ["spot"]), ("HCTR_LEX_CLASSES", "4", ["lexicon"]),
-            ("HCTR_PAT_LINES", "1", ["pattern." + p for p in PAT_NAMES] + ["pattern_set"]),
-            ("HCTR_PATSET_LDS", "0", ["pattern_set"])]
+            ("HCTR_PAT_LINES", "1", ["pattern." + p for p in PAT_NAMES] + ["pattern_set"] + PATW_PROBES),
+            ("HCTR_PATSET_LDS", "0", ["pattern_set"]), ("HCTR_WORDS_LDS", "0", ["words"]),
+            ("HCTR_WORDS_LINES", "1", ["words"])]
+BOTH = {"HCTR_PATSET_LDS": ("HCTR_PAT_LINES", "pattern_set"), "HCTR_WORDS_LDS": ("HCTR_WORDS_LINES", "words")}
 NBEST_FIELDS = ("labels", "lengths", "logps", "scores", "counts")
 REC_FIELDS = ("labels", "lengths", "starts", "ends", "logps", "alt_labels", "alt_logps", "path_logp", "text_nll")
 
@@ -82,6 +91,13 @@ class Env(object):
         self.ps = hc.patset()
         self.ps_pat = ctc.Pattern.from_sets(self.ps["arcs"], self.ps["sets"], self.ps["finals"], self.ps["num_states"], self.ps["C"])
         assert self.ps_pat.kind == 1 and all(p.kind == 0 for p in self.pats.values())
+        self.wd, self.pw = hc.words(), hc.pattern_w()
+        self.wlex = ctc.Lexicon(self.wd["entries"], num_classes=mc.C, priors=self.wd["priors"])
+        self.wpats = {k: ctc.Pattern(p["arcs"], p["finals"], p["states"], mc.C, weights=p["weights"],
+                                     final_weights=p["final_weights"]) for k, p in self.pw.items()}
+        assert all(p.kind == 2 for p in self.wpats.values())
+        for k, p in self.wpats.items():                       # equal tables: only the weights tell kind 2 from kind 0
+            assert all(p.tables()[t].tobytes() == self.pats[k].tables()[t].tobytes() for t in p.tables()), k
         self.ed, self.nb, self.wide = hc.edit(), hc.nbest(), hc.recognize_wide()
         self.arpa = hc.arpa(work)
         self.lm = codec_mod.ArpaLM(self.arpa)                        # (kept: it owns the flat handle)
@@ -94,7 +110,14 @@ class Env(object):
             C = d["logits"].shape[2]
             self.dirt[kind] = dict(case=d, lex=ctc.Lexicon(d["entries"], num_classes=C),
                                    pats=[ctc.Pattern(*p, C) for p in d["patterns"].values()],
-                                   set_pat=ctc.Pattern.from_sets(*d["set_pattern"], C))
+                                   set_pat=ctc.Pattern.from_sets(*d["set_pattern"], C),
+                                   words_lex=ctc.Lexicon(d["words_entries"], num_classes=C) if d["words_entries"] else None,
+                                   wpats=[ctc.Pattern(*p, C, weights=d["pattern_weights"][k][0],
+                                                      final_weights=d["pattern_weights"][k][1])
+                                          for k, p in d["patterns"].items()])
+        big = self.dirt["big"]
+        assert big["words_lex"].info()["nodes"] > ctc.WORDS_LDS_NODES >= big["lex"].info()["nodes"]
+        assert all(p.kind == 2 for kind in self.dirt for p in self.dirt[kind]["wpats"])
         self._bound = []
 
     def new_ctx(self):
@@ -158,6 +181,18 @@ def run_probe(E, ctx, name, dev=False):
     if name == "lexicon":
         lx = ctc.lexicon_logits(ctx, z, on, E.lex, len(E.lex), il, True)
         return {"lex." + k: getattr(lx, k) for k in ("entries", "logp", "rank", "log_total", "count", "scores")}
+    if name == "words":
+        r = ctc.words_logits(ctx, z, on, E.wlex, E.wd["bonus"], None, il)
+        return {"words." + f: getattr(r, f) for f in tw.FIELDS}
+    if name.endswith(".fwd"):                                 # the forward-only instance: logp alone
+        kind, pname, _ = name.split(".")
+        r = ctc.pattern_logits(ctx, z, on, (E.wpats if kind == "pattern_w" else E.pats)[pname], il, full=False)
+        assert r.best_logp is None and r.path is None
+        return {name + ".logp": r.logp}
+    if name.startswith("pattern_w."):
+        pname = name.split(".")[1]
+        r = ctc.pattern_logits(ctx, z, on, E.wpats[pname], il)
+        return {"patw.%s.%s" % (pname, f): getattr(r, f) for f in tpw.FIELDS}       # (weights: the host's, of the texts)
     if name.startswith("pattern."):
         pname = name.split(".")[1]
         r = ctc.pattern_logits(ctx, z, on, E.pats[pname], il)
@@ -170,6 +205,22 @@ def run_probe(E, ctx, name, dev=False):
     return {"ev." + k: getattr(ev, k) for k in ("labels", "lengths", "edits", "counts", "ref_map", "hyp_map")}
 
 
+def run_dirtier_words(E, ctx, kind, which=("scratch", "lds")):
+    """the dirtier's words calls: the big one's lexicon of more than 4096 trie nodes (the scratch form: step buffers of
+    2 * nodes * 16 bytes a line in the block, three lines of them non-finite), then its small lexicon (the LDS form's
+    exit records); the small one's one entry at W = 2. HCTR_OK, and what the contract says of the non-finite lines."""
+    ctc, d = E.ctc, E.dirt[kind]
+    c = d["case"]
+    for form in which:
+        lex = d["words_lex"] if form == "scratch" else d["lex"]
+        if lex is None:
+            continue
+        r = ctc.words_logits(ctx, c["logits"], 0, lex, c["words_bonus"], None, c["il"])
+        bad = sorted(hc.BIG_BAD) if kind == "big" else []
+        assert (r.count[bad] == 0).all() and np.isneginf(r.score[bad]).all() and np.isposinf(r.text_nll[bad]).all(), form
+        assert (np.delete(r.count, bad) >= 1).all() and np.isfinite(np.delete(r.score, bad)).all(), form
+
+
 def run_dirtier(E, ctx, kind):
     """the big or the small dirtier: every call returns HCTR_OK (``_lib.check`` raises otherwise)"""
     ctc, d = E.ctc, E.dirt[kind]
@@ -179,8 +230,13 @@ def run_dirtier(E, ctx, kind):
     ctc.align_logits(ctx, z, 0, tg, tl, il)
     ctc.spot_logits(ctx, z, 0, c["queries"], il)
     ctc.lexicon_logits(ctx, z, 0, d["lex"], min(len(d["lex"]), ctc.LEX_MAX_TOP), il, True)
+    run_dirtier_words(E, ctx, kind)
     for p in d["pats"] + [d["set_pat"]]:
         ctc.pattern_logits(ctx, z, 0, p, il)
+    for p in d["wpats"]:
+        ctc.pattern_logits(ctx, z, 0, p, il)
+        if kind == "big":
+            ctc.pattern_logits(ctx, z, 0, p, il, full=False)
     ctc.recognize_logits(ctx, z, 0)
     ctc.evaluate_logits(ctx, z, 0, tg, tl, True)
     ctc.edit_distance_sequences(ctx, c["edit"][0], c["edit"][1], True)
@@ -248,6 +304,44 @@ def test_base_of_the_set_form_against_float64(E, base):
         T = int(E.ps["il"][b])
         assert r["ps.path"][b, :T].tolist() == w[2] and r["ps.lengths"][b] == len(E.ps["labels"][b]), b
         assert r["ps.labels"][b, :r["ps.lengths"][b]].tolist() == E.ps["labels"][b], b
+
+
+def test_base_of_the_words_probe_against_float64(E, base):
+    """tests/test_gpu_words.py's ``check``: the score within 1e-5 relative + 1e-3 of words_ref's, the -inf pattern, the
+    fills, labels / count / lengths against the returned words, and the sandwich on the returned segmentation"""
+    r, c = base("words"), E.v
+    res = E.ctc.WordsResult(*[r["words." + f] for f in tw.FIELDS], input_lengths=c["il"])
+    tw.check(res, c["logits"], c["il"], E.wd["entries"], E.wd["priors"], E.wd["bonus"], E.wd["want"], "words probe")
+    want = np.array([w[0] for w in E.wd["want"]])
+    print("words probe: largest |score - float64| %.3e" % np.abs(res.score - want).max())
+    assert (res.count >= 1).all() and res.count.max() >= 2 and len(set(res.count.tolist())) >= 2
+    tw.text_nll_bits(E.ctc, E.new_ctx(), res, c["logits"], c["il"], "words probe")
+
+
+def test_base_of_the_weighted_patterns_against_float64(E, base):
+    """tests/test_gpu_pattern_w.py's ``check_against``: logp and best_logp within 1e-5 relative + 1e-3 of pattern_w_ref's
+    with an equal -inf pattern, the path, spans and the text's weight equal; the forward-only instances' logp by the
+    same rule, and with the bits of the full call's"""
+    c = E.v
+    for pname, p in E.pw.items():
+        r = base("pattern_w." + pname)
+        res = E.ctc.PatternResult(*[r["patw.%s.%s" % (pname, f)] for f in tpw.FIELDS])
+        tpw.check_against(res, p["want"], p["tab"], E.wpats[pname], c["logits"], c["il"], "pattern_w." + pname)
+        for k, f in ((0, "logp"), (1, "best_logp")):
+            want = np.array([w[k] for w in p["want"]])
+            print("pattern_w.%s: largest |%s - float64| %.3e" % (pname, f, np.abs(getattr(res, f) - want).max()))
+        plain = base("pattern." + pname)
+        texts = [res.labels[b, :res.lengths[b]].tolist() for b in range(len(res))]
+        other = [plain["pat.%s.labels" % pname][b, :plain["pat.%s.lengths" % pname][b]].tolist() for b in range(len(res))]
+        assert texts != other, pname                           # the weights decide a line: the kind-0 tables cannot pass
+    for name, want, full in (("pattern.union.fwd", [w[0] for w in E.vo["pat"]["union"]], base("pattern.union")["pat.union.logp"]),
+                             ("pattern_w.union.fwd", [w[0] for w in E.pw["union"]["want"]],
+                              base("pattern_w.union")["patw.union.logp"])):
+        got = base(name)[name + ".logp"]
+        tpw._check_scores(got, want, name)
+        print("%s: largest |logp - float64| %.3e" % (name, np.abs(got - np.array(want)).max()))
+        assert got.tobytes() == full.tobytes(), name
+    assert base("pattern.union.fwd")["pattern.union.fwd.logp"].tobytes() != base("pattern_w.union.fwd")["pattern_w.union.fwd.logp"].tobytes()
 
 
 def test_base_of_the_wide_recognition(E, base):
@@ -342,11 +436,27 @@ def test_layout_switches_after_the_big_dirtier(var, value, names, E, base, dirty
         with switch(var, value):
             got = run_probe(E, dirty_ctx, name)
         same(got, base(name), "%s under %s=%s after the big dirtier" % (name, var, value))
-    if var == "HCTR_PATSET_LDS":                              # both at once: scratch step buffers in groups of one line
+    if var in BOTH:                                           # both at once: scratch step buffers in groups of one line
+        lines, name = BOTH[var]
         run_dirtier(E, dirty_ctx, "big")
-        with switch(var, value), switch("HCTR_PAT_LINES", "1"):
-            got = run_probe(E, dirty_ctx, "pattern_set")
-        same(got, base("pattern_set"), "pattern_set under both switches")
+        with switch(var, value), switch(lines, "1"):
+            got = run_probe(E, dirty_ctx, name)
+        same(got, base(name), name + " under both switches")
+
+
+@pytest.mark.parametrize("form", ["scratch", "lds"])
+def test_words_right_after_the_big_words_calls(form, E, base, dirty_ctx):
+    """nothing in between: the probe carves its emissions, records and (in the scratch form) step buffers from the bytes
+    a words call of eight lines, three of them non-finite, just left - the large trie's scratch-form buffers and
+    records, or the LDS form's records of 160 columns, which the walk back must never follow"""
+    for switches in ((), (("HCTR_WORDS_LDS", "0"),), (("HCTR_WORDS_LDS", "0"), ("HCTR_WORDS_LINES", "1"))):
+        run_dirtier(E, dirty_ctx, "big")
+        run_dirtier_words(E, dirty_ctx, "big", which=(form,))
+        with contextlib.ExitStack() as stack:
+            for var, value in switches:
+                stack.enter_context(switch(var, value))
+            got = run_probe(E, dirty_ctx, "words")
+        same(got, base("words"), "words after the big %s-form words call, %s" % (form, dict(switches)))
 
 
 # ---- 3. the grow path -----------------------------------------------------------------------------------------------
@@ -429,6 +539,65 @@ def test_documented_fills(E, dirty):
     assert (r["lex.count"] < r["lex.entries"].shape[1]).any(), "no line leaves a place unused"
     assert (_beyond(r["lex.entries"], r["lex.count"]) == -1).all()
     assert np.isneginf(_beyond(r["lex.logp"], r["lex.count"])).all() and np.isneginf(_beyond(r["lex.rank"], r["lex.count"])).all()
+    _words_fills(dirty("words"), "the words probe", some=True)
+    for pname in E.pw:
+        _weighted_fills(dirty("pattern_w." + pname), "patw.%s." % pname, c["il"], some=True)
+
+
+def _words_fills(r, what, some=False, none=False):
+    """words / starts are -1 beyond count, labels 0 beyond lengths; a line without a segmentation has score -inf, count
+    and lengths 0, text_nll +inf. ``some`` / ``none``: there are lines with / without a segmentation, and unused places"""
+    count, lengths = r["words.count"], r["words.lengths"]
+    have = count > 0
+    assert (_beyond(r["words.words"], count) == -1).all() and (_beyond(r["words.starts"], count) == -1).all(), what
+    assert not _beyond(r["words.labels"], lengths).any(), what
+    assert np.isneginf(r["words.score"][~have]).all() and np.isposinf(r["words.text_nll"][~have]).all(), what
+    assert not lengths[~have].any() and np.isfinite(r["words.score"][have]).all() and (lengths[have] > 0).all(), what
+    if some:
+        assert have.any() and (count[have] < r["words.words"].shape[1]).any() and (lengths[have] < r["words.labels"].shape[1]).any()
+        assert all((r["words.words"][b, :n] >= 0).all() and (r["words.starts"][b, :n] >= 0).all() for b, n in enumerate(count))
+    if none:
+        assert (~have).any(), what
+
+
+def _weighted_fills(r, key, il, some=False, none=False):
+    """the pattern family's fills (labels, starts, ends, logps 0 beyond lengths; path -1 beyond the line's length, and
+    everywhere on an infeasible line), and the texts' weights: NaN exactly on the infeasible lines"""
+    for k in ("labels", "starts", "ends", "logps"):
+        assert not _beyond(r[key + k], r[key + "lengths"]).any(), key + k
+    feasible = np.isfinite(r[key + "best_logp"])
+    assert (_beyond(r[key + "path"], np.where(feasible, il, 0)) == -1).all(), key + "path"
+    assert (np.isnan(r[key + "weights"]) == ~feasible).all() and np.isfinite(r[key + "weights"][feasible]).all(), key + "weights"
+    assert not r[key + "lengths"][~feasible].any() and np.isposinf(r[key + "text_nll"][~feasible]).all(), key
+    if some:
+        assert feasible.any() and (r[key + "lengths"][feasible] < r[key + "labels"].shape[1]).any(), key
+        assert (np.asarray(il)[feasible] < r[key + "path"].shape[1]).any(), key + ": no feasible line leaves path places unused"
+    if none:
+        assert (~feasible).any(), key
+
+
+def test_documented_fills_of_lines_without_a_reading(E, dirty_ctx):
+    """the `vocab` probes of the words and the weighted pattern calls read every line, so their own results cannot show
+    the fills of a line that has no reading. At the same shape, after the big dirtier: the words call on the three
+    entries of the probe's lexicon that need the masked class 9 (no line has a segmentation), and `vocab`'s literal
+    through class 9 as a weighted pattern (no line has a path)."""
+    c = E.v
+    es = [e for e in E.wd["entries"] if 9 in e]
+    assert len(es) >= 2
+    lex = E.ctc.Lexicon(es, num_classes=mc.C, priors=np.arange(len(es), dtype=np.float32))
+    run_dirtier(E, dirty_ctx, "big")
+    r = E.ctc.words_logits(dirty_ctx, c["logits"], 0, lex, E.wd["bonus"], None, c["il"])
+    r = {"words." + f: getattr(r, f) for f in tw.FIELDS}
+    _words_fills(r, "entries through a masked class", none=True)
+    assert not r["words.count"].any() and (r["words.words"] == -1).all() and not r["words.labels"].any()
+    arcs, finals, ns = mc.patterns(c)["masked_literal"]
+    pat = E.ctc.Pattern(arcs, finals, ns, mc.C, weights=np.full(len(arcs), 1.5), final_weights=[-0.5] * len(finals))
+    assert pat.kind == 2
+    run_dirtier(E, dirty_ctx, "big")
+    r = E.ctc.pattern_logits(dirty_ctx, c["logits"], 0, pat, c["il"])
+    r = {"patw." + f: getattr(r, f) for f in tpw.FIELDS}
+    _weighted_fills(r, "patw.", c["il"], none=True)
+    assert np.isnan(r["patw.weights"]).all() and (r["patw.path"] == -1).all() and np.isneginf(r["patw.logp"]).all()
 
 
 # ---- 6. the cached tables ---------------------------------------------------------------------------------------------
@@ -460,6 +629,83 @@ def test_two_lexicons_alternate(E, base):
     tm._check_scores(b1["lex.scores"], want, "lexicon B against float64")
 
 
+def _words(E, ctx, lex, bonus=None):
+    c = E.v
+    r = E.ctc.words_logits(ctx, c["logits"], 0, lex, E.wd["bonus"] if bonus is None else bonus, None, c["il"])
+    return {"words." + f: getattr(r, f) for f in tw.FIELDS}
+
+
+def test_one_lexicon_through_the_exact_and_the_words_call(E, base):
+    """the exact-lexicon call's device copy, the words call's host tables and its device copy all go by the one serial
+    of the object: neither call takes the other's tables for its own"""
+    ctx = E.new_ctx()
+    first = {}
+    for rnd in range(2):
+        for key, call in (("lexicon", _lexicon), ("words", _words)):
+            got = call(E, ctx, E.wlex)
+            same(got, first.setdefault(key, got), "%s, round %d" % (key, rnd))
+    same(first["words"], base("words"), "words after the exact-lexicon call")
+    same(_lexicon(E, E.new_ctx(), E.wlex), first["lexicon"], "the exact-lexicon call as a first call")
+
+
+def test_one_lexicon_under_two_bonuses(E, base):
+    """the word tables hold prior + bonus: another bonus on the same lexicon is another set of tables, on the host and on
+    the device"""
+    ctx = E.new_ctx()
+    first = {}
+    for rnd in range(2):
+        for bonus in (E.wd["bonus"], 1.25):
+            got = _words(E, ctx, E.wlex, bonus)
+            same(got, first.setdefault(bonus, got), "bonus %g, round %d" % (bonus, rnd))
+    a, b = first[E.wd["bonus"]], first[1.25]
+    same(a, base("words"), "the probe's bonus")
+    assert (a["words.count"] >= 1).all() and (b["words.count"] >= 1).all()       # so 1.75 a word parts the scores
+    assert (b["words.score"] > a["words.score"] + 1.0).all()
+    same(_words(E, E.new_ctx(), E.wlex, 1.25), b, "the other bonus as a first call")
+
+
+def test_two_lexicons_alternate_through_the_words_call(E, base):
+    ctx = E.new_ctx()
+    other, es = _second_lexicon(E)
+    assert other.info()["nodes"] > E.wlex.info()["nodes"]
+    a1 = _words(E, ctx, E.wlex)
+    b1 = _words(E, ctx, other)
+    same(_words(E, ctx, E.wlex), a1, "words of lexicon A after B")
+    same(_words(E, ctx, other), b1, "words of lexicon B after A")
+    same(a1, base("words"), "words of lexicon A")
+    same(_words(E, E.new_ctx(), other), b1, "words of lexicon B as a first call")
+    c = E.v
+    res = E.ctc.WordsResult(*[b1["words." + f] for f in tw.FIELDS], input_lengths=c["il"])
+    tw.check(res, c["logits"], c["il"], es, None, E.wd["bonus"], tw.ref.words(c["logits"], es, None, E.wd["bonus"], c["il"]),
+             "words of lexicon B against float64")
+
+
+def test_lexicon_freed_and_another_built(E, base):
+    """the device copy and the host tables are recognised by serial number: a lexicon built where a freed one lay is
+    another lexicon"""
+    c = E.v
+    lists = {"probe": (E.wd["entries"], E.wd["priors"]), "heads": ([e[:2] for e in E.wd["entries"] if 9 not in e], None)}
+    fresh = {}
+    for key, (es, pr) in lists.items():
+        fresh[key] = _words(E, E.new_ctx(), E.ctc.Lexicon(es, num_classes=mc.C, priors=pr))
+    same(fresh["probe"], base("words"), "the probe's list")
+    assert fresh["heads"]["words.score"].tobytes() != fresh["probe"]["words.score"].tobytes()
+    ctx = E.new_ctx()
+    for rnd, key in enumerate(("probe", "heads", "probe", "heads")):
+        lex = E.ctc.Lexicon(lists[key][0], num_classes=mc.C, priors=lists[key][1])
+        same(_words(E, ctx, lex), fresh[key], "%s built anew (%d)" % (key, rnd))
+        del lex
+
+
+def test_pattern_kinds_in_a_row_on_the_dirty_context(E, base, dirty_ctx):
+    """kind 0, 2, 1, 2 (forward only), 0 on one context after the big dirtier: the three kinds share one device block and
+    one serial, the weighted block is the explicit one's plus the weights, and the kind-0 and kind-2 patterns here
+    have equal tables"""
+    run_dirtier(E, dirty_ctx, "big")
+    for step, name in enumerate(("pattern.union", "pattern_w.union", "pattern_set", "pattern_w.union.fwd", "pattern.union")):
+        same(run_probe(E, dirty_ctx, name), base(name), "%s, step %d of the kinds in a row" % (name, step))
+
+
 def test_two_pattern_forms_alternate(E, base):
     ctx = E.new_ctx()
     for rnd in range(2):
@@ -488,11 +734,14 @@ def test_one_table_on_two_contexts(E, base):
             same(run_probe(E, ctx, "pattern.union"), base("pattern.union"), "pattern, round %d" % rnd)
             same(run_probe(E, ctx, "pattern_set"), base("pattern_set"), "set form, round %d" % rnd)
             same(run_probe(E, ctx, "nbest_lm"), base("nbest_lm"), "LM, round %d" % rnd)
+            same(run_probe(E, ctx, "words"), base("words"), "words, round %d" % rnd)
+            same(run_probe(E, ctx, "pattern_w.union"), base("pattern_w.union"), "weighted pattern, round %d" % rnd)
 
 
 # ---- 7. the image entries of two models -------------------------------------------------------------------------------
 SHAPES = [(3, 96), (1, 33), (5, 17)]
-IMAGE_CALLS = ["greedy", "forward", "beam_frontend", "nbest", "ctc_loss", "recognize", "evaluate", "pattern"]
+IMAGE_CALLS = ["greedy", "forward", "beam_frontend", "nbest", "ctc_loss", "recognize", "evaluate", "pattern", "words",
+               "pattern_w"]
 AUTO_GUARDED = ("greedy", "forward", "beam_frontend", "evaluate")     # the calls after which the guard figures are compared
 
 
@@ -508,15 +757,28 @@ def models(pkg, synth):
     return out
 
 
-def _font_pattern(E, synth):
-    """one or more of the font's labels, at the model's vocabulary"""
+def _font_pattern(E, synth, weighted=False):
+    """one or more of the font's labels, at the model's vocabulary; ``weighted``: the same arcs with seeded weights in
+    [-2, 2] (kind 2)"""
     labels = sorted(synth.font_label(k) for k in range(synth.FONT_CLASSES))
     arcs = [(0, c, 1) for c in labels] + [(1, c, 1) for c in labels]
-    return E.ctc.Pattern(arcs, [1], 2, synth.DEFAULT_VOCAB + 2)
+    if not weighted:
+        return E.ctc.Pattern(arcs, [1], 2, synth.DEFAULT_VOCAB + 2)
+    rng = np.random.RandomState(9980)
+    return E.ctc.Pattern(arcs, [1], 2, synth.DEFAULT_VOCAB + 2, weights=rng.uniform(-2, 2, len(arcs)), final_weights=[0.5])
+
+
+def _font_lexicon(E, synth):
+    """every font label alone and every ordered pair of two different ones, with seeded priors"""
+    labels = sorted(synth.font_label(k) for k in range(synth.FONT_CLASSES))
+    es = [[a] for a in labels] + [[a, b] for a in labels for b in labels if a != b]
+    pr = (np.random.RandomState(9981).randn(len(es)) * 0.5).astype(np.float32)
+    return E.ctc.Lexicon(es, num_classes=synth.DEFAULT_VOCAB + 2, priors=pr)
 
 
 def _image_call(m, what, imgs, targets, pat):
-    """one image entry -> ({name: array}, the guard figures after it)"""
+    """one image entry -> ({name: array}, the guard figures after it); ``pat``: the plain and the weighted font pattern
+    and the font lexicon"""
     tg, tl = targets
     if what == "greedy":
         g = m.greedy(imgs)
@@ -538,9 +800,15 @@ def _image_call(m, what, imgs, targets, pat):
     elif what == "evaluate":
         ev = m.evaluate(imgs, tg, tl)
         out = {"ev." + k: getattr(ev, k) for k in ("labels", "lengths", "edits", "counts", "ref_map", "hyp_map")}
+    elif what == "words":
+        r = m.words(imgs, pat["lex"], -0.5)
+        out = {"words." + f: getattr(r, f) for f in tw.FIELDS}
+    elif what == "pattern_w":
+        r = m.pattern(imgs, pat["weighted"])
+        out = {"patw." + f: getattr(r, f) for f in tpw.FIELDS}
     else:
         assert what == "pattern"
-        r = m.pattern(imgs, pat)
+        r = m.pattern(imgs, pat["plain"])
         out = {"pat." + f: getattr(r, f) for f in r.FIELDS}
     g = m.last_guard()
     out.update({"guard.lines": np.int64(g["lines"]), "guard.flagged": np.int64(g["flagged"]), "guard.flags": g["flags"],
@@ -554,7 +822,8 @@ def test_image_entries_of_two_models(E, synth, models):
     entries leave them as they were, so they are those of the call before, which differs between the two orders: they
     are compared after the calls that set them)"""
     m1, m2 = models
-    pat = _font_pattern(E, synth)
+    pat = {"plain": _font_pattern(E, synth), "weighted": _font_pattern(E, synth, weighted=True), "lex": _font_lexicon(E, synth)}
+    assert (pat["plain"].kind, pat["weighted"].kind) == (0, 2)
     imgs = {sh: synth.make_font_lines(sh[0], sh[1], 90 + i) for i, sh in enumerate(SHAPES)}
     targets = {}
     for sh in SHAPES:                                         # each line's transcription: model 1's own greedy text

@@ -3,8 +3,12 @@ comparison of probe results meaningful and the dirtiers dirtier than the probes.
 
   * every probe's oracle holds no NaN: its figures are finite, or -inf / +inf where the contract documents them;
   * the big dirtier exceeds, and the small one stays below, every probe in every dimension a scratch layout is carved by
-    (B, W, C, the longest sequence, the distinct classes, the total length, and for the searches beam, depth and n),
-    asserted on the numbers, so that a later edit of a case cannot silently void the GPU test;
+    (B, W, C, the longest sequence, the distinct classes, the total length, the trie nodes of a words call, and for the
+    searches beam, depth and n), asserted on the numbers, so that a later edit of a case cannot silently void the GPU
+    test; the big dirtier's large lexicon needs the scratch form of the words kernel and stays within the node limit;
+  * the words probe's best segmentations have several words and differing counts, and the weighted pattern probes decode
+    another text than the same automata without weights, by the float64 yardsticks alone: a call that ran the wrong
+    tables cannot return the yardstick's result;
   * the big dirtier's non-finite rows are one NaN, one +inf and one row of nothing but -inf, one line each, inside the
     line's input length; every other line is finite;
   * the copy of the N-best logits is the one tests/test_gpu_nbest_lm.py builds its lists from;
@@ -78,6 +82,69 @@ def test_other_oracles_hold_no_nan():
         assert np.isfinite(_no_nan(wide["want"][k], "wide recognition " + k)).all()
 
 
+def test_words_probe_has_several_words_and_differing_counts():
+    """by words_ref alone: every line has a segmentation with a finite score, at least one has two or more words, the
+    counts differ between lines, and two of the lexicon's entries need the masked class 9, which no line can read"""
+    c, _ = hc.vocab()
+    wd = hc.words()
+    assert wd["entries"] == mc.entries(c) and sum(9 in e for e in wd["entries"]) >= 2
+    assert wd["priors"].dtype == np.float32 and wd["priors"].shape == (len(wd["entries"]),) and wd["bonus"] == -0.5
+    assert len(set(wd["priors"].tolist())) == len(wd["entries"]) and np.isfinite(wd["priors"]).all()
+    scores = _no_nan([w[0] for w in wd["want"]], "words score")
+    counts = [len(w[1]) for w in wd["want"]]
+    print("words probe: scores", scores, "counts", counts)
+    assert np.isfinite(scores).all() and max(counts) >= 2 and len(set(counts)) >= 2
+    for b, (_, words, starts) in enumerate(wd["want"]):
+        assert len(words) == len(starts) >= 1 and starts == sorted(set(starts)) and starts[-1] < c["il"][b], b
+        assert not any(9 in wd["entries"][e] for e in words), b
+
+
+def test_weighted_probes_decode_another_text_than_the_plain_ones():
+    """by pattern_w_ref and pattern_ref alone: the weights are float32 in [-2, 2], not all zero, every line is feasible,
+    and on at least one line the best text under the weights is not the best text without them"""
+    c, o = hc.vocab()
+    for name, p in hc.pattern_w().items():
+        arcs, finals, ns = mc.patterns(c)[name]
+        assert (p["arcs"], p["finals"], p["states"]) == (arcs, finals, ns)
+        for w, n in ((p["weights"], len(arcs)), (p["final_weights"], len(finals))):
+            assert w.dtype == np.float32 and w.shape == (n,) and (np.abs(w) <= 2).all() and np.abs(w).min() > 0
+        differ = []
+        for b, (want, plain) in enumerate(zip(p["want"], o["pat"][name])):
+            _no_nan(want[:2], name)
+            assert np.isfinite(want[0]) and np.isfinite(want[1]) and want[2] is not None and plain[2] is not None, (name, b)
+            if hc.pattern_w_ref.collapse(want[2]) != hc.pattern_w_ref.collapse(plain[2]):
+                differ.append(b)
+            assert abs(want[0] - plain[0]) > 1e-2, (name, b)      # far beyond the base check's rule: logp tells the tables apart too
+        print("pattern_w.%s: the weighted best text differs on lines %s" % (name, differ))
+        assert differ, name
+
+
+def test_big_dirtier_words_lexicon_needs_the_scratch_form(pkg):
+    """more than 4096 trie nodes (the step buffers leave LDS for the call's scratch) and at most the engine's limit, by
+    the engine's own count; the small dirtier's and the probe's tries are the python builder's sizes too"""
+    import importlib
+    import words_ref
+    ctc = importlib.import_module(pkg.__name__ + ".ctc")
+    d = hc.big()
+    es = d["words_entries"]
+    assert all(1 <= len(e) <= 4 and 1 <= min(e) and max(e) <= hc.BIG_C - 1 for e in es)
+    assert len(set(c for e in es for c in e)) == hc.BIG_C - 1            # the 63 live labels
+    nodes = ctc.Lexicon(es, num_classes=hc.BIG_C).info()["nodes"]
+    print("the big dirtier's large lexicon: %d entries, %d nodes" % (len(es), nodes))
+    assert nodes == len(words_ref.build_trie(es)[0]) == hc.dirtier_dims(d, max)["nodes"]
+    assert ctc.WORDS_LDS_NODES == words_ref.LDS_NODES == 4096 < hc.BIG_WORDS_NODES[0] <= nodes < hc.BIG_WORDS_NODES[1]
+    assert nodes <= ctc.WORDS_MAX_NODES == words_ref.MAX_NODES
+    assert d["words_bonus"] != 0 and hc.small()["words_bonus"] != 0
+    probe = hc.probe_dims()["words"]["nodes"]
+    assert probe == len(words_ref.build_trie(hc.words()["entries"])[0]) <= 1024          # one node per thread, in LDS
+    assert hc.dirtier_dims(hc.small(), min)["nodes"] == 2 < probe < len(words_ref.build_trie(d["entries"])[0]) <= 4096 < nodes
+    for dirt in (d, hc.small()):                                                     # the weighted copies
+        assert sorted(dirt["pattern_weights"]) == sorted(dirt["patterns"])
+        for k, (w, fw) in dirt["pattern_weights"].items():
+            arcs, finals, _ = dirt["patterns"][k]
+            assert w.shape == (len(arcs),) and fw.shape == (len(finals),) and np.isfinite(w).all() and w.any()
+
+
 def test_wide_recognition_grows_the_block_between_its_layouts():
     """csrc/engine.cpp's rec_pass asks for the row figures' layout first and the decoded text's loss layout second, and
     moves the kept log-sum-exps when the second outgrows the block: the wide probe's does, `vocab`'s cannot"""
@@ -113,6 +180,9 @@ def test_dirtiers_bracket_every_probe():
     for name in hc.PROBES:
         for key, v in dims[name].items():
             assert small[key] < v < big[key], (name, key, small[key], v, big[key])
+    assert small["nodes"] < dims["words"]["nodes"] < big["nodes"]       # (named: the words call's step buffers and records)
+    for name in ("pattern_w.union", "pattern_w.live_plus", "pattern.union.fwd", "pattern_w.union.fwd"):
+        assert dims[name] == dims["pattern." + name.split(".")[1]] and "states" in dims[name]
     # per family, not only over all calls: the targets, the queries, the entries and the references
     c, o = hc.vocab()
     for mine, theirs_big, theirs_small in ((c["lines"], hc.big()["lines"], hc.small()["lines"]),
